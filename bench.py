@@ -8,10 +8,19 @@ batch 2 per GPU (configs[2] of BASELINE.json, the per-GPU shard of the headline 
 480x480 images + 20-token language embeddings, deterministic random-init weights.  One step = forward +
 weighted cross-entropy (fused with the final upsample: lavt_upsample_ce_*) + backward (+ gradient all-reduce when N > 1); the optimizer is excluded.
 
-Prints ONE JSON line on rank 0 with the driver's contract plus
+A plain run sets up, warms up, times exactly K steps once, writes the last step's outputs when --dump-outputs DIR is given, and prints
+ONE JSON line on rank 0 with the driver's contract (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step).
+With --full the line also carries
   "roofline":     the kernel family with the largest us/step of this step, timed per launch with HIP events inside eager steps (profile_step),
   "roofline_conv": the decoder conv2_2 implicit GEMM timed alone (round 1's roofline entry, kept for continuity),
-  "cpu_baseline": the CPU oracle (oracle/lavt_oracle.py, a port of the reference) timed on the host cores (N=1, rank 0).
+  "cpu_baseline": the CPU oracle (oracle/lavt_oracle.py, a port of the reference) timed on the host cores (N=1, rank 0),
+and config.loss_check (eager loss vs the reference's fixture), config.optimizer_ms_separate (FusedAdamW timed alone) and further repetitions
+of the timed region (config.ms_per_step_all_repetitions).
+
+--dump-outputs DIR: what the caller of the timed step receives after its last timed step, as float32 / float64 .npy files (< 64 MB in all):
+loss, stats ([loss, sum of weights, I, U] of the fused loss), grad_norms (L2 norm of every parameter's gradient, model.named_parameters()
+order) and grad_sample (a fixed, seeded sample of the gradient values, concatenated in that order).  Weights, inputs and the DropPath
+generator are seeded, so the same arguments give the same inputs from run to run.
 """
 import argparse
 import json
@@ -338,6 +347,36 @@ def cpu_baseline(cfg):
                       f"{len(timed)} timed, median {med:.2f} s (all: {', '.join(f'{t:.2f}' for t in times)})"}
 
 
+DUMP_GRAD_SAMPLE = 4 << 20          # gradient values in grad_sample.npy (16 MB of float32)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, model, step):
+    """The last timed step's results as the caller receives them (step.loss, step.stats, every parameter's .grad) -> path/<name>.npy, float32 /
+    float64.  grad_sample draws its indices from a generator of its own (fixed seed) over the gradients concatenated in named_parameters() order;
+    a parameter without a gradient counts as zeros."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    params = list(model.named_parameters())
+    grads = [(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for _, p in params]
+    flat = torch.cat(grads)
+    idx = torch.randint(0, flat.numel(), (min(DUMP_GRAD_SAMPLE, flat.numel()),), generator=torch.Generator("cpu").manual_seed(20240607))
+    arrays = {
+        "loss": step.loss.detach().double().reshape(1).cpu().numpy(),
+        "grad_norms": torch.stack([g.double().norm() for g in grads]).cpu().numpy(),
+        "grad_sample": flat[idx.sort().values.to(flat.device)].cpu().numpy(),
+    }
+    if step.stats is not None:
+        arrays["stats"] = step.stats.detach().double().cpu().numpy()
+    del flat, grads
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    print(f"[bench] wrote {', '.join(sorted(arrays))} ({total / 2**20:.1f} MB) to {path}", file=sys.stderr)
+
+
 def spawn_ranks(a):
     """`python bench.py --gpus N` started by hand (no torch.distributed.run): start N fresh worker processes, one per GPU, BEFORE anything in this
     process touches a GPU (no re-exec of a process that has initialised HIP); relay rank 0's JSON line.  The children are supervised: the first
@@ -406,6 +445,9 @@ def main():
                     "workgroup on a CU while a collective runs; the step's compute kernels are sized to about one round of the 256 CUs, so each CU RCCL "
                     "holds turns a 1.0-round launch into 2.0 rounds for the kernels it overlaps with: fewer channels = less overlap tax, lower ring bandwidth")
     ap.add_argument("--bf16-buckets", action="store_true", help="all-reduce the gradient buckets in bf16 (half the bytes over xGMI; fp32 flat buffer kept)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: roofline / per-family kernel timing, "
+                    "attainable peak, loss check against the reference fixture, separate optimizer timing, CPU baseline, repetitions of the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (see the module docstring)")
     a = ap.parse_args()
     if a.rccl_channels > 0:
         os.environ["NCCL_MAX_NCHANNELS"] = str(a.rccl_channels)
@@ -444,6 +486,7 @@ def main():
     if a.dtype is None:
         a.dtype = "fp8" if cfg.get("fp8") else "bf16"
     lavt_hip.set_compute_dtype(a.dtype)
+    torch.manual_seed(1234 + rank)          # the DropPath draws (and anything else on the default generators): same inputs from run to run
     model = build_model(cfg, device, a.drop_path)
     if world > 1 or force:
         model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)       # train.py:589
@@ -498,15 +541,18 @@ def main():
             el = float(t)
         return el
 
-    # EXACTLY `steps` steps between the barriers, max over ranks (the contract).  When that region is short (the driver passes --steps 20: 0.2 s) it
-    # is repeated and the MEDIAN repetition is reported, so that one scheduling hiccup does not decide the number; `steps` stays what was asked for.
-    reps_all = [timed_region()]
-    while sum(reps_all) < 2.0 and len(reps_all) < 15:
-        reps_all.append(timed_region())
-    elapsed = sorted(reps_all)[len(reps_all) // 2]
+    # EXACTLY `steps` steps between the barriers, max over ranks (the contract), timed once: the headline.
+    elapsed = timed_region()
     loss = float(step.loss)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, step)
+    # --full: when that region is short (--steps 20: 0.2 s) it is repeated until 2 s have been timed, and every repetition is reported next to the
+    # headline, so that one scheduling hiccup can be told from the number
+    reps_all = [elapsed]
+    while a.full and sum(reps_all) < 2.0 and len(reps_all) < 15:
+        reps_all.append(timed_region())
     opt_ms = None
-    if rank == 0 and not a.no_optimizer:
+    if rank == 0 and a.full and not a.no_optimizer:
         # the caller's optimizer step (train.py:688-700), reported separately: fused multi-tensor AdamW over the same gradients
         from lavt_hip.optim import FusedAdamW, lavt_param_groups
         opt = FusedAdamW(lavt_param_groups(model), lr=0.0, weight_decay=1e-2, total_steps=1000)      # lr 0: leaves the weights alone
@@ -542,14 +588,14 @@ def main():
                                      "gradient_bytes_per_step": step.buckets.bytes_per_step() // (2 if step.buckets.bf16 else 1),
                                      "buckets": len(step.buckets.buckets), "overlappable_bytes": step.buckets.overlappable_bytes() // (2 if step.buckets.bf16 else 1),
                                      "late_bucket_bytes": (step.buckets.bytes_per_step() - step.buckets.overlappable_bytes()) // (2 if step.buckets.bf16 else 1)}
-        if world > 1 or force:
+        if a.full and (world > 1 or force):
             # multi-rank runs: the per-family pass would issue eager collectives on one rank only; the dominant conv kernel is timed alone instead
             # (rank 0, after the timed region, the other ranks idle at the final barrier)
             try:
                 out["roofline"] = measure_conv_kernel(device) if a.dtype in ("bf16", "fp8") else {"skipped": "fp32 parity path"}
             except Exception as e:  # noqa: BLE001
                 out["roofline"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not force:
+        if a.full and world == 1 and not force:
             try:
                 conv = measure_conv_kernel(device) if a.dtype in ("bf16", "fp8") else None
                 if a.no_profile:

@@ -2,7 +2,7 @@
 # runtime knobs of the HIP runtime against the captured step (same box, back to back)
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
-run() { python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-profile 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['config']['loss_check']['ok'])"; }
+run() { python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-profile 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['config']['loss_check']['ok'])"; }
 echo "default: $(run)"
 echo "HIP_FORCE_DEV_KERNARG=1: $(HIP_FORCE_DEV_KERNARG=1 run)"
 echo "HIP_FORCE_DEV_KERNARG=0: $(HIP_FORCE_DEV_KERNARG=0 run)"
