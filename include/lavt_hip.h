@@ -319,6 +319,22 @@ int lavt_attn_dtable_finish_multi_compact(const int64_t* desc, int n, int max_R,
 /* floats of scratch (`ws`) lavt_window_attn_bwd wants for these shapes: dS slabs + per-workgroup table histograms (0 for the exact-fp32 kernel) */
 int64_t lavt_window_attn_bwd_ws(int dtype, int nwin, int N, int heads, int bias_ld, int wd, int wh, int ww);
 
+/* Streaming (online-softmax) bf16 kernels for windows too large for the fused ones (N > 400: Video-Swin --window12, 8x12x12 = 1152 tokens;
+ * WindowAttention3D.forward, lib/video_swin_transformer.py:137-168 with window_size (8, 12, 12), lib/segmentation.py:63).  Same arithmetic
+ * contract as lavt_window_attn_fwd / _bwd above (qkv, out, region, lse, table of the FULL window, top-left index block of a clipped window), without
+ * the dense bias: K and V stream through LDS, nothing of size nwin * heads * N^2 is formed.
+ * lavt_window_attn_stream_ok: 1 when the kernels cover the problem (bf16, head_dim 32, 16 <= N <= 2048, N <= wd*wh*ww, the table column fits the LDS budget).
+ * Backward: dqkv [nwin*N][3C] (every element written); dtable ACCUMULATES the table gradient.  No float atomics: bitwise reproducible.  ws: caller-lent
+ * scratch of lavt_window_attn_stream_bwd_ws floats = nwin*heads*N (delta = rowsum(dO o O)) + heads*N*ld (dense bias gradient summed over windows,
+ * ld = N rounded up to a multiple of 32; binned by lavt_relpos_reduce). */
+int lavt_window_attn_stream_ok(int dtype, int N, int wd, int wh, int ww, int heads, int head_dim);
+int lavt_window_attn_stream_fwd(int dtype, const void* qkv, const int8_t* region, int nw_img, void* out, float* lse, const float* table,
+                                int wd, int wh, int ww, int nwin, int N, int heads, int head_dim, float scale, void* stream);
+int64_t lavt_window_attn_stream_bwd_ws(int dtype, int nwin, int N, int heads, int wd, int wh, int ww);
+int lavt_window_attn_stream_bwd(int dtype, const void* qkv, const int8_t* region, int nw_img, const void* out, const void* dout, const float* lse,
+                                void* dqkv, const float* table, float* dtable, float* ws, int64_t ws_floats, int wd, int wh, int ww, int nwin, int N,
+                                int heads, int head_dim, float scale, void* stream);
+
 /* relative_position_bias_table[(2wd-1)(2wh-1)(2ww-1)][heads] -> dense bias[heads][N][ld]   (wd = 1 for the 2-D Swin; N <= wd*wh*ww tokens) (lib/backbone.py:89-103,125-127)
  * and its transpose (dense gradient -> table gradient, deterministic, accumulates into dtable). */
 int lavt_relpos_expand(const float* table, float* dense, int wd, int wh, int ww, int N, int heads, int ld, void* stream);

@@ -1529,6 +1529,45 @@ class _WindowAttnComposed(torch.autograd.Function):
 
 
 @K.scoped
+class _WindowAttnStream(torch.autograd.Function):
+    """bf16 windows beyond the fused kernels (N > 400: Video-Swin --window12, 8x12x12 = 1152 tokens) on the streaming kernels (csrc/attention_stream.hip):
+    K / V stream through LDS with an online softmax, backward recomputes P from lse -- only lse is saved, nothing of size nwin * heads * N^2 is formed.
+    The backward uses no float atomics (bitwise reproducible); its scratch (delta + the dense bias gradient) comes from the caching allocator."""
+
+    @staticmethod
+    def forward(ctx, qkv, table, region, win, heads, N):
+        qkv = qkv.contiguous()
+        wd, wh, ww = win
+        Cc = qkv.shape[1] // 3
+        nwin = qkv.shape[0] // N
+        out = torch.empty(nwin * N, Cc, dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty(nwin, heads, N, dtype=torch.float32, device=qkv.device)
+        nw_img = region.shape[0] if region is not None else 0
+        scale = float((Cc // heads) ** -0.5)
+        _note(f"wattn-stream {nwin * N}x{Cc} N{N}", 4.0 * nwin * heads * N * N * 32)
+        K.check(K.lib.lavt_window_attn_stream_fwd(K.dt(qkv.dtype), K.ptr(qkv), K.ptr(region), nw_img, K.ptr(out), K.ptr(lse), K.ptr(_f32(table)),
+                                                  wd, wh, ww, nwin, N, heads, Cc // heads, scale, K.stream()))
+        ctx.save_for_backward(qkv, out, lse, table, region)
+        ctx.dims = (win, heads, nwin, N, Cc, nw_img, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse, table, region = ctx.saved_tensors
+        win, heads, nwin, N, Cc, nw_img, scale = ctx.dims
+        wd, wh, ww = win
+        dout = dout.contiguous()
+        dqkv = torch.empty_like(qkv)
+        nws = int(K.lib.lavt_window_attn_stream_bwd_ws(K.dt(qkv.dtype), nwin, N, heads, wd, wh, ww))
+        ws = _scratch(nws, qkv.device)
+        dtable, ts = sinks.buf(table, ((2 * wd - 1) * (2 * wh - 1) * (2 * ww - 1), heads))
+        _note(f"wattn-stream-bwd {nwin * N}x{Cc} N{N}", 10.0 * nwin * heads * N * N * 32)
+        K.check(K.lib.lavt_window_attn_stream_bwd(K.dt(qkv.dtype), K.ptr(qkv), K.ptr(region), nw_img, K.ptr(out), K.ptr(dout), K.ptr(lse), K.ptr(dqkv),
+                                                  K.ptr(_f32(table)), K.ptr(dtable), K.ptr(ws), nws, wd, wh, ww, nwin, N, heads, Cc // heads, scale, K.stream()))
+        return dqkv, sinks.done(table, dtable, ts), None, None, None, None
+
+
+@K.scoped
 class _WmsaFused(torch.autograd.Function):
     """norm1 -> window partition / shift / pad -> qkv -> attention core of a Swin block as ONE forward kernel (csrc/wmsa_fused.hip; reference
     lib/backbone.py:201-217 + 113-140).  x [tokens, C] is the residual stream; returns (o [nwin * N, C] in window order -- the proj GEMM scatters it
@@ -1675,9 +1714,13 @@ def window_attention(qkv, table, region, win, heads, N=None):
     win = _win3(win)
     if N is None:
         N = win[0] * win[1] * win[2]
+    composed = os.environ.get("LAVT_ATTN_COMPOSED", "0") == "1"
     if N <= FUSED_ATTN_MAX_N or (qkv.dtype == torch.bfloat16 and N <= FUSED_ATTN_MAX_N_BF16 and K.lib.lavt_attn_uses_table(K.dt(qkv.dtype), N)
-                                 and os.environ.get("LAVT_ATTN_COMPOSED", "0") != "1"):
+                                 and not composed):
         return _WindowAttn.apply(qkv, table, region, win, heads, N)
+    if (qkv.dtype == torch.bfloat16 and N > FUSED_ATTN_MAX_N_BF16 and not composed
+            and K.lib.lavt_window_attn_stream_ok(K.dt(qkv.dtype), N, *win, heads, qkv.shape[1] // 3 // heads)):
+        return _WindowAttnStream.apply(qkv, table, region, win, heads, N)
     return _WindowAttnComposed.apply(qkv, table, region, win, heads, N)
 
 

@@ -8,8 +8,10 @@ kernel launched through lavt_hip.ops.
 Data layout: tokens stay [B*D*H*W, C] (NDHWC) through the whole backbone.  The 3-D pad -> roll -> window_partition ...
 window_reverse -> roll -> crop sequence (:230-262) is a row map on the qkv / proj GEMMs; the dense 0/-100 mask of
 compute_mask (:315-328) is an int8 region table; Conv3d of SepTPWAM is an implicit GEMM over NDHWC rows with a
-kd x kh x kw tap gather.  Windows of up to 160 tokens run in the fused attention kernels, larger ones (8x7x7 = 392,
-8x12x12 = 1152) through the composed GEMM -> softmax -> GEMM path.
+kd x kh x kw tap gather.  Windows of up to 160 tokens run in the fused attention kernels in both dtypes; in bf16 the fused
+MFMA kernels take windows up to 400 tokens (8x7x7 = 392) and the streaming online-softmax kernels (csrc/attention_stream.hip)
+the larger ones (`--window12`: 8x12x12 = 1152 tokens, clipped windows of more than 400); the exact-fp32 path above 160 tokens
+runs the composed GEMM -> softmax -> GEMM path.
 
 In scope: the default per-stage PWAM and the README training recipe
 `--sep_t_pwam --conv3d_kernel_size_t 3-3-3 --conv3d_kernel_size_s 1-1-1 --w_t3x3_s1x1 --mm_t3x3_s1x1` (SepTPWAM).
