@@ -600,6 +600,30 @@ int lavt_adamw_step(const int64_t* desc, const float* hyper, int count, float* s
  * [chunk * lavt_adamw_chunk_elems(), ...) of its tensor, so every workgroup has work.  hyper, step, schedule as above. */
 int lavt_adamw_chunk_elems(void);
 int lavt_adamw_step_chunks(const int64_t* desc, const float* hyper, const int32_t* chunks, int nchunks, float* step, float total_steps, float power, void* stream);
+/* The guard around the optimizer step (csrc/optim_guard.hip): every decision is taken on the device, so the sequence can be captured into a
+ * hipGraph.  All three entry points were added under ABI v7 (new symbols only: no existing prototype or struct changed).
+ *
+ * Control block `ctl`: device fp32[8], zero-initialised by the caller except ctl[1] = 1.
+ *   [0] global L2 norm of the gradients        [1] clip coefficient the update multiplies every gradient by
+ *   [2] skip: 1 = this update must not happen  [3] running count of skipped updates (incremented by the guarded update's tick)
+ *   [4] hold: written by the HOST only; non-zero = the update does nothing and nothing is counted      [5..7] reserved, zero
+ *
+ * lavt_grad_norm: global L2 norm over the gradients listed by the desc / chunks tables of the chunked update above (so it covers exactly the
+ * tensors the update touches), in two launches without atomics: one workgroup per chunk writes an fp32 sum of squares to ws[chunk], one
+ * workgroup adds the partials in fp64 in a fixed order -- the result is bitwise reproducible from run to run.  It then writes
+ *   ctl[0] = norm;  ctl[1] = min(1, max_norm / (norm + 1e-6)) if max_norm > 0 and the norm is finite, else 1 (torch.nn.utils.clip_grad_norm_);
+ *   ctl[2] = 1 if skip_nonfinite != 0 and the norm is NaN or Inf, else 0 (rewritten by every call).
+ * A chunk's fp32 sum of squares that overflows for finite gradients (|g| ~ 1e19 and beyond) makes the norm Inf: that counts as non-finite.
+ * ws: device scratch of lavt_grad_norm_ws floats; the formula is part of the interface:  ws floats = nchunks  (one partial per chunk).
+ *
+ * lavt_adamw_step_chunks_guarded: the chunked update with every gradient multiplied by ctl[1]; if ctl[2] != 0 or ctl[4] != 0 every workgroup
+ * returns before its first store (parameters, both moments and the bf16 `copy` column stay untouched) and the step counter does not advance;
+ * ctl[3] += ctl[2] unless on hold (hence the non-const pointer).  With ctl[1] = 1, ctl[2] = ctl[4] = 0 the result equals the unguarded
+ * update's bit for bit (one shared update body). */
+int64_t lavt_grad_norm_ws(int nchunks);
+int lavt_grad_norm(const int64_t* desc, const int32_t* chunks, int nchunks, float* ws, float* ctl, float max_norm, int skip_nonfinite, void* stream);
+int lavt_adamw_step_chunks_guarded(const int64_t* desc, const float* hyper, const int32_t* chunks, int nchunks, float* step, float total_steps, float power,
+                                   float* ctl, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Text side (lavt_one / lavt_video carry BERT inside the model: lib/_utils.py:38-52; train.py:595-602; the encoder is HF transformers

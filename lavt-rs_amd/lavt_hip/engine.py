@@ -15,6 +15,9 @@ replay issues forward, backward and the overlapped RCCL all-reduces without any 
 capture (its collectives become graph kernel nodes); `tools/nccl_graph_probe.py` and tests/test_gpu_modules.py exercise the
 mechanics on one GPU in a 1-rank group.  LAVT_DDP_GRAPH=0 (or a failed capture) falls back to eager launching, where the
 step is bound by the ~23 ms of host-side launch work.
+
+The optimizer is the caller's by default (opt.step() after TrainStep.step()).  TrainStep.make_optimizer() / attach_optimizer() make the step OWN a
+FusedAdamW on the step's context: its update then ends the step's body, inside the same capture, and one replay is one whole training iteration.
 """
 import os
 import sys
@@ -76,6 +79,38 @@ class TrainStep:
         self._params = [p for p in model.parameters()]
         self._seen = None
         self._one = None
+        self.opt = None                          # the owned optimizer (make_optimizer / attach_optimizer): its step ends _body
+        self._warmed = False
+
+    # ---- owned optimizer ----
+    def make_optimizer(self, param_groups=None, **adamw_kwargs):
+        """Build a FusedAdamW on THIS step's context, attach it and return it.  param_groups=None: lavt_param_groups(model) when the model has a
+        `backbone` and a `classifier` (the reference's groups), else all its parameters.  adamw_kwargs go to FusedAdamW (lr, weight_decay,
+        total_steps, power, max_grad_norm, skip_nonfinite, ...).  Before warmup_and_capture() only."""
+        from .optim import FusedAdamW, lavt_param_groups
+        self._check_attach_window()
+        if "context" in adamw_kwargs:
+            raise TypeError("TrainStep.make_optimizer: the optimizer is built on the step's own context")
+        if param_groups is None:
+            param_groups = (lavt_param_groups(self.model) if hasattr(self.model, "backbone") and hasattr(self.model, "classifier")
+                            else [p for p in self.model.parameters() if p.requires_grad])
+        return self.attach_optimizer(FusedAdamW(param_groups, context=self.context, **adamw_kwargs))
+
+    def attach_optimizer(self, opt):
+        """Make an existing FusedAdamW part of the step (see make_optimizer).  It must maintain THIS step's context."""
+        self._check_attach_window()
+        if opt.context is not self.context:
+            raise ValueError("TrainStep.attach_optimizer: the optimizer maintains the compute copies of another ops.StepContext than this step's: every "
+                             "replay would read bf16 / packed weight copies that are never refreshed (training on frozen weights, silently).  "
+                             "Construct it with FusedAdamW(..., context=step.context), or use step.make_optimizer()")
+        self.opt = opt
+        return opt
+
+    def _check_attach_window(self):
+        if self._warmed:
+            raise RuntimeError("TrainStep: the optimizer must be attached before warmup_and_capture() (the captured launch sequence is frozen)")
+        if self.opt is not None:
+            raise RuntimeError("TrainStep: an optimizer is already attached")
 
     def _param_stamp(self):
         return sum(p._version for p in self._params), sum(p.data_ptr() for p in self._params)
@@ -104,14 +139,32 @@ class TrainStep:
         self.buckets.finish()                    # stragglers (never-used parameters) + join of the communication stream
         ops.zero_arena.end_step()
         ops.fp8.end_step()
+        if self.opt is not None:
+            # after buckets.finish(): with world > 1 the gradients are all-reduced already, the update needs no collective of its own.  Eager: the host-side
+            # scan (re)builds the descriptor tables; inside the capture they are final (step(check_tables=False) raises if they are not).
+            self.opt.step(check_tables=not torch.cuda.is_current_stream_capturing())
         return loss.detach()
 
-    @_in_context
     def warmup_and_capture(self, eager_iters=3):
-        """Side effects beyond `eager_iters` steps: one more eager step when the bucket layout is still to settle (eager_iters = 1), and the zero-fill-skip validation below replays the captured step up to three more times on
+        """With an owned optimizer (make_optimizer / attach_optimizer) the optimizer is on hold (FusedAdamW.hold) for every eager iteration and validation
+        replay below, and released at the end: parameters, both moments, the optimizer's step and skipped-step counters and the compute copies are
+        bit for bit what they were on entry (the copies are re-cast from the unchanged parameters).  The NaN-poison validation is unaffected: the
+        update reads gradients and never writes them.
+        Side effects beyond `eager_iters` steps: one more eager step when the bucket layout is still to settle (eager_iters = 1), and the zero-fill-skip validation below replays the captured step up to three more times on
         NaN-poisoned gradient buffers.  Each of those replays is a real training step of the forward pass -- BatchNorm running statistics and
         `num_batches_tracked`, the fp8 |max| history and the DropPath generator advance, and with world > 1 the poisoned buckets are all-reduced
         (NaN on every rank alike) -- the gradients of such a replay are discarded by the next step's fill.  LAVT_ZERO_SKIP=0 captures once."""
+        self._warmed = True
+        if self.opt is None:
+            return self._warmup_and_capture(eager_iters)
+        self.opt.hold(True)
+        try:
+            return self._warmup_and_capture(eager_iters)
+        finally:
+            self.opt.hold(False)
+
+    @_in_context
+    def _warmup_and_capture(self, eager_iters):
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):

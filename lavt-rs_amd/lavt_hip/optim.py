@@ -7,7 +7,12 @@
 `torch.optim.Optimizer`-shaped (param_groups, state_dict / load_state_dict in torch.optim.AdamW's layout) so that the reference's
 checkpoint code (train.py:749-763) keeps working.  The step counter and the schedule live on the device: the optimizer step can be
 captured into the same hipGraph as forward/backward and still follows (1 - it/T)^0.9 on every replay (a LambdaLR on the host would be
-frozen at capture time).  amsgrad (off by default in the reference) is not implemented.
+frozen at capture time): engine.TrainStep.make_optimizer() does exactly that.  amsgrad (off by default in the reference) is not implemented.
+
+The guard (opt-in: max_grad_norm > 0, skip_nonfinite=True, or hold()): a device fp32[8] control block `opt.guard` = [global gradient norm, clip
+coefficient, skip flag, skipped-step count, hold flag, 0, 0, 0].  lavt_grad_norm fills the first three from the gradients the update is about to
+read, the guarded update multiplies every gradient by the coefficient and does nothing at all (no store, no tick of the step counter) when skip
+or hold is set -- no device-to-host synchronisation and no data-dependent launch, so it survives graph capture.
 """
 import os
 from typing import Iterable
@@ -40,8 +45,12 @@ def ops_generation():
 
 
 class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params: Iterable, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, total_steps=0, power=0.9, context=None):
-        """context: the ops.StepContext whose compute-dtype weight copies this optimizer maintains (None = the process-wide default; pass the one given to
+    def __init__(self, params: Iterable, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, total_steps=0, power=0.9, context=None,
+                 max_grad_norm=0.0, skip_nonfinite=False):
+        """max_grad_norm > 0: clip by the global L2 norm (torch.nn.utils.clip_grad_norm_'s coefficient); skip_nonfinite: leave parameters, moments, compute
+        copies and the step counter untouched when that norm is NaN / Inf (counted in skipped_steps()).  With both off and hold() never called, step()
+        is the unguarded launch sequence: no control block, no extra launch.
+        context: the ops.StepContext whose compute-dtype weight copies this optimizer maintains (None = the process-wide default; pass the one given to
         engine.TrainStep when the model runs in a private context)"""
         from . import ops
         self.context = context if context is not None else ops.default_context()
@@ -53,6 +62,46 @@ class FusedAdamW(torch.optim.Optimizer):
         self._tables = None
         self._probe = []
         self._step = None
+        self.max_grad_norm, self.skip_nonfinite = float(max_grad_norm), bool(skip_nonfinite)
+        self.guard = None          # the device control block (see the module docstring); None = the unguarded path
+        self._norm_ws = None       # lavt_grad_norm's per-chunk partial sums
+        if self._wants_norm():
+            self._make_guard()
+
+    # ---- the guard ----
+    def _wants_norm(self):
+        return self.max_grad_norm > 0.0 or self.skip_nonfinite
+
+    def _device(self):
+        return next(p for g in self.param_groups for p in g["params"]).device
+
+    def _make_guard(self):
+        if self.guard is None:
+            dev = self._device()
+            if dev.type != "cuda":
+                raise RuntimeError("FusedAdamW runs on GPU memory only (no CPU fallback)")
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FusedAdamW: the control block cannot be created inside a graph capture (construct with the guard options, or call hold() first)")
+            self.guard = torch.tensor([0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float32).to(dev)
+        return self.guard
+
+    def hold(self, flag=True):
+        """While held, step() changes nothing -- parameters, moments, compute copies, step counter, skipped-step count -- whatever the gradients hold
+        (TrainStep uses it for its warm-up iterations and validation replays).  A host write of guard[4]: call it outside any capture; it waits for the
+        device on both sides, so it is ordered against work on every stream."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdamW.hold() is a host write: call it outside the graph capture")
+        g = self._make_guard()
+        torch.cuda.synchronize(g.device)
+        g[4:5].fill_(1.0 if flag else 0.0)
+        torch.cuda.synchronize(g.device)
+
+    def last_grad_norm(self):
+        """global gradient norm of the last guarded step (synchronises); None when no norm is computed"""
+        return float(self.guard[0].item()) if self.guard is not None and self._wants_norm() else None
+
+    def skipped_steps(self) -> int:
+        return int(self.guard[3].item()) if self.guard is not None else 0
 
     # ---- flat optimizer state + device descriptor tables (built lazily: gradients must exist / be re-pointed first) ----
     def _build(self):
@@ -101,6 +150,10 @@ class FusedAdamW(torch.optim.Optimizer):
         self._probe = [(p, p.grad.data_ptr()) for _, p in ps if p.grad is not None]
         self._tables = (key, torch.tensor(desc, dtype=torch.int64).to(dev), torch.tensor(hyper, dtype=torch.float32).to(dev), len(desc),
                         torch.tensor(chunks, dtype=torch.int32).to(dev), len(chunks), dict(fused))
+        if self._wants_norm():
+            need = int(K.lib.lavt_grad_norm_ws(len(chunks)))
+            if self._norm_ws is None or self._norm_ws.numel() < need:
+                self._norm_ws = torch.empty(need, dtype=torch.float32, device=dev)
 
     def _current_key(self):
         out = []
@@ -132,11 +185,18 @@ class FusedAdamW(torch.optim.Optimizer):
             # read at its OLD offsets)
             raise RuntimeError("FusedAdamW.step(check_tables=False): a compute copy was re-allocated or the flat gradient buffer was laid out again "
                                "after the descriptor table was built; call step() once with check_tables=True (outside a capture) first")
-        K.check(K.lib.lavt_adamw_step_chunks(K.ptr(desc), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(self._step), self.total_steps, self.power, K.stream()))
+        if self.guard is None:
+            K.check(K.lib.lavt_adamw_step_chunks(K.ptr(desc), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(self._step), self.total_steps, self.power, K.stream()))
+        else:
+            if self._wants_norm():
+                K.check(K.lib.lavt_grad_norm(K.ptr(desc), K.ptr(chunks), nchunks, K.ptr(self._norm_ws), K.ptr(self.guard), self.max_grad_norm, int(self.skip_nonfinite), K.stream()))
+            K.check(K.lib.lavt_adamw_step_chunks_guarded(K.ptr(desc), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(self._step), self.total_steps, self.power,
+                                                         K.ptr(self.guard), K.stream()))
         # The kernel writes the parameters through raw pointers: p._version does not move, so the cached compute copies (bf16 Linear weights,
         # packed conv weights) are stale now.  They are part of the optimizer's output (fp32 master weights + the compute-dtype copies the next
         # forward reads, as in any mixed-precision trainer): re-cast them here, on the same stream, so that the forward/backward step itself
         # carries no cast kernels (the step harness refreshes them only when asked to: TrainStep(refresh_weights_in_step=True)).
+        # (after a skipped or held step the same casts run on unchanged weights: harmless, and the launch sequence stays fixed for a capture)
         from . import ops
         ops.weights.refresh_all(done=fused)          # the copies in `fused` were written by the update kernel: only their stamps move
         return loss
@@ -151,6 +211,8 @@ class FusedAdamW(torch.optim.Optimizer):
     def state_dict(self):
         sd = super().state_dict()
         sd["lavt_schedule"] = {"total_steps": self.total_steps, "power": self.power, "steps_taken": self.steps_taken()}
+        if self.guard is not None:
+            sd["lavt_schedule"]["skipped_steps"] = self.skipped_steps()
         return sd
 
     def load_state_dict(self, state_dict):
@@ -168,4 +230,6 @@ class FusedAdamW(torch.optim.Optimizer):
         self._step = torch.full((1,), float(steps or 0), dtype=torch.float32, device=dev)
         for st in self.state.values():
             st["step"] = self._step
+        if sched is not None and "skipped_steps" in sched and (self.guard is not None or sched["skipped_steps"]):
+            self._make_guard()[3:4].fill_(float(sched["skipped_steps"]))
         self._tables = None
