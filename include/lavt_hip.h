@@ -4,10 +4,10 @@
  * Every entry point is `extern "C"`, takes raw DEVICE pointers + sizes + a hipStream_t (as void*),
  * allocates nothing, launches asynchronously on the given stream and returns 0 or a negative LAVT_ERR_*
  * code.  No torch types anywhere.  Global state: the (thread-local) last-error string and one table of
- * tuning switches -- the LAVT_* environment variables listed in lavt-rs_amd/csrc/tuning.hip, which choose
- * between equivalent kernel configurations (tile sizes, ring depths, A/B forms).  They are read once, at
- * the first launch; lavt_tuning_reload() re-reads them.  No launch path calls getenv, and no switch makes
- * a kernel skip work.
+ * dispatch switches -- the LAVT_* environment variables listed in lavt-rs_amd/csrc/tuning.hip (and in
+ * INTEGRATION.md), which force one of several equivalent kernel configurations (tile sizes, ring depths)
+ * for the test-suite.  They are read once, at the first launch; lavt_tuning_reload() re-reads them.  No
+ * launch path calls getenv, and no switch makes a kernel skip work.
  *
  * The reference (Yxxxb/LAVT-RS) is pure PyTorch and has no native layer; each group of functions
  * below names the reference code (file:line under the reference root) whose arithmetic it replaces.
@@ -107,7 +107,7 @@ typedef struct lavt_gemm_nt {
     const int32_t* c_rowmap;
     int32_t c_f32;
     const void* zeros; /* optional: >= 16 bytes of zeros in device memory; enables the LDS-DMA pipeline kernel (bf16) */
-    int32_t epi_lds;   /* set by the library (LAVT_GEMM_EPI=lds): stage the C tile through LDS for full-row stores */
+    int32_t epi_lds;   /* reserved: always 0 */
     /* 3-D generalisation of the implicit-GEMM convolution (Conv3d of SepTPWAM, lib/video_swin_transformer.py:1327-1460): rows are voxels of a
      * (batch, conv_d, conv_h, conv_w) grid and the taps run over conv_kd x conv_kh x conv_kw (each 1 or 3, 'same' zero padding), kw fastest.
      * All zero = the 2-D default (conv_d = 1, taps 1 x 3 x 3). */

@@ -396,9 +396,8 @@ int lavt_attn_dtable_run_mfma(const lavt_dtable_job_t* jb, hipStream_t st);
 int lavt_attn_dtable_finish_multi_impl(const int64_t* desc, int n, int max_R, int max_heads, int total_heads, hipStream_t st);
 int lavt_window_attn_bwd_pieces_mfma(int nwin, int N, int heads);
 int64_t lavt_window_attn_bwd_ws_mfma(int nwin, int N, int heads, int bias_ld, int wd, int wh, int ww);
-// LAVT_ATTN_SIMPLE=1 forces the VALU formulation for bf16 too (A/B tests of the MFMA kernels)
 static bool use_mfma(int dtype, int N, int bias_ld) {
-    return dtype == LAVT_BF16 && N <= 400 && bias_ld >= (N <= 64 ? 64 : N <= 160 ? 160 : 416) && !lavt_tuning().attn_simple;
+    return dtype == LAVT_BF16 && N <= 400 && bias_ld >= (N <= 64 ? 64 : N <= 160 ? 160 : 416);
 }
 
 extern "C" int lavt_window_attn_fwd(int dtype, const void* qkv, const float* bias, int bias_ld, const int8_t* region, int nw_img, void* out,

@@ -655,16 +655,14 @@ int lavt_window_attn_bwd_mfma(const void* qkv, const float* table, const int8_t*
     const int R = (2 * wd - 1) * (2 * wh - 1) * (2 * ww - 1);
     // >= 2 workgroups per CU when there is that much work
     // (round 6: one window per workgroup up to 2048 units -- 800 units as 400 two-window workgroups took 39.7 us against 36.7 as 800 + pieces, 1152 units 56.5
-    // against 49.8: more workgroups than resident slots cost less than a second window behind the first.  LAVT_ATTN_WPB_UNITS = 768 restores the round-5 rule.)
-    static const long wpb_units = getenv("LAVT_ATTN_WPB_UNITS") ? atol(getenv("LAVT_ATTN_WPB_UNITS")) : 2048;
+    // against 49.8: more workgroups than resident slots cost less than a second window behind the first; the round-5 rule was 768.)
+    constexpr long wpb_units = 2048;
     int wpb = (int)(((long)nwin * heads + wpb_units - 1) / wpb_units);
     if (wpb < 1) wpb = 1;
     const int chunks = cdiv(nwin, wpb);
-    const int force_waves = lavt_tuning().attn_bwd_waves;
-    const int waves = force_waves ? force_waves : 8;
     // riders only on the 8-wave variants that sit two per CU (N <= 160): a rider occupies a whole workgroup slot, and the 392-token video kernel (149 KB of
     // LDS, one workgroup per CU) would run them as an extra round
-    const bool eight = !(N <= 64) && !(N <= 144 && waves != 8) && (N <= 160 || lavt_tuning().probe[3] != 0);
+    const bool eight = N > 64 && N <= 160;
     DtableJob job{};
     int riders = 0;
     if (prev != nullptr) {
@@ -682,7 +680,7 @@ int lavt_window_attn_bwd_mfma(const void* qkv, const float* table, const int8_t*
     // 21.0 unsplit, 480 units 28.5 against 23.1; 288 -> 16.4-16.7 against 20.3-20.7, 384 -> 19.7 against 20.9, 576 -> 29.6 against 30.3.)
     const int units = chunks * heads, extra = units % 256;
     int split_from = units, split_pieces = 1;
-    if (wpb == 1 && units > 256 && extra > 0 && extra <= 128 && !lavt_tuning().attn_bwd_split_off) {
+    if (wpb == 1 && units > 256 && extra > 0 && extra <= 128) {
         split_pieces = 256 / extra < 8 ? 256 / extra : 8;
         split_from = units - extra;
     }
@@ -710,9 +708,9 @@ int lavt_window_attn_bwd_mfma(const void* qkv, const float* table, const int8_t*
         else LAVT_BWD_K(NT_, WV_, false);                                                                                                    \
     } while (0)
     // 8 waves share one window-head, capped at 128 VGPRs so two workgroups (16 waves) sit on a CU: 5-9% faster than 4 waves x 2 at every
-    // stage shape of Swin-B w12 @480 (measured, tools/attn_bench2.py).  LAVT_ATTN_BWD_WAVES=4 keeps the 4-wave variant reachable.
+    // stage shape of Swin-B w12 @480 (measured, tools/attn_bench2.py).
     if (N <= 64) LAVT_BWD(4, 4);
-    else if (N <= 144) { if (waves == 8) LAVT_BWD(9, 8); else LAVT_BWD(9, 4); }
+    else if (N <= 144) LAVT_BWD(9, 8);
     else if (N <= 160) LAVT_BWD(10, 8);
     else LAVT_BWD(25, 8);                  // Video-Swin 8x7x7 windows: 149 KB of LDS, one workgroup per CU
 #undef LAVT_BWD

@@ -39,7 +39,7 @@ struct CwArgs {
     int c1;                                        // channels of x1 (Cin - c1 come from x2)
     int B, H, W, Cout, Cin;
     float* parts;                                  // [pieces][tiles][8 waves][4 fragment rows][9 taps][64 lanes] float4 = pieces x Cout x 9 x Cin floats
-    int pieces, rows_per_piece, xcd_order;
+    int pieces, rows_per_piece;
     const void* zeros;
 };
 
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(CW_THREADS) void conv_wgrad3x3_kernel(const CwArgs 
     // Workgroups go round-robin over the 8 XCDs (private L2 each); with gridDim.x a multiple of 8 a tile keeps its XCD in every piece.  Give an XCD a
     // contiguous run of tiles (tile_j fastest): its workgroups of one piece then share the dY panel of (mostly) one tile_i -- measured before: every
     // dY panel crossed the fabric once per tile_j (8 x 29.5 MB of the 343 MB per launch).
-    const int tile_lin = ((gridDim.x & 7) == 0 && a.xcd_order) ? xcd_tile_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int tile_lin = ((gridDim.x & 7) == 0) ? xcd_tile_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     const int tile_i = tile_lin / tiles_j, tile_j = tile_lin - tile_i * tiles_j;
     const int i0 = tile_i * CW_BI, j0 = tile_j * CW_BJ;
     const int W = a.W, H = a.H, rows = a.B * a.H;
@@ -310,7 +310,7 @@ struct Cw8Args {
     int c1;
     int B, H, W, Cout, Cin;
     float* parts;
-    int pieces, rows_per_piece, xcd_order;
+    int pieces, rows_per_piece;
     const void* zeros;
 };
 
@@ -344,7 +344,7 @@ __global__ __launch_bounds__(CW_THREADS) void conv_wgrad3x3_f8_kernel(const Cw8A
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wi = wave >> 2, wj = wave & 3;
     const int tiles_j = (a.Cin + CW_BJ - 1) / CW_BJ;
-    const int tile_lin = ((gridDim.x & 7) == 0 && a.xcd_order) ? xcd_tile_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int tile_lin = ((gridDim.x & 7) == 0) ? xcd_tile_id(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     const int tile_i = tile_lin / tiles_j, tile_j = tile_lin - tile_i * tiles_j;
     const int i0 = tile_i * CW_BI, j0 = tile_j * CW_BJ;
     const int W = a.W, H = a.H, rows = a.B * a.H;
@@ -487,7 +487,6 @@ extern "C" int lavt_conv3x3_wgrad(const void* dy, int64_t ldy, const void* x1, i
     a.dy = (const bf16*)dy; a.ldy = ldy; a.x1 = (const bf16*)x1; a.ldx1 = ldx1; a.x2 = (const bf16*)x2; a.ldx2 = ldx2; a.c1 = c1;
     a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.Cin = Cin; a.parts = parts; a.pieces = pieces; a.zeros = zeros;
     a.rows_per_piece = rpp;
-    a.xcd_order = lavt_tuning().probe[1] ? 0 : 1;
     const int tiles_j = (Cin + CW_BJ - 1) / CW_BJ;
     const dim3 grid((Cout / CW_BI) * tiles_j, pieces);
 #define CW_LAUNCH(KS_)                                                                                                                          \
@@ -533,7 +532,6 @@ extern "C" int lavt_conv3x3_wgrad_f8(const void* dy, int64_t ldy, const float* a
     a.dy = (const unsigned char*)dy; a.ldy = ldy; a.x1 = (const unsigned char*)x1; a.ldx1 = ldx1; a.x2 = (const unsigned char*)x2; a.ldx2 = ldx2; a.c1 = c1;
     a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.Cin = Cin; a.parts = parts; a.pieces = pieces; a.zeros = zeros;
     a.rows_per_piece = rpp;
-    a.xcd_order = lavt_tuning().probe[1] ? 0 : 1;
     const int tiles_j = (Cin + CW_BJ - 1) / CW_BJ;
     const dim3 grid((Cout / CW_BI) * tiles_j, pieces);
 #define CW8_LAUNCH(RPK_)                                                                                                                        \

@@ -823,7 +823,7 @@ extern "C" int lavt_bilinear_fwd(int dtype, const void* x, void* y, int B, int H
     LAVT_CHECK_ARG(x && y && B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C % EPC_OF(dtype) == 0, "lavt_bilinear_fwd: bad arguments");
     LAVT_CHECK_ARG((int64_t)B * Ho * Wo * (C / EPC_OF(dtype)) < (1LL << 31) - (1LL << 21), "lavt_bilinear_fwd: more than 2^31 output chunks");
     const int64_t nc = (int64_t)B * Ho * Wo * (C / EPC_OF(dtype));
-    if (dtype == LAVT_BF16 && lavt_tuning().probe[7] != 1) {          // row-staged form (LDS-DMA): every decoder shape
+    if (dtype == LAVT_BF16 && lavt_tuning().bilinear_rows) {          // row-staged form (LDS-DMA): every decoder shape
         const int cblk = bl_rows_cblk(B, Hi, Wi, C);
         if (cblk) {
             hipLaunchKernelGGL((bilinear_rows_fwd_kernel<false>), dim3(Hi, B, C / cblk), dim3(256), bl_rows_lds(Wi, cblk), ST, (const bf16*)x, (bf16*)y, Hi, Wi, Ho, Wo, C, cblk,
@@ -841,7 +841,7 @@ extern "C" int lavt_bilinear_fwd_q8(const void* x, void* y, void* q, const float
     LAVT_CHECK_ARG(x && y && q && amax_cur && B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C % 8 == 0, "lavt_bilinear_fwd_q8: bad arguments");
     const int64_t nc = (int64_t)B * Ho * Wo * (C / 8);
     LAVT_CHECK_ARG(nc < (1LL << 31) - (1LL << 21), "lavt_bilinear_fwd_q8: more than 2^31 output chunks");
-    if (lavt_tuning().probe[7] != 1) {
+    if (lavt_tuning().bilinear_rows) {
         const int cblk = bl_rows_cblk(B, Hi, Wi, C);
         if (cblk && (long)Hi * B * (C / cblk) <= 1024) {          // (one same-address |max| atomic per workgroup: keep them few)
             hipLaunchKernelGGL((bilinear_rows_fwd_kernel<true>), dim3(Hi, B, C / cblk), dim3(256), bl_rows_lds(Wi, cblk), ST, (const bf16*)x, (bf16*)y, Hi, Wi, Ho, Wo, C, cblk,
@@ -898,7 +898,7 @@ extern "C" int lavt_upsample_ce_bwd(int dtype, const void* x, const int64_t* tar
     const int64_t n = (int64_t)B * Hi * Wi;
     // tiled form: the full-resolution region of a TL x TL tile must fit LDS (bl_range: (TL + 1) / scale + 5 rows / columns)
     const float sh = bl_scale(Hi, Ho), sw = bl_scale(Wi, Wo);
-    if (sh > 0.f && sw > 0.f && !lavt_tuning().upce_tile_off) {
+    if (sh > 0.f && sw > 0.f) {
         const long ny = (long)((UPCE_TL + 1) / sh) + 6, nx = (long)((UPCE_TL + 1) / sw) + 6;
         const long tiles = (long)B * cdiv(Hi, UPCE_TL) * cdiv(Wi, UPCE_TL);
         if (ny * nx * 8 <= 48 * 1024 && tiles < (1L << 30)) {
@@ -1001,8 +1001,7 @@ extern "C" int lavt_pack_conv3x3(const float* w, int dtype, void* packed, int Co
 extern "C" int lavt_unpack_conv_grad(const float* packed, float* dw, int Cout, int Cin, int taps, void* stream) {
     LAVT_CHECK_ARG(packed && dw && Cout > 0 && Cin > 0 && taps > 0, "lavt_unpack_conv_grad: bad arguments");
     const int64_t n = (int64_t)Cout * Cin * taps;
-    const bool tiled = lavt_tuning().unpack_tiled;
-    if (tiled && taps <= 32 && Cout <= 65535) hipLaunchKernelGGL(unpack_conv_grad_tiled_kernel, dim3((Cin + 127) / 128, Cout), dim3(256), (size_t)taps * 129 * 4, ST, packed, dw, Cin, taps);
+    if (taps <= 32 && Cout <= 65535) hipLaunchKernelGGL(unpack_conv_grad_tiled_kernel, dim3((Cin + 127) / 128, Cout), dim3(256), (size_t)taps * 129 * 4, ST, packed, dw, Cin, taps);
     else hipLaunchKernelGGL(unpack_conv_grad_kernel, dim3(ew_grid(n)), dim3(256), 0, ST, packed, dw, Cout, Cin, taps);
     LAVT_CHECK_LAUNCH("lavt_unpack_conv_grad");
     return LAVT_OK;

@@ -176,12 +176,6 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const lavt_gemm_nt_t p) {
         __syncthreads();
     }
 
-    if constexpr (std::is_same<T, bf16>::value) {
-        if (p.epi_lds && !(p.mul || p.c_f32 || (p.ldc % 8) || (p.C2 && (p.ldc2 % 8 || p.c_split % 8)) || (p.R && p.ldr % 8) || (p.Cpre && p.ldcpre % 8))) {
-            nt_epilogue_lds<BM, BN, MI, NI>(p, acc, reinterpret_cast<bf16*>(smem), m0, n0, wm * WM, wn * WN, tid, lane, bz);
-            return;
-        }
-    }
     nt_epilogue<T, MI, NI>(p, acc, m0 + wm * WM, n0 + wn * WN, lane, bz);
 }
 
@@ -380,8 +374,7 @@ template <typename T, int BI, int BJ> int launch_tn(const lavt_gemm_tn_t& p, hip
     const int ktiles = cdiv(p.K, BK);
     int split = p.split_k;
     if (split <= 0) {
-        split = lavt_tuning().tn_split;
-        if (split <= 0) split = (int)(768 / ((long)tiles * p.batch));
+        split = (int)(768 / ((long)tiles * p.batch));
         if (split < 1) split = 1;
         const int max_split = (ktiles + 3) / 4;        // at least 4 K tiles per workgroup
         if (split > max_split) split = max_split;
@@ -449,13 +442,13 @@ extern "C" int lavt_gemm_nt(const lavt_gemm_nt_t* pp, void* stream) {
                    "lavt_gemm_nt: LAVT_ACT_GELU_D exists in the LayerNorm-folded launch only (ln_wsum), needs Cpre and takes no multiplier / split / residual / row scale / row map");
     LAVT_CHECK_ARG(!p.res_first || (p.dact_pre && p.R), "lavt_gemm_nt: res_first orders the residual before the fused activation gradient (needs dact_pre and R)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    { p.epi_lds = lavt_tuning().gemm_epi_lds ? 1 : 0;
-      const bool wide_off = lavt_tuning().gemm_epi_narrow;          // LAVT_GEMM_EPI=narrow: the 8-byte store form
-      p.epi_wide = (!wide_off && p.dtype != LAVT_F32 && !p.c_f32 && p.ldc % 8 == 0 && (!p.C2 || (p.ldc2 % 8 == 0 && p.c_split % 8 == 0)) && (!p.R || p.ldr % 4 == 0) &&
+    { p.epi_lds = 0;          // (reserved)
+      // the 16-byte store form where every alignment holds; else the narrow 8-byte stores
+      p.epi_wide = (p.dtype != LAVT_F32 && !p.c_f32 && p.ldc % 8 == 0 && (!p.C2 || (p.ldc2 % 8 == 0 && p.c_split % 8 == 0)) && (!p.R || p.ldr % 4 == 0) &&
                     (!p.Cpre || p.ldcpre % 8 == 0) && (!p.dact_pre || p.lddact % 4 == 0) && (!p.bias || (p.strideBias % 4 == 0 && ((uintptr_t)p.bias % 16) == 0)) &&
                     ((uintptr_t)p.C % 16) == 0 && (!p.C2 || ((uintptr_t)p.C2 % 16) == 0) && (!p.Cpre || ((uintptr_t)p.Cpre % 16) == 0) && (p.strideC % 8 == 0)) ? 1 : 0;
-      // bit 1: the epilogue's side inputs are requested before the K loop (gemm_common.h NtSide; LAVT_SIDE_PRE=0: at the head of the epilogue, the round-2 form)
-      if (p.epi_wide && !lavt_tuning().side_pre_off && p.batch == 1) p.epi_wide |= 2; }
+      // bit 1: the epilogue's side inputs are requested before the K loop (gemm_common.h NtSide)
+      if (p.epi_wide && p.batch == 1) p.epi_wide |= 2; }
     if (p.colstats) {
         int rpb = 0;
         LAVT_CHECK_ARG(lavt_gemm_nt_colstats_plan(&p, &rpb) > 0, "lavt_gemm_nt: colstats only where lavt_gemm_nt_colstats_plan accepts the problem (pipelined bf16 tiles, plain epilogue)");
@@ -493,16 +486,14 @@ extern "C" int lavt_gemm_tn(const lavt_gemm_tn_t* pp, void* stream) {
     return p.dtype == LAVT_F32 ? dispatch_tn<float>(p, st) : dispatch_tn<bf16>(p, st);
 }
 
-// upper bound of the K pieces of lavt_gemm_tn (>= 8 K tiles of 64 rows per piece, unless LAVT_TN_SPLIT forces a count)
+// upper bound of the K pieces of lavt_gemm_tn (>= 8 K tiles of 64 rows per piece)
 extern "C" int lavt_gemm_tn_pieces(const lavt_gemm_tn_t* p) {
     if (!p || p->K <= 0) return 1;
     const int ktiles = cdiv(p->K, 64);
-    const int se = lavt_tuning().tn_split;
-    // (batched problems -- the per-sample word-side reductions of the fused PWAM node: 2-4 output tiles -- are cut down to 2 K tiles per piece, LAVT_PROBE[4]
-    // overrides: a piece is a serial chain of ~1 us per K tile on the 2-stage ring, and the launch sits on the critical chain)
-    const int min_kt = p->batch > 1 ? (lavt_tuning().probe[4] > 0 ? lavt_tuning().probe[4] : 2) : 8;
+    // (batched problems -- the per-sample word-side reductions of the fused PWAM node: 2-4 output tiles -- are cut down to 2 K tiles per piece:
+    // a piece is a serial chain of ~1 us per K tile on the 2-stage ring, and the launch sits on the critical chain)
+    const int min_kt = p->batch > 1 ? 2 : 8;
     int n = cdiv(ktiles, min_kt);
-    if (se > n) n = se;
     if (n > ktiles) n = ktiles;
     return n < 1 ? 1 : n;
 }

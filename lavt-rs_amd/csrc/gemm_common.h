@@ -458,79 +458,4 @@ __device__ __forceinline__ void nt_epilogue(const lavt_gemm_nt_t& p, f32x4 (&acc
     }
 }
 
-
-// ---- bf16 NT epilogue staged through LDS: full-row 16-byte stores -------------------------------------------------------
-// The direct epilogue above issues 8-byte stores that touch 16 different rows per wave-instruction (32-B segments): the
-// store tail is issue-bound (cdna_hip_programming.md T21).  Here the C tile goes registers -> LDS ([BM][BN+8] bf16) -> global
-// as 16 B per lane, 4 full 256-B rows per wave-instruction; the residual is read with the same coalesced pattern.
-template <int BM, int BN, int MI, int NI, bool GD = false>
-__device__ __forceinline__ void nt_epilogue_lds(const lavt_gemm_nt_t& p, f32x4 (&acc)[MI][NI], bf16* sC, int m0, int n0, int wm_off, int wn_off,
-                                                int tid, int lane, int bz) {
-    constexpr int LD = BN + 8, CPR = BN / 8, CHUNKS = BM * CPR;
-    const float* bias = p.bias ? p.bias + (int64_t)bz * p.strideBias : nullptr;
-    const float* rscale = p.row_scale ? p.row_scale + (int64_t)bz * p.strideRowScale : nullptr;
-    const int64_t c_off = (int64_t)bz * p.strideC;
-    float rs[MI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-        const int m = m0 + wm_off + i * 16 + (lane & 15);
-        rs[i] = (rscale && m < p.M) ? rscale[p.row_scale_div > 1 ? m / p.row_scale_div : m] : 1.f;
-    }
-    const int npass = p.Cpre ? 2 : 1;
-    for (int pass = 0; pass < npass; ++pass) {
-        const bool pre = p.Cpre && pass == 0;
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-            const int ml = wm_off + i * 16 + (lane & 15);
-#pragma unroll
-            for (int j = 0; j < NI; ++j) {
-                const int nl = wn_off + j * 16 + 4 * (lane >> 4);
-                const int n = n0 + nl;
-                float v[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[r] = p.alpha * acc[i][j][r];
-                    if (bias && n + r < p.N) v[r] += bias[n + r];
-                    v[r] *= rs[i];
-                    if (!pre && p.act) v[r] = apply_act<true>(p.act, v[r]);
-                    if (GD && pre) v[r] = gelu_grad_f_fast(v[r]);
-                }
-                *reinterpret_cast<uint2*>(sC + ml * LD + nl) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
-            }
-        }
-        __syncthreads();
-        for (int idx = tid; idx < CHUNKS; idx += (int)blockDim.x) {
-            const int row = idx / CPR, c = idx - row * CPR;
-            const int m = m0 + row, n = n0 + c * 8;
-            if (m >= p.M || n >= p.N) continue;
-            const int orow = p.c_rowmap ? p.c_rowmap[m] : m;
-            if (orow < 0) continue;
-            uint4 v = *reinterpret_cast<const uint4*>(sC + row * LD + c * 8);
-            const bool full = n + 8 <= p.N;
-            bf16* dst;
-            if (pre) dst = reinterpret_cast<bf16*>(p.Cpre) + (int64_t)orow * p.ldcpre + n;
-            else {
-                const bool second = p.C2 != nullptr && n >= p.c_split;
-                dst = reinterpret_cast<bf16*>(second ? p.C2 : p.C) + c_off + (int64_t)orow * (second ? p.ldc2 : p.ldc) + (second ? n - p.c_split : n);
-            }
-            if (!pre && p.R) {
-                const bf16* rp = reinterpret_cast<const bf16*>(p.R) + (int64_t)orow * p.ldr + n;
-                float a[8], b[8];
-                chunk_to_f<bf16>(v, a);
-                if (full) chunk_to_f<bf16>(*reinterpret_cast<const uint4*>(rp), b);
-                else for (int e = 0; e < 8; ++e) b[e] = n + e < p.N ? to_f<bf16>(rp[e]) : 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) a[e] += b[e];
-                v = f_to_chunk<bf16>(a);
-            }
-            if (full) *reinterpret_cast<uint4*>(dst) = v;
-            else {
-                const bf16* sv = reinterpret_cast<const bf16*>(&v);
-                for (int e = 0; e < 8; ++e) if (n + e < p.N) dst[e] = sv[e];
-            }
-        }
-    }
-}
-
 }  // namespace lavt_gemm

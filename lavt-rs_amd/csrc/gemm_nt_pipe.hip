@@ -29,10 +29,6 @@
 #include "gemm_v2_helpers.h"
 
 namespace {
-// workgroups of the 128x128 tile from which the 2-stage ring (two workgroups per CU) replaces the 4-stage one (LAVT_PROBE slot 7 >= 100 overrides: experiments)
-static inline long s2_min128() { const int v = lavt_tuning().probe[7]; return v >= 100 ? v : 257; }
-
-
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((__vector_size__(8 * sizeof(int)))) int i32x8;
 
@@ -684,7 +680,7 @@ template <int BM, int BN, bool BKM, int STAGES, int MODE, int LEAN, bool F8 = fa
 }
 template <int BM, int BN, bool BKM, int STAGES, int MODE> int launch_pipe_lean(const lavt_gemm_nt_t& p, hipStream_t st) {
     if constexpr (BM == 256 && BKM && MODE == 2) {          // split-output data gradient of a concat convolution: the plain store with the second output kept (LEAN 3)
-        if (p.C2 && p.act == 0 && !p.mul && !p.Cpre && !p.bias && !p.R && !p.row_scale && !p.c_rowmap && lavt_tuning().probe[7] != 1)
+        if (p.C2 && p.act == 0 && !p.mul && !p.Cpre && !p.bias && !p.R && !p.row_scale && !p.c_rowmap)
             return launch_pipe_<BM, BN, BKM, STAGES, MODE, 3>(p, st);
     }
     if (MODE != 0 && p.act == 0 && !p.mul && !p.Cpre && !p.C2) {      // epilogue instantiations without the features a launch does not use (gemm_common.h)
@@ -720,13 +716,12 @@ template <int BM, int BN, bool BKM, int STAGES> int launch_pipe(const lavt_gemm_
     const int64_t b_rows = p.b_kmajor ? (int64_t)conv_taps_of(p) * p.conv_kc : p.N;
     const bool small = a_rows * p.lda * 2 < lim && (p.A2 == nullptr || a_rows * p.lda2 * 2 < lim) && b_rows * p.ldb * 2 + (int64_t)p.batch * p.strideB * 2 < lim;
     const bool convfast = p.conv_kc > 0 && p.conv_kc % 64 == 0 && (p.A2 == nullptr || p.a_split % 64 == 0) && conv_taps_of(p) <= 32 && small;
-    if (simple && !lavt_tuning().gemm_general) return launch_pipe_lean<BM, BN, BKM, STAGES, 1>(p, st);
-    if (convfast && !lavt_tuning().gemm_general) return launch_pipe_lean<BM, BN, BKM, STAGES, 2>(p, st);
+    if (simple) return launch_pipe_lean<BM, BN, BKM, STAGES, 1>(p, st);
+    if (convfast) return launch_pipe_lean<BM, BN, BKM, STAGES, 2>(p, st);
     if constexpr (!BKM) {          // k-contiguous weights [Cout][taps][Cin] with Cin % 64 != 0 (Cin % 8 == 0; a concat boundary on a 64-channel block): the partial-block form
         const bool convtail = p.conv_kc > 0 && p.conv_kc % 64 != 0 && p.conv_kc % 8 == 0 && (p.A2 == nullptr || p.a_split % 64 == 0) && conv_taps_of(p) <= 32 && small &&
-                              p.conv_kc_split <= 0 && p.conv_tap_split <= 0 && p.batch == 1 && p.K == conv_taps_of(p) * p.conv_kc && p.ldb >= (int64_t)conv_taps_of(p) * p.conv_kc &&
-                              !lavt_tuning().conv_tail_off;
-        if (convtail && !lavt_tuning().gemm_general) return launch_pipe_lean<BM, BN, BKM, STAGES, 3>(p, st);
+                              p.conv_kc_split <= 0 && p.conv_tap_split <= 0 && p.batch == 1 && p.K == conv_taps_of(p) * p.conv_kc && p.ldb >= (int64_t)conv_taps_of(p) * p.conv_kc;
+        if (convtail) return launch_pipe_lean<BM, BN, BKM, STAGES, 3>(p, st);
     }
     return launch_pipe_lean<BM, BN, BKM, STAGES, 0>(p, st);
 }
@@ -741,28 +736,23 @@ int lavt_gemm_nt_pipe_tile(const lavt_gemm_nt_t& p, int* stages_out) {
     if ((p.dtype != LAVT_BF16 && p.dtype != LAVT_FP8) || p.zeros == nullptr) return 0;
     const lavt_tuning_t& tun = lavt_tuning();
     const int pipe = tun.gemm_pipe;                 // 0: gemm_v2 K loops only; 1: the 256x256 tile; 2: + 128x128 for K >= 1024; 3: + every 128x128 problem
-    if (tun.gemm_v2_off || pipe < 1) return 0;
+    if (pipe < 1) return 0;
     if (p.dtype == LAVT_FP8) {          // e4m3 operands: k-contiguous, 128-element K tiles, plain or tap-walking issue (anything else: gemm_v2.hip's fp8 form)
-        if (tun.gemm_general || tun.fp8_pipe_off || p.b_kmajor || p.c_f32 || p.conv_kc_split > 0 || p.conv_tap_split > 0 || p.lda % 16 || p.ldb % 16 || (p.A2 && p.lda2 % 16)) return 0;
+        if (p.b_kmajor || p.c_f32 || p.conv_kc_split > 0 || p.conv_tap_split > 0 || p.lda % 16 || p.ldb % 16 || (p.A2 && p.lda2 % 16)) return 0;
         if (!pipe_f8_simple(p) && !pipe_f8_convfast(p)) return 0;
     }
     if (p.lda % 8 || p.ldb % 8 || (p.A2 && p.lda2 % 8)) return 0;
     if (p.ln_wsum || p.dact_pre) return 0;
     if (p.conv_kc_split > 0) {          // the channel-split reduction exists in this kernel's tap-walking mode only
-        if (tun.gemm_general) return 0;          // (LAVT_GEMM_GENERAL forces the general decode: lavt_gemm_nt then refuses the problem)
         *stages_out = 4;
         return 128;
     }
     const int force = tun.gemm_tile;
     const long tiles128 = (long)cdiv(p.M, 128) * cdiv(p.N, 128) * p.batch;
     const long tiles64 = (long)cdiv(p.M, 64) * cdiv(p.N, 64) * p.batch;
-    const int big_long = tun.gemm_big_long;
-    const bool big = force ? force == 128 : ((tiles128 >= 200 || (big_long > 0 && p.K >= 64 * 64 && tiles128 >= big_long)) && p.N >= 128);
+    const bool big = force ? force == 128 : ((tiles128 >= 200 || (p.K >= 64 * 64 && tiles128 >= GEMM_BIG_LONG)) && p.N >= 128);
     const long wgs = big ? tiles128 : tiles64;
-    const int stages = tun.gemm_stages ? tun.gemm_stages : (wgs >= (big ? s2_min128() : 512) ? 2 : 4);
-    const long tiles256 = (long)cdiv(p.M, 128) * cdiv(p.N, 256) * p.batch;
-    const bool wide = force ? force == 256 : (tun.gemm_wide && tiles256 >= 256 && p.N % 256 == 0 && p.K >= 1024);
-    if (wide) return 0;
+    const int stages = tun.gemm_stages ? tun.gemm_stages : (wgs >= (big ? S2_MIN128 : 512) ? 2 : 4);
     const long tiles256x = (long)cdiv(p.M, 256) * cdiv(p.N, 256) * p.batch;
     const long rounds = (tiles256x + 255) / 256;
     // (round 5: N within 1/16 of a multiple of 256 also takes the large tile -- Swin-T's 480-column data gradient of the concat convolution ran 439 us on 3600
@@ -770,7 +760,7 @@ int lavt_gemm_nt_pipe_tile(const lavt_gemm_nt_t& p, int* stages_out) {
     const bool n_fits = p.N % 256 == 0 || (p.N % 8 == 0 && (long)p.N * 16 >= (long)cdiv(p.N, 256) * 256 * 15);
     const bool huge = force ? force == 512 : (n_fits && p.K >= 1024 && tiles256x >= 128 && tiles256x * 10 >= rounds * 256 * 8);
     if (huge) { *stages_out = 2; return 256; }
-    if (big && tun.gemm_waves == 8 && (pipe >= 3 || (pipe == 2 && p.K >= 1024))) { *stages_out = stages == 2 ? 2 : 4; return 128; }
+    if (big && (pipe >= 3 || (pipe == 2 && p.K >= 1024))) { *stages_out = stages == 2 ? 2 : 4; return 128; }
     return 0;
 }
 

@@ -93,14 +93,14 @@ struct TnpMember {
     float* part;
     int pieces, kt_per, tiles;
 };
-struct TnpGroup { TnpMember m[TNP_MAX]; int n, tiles, dbg; };
+struct TnpGroup { TnpMember m[TNP_MAX]; int n, tiles; };
 struct TnpRider {
     const bf16* dy; const bf16* x; const float* gamma; const float* mean; const float* rstd; bf16* dx; float* partials; const bf16* dres;
     int rows, C, blocks;
 };
 
 constexpr unsigned TNP_OOB = 0x80000000u;
-// Ablation builds (tools/r05_tnp_ablate.sh compiles this file with -DTNP_ABL=n into libraries OUTSIDE the shipped one; the shipped build has no switch):
+// Ablation builds (this file compiled with -DTNP_ABL=n into libraries OUTSIDE the shipped one; the shipped build has no switch):
 // bit 0: no MFMAs; bit 1: no fragment reads; bit 2: no DMA inside the K loop (the ring keeps the prologue's tiles); bit 3: ONE K tile (what a launch costs
 // outside its K loop: dispatch, prologue, epilogue)
 #ifndef TNP_ABL
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(512) void gemm_tn_pipe_kernel(const TnpGroup g, con
         return;
     }
     // (tile = block index: an XCD-contiguous order measured 1 us slower -- 38.3 vs 37.2 us -- the eight L2s then see the members one after the other)
-    const int t = (g.dbg & 2) ? xcd_tile_id(bid, g.tiles) : bid;
+    const int t = bid;
     int k = 0;
     while (k + 1 < g.n && t >= g.m[k].tile_end) ++k;
     const TnpMember& m = g.m[k];
@@ -576,7 +576,7 @@ int lavt_gemm_tn_grouped_pipe(const lavt_gemm_tn_t* probs, int n, hipStream_t st
         m.rs_div = p.a_rowscale ? p.a_rowscale_div : 1 << 30;
         m.rs_n = p.a_rowscale ? (p.K + p.a_rowscale_div - 1) / p.a_rowscale_div : 0;
         m.flags = (p.accumulate ? TNP_ACCUMULATE : 0) | (p.colsum_atomic ? TNP_COLSUM_ATOMIC : 0) | (no_b ? TNP_NO_B : 0) |
-                  ((((uintptr_t)p.C & 15) == 0 && p.ldc % 4 == 0) ? TNP_VEC4 : 0) | (tun.probe[5] == 1 ? 0 : TNP_WT);
+                  ((((uintptr_t)p.C & 15) == 0 && p.ldc % 4 == 0) ? TNP_VEC4 : 0) | TNP_WT;
         m.alpha = p.alpha;
         m.part = nullptr; m.pieces = 1; m.kt_per = cdiv(p.K, 64);
         base_tiles += m.tiles;
@@ -643,7 +643,7 @@ int lavt_gemm_tn_grouped_pipe(const lavt_gemm_tn_t* probs, int n, hipStream_t st
         if (tiles < 96 || tiles > 256) return 1;
     }
     for (int i = n; i < TNP_MAX; ++i) { g.m[i] = g.m[0]; g.m[i].tile_end = tiles; g.m[i].pieces = 1; }
-    g.n = n; g.tiles = tiles; g.dbg = tun.probe[6];
+    g.n = n; g.tiles = tiles;
     TnpRider r{};
     int rider_wgs = 0, lpr = 0;
     if (ln != nullptr && !drop_rider) {
@@ -654,7 +654,7 @@ int lavt_gemm_tn_grouped_pipe(const lavt_gemm_tn_t* probs, int n, hipStream_t st
             rider_wgs = (blocks + 1) / 2;
         } else lpr = 0;
     }
-    const int stages = tun.tn_pipe_stages == 3 ? 3 : tun.tn_pipe_stages == 5 ? 5 : tun.tn_pipe_stages == 2 ? 2 : 4;
+    const int stages = tun.tn_pipe_stages == 3 ? 3 : 4;
 #define TNP_GO(S_)                                                                  \
     do {                                                                            \
         if (lpr == 64) tnp_launch<S_, 64>(g, r, rider_wgs, st);                     \
@@ -662,7 +662,7 @@ int lavt_gemm_tn_grouped_pipe(const lavt_gemm_tn_t* probs, int n, hipStream_t st
         else if (lpr == 16) tnp_launch<S_, 16>(g, r, rider_wgs, st);                \
         else tnp_launch<S_, 0>(g, r, 0, st);                                        \
     } while (0)
-    if (stages == 3) TNP_GO(3); else if (stages == 5) TNP_GO(5); else if (stages == 2) TNP_GO(2); else TNP_GO(4);
+    if (stages == 3) TNP_GO(3); else TNP_GO(4);
 #undef TNP_GO
     if (any_pieces) {
         int max_ns = 1;

@@ -631,8 +631,7 @@ int lavt_ln_bwd_geometry(int dtype, int rows, int C, int* lpr, int* cpl, int* wa
 // ln != NULL: a LayerNorm backward to run as rider workgroups of the launch; returns 3 when the group was launched WITHOUT it (the caller launches it)
 int lavt_gemm_tn_grouped_pipe(const lavt_gemm_tn_t* probs, int n, hipStream_t st, const lavt_ln_rider_t* ln);
 int lavt_gemm_tn_grouped_v2(const lavt_gemm_tn_t* probs, int n, hipStream_t st, const lavt_ln_rider_t* ln) {
-    const lavt_tuning_t& tun = lavt_tuning();
-    if (tun.gemm_v2_off || n < 2 || n > TN_GROUP_MAX) return 1;
+    if (n < 2 || n > TN_GROUP_MAX) return 1;
     {   // short reductions on enough 128x128 tiles (the Swin-block groups of stages 2 / 3): the software-pipelined launch of gemm_tn_pipe.hip
         const int rc = lavt_gemm_tn_grouped_pipe(probs, n, st, ln);
         if (rc != 1) return rc;
@@ -640,24 +639,18 @@ int lavt_gemm_tn_grouped_v2(const lavt_gemm_tn_t* probs, int n, hipStream_t st, 
     TnGroup g;
     bool maps = false;
     int tiles = 0;
-    // Tile configuration of the grouped launch: LAVT_TNG_CFG = "tile,waves,stages" (64,4,2 = the round-1/2 form).
-    const int cfg_tile = tun.tng_tile, cfg_waves = tun.tng_waves, cfg_stages = tun.tng_stages;
-    int TB = cfg_tile;
-    {   // the large tile only where its tiles still occupy most of the chip
-        long t128 = 0;
-        for (int i = 0; i < n; ++i) t128 += (long)cdiv(probs[i].I, 128) * cdiv(probs[i].J, 128);
-        if (TB == 128 && t128 < 128) TB = 64;
-    }
+    // Tile configuration of the grouped launch: 64x64 tiles, 4 waves, 2-stage ring.
     // (rectangular 64 x 128 / 128 x 64 tiles, 4 waves -- 24 KB per K tile for 1.05 MFLOP -- measured level with the square tile in round 4: 39.0 / 41.2 vs
     // 39.0 us per stage-2 launch, 8.66 / 8.74 vs 8.56 ms per step; the instantiations are gone)
-    const int TBI = TB, TBJ = TB;
+    constexpr int TBI = 64, TBJ = 64;
     bool any_colsum = false;
     // Pieces per member.  A member with a partials scratch (lavt_gemm_tn_t.partials: its pieces are stored as plain tiles and added into C by one
     // small second kernel) may be cut as finely as its K allows -- the long-K weight gradients of PWAM (K = 28 800 rows = 450 K tiles on 4
     // output tiles each) then run as ONE launch of ~1000 workgroups instead of four launches of ~230 at one workgroup per CU; a member
     // without one is cut into at most 4 pieces that meet through atomics (only if its C holds zeros: split_k < 0), and a chain of more than
     // 128 K tiles without a scratch keeps the group from forming (it would run serially while the short members supply the tile count).
-    const int chain = tun.tng_chain, piece_tiles = tun.tng_piece;
+    constexpr int chain = 48;          // 32 / 48 / 64 / 128: video step 23.16 / 22.93 / 22.82 / 22.87 ms, image step level
+    constexpr int piece_tiles = 8;
     bool any_parts = false;
     int64_t max_total = 0;
     // ... and only where cutting pays: a group whose uncut 64x64 tiles already give every CU two workgroups (>= 512: the Swin-block launch at
@@ -684,7 +677,7 @@ int lavt_gemm_tn_grouped_v2(const lavt_gemm_tn_t* probs, int n, hipStream_t st, 
                 if (ktiles > 128) return 1;
                 // (a group whose uncut tiles already give every CU two workgroups is not cut through atomics either: at 4 images per GPU -- K = 3600 = 57 K tiles --
                 // two atomic pieces per tile cost 12.60 vs 12.34 ms per step, and a plainly stored gradient needs no zero fill: engine.TrainStep)
-                ns = (p.split_k < 0 && chain > 0 && cut_pays) ? cdiv(ktiles, chain) : 1;
+                ns = (p.split_k < 0 && cut_pays) ? cdiv(ktiles, chain) : 1;
                 if (ns > 4) ns = 4;
             }
             const int per = cdiv(ktiles, ns);
@@ -699,43 +692,11 @@ int lavt_gemm_tn_grouped_v2(const lavt_gemm_tn_t* probs, int n, hipStream_t st, 
     }
     for (int i = n; i < TN_GROUP_MAX; ++i) { g.p[i] = probs[0]; g.p[i].partials = nullptr; g.tile_end[i] = tiles; g.split[i] = 1; }
     g.n = n;
-    if (tiles < (TB == 64 ? 256 : 128)) return 1;   // too few workgroups to fill the chip
+    if (tiles < 256) return 1;   // too few workgroups to fill the chip
     // (round 2: an XCD-contiguous tile order inside each member -- it cuts the 152 MB of fabric traffic -- and a 3-stage ring were both measured
     // on the step: 10.63 vs 10.64 ms and 10.81 vs 10.62 ms; neither is kept)
-    if (TB != 64 || cfg_waves != 4 || cfg_stages != 2) {
-#define TNG_GO(BT_, WV_, SG_) TNG_GO2(BT_, BT_, WV_, SG_)
-#define TNG_GO2(BT_, BU_, WV_, SG_)                                                                                                                          \
-    do {                                                                                                                                               \
-        const size_t l = SG_ * (size_t)(64 * (BT_ + BU_) * 2) + (maps ? (2 * (SG_ - 1) + 1) * 768 + 256 : 0);                                          \
-        static bool attr = false;                                                                                                                      \
-        if (!attr && l > 65536) {                                                                                                                      \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_v2_grouped_kernel<BT_, BU_, WV_, SG_, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l);  \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_v2_grouped_kernel<BT_, BU_, WV_, SG_, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l); \
-            attr = true;                                                                                                                               \
-        }                                                                                                                                              \
-        if (maps) hipLaunchKernelGGL((gemm_tn_v2_grouped_kernel<BT_, BU_, WV_, SG_, true, 2>), dim3(tiles), dim3(WV_ * 64), l, st, g);                 \
-        else hipLaunchKernelGGL((gemm_tn_v2_grouped_kernel<BT_, BU_, WV_, SG_, false, 2>), dim3(tiles), dim3(WV_ * 64), l, st, g);                     \
-    } while (0)
-        bool done = true;
-        if (TB == 128 && cfg_waves == 8 && cfg_stages == 2) TNG_GO(128, 8, 2);
-        else if (TB == 128 && cfg_waves == 8 && cfg_stages == 3) TNG_GO(128, 8, 3);
-        else if (TB == 128 && cfg_waves == 8 && cfg_stages == 4) TNG_GO(128, 8, 4);
-        else if (TB == 128 && cfg_waves == 4 && cfg_stages == 2) TNG_GO(128, 4, 2);
-        else if (TB == 128 && cfg_waves == 4 && cfg_stages == 3) TNG_GO(128, 4, 3);
-        else if (TB == 128 && cfg_waves == 4 && cfg_stages == 4) TNG_GO(128, 4, 4);
-        else if (TB == 64 && cfg_waves == 4 && cfg_stages == 4) TNG_GO(64, 4, 4);
-        else if (TB == 64 && cfg_waves == 4 && cfg_stages == 3) TNG_GO(64, 4, 3);
-        else done = false;
-#undef TNG_GO
-#undef TNG_GO2
-        if (done) {
-            if (any_parts) hipLaunchKernelGGL(tn_reduce_pieces_group, dim3((unsigned)cdiv(max_total, 64), n), dim3(256), 0, st, g);
-            LAVT_CHECK_LAUNCH("lavt_gemm_tn_grouped(v2)");
-            return ln ? 3 : LAVT_OK;
-        }
-    }
     const size_t lds = 2 * (size_t)(64 * (64 + 64) * 2) + (maps ? 3 * 768 + 256 : 0);
-    if (ln != nullptr && any_colsum && lavt_tuning().probe[2] == 0) {
+    if (ln != nullptr && any_colsum) {
         int lpr, cpl, waves;
         const int blocks = lavt_ln_bwd_geometry(LAVT_BF16, ln->rows, ln->C, &lpr, &cpl, &waves);
         LnRider r{(const bf16*)ln->dy, (const bf16*)ln->x, ln->gamma, ln->mean, ln->rstd, (bf16*)ln->dx, ln->partials, (const bf16*)ln->dres, ln->rows, ln->C, blocks};
@@ -772,8 +733,7 @@ int lavt_gemm_tn_grouped_v2(const lavt_gemm_tn_t* probs, int n, hipStream_t st, 
 // ---- stream-K grouped launch: host side.  sk_plan fills g / sk and returns the scratch floats needed (0 = the group does not qualify).
 static int64_t sk_plan(const lavt_gemm_tn_t* probs, int n, TnGroup& g, TnSk& sk, bool& maps, bool& any_colsum) {
     constexpr int TB = 128;
-    const lavt_tuning_t& tun = lavt_tuning();
-    if (tun.gemm_v2_off || !tun.tn_streamk || n < 2 || n > TN_GROUP_MAX) return 0;
+    if (n < 2 || n > TN_GROUP_MAX) return 0;
     maps = false; any_colsum = false;
     int its = 0, tiles = 0;
     for (int i = 0; i < n; ++i) {
@@ -793,7 +753,7 @@ static int64_t sk_plan(const lavt_gemm_tn_t* probs, int n, TnGroup& g, TnSk& sk,
     g.n = n;
     // worth it when the 128x128 tiles alone cannot fill the chip in whole rounds but there is enough work for every run to amortise its ring
     // prologue (>= 6 K tiles per run) -- the Swin-block launches of stages 1-3; many-tile members (stage 0: K = 28 800) keep the piece form
-    int nw = tun.probe[0] > 0 ? tun.probe[0] : 512;
+    int nw = 512;
     if (its / nw < 6) nw = its / 6;
     if (nw < 128 || tiles < 32) return 0;
     sk.total = its; sk.nw = nw;
@@ -828,29 +788,25 @@ int lavt_gemm_tn_grouped_sk_v2(const lavt_gemm_tn_t* probs, int n, float* scratc
 
 int lavt_gemm_tn_v2(const lavt_gemm_tn_t& p, hipStream_t st) {
     if (p.dtype != LAVT_BF16 || p.zeros == nullptr) return 1;
-    const lavt_tuning_t& tun = lavt_tuning();
-    if (tun.gemm_v2_off) return 1;
     if (!tn_v2_eligible(p)) return 1;                            // (only 0 / constant row masks can be folded into the row fetch)
     // Measured (tools/gemm_bench.py tn): the 64x64 / 4-wave tile wins on every weight-gradient shape of the step, the conv wgrads included
     // (369 vs 230 TF/s for 128x128); the split-K factor trades workgroup count (latency hiding) against fp32 atomic traffic.
-    const int force = tun.gemm_tile;
+    const int force = lavt_tuning().gemm_tile;
     const int ktiles = cdiv(p.K, 64);
     const long tiles64 = (long)cdiv(p.I, 64) * cdiv(p.J, 64) * p.batch;
     const long tiles128 = (long)cdiv(p.I, 128) * cdiv(p.J, 128) * p.batch;
     // conv weight gradients (long K, >= 48 tiles of 128x128 -- the Swin-T decoder's 384-channel convolutions have 102): the larger tile halves the
     // L2->LDS bytes per MFMA (measured 303 vs 357 us on Swin-B's; 16.9 -> 16.1 ms per Swin-T step)
-    const bool tn128 = tun.tn_big;
-    const int tn_big_min = tun.tn_big_min;
-    const bool big = force ? force == 128 : (tn128 && p.conv_kc > 0 && tiles128 >= tn_big_min && ktiles >= 64);
+    constexpr int TN_BIG_MIN = 48;
+    const bool big = force ? force == 128 : (p.conv_kc > 0 && tiles128 >= TN_BIG_MIN && ktiles >= 64);
     const long tiles = big ? tiles128 : tiles64;
     int split = p.split_k;
-    if (tun.tn_split) split = tun.tn_split;
     if (split <= 0) {
-        const int target = tun.tn_target;
+        constexpr int target = 768;
         split = big ? (int)((384 + tiles / 2) / tiles) : (int)((target + tiles / 2) / tiles);      // ~3 (64-tile) / ~1.5 (128-tile) workgroups per CU
         const int long_k = (ktiles + 127) / 128;          // no workgroup walks more than ~128 K tiles
         if (split < long_k) split = long_k;
-        const int min_kt = p.batch > 1 ? (tun.probe[4] > 0 ? tun.probe[4] : 2) : 8;          // (as lavt_gemm_tn_pieces: batched problems down to 2 K tiles per piece)
+        const int min_kt = p.batch > 1 ? 2 : 8;          // (as lavt_gemm_tn_pieces: batched problems down to 2 K tiles per piece)
         const int max_split = (ktiles + min_kt - 1) / min_kt;           // >= 8 K tiles per workgroup (2 for batched problems)
         if (split > max_split) split = max_split;
         if (split < 1) split = 1;

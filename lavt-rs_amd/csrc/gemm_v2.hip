@@ -20,10 +20,6 @@
 #include "gemm_v2_helpers.h"
 
 namespace {
-// workgroups of the 128x128 tile from which the 2-stage ring (two workgroups per CU) replaces the 4-stage one (LAVT_PROBE slot 7 >= 100 overrides: experiments)
-static inline long s2_min128() { const int v = lavt_tuning().probe[7]; return v >= 100 ? v : 257; }
-
-
 // SIMPLE = no conv taps, no concat source, K % 64 == 0: every lane's DMA source is a fixed pointer that advances by a constant per K tile,
 // so the K loop carries ~3 instructions per DMA instead of the general path's address arithmetic (which made small GEMMs issue-bound:
 // ~220 VALU/SALU instructions per K tile on the one wave a SIMD holds, measured 0.78 us per K tile at M=2592, N=512).
@@ -273,7 +269,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_nt_v2_kernel(const lavt_gemm_
     NtSide<(MI * NI <= 8 ? MI : 1), NI> side;
     side.have = false;
     if constexpr (SIDE_PRE) {
-        if ((p.epi_wide & 2) && nt_takes_wide<T, MI, NI>(p, n0 + wn * WN) && (DACT || p.R || p.mul) && (!p.epi_lds || p.mul || (p.ldc % 8)))
+        if ((p.epi_wide & 2) && nt_takes_wide<T, MI, NI>(p, n0 + wn * WN) && (DACT || p.R || p.mul))
             nt_side_load<MI, NI, DACT, GD, LEAN>(p, side, m0 + wm * WM, n0 + wn * WN, lane);
     }
     const int ktiles = (p.K + BK - 1) / BK;
@@ -412,10 +408,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_nt_v2_kernel(const lavt_gemm_
         }
     }
     if constexpr (DACT) { nt_epilogue<T, MI, NI, true, GD>(p, acc, m0 + wm * WM, n0 + wn * WN, lane, bz, SIDE_PRE ? &side : nullptr); return; }
-    if (!p.epi_lds || p.mul || p.c_f32 || (p.ldc % 8) || (p.C2 && (p.ldc2 % 8 || p.c_split % 8)) || (p.R && p.ldr % 8) || (p.Cpre && p.ldcpre % 8))
-        nt_epilogue<T, MI, NI, false, GD, LEAN>(p, acc, m0 + wm * WM, n0 + wn * WN, lane, bz, SIDE_PRE ? &side : nullptr);           // (GD = LAVT_ACT_GELU_D: its own instantiation of the LayerNorm-folded launch)
-    else
-        nt_epilogue_lds<BM, BN, MI, NI, GD>(p, acc, reinterpret_cast<bf16*>(smem), m0, n0, wm * WM, wn * WN, tid, lane, bz);
+    nt_epilogue<T, MI, NI, false, GD, LEAN>(p, acc, m0 + wm * WM, n0 + wn * WN, lane, bz, SIDE_PRE ? &side : nullptr);           // (GD = LAVT_ACT_GELU_D: its own instantiation of the LayerNorm-folded launch)
     }
 }
 
@@ -452,10 +445,10 @@ int launch_nt_v2_lna(const lavt_gemm_nt_t& p, hipStream_t st) {
     const long tiles128 = (long)cdiv(p.M, 128) * cdiv(p.N, 128), tiles64 = (long)cdiv(p.M, 64) * cdiv(p.N, 64);
     // (LAVT_ACT_GELU_D is its own instantiation: with the branch on p.act inside one kernel, the classic form ran 3 us per launch slower)
     if (p.act == LAVT_ACT_GELU_D && !p.mul && !p.C2 && !p.R && !p.row_scale && !p.c_rowmap) {
-        if (tiles128 >= 200 && p.N >= 128) return tiles128 >= s2_min128() ? launch_nt_v2_<128, 128, false, 2, 8, 1, false, false, true, true>(p, st) : launch_nt_v2_<128, 128, false, 4, 8, 1, false, false, true, true>(p, st);
+        if (tiles128 >= 200 && p.N >= 128) return tiles128 >= S2_MIN128 ? launch_nt_v2_<128, 128, false, 2, 8, 1, false, false, true, true>(p, st) : launch_nt_v2_<128, 128, false, 4, 8, 1, false, false, true, true>(p, st);
         return tiles64 >= 512 ? launch_nt_v2_<64, 64, false, 2, 4, 1, false, false, true, true>(p, st) : launch_nt_v2_<64, 64, false, 4, 4, 1, false, false, true, true>(p, st);
     }
-    if (tiles128 >= 200 && p.N >= 128) return tiles128 >= s2_min128() ? launch_nt_v2_<128, 128, false, 2, 8, 1, false, false, true>(p, st) : launch_nt_v2_<128, 128, false, 4, 8, 1, false, false, true>(p, st);
+    if (tiles128 >= 200 && p.N >= 128) return tiles128 >= S2_MIN128 ? launch_nt_v2_<128, 128, false, 2, 8, 1, false, false, true>(p, st) : launch_nt_v2_<128, 128, false, 4, 8, 1, false, false, true>(p, st);
     return tiles64 >= 512 ? launch_nt_v2_<64, 64, false, 2, 4, 1, false, false, true>(p, st) : launch_nt_v2_<64, 64, false, 4, 4, 1, false, false, true>(p, st);
 }
 // fp8 operands (LAVT_FP8): k-contiguous A and B, 128-element K tiles; 128x128 / 8 waves when that fills the chip, else 64x64 / 4 waves
@@ -472,7 +465,7 @@ int launch_nt_v2_fp8(const lavt_gemm_nt_t& p, hipStream_t st) {
         return LAVT_ERR_INVALID;
     }
     const long tiles128 = (long)cdiv(p.M, 128) * cdiv(p.N, 128) * p.batch, tiles64 = (long)cdiv(p.M, 64) * cdiv(p.N, 64) * p.batch;
-    if (tiles128 >= 200 && p.N >= 128) return tiles128 >= s2_min128() ? launch_nt_v2_f8<128, 128, 2, 8>(p, st) : launch_nt_v2_f8<128, 128, 4, 8>(p, st);
+    if (tiles128 >= 200 && p.N >= 128) return tiles128 >= S2_MIN128 ? launch_nt_v2_f8<128, 128, 2, 8>(p, st) : launch_nt_v2_f8<128, 128, 4, 8>(p, st);
     return tiles64 >= 512 ? launch_nt_v2_f8<64, 64, 2, 4>(p, st) : launch_nt_v2_f8<64, 64, 4, 4>(p, st);
 }
 // Fused activation-gradient epilogue (dact_pre): data gradients only (k-major B, plain K walk); the flag is a template parameter so that no
@@ -485,18 +478,17 @@ int launch_nt_v2_dact(const lavt_gemm_nt_t& p, hipStream_t st) {
     const long tiles128 = (long)cdiv(p.M, 128) * cdiv(p.N, 128) * p.batch, tiles64 = (long)cdiv(p.M, 64) * cdiv(p.N, 64) * p.batch;
     // the stored-derivative form (dact = LAVT_ACT_STORED, no residual) is its own instantiation (GD): a multiply, none of the transcendental forms
     if (p.dact == LAVT_ACT_STORED && !p.R && !p.bias && !p.c_rowmap && !p.act && !p.mul && !p.Cpre && !p.C2) {      // (its wide epilogue has none of these: any of them takes the general instantiation)
-        if (tiles128 >= 200 && p.N >= 128) return tiles128 >= s2_min128() ? launch_nt_v2_<128, 128, true, 2, 8, 1, true, false, false, true>(p, st) : launch_nt_v2_<128, 128, true, 4, 8, 1, true, false, false, true>(p, st);
+        if (tiles128 >= 200 && p.N >= 128) return tiles128 >= S2_MIN128 ? launch_nt_v2_<128, 128, true, 2, 8, 1, true, false, false, true>(p, st) : launch_nt_v2_<128, 128, true, 4, 8, 1, true, false, false, true>(p, st);
         return tiles64 >= 512 ? launch_nt_v2_<64, 64, true, 2, 4, 1, true, false, false, true>(p, st) : launch_nt_v2_<64, 64, true, 4, 4, 1, true, false, false, true>(p, st);
     }
-    if (tiles128 >= 200 && p.N >= 128) return tiles128 >= s2_min128() ? launch_nt_v2_<128, 128, true, 2, 8, 1, true>(p, st) : launch_nt_v2_<128, 128, true, 4, 8, 1, true>(p, st);
+    if (tiles128 >= 200 && p.N >= 128) return tiles128 >= S2_MIN128 ? launch_nt_v2_<128, 128, true, 2, 8, 1, true>(p, st) : launch_nt_v2_<128, 128, true, 4, 8, 1, true>(p, st);
     return tiles64 >= 512 ? launch_nt_v2_<64, 64, true, 2, 4, 1, true>(p, st) : launch_nt_v2_<64, 64, true, 4, 4, 1, true>(p, st);
 }
 template <int BM, int BN, bool BKM, int STAGES, int WAVES> int launch_nt_v2(const lavt_gemm_nt_t& p, hipStream_t st) {
-    const bool general_only = lavt_tuning().gemm_general;
     const bool simple = p.conv_kc <= 0 && p.A2 == nullptr && p.K % 64 == 0;
     const bool convfast = p.conv_kc > 0 && p.conv_kc % 64 == 0 && (p.A2 == nullptr || p.a_split % 64 == 0) && conv_taps_of(p) <= 32;     // (a bit per tap)
-    if (simple && !general_only) return launch_nt_v2_<BM, BN, BKM, STAGES, WAVES, 1>(p, st);
-    if (convfast && !general_only) return launch_nt_v2_<BM, BN, BKM, STAGES, WAVES, 2>(p, st);
+    if (simple) return launch_nt_v2_<BM, BN, BKM, STAGES, WAVES, 1>(p, st);
+    if (convfast) return launch_nt_v2_<BM, BN, BKM, STAGES, WAVES, 2>(p, st);
     return launch_nt_v2_<BM, BN, BKM, STAGES, WAVES, 0>(p, st);
 }
 
@@ -508,20 +500,18 @@ int lavt_gemm_nt_v2(const lavt_gemm_nt_t& p, hipStream_t st) {
     if (p.dtype == LAVT_FP8) return launch_nt_v2_fp8(p, st);
     if (p.dtype != LAVT_BF16 || p.zeros == nullptr) return 1;
     const lavt_tuning_t& tun = lavt_tuning();
-    if (tun.gemm_v2_off) return 1;
     if (p.lda % 8 || p.ldb % 8 || (p.A2 && p.lda2 % 8)) return 1;
     if (p.ln_wsum) return launch_nt_v2_lna(p, st);
     if (p.dact_pre) return launch_nt_v2_dact(p, st);
     // Dispatch measured on MI355X (tools/gemm_bench.py, hipGraph-timed): 128x128 tile with 8 waves (2 per SIMD: one wave's DMA issue and
     // LDS reads hide under the other's MFMAs) and a 2-stage ring (64-80 KiB -> 2 workgroups per CU) once there are >= 200 such tiles;
-    // otherwise 64x64 tiles / 4 waves (5 workgroups per CU), 3 stages only for long-K problems with few tiles.
+    // otherwise 64x64 tiles / 4 waves (5 workgroups per CU).
     const int force = tun.gemm_tile;
     const long tiles128 = (long)cdiv(p.M, 128) * cdiv(p.N, 128) * p.batch;
     const long tiles64 = (long)cdiv(p.M, 64) * cdiv(p.N, 64) * p.batch;
     // long reductions on few tiles (3-D convolutions of SepTPWAM: K = 27 C on 144 tiles of 128x128) also take the 128x128 tile: a launch lasts as
     // long as its serial chain of K tiles, and the larger tile moves half the bytes per K tile and flop
-    const int big_long = tun.gemm_big_long;
-    const bool big = force ? force == 128 : ((tiles128 >= 200 || (big_long > 0 && p.K >= 64 * 64 && tiles128 >= big_long)) && p.N >= 128);
+    const bool big = force ? force == 128 : ((tiles128 >= 200 || (p.K >= 64 * 64 && tiles128 >= GEMM_BIG_LONG)) && p.N >= 128);
 
     // Ring depth.  In isolation (operands L2-resident) 2 stages win everywhere; inside the training step the operands of the small
     // GEMMs arrive cold from HBM / Infinity Cache and a 4-deep ring is worth 0.8 ms per step.  The many-tile long-K problems (decoder
@@ -531,31 +521,14 @@ int lavt_gemm_nt_v2(const lavt_gemm_nt_t& p, hipStream_t st) {
     // barrier stalls overlap) wins: batch 4 11.70 -> 11.39 ms, Video-Swin-B 19.55 -> 18.77, Swin-T batch 8 10.89 -> 10.73, headline 7.61 -> 7.58
     // (profiles/r05_zz_ring_depth_threshold_sweep.txt, ..._rule_ab.txt).  Up to 256 workgroups (the M = 1800 GEMMs of batch 2) the 4-deep ring stays.
     const long wgs = big ? tiles128 : tiles64;
-    const int stages = tun.gemm_stages ? tun.gemm_stages : (wgs >= (big ? s2_min128() : 512) ? 2 : 4);
-    const int waves = tun.gemm_waves;
+    const int stages = tun.gemm_stages ? tun.gemm_stages : (wgs >= (big ? S2_MIN128 : 512) ? 2 : 4);
 #define GO(BM_, BN_, KM_, ST_, WV_) return launch_nt_v2<BM_, BN_, KM_, ST_, WV_>(p, st)
-    // 128x256 tile, 8 waves of 64x64: fewer LDS bytes (DMA fill and fragment reads) per MFMA than 128x128; for the long-K, many-tile problems
-    const long tiles256 = (long)cdiv(p.M, 128) * cdiv(p.N, 256) * p.batch;
-    const bool wide = force ? force == 256 : (tun.gemm_wide && tiles256 >= 256 && p.N % 256 == 0 && p.K >= 1024);
-    if (wide) { if (p.b_kmajor) GO(128, 256, true, 2, 8); else GO(128, 256, false, 2, 8); }
-    // 256x256 tile (gemm_nt_pipe.hip: 8 waves of 128 x 64), one workgroup per CU: 128 flop per byte of LDS fill -- every CU ingests at ~50 GB/s whatever
-    // the tile, so the 128x128 tile is fill-bound at half the rate (measured 1.05-1.1 vs 0.6-0.85 PFLOP/s on the decoder conv shapes).
-    // Only when its tiles fill the 256 CUs well (whole rounds at >= 80 %).
-    const long tiles256x = (long)cdiv(p.M, 256) * cdiv(p.N, 256) * p.batch;
-    const long rounds = (tiles256x + 255) / 256;
-    const bool huge = force ? force == 512 : (p.N % 256 == 0 && p.K >= 1024 && tiles256x >= 128 && tiles256x * 10 >= rounds * 256 * 8);
-    (void)huge;                                     // (the 256x256 tile and the long-K 128x128 problems are taken by gemm_nt_pipe.hip before this dispatcher: gemm.hip)
+    // (the 256x256 tile and the long-K 128x128 problems are taken by gemm_nt_pipe.hip before this dispatcher: gemm.hip)
     if (big) {
-        if (waves == 8) {
-            if (stages == 2) { if (p.b_kmajor) GO(128, 128, true, 2, 8); else GO(128, 128, false, 2, 8); }
-            if (stages == 3) { if (p.b_kmajor) GO(128, 128, true, 3, 8); else GO(128, 128, false, 3, 8); }
-            if (p.b_kmajor) GO(128, 128, true, 4, 8); else GO(128, 128, false, 4, 8);
-        }
-        if (stages == 2) { if (p.b_kmajor) GO(128, 128, true, 2, 4); else GO(128, 128, false, 2, 4); }
-        if (p.b_kmajor) GO(128, 128, true, 3, 4); else GO(128, 128, false, 3, 4);
+        if (stages == 2) { if (p.b_kmajor) GO(128, 128, true, 2, 8); else GO(128, 128, false, 2, 8); }
+        if (p.b_kmajor) GO(128, 128, true, 4, 8); else GO(128, 128, false, 4, 8);
     }
     if (stages == 2) { if (p.b_kmajor) GO(64, 64, true, 2, 4); else GO(64, 64, false, 2, 4); }
-    if (stages == 3) { if (p.b_kmajor) GO(64, 64, true, 3, 4); else GO(64, 64, false, 3, 4); }
     if (p.b_kmajor) GO(64, 64, true, 4, 4); else GO(64, 64, false, 4, 4);
 #undef GO
 }

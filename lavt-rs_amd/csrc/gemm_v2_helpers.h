@@ -9,6 +9,12 @@ using namespace lavt_gemm;
 
 namespace {
 
+// Dispatch constants shared by the NT dispatchers (gemm_v2.hip, gemm_nt_pipe.hip).
+// Workgroups of the 128x128 tile from which the 2-stage ring (two workgroups per CU) replaces the 4-stage one: more workgroups than the 256 CUs.
+constexpr long S2_MIN128 = 257;
+// Long reductions (K >= 4096) take the 128x128 tile from this many tiles up (below the general threshold of 200).
+constexpr long GEMM_BIG_LONG = 128;
+
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void gbl_void;
 

@@ -583,14 +583,12 @@ static int ln_bwd_geometry(int dtype, int rows, int C, int* lpr_out, int* cpl_ou
     // chip), so up to 1280 blocks run as ONE round.  (8-wave workgroups: two per CU -- 576 blocks (Video-Swin stage 2, 4608 rows) or 900 (stage 0)
     // were two rounds, 16.9 us for 19 MB; 4 waves x 2 serial rows: the second row's loads started after the first row's reductions.)
     // More rows than one round holds: two (or more, grid-stride) serial rows per wave.
-    int waves = 4;
+    const int waves = 4;
     const int rpb = 4 * (64 / lpr);
     int blocks = cdiv(rows, rpb);
     if (blocks > 1280) blocks = cdiv(rows, 2 * rpb);
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
-    const int old_geom = lavt_tuning().ln_bwd_waves;
-    if (old_geom == 8 && cpl <= 2 && rows > 256) { waves = 8; blocks = cdiv(rows, 8 * (64 / lpr)); if (blocks > 1024) blocks = 1024; }
     *lpr_out = lpr; *cpl_out = cpl;
     if (waves_out) *waves_out = waves;
     return blocks;
@@ -616,8 +614,7 @@ static int layernorm_bwd_impl(int dtype, const void* dy, const void* x, const in
 #define LN_BWD_F(LPR_, CPL_, WV_, F_) hipLaunchKernelGGL((layernorm_bwd_kernel<T, LPR_, CPL_, WV_, F_>), dim3(blocks), dim3(WV_ * 64), 0, st, (const T*)dy, (const T*)x, gather, gamma, mean, rstd, (T*)dx, dgamma, dbeta, partials, (const T*)dres, rows, C, (T*)xn_out, beta)
 #define LN_BWD(LPR_, CPL_, WV_) do { if (gather) LN_BWD_F(LPR_, CPL_, WV_, 1); else if (xn_out) LN_BWD_F(LPR_, CPL_, WV_, 2); else LN_BWD_F(LPR_, CPL_, WV_, 0); } while (0)
     DISPATCH_T(dtype, "lavt_layernorm_bwd",
-               if (waves == 8) { if (lpr == 16) LN_BWD(16, 1, 8); else if (lpr == 32) LN_BWD(32, 1, 8); else if (cpl == 1) LN_BWD(64, 1, 8); else LN_BWD(64, 2, 8); }
-               else if (lpr == 16) LN_BWD(16, 1, 4); else if (lpr == 32) LN_BWD(32, 1, 4);
+               if (lpr == 16) LN_BWD(16, 1, 4); else if (lpr == 32) LN_BWD(32, 1, 4);
                else if (cpl == 1) LN_BWD(64, 1, 4); else if (cpl == 2) LN_BWD(64, 2, 4); else if (cpl <= 4) LN_BWD(64, 4, 4); else LN_BWD(64, 8, 4));
 #undef LN_BWD
 #undef LN_BWD_F

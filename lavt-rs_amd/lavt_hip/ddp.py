@@ -169,9 +169,7 @@ class GradBuckets:
         return sum(4 * (e - s) for b, (s, e) in enumerate(self.buckets) if b != self.late_bucket)
 
     # ---- step protocol: zero() -> forward/backward -> finish() -------------------------------------------------
-    def zero(self, defer_fill=False, also_zero=None):
-        """defer_fill (step harness): the zero fill of the flat buffer is handed to lavt_hip.ops.fill_riders -- forward launches zero it slice by slice
-        with rider workgroups, and the harness calls ops.fill_riders.finish() before backward starts"""
+    def zero(self, also_zero=None):
         if self._relayout:          # learnt in the first step: parameters nothing reports during backward join the late bucket
             if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("GradBuckets: the bucket layout changes after the first step; run one eager step before capturing")
@@ -180,18 +178,13 @@ class GradBuckets:
                 from . import ops
                 ops.sinks.set(self.params, on_ready=self._on_grad)
         self._relayout = None
-        taken = False
-        if defer_fill:
-            from . import ops
-            taken = ops.fill_riders.begin(self.flat)
-        if not taken:
-            if self._zero_views is not None:
-                # everything but the parameters whose gradient launch overwrites its buffer (set_zero_skip); `also_zero`: a float32 tensor of the caller's
-                # (the step harness's arena of small zero-initialised buffers) cleared by the same multi-tensor launch
-                torch._foreach_zero_(self._zero_views + [also_zero] if also_zero is not None else self._zero_views)
-                also_zero = None
-            else:
-                self.flat.zero_()
+        if self._zero_views is not None:
+            # everything but the parameters whose gradient launch overwrites its buffer (set_zero_skip); `also_zero`: a float32 tensor of the caller's
+            # (the step harness's arena of small zero-initialised buffers) cleared by the same multi-tensor launch
+            torch._foreach_zero_(self._zero_views + [also_zero] if also_zero is not None else self._zero_views)
+            also_zero = None
+        else:
+            self.flat.zero_()
         if also_zero is not None:
             also_zero.zero_()
         lo, hi = self.flat.data_ptr(), self.flat.data_ptr() + self.flat.numel() * 4

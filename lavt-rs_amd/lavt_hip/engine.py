@@ -120,7 +120,7 @@ class TrainStep:
         if self.refresh_in_step:
             ops.weights.refresh_all()            # re-cast weights inside the step (for optimizers that do not maintain the compute copies)
         arena = ops.zero_arena.begin_step(self.x.device, defer=True)          # one fill for every small zero-initialised buffer of the step ...
-        self.buckets.zero(defer_fill=True, also_zero=arena)                    # ... shared with the gradient buffer's (the 475 MB fill of an unskipped buffer rides on forward launches: ops.fill_riders)
+        self.buckets.zero(also_zero=arena)                    # ... shared with the gradient buffer's
         ops.dtable_chain.job, ops.dtable_chain.keep = None, None          # (a backward that raised mid-way must not leave its binning job to the next step)
         if fp8_enabled():
             ops.fp8.advance()                    # delayed scaling: last step's |max| values become this step's quantisation scales
@@ -130,7 +130,6 @@ class TrainStep:
         else:
             out = self.model(self.x, self.l, self.m)
             loss = F.cross_entropy(out, self.t, weight=self.w)
-        ops.fill_riders.finish()                 # whatever of the gradient buffer no forward launch has zeroed
         if self._one is None or self._one.shape != loss.shape or self._one.dtype != loss.dtype:
             self._one = torch.ones_like(loss)    # (first eager step) the root gradient as a persistent tensor: `loss.backward()` fills a fresh ones_like every step,
         loss.backward(self._one)                 # one more 4.5 us launch on the captured chain

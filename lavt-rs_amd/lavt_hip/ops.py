@@ -348,40 +348,30 @@ fp8 = _Proxy("fp8")
 # fp8 contractions).  Measured on MI355X, Swin-B 4x480x480 against the reference's fp32 run: convolutions only -- pixel agreement 0.974, mask IoU on
 # decisive pixels 0.984, 18.73 ms/step (bf16 18.83); plus every Linear with >= 4096 rows (stages 0-1, qkv of stage 2) -- agreement 0.930, IoU on
 # decisive pixels 0.753 and 19.31 ms/step: per-tensor e4m3 on the early backbone features costs accuracy and, at one quantisation launch per
-# GEMM, time.  LAVT_FP8_LINEAR_MIN_ROWS=<rows> enables it for experiments.
-_FP8_LINEAR_MIN_ROWS = int(os.environ.get("LAVT_FP8_LINEAR_MIN_ROWS", str(1 << 30)))
+# GEMM, time.  (A module attribute: the tests lower it.)
+_FP8_LINEAR_MIN_ROWS = 1 << 30
 # e4m3 convolutions only where the problem fills the chip with 128x128 tiles (the pipelined fp8 kernel's smallest): below that -- the 30x30 maps of decoder
 # level 4 -- the fp8 launch falls to gemm_v2's 64x64 K loop (55 us at 4x30x30 against 44 us for the bf16 pipelined kernel) and buys nothing
-_FP8_CONV_MIN_TILES = int(os.environ.get("LAVT_FP8_CONV_MIN_TILES", "200"))
-
-
-_FP8_WGRAD = os.environ.get("LAVT_FP8_WGRAD", "1") != "0"          # e4m3 weight gradients of the fp8 convolutions (0: the bf16 fused-tap kernel)
+_FP8_CONV_MIN_TILES = 200
 
 
 def _fp8_conv_fills(M, N):
     return -(-M // 128) * -(-N // 128) >= _FP8_CONV_MIN_TILES
 
 
-_FP8_TWINS = os.environ.get("LAVT_FP8_TWINS", "1") != "0"          # producers write the e4m3 twin / record the gradient |max| (0: separate quantiser launches)
-
-
 def fp8_act_site(weight, M, C1, C2=0):
     """the quantisation site of the activations a 3x3 convolution with `weight` contracts in e4m3, or None when that convolution stays in bf16: what a
     producer of its first input passes to `bilinear(..., fp8_site=)` / `batch_norm_relu(..., fp8_site=)` to write the e4m3 twin itself"""
-    if not (_FP8_TWINS and fp8_enabled() and C1 % 16 == 0 and C2 % 16 == 0 and _fp8_conv_fills(M, weight.shape[0])):
+    if not (fp8_enabled() and C1 % 16 == 0 and C2 % 16 == 0 and _fp8_conv_fills(M, weight.shape[0])):
         return None
     return id(weight)
 
 
 def fp8_dy_site(weight, M, C1):
     """the site of the output gradient of the convolution with `weight` when its backward quantises it (e4m3 data gradient), else None"""
-    if not (_FP8_TWINS and fp8_enabled() and _FP8_DGRAD and weight.shape[0] % 16 == 0 and _fp8_conv_fills(M, C1)):
+    if not (fp8_enabled() and weight.shape[0] % 16 == 0 and _fp8_conv_fills(M, C1)):
         return None
     return (id(weight), "dy")
-
-
-# data gradients of the decoder's convolutions in e4m3 as well (dY quantised with current scaling against its own |max|); 0 = bf16 data gradients
-_FP8_DGRAD = os.environ.get("LAVT_FP8_DGRAD", "1") != "0"
 
 
 class _GradSinks:
@@ -469,8 +459,7 @@ def _scratch(n_floats, device):
     return torch.empty(int(n_floats), dtype=torch.float32, device=device)
 
 
-_PWAM_RECORDS = os.environ.get("LAVT_PWAM_RECORDS", "1") != "0"          # A/B switch: 0 = the round-5 launch sequence (word-side reductions as TN launches + their reduction launches)
-_TN_PARTIALS_MINK = int(os.environ.get("LAVT_TN_PARTIALS_MINK", "2048"))
+_TN_PARTIALS_MINK = 2048          # shortest reduction (rows) whose single weight-gradient launch is lent a partial-tile scratch
 
 
 def _tn_parts(n_floats, device):
@@ -497,7 +486,7 @@ class _ZeroArena:
     ~12 fill kernels of ~5 us per step, each a node of the captured chain.  Under the step harness they are carved from ONE arena whose used prefix
     (the high-water mark of the previous step) is zeroed by a single fill at the start of the step; a request the prefix cannot serve -- the first
     step, a different call sequence, a call outside the harness -- falls back to torch.zeros.  A buffer lives until the end of its step only."""
-    BYTES = int(os.environ.get("LAVT_ZERO_ARENA_MB", "64")) << 20
+    BYTES = 64 << 20
 
     def __init__(self):
         self.buf, self.off, self.hw, self.zeroed, self.active = None, 0, 0, 0, False
@@ -505,8 +494,6 @@ class _ZeroArena:
     def begin_step(self, device, defer=False):
         """defer: the used prefix is returned (as a float32 view) for the caller to zero with its own fill -- the step harness hands it to the gradient
         buffer's multi-tensor zero, one launch for both"""
-        if os.environ.get("LAVT_ZERO_ARENA", "1") == "0":
-            return None
         if self.buf is None or self.buf.device != device:
             self.buf = torch.empty(self.BYTES, dtype=torch.uint8, device=device)
             self.hw = 0
@@ -538,47 +525,6 @@ class _ZeroArena:
 
 
 zero_arena = _Proxy("zero_arena")
-
-
-class _FillRiders:
-    """The zero fill of the step's flat gradient buffer (475 MB for Swin-B: 58 us at the HBM rate) is needed by nothing before backward, yet as one
-    launch it headed the captured chain.  Under the step harness it is handed over here (begin) and consumed in 32 MB slices by the fused W-MSA forward
-    launches, which zero their slice with rider workgroups (lavt_wmsa_fwd_rider); finish() -- called between forward and backward -- zeroes whatever is
-    left with an ordinary fill (all of it for a model without such launches)."""
-    CHUNK = int(os.environ.get("LAVT_FILL_CHUNK_MB", "32")) << 20
-
-    def __init__(self):
-        self.buf, self.off = None, 0
-        # measured (round 4): 8.311 / 8.321 ms per step with the riders against 8.328 without -- a 32 MB slice of writes per launch slows the DMA-latency-bound
-        # forward launch by about what the stand-alone fill costs (the binning and LayerNorm riders read 7-13 MB per launch and are free).  Off by default.
-        self.enabled = os.environ.get("LAVT_FILL_RIDERS", "0") == "1"
-
-    def begin(self, flat):
-        """-> True when the buffer's zero fill has been taken over (the caller must not fill it itself)"""
-        if not self.enabled or not flat.is_cuda:
-            return False
-        self.buf, self.off = flat.view(torch.uint8), 0
-        return True
-
-    def take(self):
-        """-> (address, bytes) of the next slice to zero inside a launch, or (None, 0)"""
-        if self.buf is None:
-            return None, 0
-        n = min(self.CHUNK, ((self.buf.numel() - self.off) // 16) * 16)
-        if n <= 0:
-            return None, 0
-        ptr = self.buf.data_ptr() + self.off
-        self.off += n
-        return ptr, n
-
-    def finish(self):
-        if self.buf is not None:
-            if self.off < self.buf.numel():
-                self.buf[self.off:].zero_()
-            self.buf, self.off = None, 0
-
-
-fill_riders = _Proxy("fill_riders")
 
 
 def _zero_page_tensor(device):
@@ -696,18 +642,10 @@ def assign_partials(items, device):
                 off += nf
 
 
-_LN_RIDER = os.environ.get("LAVT_LN_RIDER", "1") != "0"
-
-
 def _launch_ln_partial(rider):
     dy_, x_, g_, mean_, rstd_, dx_, ws_, dres_, rows_, C_ = rider
     K.check(K.lib.lavt_layernorm_bwd_partial(K.dt(x_.dtype), K.ptr(dy_), K.ptr(x_), None, K.ptr(g_), K.ptr(mean_), K.ptr(rstd_), K.ptr(dx_), K.ptr(ws_), ws_.numel(),
                                              K.ptr(dres_), rows_, C_, K.stream()))
-
-
-# measured (round 4, tools/wgrad_sk_time.py): 70-78 us against 39.6 us for the 64x64-tile launch of the stage-2 block -- contiguous runs lose the L2 / MALL sharing
-# of operand panels between workgroups that sweep K together.  Off by default; the launch stays reachable for experiments.
-_STREAMK = os.environ.get("LAVT_WGRAD_STREAMK", "0") == "1"
 
 
 class _WgradQueue:
@@ -723,7 +661,7 @@ class _WgradQueue:
         self.pending = set()         # ids of parameters whose weight gradient is still queued (their autograd hook fires before the launch)
 
     def active(self):
-        return self.enabled and sinks.map and os.environ.get("LAVT_WGRAD_GROUP", "1") != "0"
+        return self.enabled and sinks.map
 
     def add(self, p, tensors, extra=False, rider=None):
         """extra: a side member (at most two per group: lavt_gemm_tn_grouped takes six problems) that does not count towards the four-member flush.
@@ -737,10 +675,8 @@ class _WgradQueue:
         # a member that brings a rider closes the group: it is the last weight gradient of its Swin block (qkv), so groups are the block's own four
         # members + side member -- without this the four-member count ran one member out of phase (fc1, proj, side, qkv of a block + fc2 of the next)
         # and the launch was issued from the next block's MLP backward, where no LayerNorm waits to ride
-        if self.primary == 4 or len(self.items) == 6 or (rider is not None and _LN_RIDER):
+        if self.primary == 4 or len(self.items) == 6 or rider is not None:
             self.flush(rider)
-        elif rider is not None:
-            _launch_ln_partial(rider)
 
     def notify(self, param):
         # The op returns None for this parameter's gradient, and PyTorch runs the parameter's post-accumulate hook all the same -- BEFORE the
@@ -753,10 +689,9 @@ class _WgradQueue:
         if not self.items and rider is not None:
             _launch_ln_partial(rider)
         if self.items:
-            if not _STREAMK:             # grouped members store plainly (direct tiles and the reduction of partial tiles alike) unless asked to accumulate
-                for q in self.items:
-                    if not q.accumulate:
-                        sinks.mark_assigned_ptr(q.C)
+            for q in self.items:         # grouped members store plainly (direct tiles and the reduction of partial tiles alike) unless asked to accumulate
+                if not q.accumulate:
+                    sinks.mark_assigned_ptr(q.C)
             assign_partials(self.items, next(t for t in self.keep[0] if t is not None).device)
             arr = (K.GemmTN * len(self.items))(*self.items)
             if K.prof.enabled:       # a grouped launch mixes scopes (qkv / proj with fc1 / fc2): the note carries the per-member flops and labels
@@ -764,28 +699,13 @@ class _WgradQueue:
                 K.prof.note = {"flops": sum(fl), "shape": "tn-grouped " + "+".join(f"{q.I}x{q.J}x{q.K}" for q in self.items),
                                "members": list(zip(self.scopes, fl))}
             n_items = len(self.items)
-            tensors = [t for tup in self.keep for t in tup if t is not None]
-            sk = int(K.lib.lavt_gemm_tn_grouped_sk_ws(arr, n_items)) if _STREAMK else 0
-            if sk:
-                # stream-K form (csrc/gemm_tn_v2.hip): 128x128 tiles, equal runs of K-tile iterations per persistent workgroup, split tiles through a scratch
-                dev = tensors[0].device
-                scr = _ctx.sk_scratch.get(dev)
-                if scr is None or scr.numel() < sk:
-                    scr = _ctx.sk_scratch[dev] = torch.empty(sk, dtype=torch.float32, device=dev)
-                K.check(K.lib.lavt_gemm_tn_grouped_sk(arr, n_items, K.ptr(scr), scr.numel(), K.stream()))
-                if rider is not None:
-                    _launch_ln_partial(rider)
-                self._after_flush()
-                return
-            if rider is not None and _LN_RIDER:
+            if rider is not None:
                 dy_, x_, g_, mean_, rstd_, dx_, ws_, dres_, rows_, C_ = rider
                 K.check(K.lib.lavt_gemm_tn_grouped_ln(arr, n_items, K.ptr(dy_), K.ptr(x_), K.ptr(g_), K.ptr(mean_), K.ptr(rstd_), K.ptr(dx_), K.ptr(ws_), ws_.numel(),
                                                       K.ptr(dres_), rows_, C_, K.stream()))
                 self._after_flush()
                 return
             K.check(K.lib.lavt_gemm_tn_grouped(arr, n_items, K.stream()))
-            if rider is not None:
-                _launch_ln_partial(rider)
         self._after_flush()
 
     def _after_flush(self):
@@ -800,23 +720,20 @@ class _WgradQueue:
 wgrads = _Proxy("wgrads")
 
 
-_LN_REDUCE_COMPACT = os.environ.get("LAVT_LN_REDUCE_COMPACT", "1") != "0"          # A/B switch: 0 = the (128 column blocks x sets) grid of round 3
-
-
 class _LnDeferred:
     """LayerNorm weight / bias gradients feed nothing but the gradient buffer, so under the step harness their per-workgroup partial sums are
     parked in a persistent arena and reduced by ONE launch at the end of backward (lavt_reduce_partials_multi) instead of one two-kernel
     reduction per LayerNorm (56 per Swin-B step, ~4.9 us each).  The arena offsets and the sink addresses repeat from step to step, so the
     device descriptor table is built once (outside a capture) and reused; a step whose sequence differs rebuilds it (not possible while
     capturing: that raises)."""
-    ARENA_FLOATS = int(os.environ.get("LAVT_LN_ARENA_M", "96")) << 20          # 384 MiB of the 288 GB: Swin-B needs 37 x 450 x 1024 + ... = 24 M floats, Video-Swin-B (4608 rows) 50 M; beyond it a LayerNorm reduces at once
+    ARENA_FLOATS = 96 << 20          # 384 MiB of the 288 GB: Swin-B needs 37 x 450 x 1024 + ... = 24 M floats, Video-Swin-B (4608 rows) 50 M; beyond it a LayerNorm reduces at once
 
     def __init__(self):
         self.arena, self.off, self.items, self.params, self.tables = None, 0, [], [], []
         self.desc, self.desc_key, self.tdesc, self.tdesc_key = None, None, None, None
 
     def active(self):
-        return wgrads.active() and os.environ.get("LAVT_LN_DEFER", "1") != "0"
+        return wgrads.active()
 
     def alloc(self, nfloats, device):
         if self.arena is None or self.arena.device != device:
@@ -848,7 +765,7 @@ class _LnDeferred:
                     raise RuntimeError("deferred table gradients: the step being captured differs from the warm-up steps")
                 self.tdesc = torch.tensor(self.tables, dtype=torch.int64).to(self.arena.device)
                 self.tdesc_key = key
-            if len(self.tables) <= 64 and _LN_REDUCE_COMPACT:
+            if len(self.tables) <= 64:
                 K.check(K.lib.lavt_attn_dtable_finish_multi_compact(K.ptr(self.tdesc), len(self.tables), max(t[3] for t in self.tables), sum(t[2] for t in self.tables), K.stream()))
             else:
                 K.check(K.lib.lavt_attn_dtable_finish_multi(K.ptr(self.tdesc), len(self.tables), max(t[3] for t in self.tables), max(t[2] for t in self.tables), K.stream()))
@@ -860,7 +777,7 @@ class _LnDeferred:
                     raise RuntimeError("deferred LayerNorm reductions: the step being captured differs from the warm-up steps (descriptor table would need a host copy)")
                 self.desc = torch.tensor(self.items, dtype=torch.int64).to(self.arena.device)
                 self.desc_key = key
-            K.check(K.lib.lavt_reduce_partials_multi(K.ptr(self.desc), len(self.items), sum(int(K.lib.lavt_reduce_partials_column_blocks(it[2])) for it in self.items) if _LN_REDUCE_COMPACT else 0, K.stream()))
+            K.check(K.lib.lavt_reduce_partials_multi(K.ptr(self.desc), len(self.items), sum(int(K.lib.lavt_reduce_partials_column_blocks(it[2])) for it in self.items), K.stream()))
         params = self.params
         self.items, self.params, self.off = [], [], 0
         for p in params:
@@ -880,12 +797,10 @@ class _DtableChain:
 
     def __init__(self):
         self.job, self.keep = None, None
-        self.enabled = os.environ.get("LAVT_DTABLE_CHAIN", "1") != "0"
-        self.ln_host = os.environ.get("LAVT_DTABLE_LN_HOST", "1") != "0"          # A/B switch: 0 = riders only in attention-backward launches
 
     def take_for_layernorm(self):
-        """the pending job for a LayerNorm-backward launch to carry (None: nothing pending / switched off); the caller reports back with done_by_layernorm()"""
-        return self.job if (self.job is not None and self.ln_host) else None
+        """the pending job for a LayerNorm-backward launch to carry (None: nothing pending); the caller reports back with done_by_layernorm()"""
+        return self.job
 
     def done_by_layernorm(self):
         self.job, self.keep = None, None
@@ -1016,8 +931,7 @@ class _Linear(torch.autograd.Function):
             xq, a_ptr = fp8.quantize(x, id(weight))
             gemm_nt(torch.uint8, M, N, Kd, xq, Kd, Wq, Kd, y, N, a_rowmap=o.in_map, bias=_f32(bias), row_scale=o.row_scale, row_scale_div=o.row_scale_div,
                     act=o.act, Cpre=pre, ldcpre=N, R=residual, ldr=N, c_rowmap=o.out_map, deq=(a_ptr, w_amax.data_ptr()))
-        elif (o.out_inv is not None and o.out_map is not None and o.in_map is None and out_rows < M and not o.zero_init
-              and os.environ.get("LAVT_TOKEN_ORDER_DGRAD", "1") != "0"):
+        elif (o.out_inv is not None and o.out_map is not None and o.in_map is None and out_rows < M and not o.zero_init):
             # windowed rows scattered back to tokens (proj): one GEMM row per TOKEN, its input row gathered through the inverse map -- the rows of
             # padded window positions (dropped by the scatter) are never computed, and the output is written densely
             gemm_nt(dtype, out_rows, N, Kd, x, Kd, Wc, Kd, y, N, a_rowmap=o.out_inv, bias=_f32(bias), row_scale=o.row_scale,
@@ -1053,8 +967,7 @@ class _Linear(torch.autograd.Function):
                 bbuf, bsink = sinks.buf(bias, (N,))
             binary = o.row_scale is not None and o.row_scale_value != 0.0
             grouped = wgrads.active() and wsink and (bbuf is None or bsink) and dtype == torch.bfloat16 and (o.row_scale is None or binary)
-            token_order = (o.out_inv is not None and o.out_map is not None and o.in_map is None and g.shape[0] < M and dtype == torch.bfloat16
-                           and os.environ.get("LAVT_TOKEN_ORDER_WGRAD", "1") != "0")
+            token_order = (o.out_inv is not None and o.out_map is not None and o.in_map is None and g.shape[0] < M and dtype == torch.bfloat16)
             if token_order and grouped:
                 # windowed rows scattered back to tokens (proj): dW = sum over the TOKENS of dy[t]^T x[inv[t]] -- the padded window positions (dy = 0
                 # there) drop out of the reduction: K = tokens instead of window rows (1800 instead of 2592 at stage 2, 450 instead of 1152 at stage 3)
@@ -1148,8 +1061,8 @@ def linear(x, weight, bias=None, residual=None, **kw):
 # The LayerNorm-folded MLP node keeps GELU'(pre) instead of pre for backward (LAVT_ACT_GELU_D / LAVT_ACT_STORED): the derivative shares the
 # activation's exponential in the fc1 epilogue (+2 fma per element), and the fc2 data gradient's epilogue becomes one multiply instead of an erf +
 # two exponentials per element (5 us of vector math on a 10 us GEMM at stage 2, tools/mlp_gemm_probe.py).  Only that launch is built with the
-# branch: compiled into every NT kernel's epilogue it made the whole step 0.16 ms slower (tools/ab_lib.sh).  LAVT_GELU_D=0: the pre-activation form.
-_GELU_FWD, _GELU_BWD = (K.ACT_GELU_D, K.ACT_STORED) if os.environ.get("LAVT_GELU_D", "1") != "0" else (K.ACT_GELU, K.ACT_GELU)
+# branch: compiled into every NT kernel's epilogue it made the whole step 0.16 ms slower (tools/ab_lib.sh).
+_GELU_FWD, _GELU_BWD = K.ACT_GELU_D, K.ACT_STORED
 
 
 @K.scoped
@@ -1449,7 +1362,7 @@ class _WindowAttn(torch.autograd.Function):
         pieces = int(K.lib.lavt_window_attn_bwd_pieces(K.dt(qkv.dtype), nwin, N, heads, ld)) if (ts and ln_deferred.active()) else 0
         parts = ln_deferred.alloc(pieces * heads * R, qkv.device) if pieces > 0 else None
         _note(f"wattn-bwd {nwin * N}x{Cc} N{N}", 10.0 * nwin * heads * N * N * 32)
-        if parts is not None and ws is not None and dtable_chain.enabled:
+        if parts is not None and ws is not None:
             dtable_chain.launch(qkv.dtype, qkv, ld, region, nw_img, out, dout, lse, dqkv, table, ws, parts, wd, wh, ww, nwin, N, heads, Cc // heads, scale)
         else:
             K.check(K.lib.lavt_window_attn_bwd(K.dt(qkv.dtype), K.ptr(qkv), K.ptr(dense), ld, K.ptr(region), nw_img, K.ptr(out), K.ptr(dout),
@@ -1591,11 +1504,9 @@ class _WmsaFused(torch.autograd.Function):
         nw_img = region.shape[0] if region is not None else 0
         scale = float((Cc // heads) ** -0.5)
         _note(f"wmsa {Mw}x{Cc} N{N}", 2.0 * Mw * Cc * 3 * Cc + 4.0 * nwin * heads * N * N * 32)
-        # (a launch that leaves resident slots free -- <= 400 (window, head) workgroups for 512 -- also zeroes a slice of the step's gradient buffer)
-        fptr, fbytes = fill_riders.take() if nwin * heads <= 400 else (None, 0)
         K.check(K.lib.lavt_wmsa_fwd_rider(K.ptr(x), K.ptr(wmap), K.ptr(Wg), K.ptr(wsum), K.ptr(biasp), K.ptr(_f32(bq)), K.ptr(_f32(gamma)), K.ptr(_f32(beta)), K.ptr(_f32(table)),
                                           K.ptr(region), nw_img, K.ptr(out), K.ptr(lse), K.ptr(qkv), K.ptr(xn), K.ptr(st[0]), K.ptr(st[1]), _zero_page(dev), ws, nwin, N,
-                                          heads, Cc, eps, scale, fptr, fbytes, K.stream()))
+                                          heads, Cc, eps, scale, None, 0, K.stream()))
         ctx.save_for_backward(x, gamma, beta, wq, bq, table, region, wmap, out, qkv, xn, lse, st)
         ctx.dims = (ws, heads, nwin, N, Cc, nw_img, scale, Mw)
         ctx.tok = tok if tok is not None else (None, None)
@@ -1618,7 +1529,7 @@ class _WmsaFused(torch.autograd.Function):
         pieces = int(K.lib.lavt_window_attn_bwd_pieces(K.dt(dtype), nwin, N, heads, ld)) if (ts and ln_deferred.active()) else 0
         parts = ln_deferred.alloc(pieces * heads * R, dev) if pieces > 0 else None
         _note(f"wattn-bwd {Mw}x{Cc} N{N}", 10.0 * nwin * heads * N * N * 32)
-        if parts is not None and wsb is not None and dtable_chain.enabled:
+        if parts is not None and wsb is not None:
             dtable_chain.launch(dtype, qkv, ld, region, nw_img, out, dout, lse, dqkv, table, wsb, parts, 1, ws_, ws_, nwin, N, heads, Cc // heads, scale)
         else:
             K.check(K.lib.lavt_window_attn_bwd(K.dt(dtype), K.ptr(qkv), None, ld, K.ptr(region), nw_img, K.ptr(out), K.ptr(dout), K.ptr(lse), K.ptr(dqkv), K.ptr(_f32(table)),
@@ -1633,7 +1544,7 @@ class _WmsaFused(torch.autograd.Function):
         Wc = weights.get(wq, dtype, "lin")
         dxn = torch.empty_like(x)
         inv, padrows = ctx.tok
-        if inv is not None and os.environ.get("LAVT_TOKEN_ORDER_DGRAD", "1") != "0":
+        if inv is not None:
             # token order: one output row per real token, its dqkv row gathered through the inverse window map (the rows of padded window
             # positions are never computed: 1800 instead of 2592 rows at stage 2, 450 instead of 1152 at stage 3)
             gemm_nt(dtype, M, Cc, 3 * Cc, dqkv, 3 * Cc, Wc, Cc, dxn, Cc, b_kmajor=True, a_rowmap=inv)
@@ -1656,7 +1567,7 @@ class _WmsaFused(torch.autograd.Function):
         wbuf, wsink = sinks.buf(wq, (3 * Cc, Cc))
         bbuf, bsink = sinks.buf(bq, (3 * Cc,))
         rode = False
-        if wgrads.active() and wsink and bsink and inv is not None and padrows.numel() > 0 and os.environ.get("LAVT_TOKEN_ORDER_WGRAD", "1") != "0":
+        if wgrads.active() and wsink and bsink and inv is not None and padrows.numel() > 0:
             # token order: dW = sum over the REAL tokens of dqkv[inv[t]]^T xn[t] (padded window positions have xn = 0: K = tokens instead of window
             # rows); their dq / dk / dv still belong to the bias gradient (the reference pads after norm1): a side member of the grouped launch sums
             # those rows alone (B = the zero page, 8 dummy columns), both column sums added atomically into the zeroed bias gradient
@@ -1691,7 +1602,7 @@ class _WmsaFused(torch.autograd.Function):
         return dx, g_g, g_be, g_w, g_b, g_table, None, None, None, None, None, None
 
 
-_WMSA_FUSED_MAX_C = int(os.environ.get("LAVT_WMSA_FUSED_MAX_C", "1024"))
+_WMSA_FUSED_MAX_C = 1024
 
 
 def wmsa_fused_ok(x, ws, heads, has_bias):
@@ -1810,9 +1721,6 @@ def syncbn_exchange_backward(s: torch.Tensor, group):
     return s
 
 
-_CONV_STATS = os.environ.get("LAVT_CONV_STATS", "1") != "0"
-
-
 class _ConvStats:
     """Column statistics that a convolution's epilogue stored beside its output (csrc/gemm_nt_pipe.hip: per block of rows the column sums and the second
     moments about the block's mean, from the fp32 accumulators): the BatchNorm that follows (reference lib/mask_predictor.py:60-97) combines the blocks
@@ -1850,12 +1758,11 @@ class StepContext:
         self.fp8 = _Fp8State()
         self.sinks = _GradSinks()
         self.zero_arena = _ZeroArena()
-        self.fill_riders = _FillRiders()
         self.wgrads = _WgradQueue()
         self.ln_deferred = _LnDeferred()
         self.dtable_chain = _DtableChain()
         self.conv_stats = _ConvStats()
-        self.tn_parts, self.sink_out, self.sk_scratch = {}, {}, {}          # per-device scratch of the split reductions (single-stream order within a context)
+        self.tn_parts, self.sink_out = {}, {}          # per-device scratch of the split reductions (single-stream order within a context)
         self.dp_state = {}                                                   # per-device DropPath generator (seed, draw counter)
 
     def __enter__(self):
@@ -2199,23 +2106,15 @@ class _PwamGate(torch.autograd.Function):
         _note(f"words {M}x{Cc}", 2.0 * M * Cc * KV_LD)
         lf = torch.empty(B * (2 * Cc + KV_LD + KV_LD * KV_LD), dtype=torch.float32, device=dev)
         beta, rw, pbar, cov = lf[:B * Cc], lf[B * Cc:2 * B * Cc], lf[2 * B * Cc:2 * B * Cc + B * KV_LD], lf[2 * B * Cc + B * KV_LD:]
-        rec, nrec = None, 0
-        if _PWAM_RECORDS:
-            # P^T P, colsum(P) as a by-product of the word kernel: per-workgroup records that the language kernel adds (no P^T P launch, no reduction launch)
-            nrec = int(K.lib.lavt_pwam_words_records(B, T, Cc))
-            rec = _scratch(B * nrec * (KV_LD * KV_LD + KV_LD), dev)
-            K.check(K.lib.lavt_pwam_words_fwd_moments(K.ptr(q), Cc, K.ptr(k), kld, K.ptr(mean), K.ptr(rstd), K.ptr(maskbias), K.ptr(P), K.ptr(rec), B, T, Cc, n_l, alpha, K.stream()))
-            PP = sumP = None
-        else:
-            K.check(K.lib.lavt_pwam_words_fwd(K.ptr(q), Cc, K.ptr(k), kld, K.ptr(mean), K.ptr(rstd), K.ptr(maskbias), K.ptr(P), B, T, Cc, n_l, alpha, K.stream()))
-            st = zero_arena.take(B * (KV_LD * KV_LD + KV_LD), torch.float32, dev)
-            PP, sumP = st[:B * KV_LD * KV_LD], st[B * KV_LD * KV_LD:]
-            gemm_tn(dtype, KV_LD, KV_LD, T, P, KV_LD, P, KV_LD, PP, KV_LD, batch=B, strideA=T * KV_LD, strideB=T * KV_LD, strideC=KV_LD * KV_LD, colsum=sumP, strideColsum=KV_LD)
+        # P^T P, colsum(P) as a by-product of the word kernel: per-workgroup records that the language kernel adds (no P^T P launch, no reduction launch)
+        nrec = int(K.lib.lavt_pwam_words_records(B, T, Cc))
+        rec = _scratch(B * nrec * (KV_LD * KV_LD + KV_LD), dev)
+        K.check(K.lib.lavt_pwam_words_fwd_moments(K.ptr(q), Cc, K.ptr(k), kld, K.ptr(mean), K.ptr(rstd), K.ptr(maskbias), K.ptr(P), K.ptr(rec), B, T, Cc, n_l, alpha, K.stream()))
         VWc = torch.empty(B, Cc, KV_LD, dtype=dtype, device=dev)
         VWw = torch.empty(B, KV_LD, Cc, dtype=dtype, device=dev)
         mm = torch.empty_like(vpre)
         _note(f"lang {B}x{Cc}")
-        K.check(K.lib.lavt_pwam_lang_fwd_records(K.ptr(v), kld, K.ptr(weights.get(Wo, dtype, "lin")), K.ptr(PP), K.ptr(sumP), K.ptr(rec), nrec, K.ptr(VWc), K.ptr(VWw),
+        K.check(K.lib.lavt_pwam_lang_fwd_records(K.ptr(v), kld, K.ptr(weights.get(Wo, dtype, "lin")), None, None, K.ptr(rec), nrec, K.ptr(VWc), K.ptr(VWw),
                                                  K.ptr(beta), K.ptr(rw), K.ptr(pbar), K.ptr(cov), B, T, Cc, 1e-5, K.stream()))
         _note(f"mix0 {M}x{Cc}", 2.0 * M * Cc * KV_LD)
         K.check(K.lib.lavt_pwam_mix(0, K.ptr(P), K.ptr(VWc), K.ptr(beta), None, K.ptr(_f32(bv)), K.ptr(vpre), Cc, None, 0, K.ptr(mm), Cc, None, 0, B, T, Cc, K.stream()))
@@ -2271,30 +2170,16 @@ class _PwamGate(torch.autograd.Function):
         _note(f"mix1 {M}x{Cc}", 2.0 * M * Cc * KV_LD)
         Qp = torch.empty(B * int(K.lib.lavt_pwam_q_parts(Cc)) * (KV_LD * KV_LD + KV_LD), dtype=torch.float32, device=dev)      # partial records, written plainly
         dVW = torch.empty(B * KV_LD, Cc, dtype=dtype, device=dev)
-        # one zeroed side buffer for the targets of the split reductions (partial tiles, then += the fixed-order sum): G, colsum(dS) (+ H^T, s on the round-5 path)
-        if _PWAM_RECORDS:
-            # H^T = dwhat^T P and colsum(dwhat) as a by-product of the mix kernel: per-workgroup records that the language kernel adds
-            nrec1 = int(K.lib.lavt_pwam_mix1_records(B, T, Cc))
-            rec1 = _scratch(B * nrec1 * Cc * (KV_LD + 1), dev)
-            K.check(K.lib.lavt_pwam_mix1(K.ptr(P), K.ptr(VWc), K.ptr(beta), K.ptr(_f32(bv)), K.ptr(vpre), Cc, K.ptr(dmm), Cc, K.ptr(g), 2 * Cc, K.ptr(dwh), Cc, K.ptr(rec1),
-                                         B, T, Cc, K.stream()))
-            z = zero_arena.take(B * (KV_LD * Cc + KV_LD), torch.float32, dev)
-            G, sdS = z[:B * KV_LD * Cc], z[B * KV_LD * Cc:]
-            _note(f"lang {B}x{Cc}")
-            K.check(K.lib.lavt_pwam_lang_bwd1_records(None, None, K.ptr(rec1), nrec1, K.ptr(VWc), K.ptr(rw), K.ptr(pbar), K.ptr(cov), K.ptr(dVW), K.ptr(Qp), B, T, Cc, K.stream()))
-        else:
-            K.check(K.lib.lavt_pwam_mix(1, K.ptr(P), K.ptr(VWc), K.ptr(beta), None, K.ptr(_f32(bv)), K.ptr(vpre), Cc, K.ptr(dmm), Cc, K.ptr(g), 2 * Cc, K.ptr(dwh), Cc,
-                                        B, T, Cc, K.stream()))
-            nz = B * (Cc * KV_LD + Cc + KV_LD * Cc + KV_LD)
-            z = zero_arena.take(nz, torch.float32, dev)
-            o = 0
-            HT = z[o:o + B * Cc * KV_LD]; o += B * Cc * KV_LD
-            s = z[o:o + B * Cc]; o += B * Cc
-            G = z[o:o + B * KV_LD * Cc]; o += B * KV_LD * Cc
-            sdS = z[o:o + B * KV_LD]
-            gemm_tn(dtype, Cc, KV_LD, T, dwh, Cc, P, KV_LD, HT, KV_LD, batch=B, strideA=T * Cc, strideB=T * KV_LD, strideC=Cc * KV_LD, colsum=s, strideColsum=Cc)
-            _note(f"lang {B}x{Cc}")
-            K.check(K.lib.lavt_pwam_lang_bwd1(K.ptr(HT), K.ptr(s), K.ptr(VWc), K.ptr(rw), K.ptr(pbar), K.ptr(cov), K.ptr(dVW), K.ptr(Qp), B, T, Cc, K.stream()))
+        # H^T = dwhat^T P and colsum(dwhat) as a by-product of the mix kernel: per-workgroup records that the language kernel adds
+        nrec1 = int(K.lib.lavt_pwam_mix1_records(B, T, Cc))
+        rec1 = _scratch(B * nrec1 * Cc * (KV_LD + 1), dev)
+        K.check(K.lib.lavt_pwam_mix1(K.ptr(P), K.ptr(VWc), K.ptr(beta), K.ptr(_f32(bv)), K.ptr(vpre), Cc, K.ptr(dmm), Cc, K.ptr(g), 2 * Cc, K.ptr(dwh), Cc, K.ptr(rec1),
+                                     B, T, Cc, K.stream()))
+        # one zeroed side buffer for the targets of the split reductions (partial tiles, then += the fixed-order sum): G, colsum(dS)
+        z = zero_arena.take(B * (KV_LD * Cc + KV_LD), torch.float32, dev)
+        G, sdS = z[:B * KV_LD * Cc], z[B * KV_LD * Cc:]
+        _note(f"lang {B}x{Cc}")
+        K.check(K.lib.lavt_pwam_lang_bwd1_records(None, None, K.ptr(rec1), nrec1, K.ptr(VWc), K.ptr(rw), K.ptr(pbar), K.ptr(cov), K.ptr(dVW), K.ptr(Qp), B, T, Cc, K.stream()))
         dS = torch.empty_like(P)
         _note(f"words {M}x{Cc}", 2.0 * M * (Cc + KV_LD) * KV_LD)
         K.check(K.lib.lavt_pwam_words_bwd(K.ptr(dwh), Cc, K.ptr(VWw), K.ptr(Qp), K.ptr(pbar), K.ptr(P), K.ptr(dS), B, T, Cc, K.stream()))
@@ -2709,10 +2594,10 @@ class _ConvTaps(torch.autograd.Function):
             x2q = fp8.quantize(x2, id(weight))[0] if x2 is not None else None
             st = gemm_nt(torch.uint8, M, Cout, taps * Cin, x1q, C1, Wq, taps * Cin, y, Cout, A2=x2q, lda2=C2, a_split=C1,
                          conv=(H, W, Cin, 0, D, kd, kh, kw), bias=_f32(bias), act=act, Cpre=pre, ldcpre=Cout, deq=(a_ptr, w_amax.data_ptr()),
-                         want_colstats=_CONV_STATS and stats and bias is None and act == K.ACT_NONE)
+                         want_colstats=stats and bias is None and act == K.ACT_NONE)
             if st is not None:          # (the pipelined e4m3 kernel has the statistics epilogue of the bf16 one)
                 conv_stats.put(y, st)
-            if _FP8_WGRAD and (kd, kh, kw) == (1, 3, 3) and bias is None and D == 1 and K.lib.lavt_conv3x3_wgrad_f8_ok(B, H, W, Cout, Cin, C1 if x2 is not None else Cin):
+            if (kd, kh, kw) == (1, 3, 3) and bias is None and D == 1 and K.lib.lavt_conv3x3_wgrad_f8_ok(B, H, W, Cout, Cin, C1 if x2 is not None else Cin):
                 ctx.fp8_x_amax = a_ptr          # the e4m3 copies stay alive for the weight gradient (half the bytes of the bf16 tensors beside them)
             else:
                 x1q = x2q = None
@@ -2731,7 +2616,7 @@ class _ConvTaps(torch.autograd.Function):
         else:
             st = gemm_nt(dtype, M, Cout, taps * Cin, x1, C1, Wp, taps * Cin, y, Cout, A2=x2, lda2=C2, a_split=C1,
                          conv=(H, W, Cin, 0, D, kd, kh, kw), bias=_f32(bias), act=act, Cpre=pre, ldcpre=Cout,
-                         want_colstats=_CONV_STATS and stats and bias is None and act == K.ACT_NONE)
+                         want_colstats=stats and bias is None and act == K.ACT_NONE)
             if st is not None:
                 conv_stats.put(y, st)
         ctx.save_for_backward(x1, x2, weight, bias, pre, x1q if ctx.fp8_x_amax else None, x2q if ctx.fp8_x_amax else None)
@@ -2757,7 +2642,7 @@ class _ConvTaps(torch.autograd.Function):
         if ctx.needs_input_grad[0] or (x2 is not None and ctx.needs_input_grad[1]):
             dx1 = torch.empty_like(x1)
             dx2 = torch.empty_like(x2) if x2 is not None else None
-            if dtype == torch.bfloat16 and fp8_enabled() and _FP8_DGRAD and Cout % 16 == 0 and C1 % 4 == 0 and C2 % 4 == 0 and _fp8_conv_fills(M, C1):
+            if dtype == torch.bfloat16 and fp8_enabled() and Cout % 16 == 0 and C1 % 4 == 0 and C2 % 4 == 0 and _fp8_conv_fills(M, C1):
                 # configs[4]: e4m3 dY (current scaling: its own |max|, computed in front of the quantiser) x the transposed e4m3 weight copy [Cin][taps][Cout] on the fp8 MFMA; a concat
                 # convolution runs as one launch per source (row blocks of the transposed weight), like the bf16 split below
                 WqT, w_amax = weights.get_fp8(weight, "conv3t")
@@ -2766,7 +2651,7 @@ class _ConvTaps(torch.autograd.Function):
                 for dxo, Cn, roff in ((dx1, C1, 0),) + (((dx2, C2, C1),) if x2 is not None else ()):
                     gemm_nt(torch.uint8, M, Cn, taps * Cout, dyq, Cout, WqT, taps * Cout, dxo, Cn, conv=(H, W, Cout, 1, D, kd, kh, kw),
                             b_off=roff * taps * Cout, deq=(a_ptr, w_amax.data_ptr()))
-            elif x2 is not None and C1 % 256 == 0 and C2 % 64 == 0 and dtype == torch.bfloat16 and os.environ.get("LAVT_DGRAD_SPLIT", "1") != "0":
+            elif x2 is not None and C1 % 256 == 0 and C2 % 64 == 0 and dtype == torch.bfloat16:
                 # concat convolution (conv1_2: 512 + 128 input channels): N = 640 is not a multiple of the 256-wide tile, so the whole data gradient
                 # fell back to 128x128 tiles (239 us at 2x120x120).  As two launches over column blocks of the packed weight the 512-channel part
                 # runs on the 256x256 tile and the skip part on its own.
@@ -2841,8 +2726,8 @@ class _ConvTaps(torch.autograd.Function):
                 None, None, None, None, None, None)
 
 
-# (round 5: 4096 -- decoder level 4 at batch 4 has 3600 rows: 11.37 -> 11.32 ms; 2048 was sized on batch 2; tools/r05_knob_sweep2.sh)
-_CONV_SPLIT_MAX_ROWS = int(os.environ.get("LAVT_CONV_SPLIT_ROWS", "4096"))
+# (round 5: 4096 -- decoder level 4 at batch 4 has 3600 rows: 11.37 -> 11.32 ms; 2048 was sized on batch 2)
+_CONV_SPLIT_MAX_ROWS = 4096
 
 
 def _conv_split(dtype, M, N, Kc, C1, C2, taps, bias, act):
@@ -2857,7 +2742,7 @@ def _conv_split(dtype, M, N, Kc, C1, C2, taps, bias, act):
     d = _kc_pieces(M, N, Kc) if taps == 9 else 0
     if d:
         return d, True
-    return (int(os.environ.get("LAVT_CONV_SPLIT_N", "3")) if taps == 9 else taps // 3), False
+    return taps // 3, False          # (tap groups of a kernel row / plane: 3 pieces for 3x3, 9 for 3x3x3)
 
 
 # Channel-block pieces of a few-pixel 3x3 convolution's reduction (0 = cut at tap boundaries instead: 3 pieces).  Measured on MI355X (tools/conv_small_probe.py,
@@ -2869,7 +2754,7 @@ _CONV_KC_SPLITS = os.environ.get("LAVT_CONV_KC_SPLITS", "auto")
 
 
 def _kc_pieces(M, N, Kc):
-    if _CONV_KC_SPLITS == "0" or os.environ.get("LAVT_GEMM_PIPE", "2") == "0" or os.environ.get("LAVT_GEMM_GENERAL") is not None or os.environ.get("LAVT_GEMM_V2", "1") == "0" or Kc % 64:
+    if _CONV_KC_SPLITS == "0" or os.environ.get("LAVT_GEMM_PIPE", "2") == "0" or Kc % 64:
         return 0
     cb, tiles = Kc // 64, -(-M // 128) * -(-N // 128)
     if _CONV_KC_SPLITS != "auto":

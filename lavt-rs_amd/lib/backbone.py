@@ -51,7 +51,7 @@ class _LangCtx:
 
     def kv(self, f_key, f_value):
         """-> (k, v, gradient sinks or None) for this module's projections"""
-        if self.plan is not None and os.environ.get("LAVT_KV_HOIST", "1") != "0":
+        if self.plan is not None:
             if self.kv_done is None:
                 self.kv_done = ops.kv_all(self.lt, self, self.plan)
             for (fk, fv), res in zip(self.plan, self.kv_done):

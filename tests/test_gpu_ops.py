@@ -593,15 +593,15 @@ def test_bilinear_row_staged_equals_element_indexed(B, C, Hi, Wi, Ho, Wo, monkey
     from lavt_hip import ops, _capi as K
     x = rnd(B * Hi * Wi, C, seed=1).to(torch.bfloat16).to(dev())
 
-    def run(probe):
-        monkeypatch.setenv("LAVT_PROBE", probe)
+    def run(rows):
+        monkeypatch.setenv("LAVT_BILINEAR_ROWS", rows)
         K.lib.lavt_tuning_reload()
         y = torch.empty(B * Ho * Wo, C, dtype=torch.bfloat16, device=dev())
         K.check(K.lib.lavt_bilinear_fwd(K.BF16, K.ptr(x), K.ptr(y), B, Hi, Wi, Ho, Wo, C, K.stream()))
         torch.cuda.synchronize()
         return y.cpu()
-    request.addfinalizer(lambda: (os.environ.pop("LAVT_PROBE", None), K.lib.lavt_tuning_reload()))
-    new, old = run("0,0,0,0,0,0,0,0"), run("0,0,0,0,0,0,0,1")
+    request.addfinalizer(lambda: (os.environ.pop("LAVT_BILINEAR_ROWS", None), K.lib.lavt_tuning_reload()))
+    new, old = run("1"), run("0")
     d = (new.float() - old.float()).abs()
     assert float((d / old.float().abs().clamp_min(1e-3)).max()) <= 2.0 ** -7 and float((d > 0).float().mean()) < 0.01
     ref = F.interpolate(x.float().cpu().view(B, Hi, Wi, C).permute(0, 3, 1, 2), size=(Ho, Wo), mode="bilinear", align_corners=True).permute(0, 2, 3, 1).reshape(B * Ho * Wo, C)

@@ -469,3 +469,32 @@ def test_fp8_twin_registry_and_sites_host_logic():
         st.end_step()
         assert not st.step_active and not st.twins and not st.dy_amax
     assert not ops._Fp8State().step_active, "a fresh state (an eager loop without the harness) never takes the producer path"
+
+
+def test_env_switch_table_matches_the_tree():
+    """Every LAVT_* environment variable the product reads -- getenv / env_int / env_is in csrc/, os.environ in lavt-rs_amd/**/*.py -- is a row of the
+    "Environment switches" table of INTEGRATION.md and the table names nothing else; the C library reads the environment in tuning.hip alone (no launch
+    path calls getenv); the anonymous LAVT_PROBE integers are gone."""
+    pkg = os.path.join(ROOT, "lavt-rs_amd")
+    csrc = os.path.join(pkg, "csrc")
+    read, getenv_files, probe_files = set(), set(), set()
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".hip", ".h")):
+            continue
+        text = open(os.path.join(csrc, name)).read()
+        read |= set(re.findall(r'\b(?:getenv|env_int|env_is)\(\s*"(LAVT_[A-Z0-9_]+)"', text))
+        if "getenv" in text:
+            getenv_files.add(name)
+        if "LAVT_PROBE" in text or "probe[" in text:
+            probe_files.add(name)
+    for d, _, files in os.walk(pkg):
+        for name in files:
+            if name.endswith(".py"):
+                text = open(os.path.join(d, name)).read()
+                read |= set(re.findall(r'os\.environ(?:\.\w+)?\s*[\(\[]\s*["\'](LAVT_[A-Z0-9_]+)["\']', text))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = doc.split("## Environment switches", 1)[1].split("\n## ", 1)[0]
+    table = set(re.findall(r"^\| `(LAVT_[A-Z0-9_]+)` \|", section, flags=re.M))
+    assert read == table, (sorted(read - table), sorted(table - read))
+    assert getenv_files == {"tuning.hip"}
+    assert not probe_files

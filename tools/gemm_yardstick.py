@@ -77,7 +77,7 @@ SHAPES = [
 
 
 # the same layer shapes at batch 4 (3600 rows) and in the video workload's stage 2 (4608 rows): the rows the ring-depth rule of the second session of round 5 changed
-# (`python tools/gemm_yardstick.py b4`; LAVT_PROBE=0,0,0,0,0,0,0,600 gives the old rule)
+# (`python tools/gemm_yardstick.py b4`)
 SHAPES_B4 = [
     ("fc1 s2 fwd b4", "nt", 3600, 2048, 512, 18), ("fc2 s2 fwd b4", "nt", 3600, 512, 2048, 18), ("proj s2 fwd b4", "nt", 3600, 512, 512, 18),
     ("d-fc2 s2 b4", "ntk", 3600, 2048, 512, 18), ("d-fc1 s2 b4", "ntk", 3600, 512, 2048, 18), ("d-qkv s2 b4", "ntk", 3600, 512, 1536, 18),

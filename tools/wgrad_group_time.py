@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Times the stage-2 grouped weight-gradient launch (tools/wgrad_group_one.py's four problems) under the tile configuration in LAVT_TNG_CFG
-("tile,waves,stages"), and checks the first and third members against a torch fp32 contraction."""
+"""Times the stage-2 grouped weight-gradient launch (tools/wgrad_group_one.py's four problems) and checks the first and third members against a
+torch fp32 contraction."""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "lavt-rs_amd"))
@@ -44,4 +44,4 @@ e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
 gr.replay(); torch.cuda.synchronize()
 e[0].record(); [gr.replay() for _ in range(10)]; e[1].record(); torch.cuda.synchronize()
 us = e[0].elapsed_time(e[1]) * 1e3 / 200
-print(f"cfg {os.environ.get('LAVT_TNG_CFG', '64,4,2'):8s}  {us:7.2f} us / launch  {flops / us * 1e-6:7.1f} TF/s  frac {flops / us * 1e-6 / 2500:.3f}   err {e0:.2e} {e2:.2e} colsum {c0:.2e}")
+print(f"{us:7.2f} us / launch  {flops / us * 1e-6:7.1f} TF/s  frac {flops / us * 1e-6 / 2500:.3f}   err {e0:.2e} {e2:.2e} colsum {c0:.2e}")

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Stage-1/2/3 grouped weight-gradient launches in token order (five members): the 64x64-tile grouped launch against the stream-K form
-(lavt_gemm_tn_grouped_sk), hipGraph-timed.  LAVT_PROBE=<runs> sets the number of persistent workgroups.  Run on the GPU box."""
+(lavt_gemm_tn_grouped_sk), hipGraph-timed.  Run on the GPU box."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "lavt-rs_amd")); sys.path.insert(0, os.path.join(ROOT, "tools"))
