@@ -626,6 +626,30 @@ int lavt_adamw_step_chunks_guarded(const int64_t* desc, const float* hyper, cons
                                    float* ctl, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Inference path (csrc/infer.hip; reference test.py:60-110 and test_ytvos.py:230-260: batch-1 forward under model.eval() / torch.no_grad(), argmax,
+ * I / U).  New symbols only, added under ABI v7: no existing prototype or struct changed.
+ *
+ * lavt_conv_bn_fold: an eval-mode BatchNorm folded into the convolution in front of it (lib/mask_predictor.py:61-66 and the five sibling
+ *   conv -> bn -> relu triples under eval()).  In fp32: s[co] = gamma[co] / sqrt(running_var[co] + eps);
+ *   w_packed[co][tap][ci] = dtype(w[co][ci][tap] * s[co]) -- the [Cout][taps][Cin] layout of lavt_pack_conv3x3 --
+ *   and bias[co] (fp32) = beta[co] - running_mean[co] * s[co].  gamma / beta NULL = 1 / 0.  dtype (of w_packed): LAVT_F32 or LAVT_BF16.
+ * lavt_splitk_reduce_epi: lavt_splitk_reduce (same partial layout, same summation order) with out = act(sum + bias[n]) before the store;
+ *   bias fp32 [N] or NULL, act = LAVT_ACT_NONE / GELU / RELU / TANH.  With it a split-K convolution carries the folded BatchNorm + ReLU;
+ *   bias NULL and LAVT_ACT_NONE store the bytes lavt_splitk_reduce stores.
+ * lavt_upsample_mask: the final upsample fused with the caller's argmax(1) and pixel counts (lib/_utils.py:21 + test.py:81-83, 242-246):
+ *   x = decoder logit rows [B*Hi*Wi][2] (dtype); mask uint8 [B][Ho][Wo] = (v1 > v0), a tie gives 0 as argmax does, where v is the bilinear
+ *   align_corners=True interpolation in fp32 with the coordinate arithmetic of lavt_logits_up_fwd.  Hm = Wm = 0: one interpolation
+ *   (Hi, Wi) -> (Ho, Wo); otherwise the composition (Hi, Wi) -> (Hm, Wm) -> (Ho, Wo) of test_ytvos.py:249-253 (the model's own upsample to the
+ *   network input size, then the caller's to the original frame size): the four corners on the intermediate grid are interpolated themselves,
+ *   no intermediate map is written.  target (optional) int64 [B][Ho][Wo], nonzero = foreground; with it iu int32 [B][2] receives
+ *   += sum(pred & gt), += sum(pred | gt) per sample through integer atomics: the CALLER zeroes iu in front of every launch. */
+int lavt_conv_bn_fold(const float* w, const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps, int dtype,
+                      void* w_packed, float* bias, int Cout, int Cin, int taps, void* stream);
+int lavt_splitk_reduce_epi(int dtype, const float* parts, int splits, int64_t M, int N, const float* bias, int act, void* out, int64_t ldc, void* stream);
+int lavt_upsample_mask(int dtype, const void* x, int B, int Hi, int Wi, int Hm, int Wm, int Ho, int Wo, uint8_t* mask, const int64_t* target, int32_t* iu,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Text side (lavt_one / lavt_video carry BERT inside the model: lib/_utils.py:38-52; train.py:595-602; the encoder is HF transformers
  * 3.0.2 `BertModel`, absent from the reference tree).  Its Linear / LayerNorm / GELU / attention GEMMs use the entry points above.
  * lavt_bert_embed_fwd: out[r] = word[ids[r]] + type[token_type ? token_type[r] : 0] + pos[r % N]  (BertEmbeddings.forward before LayerNorm;

@@ -254,6 +254,9 @@ _PROTOTYPES = {
     "lavt_nhwc_to_nchw": [i32, vp, i32, vp, i32, i32, i32, vp],
     "lavt_pack_conv3x3": [vp, i32, vp, i32, i32, i32, vp],
     "lavt_cast_multi": [vp, i32, i32, vp],
+    "lavt_conv_bn_fold": [vp, vp, vp, vp, vp, f32, i32, vp, vp, i32, i32, i32, vp],
+    "lavt_splitk_reduce_epi": [i32, vp, i32, i64, i32, vp, i32, vp, i64, vp],
+    "lavt_upsample_mask": [i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
 }
 for _name, _args in _PROTOTYPES.items():
     _fn = getattr(_cdll, _name)          # AttributeError here = header/library mismatch: fail loudly

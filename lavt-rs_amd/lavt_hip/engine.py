@@ -255,3 +255,108 @@ class TrainStep:
         else:
             self.loss = self._body()
         return self.loss
+
+
+class Predictor:
+    """The inference sibling of TrainStep: the reference's evaluation loop body (test.py:60-83, test_ytvos.py:230-260)
+
+        model.eval(); with torch.no_grad(): out = model(image, l, l_mask); mask = out.argmax(1); I, U = computeIoU(mask, target)
+
+    as one captured launch sequence: forward_lowres(folded=True, expand=S) -> ops.upsample_mask.  The BatchNorm layers of the decoder live in the
+    convolution weights, the full-resolution logits are never written, the mask leaves as uint8 and the pixel counts as 2 integers per sample.
+
+    image, lang, l_mask (and target) are STATIC device buffers: copy each sample into them, call step(), read `.mask` / `.iu`.
+      lang        language features (B*S, 768, N_l) for LAVT; token ids (B*S, N_l) for LAVTOne / LAVTVideo (BERT runs inside the model)
+      l_mask      (B*S, N_l, 1) for LAVT, (B*S, N_l) for LAVTOne / LAVTVideo -- what the model's forward takes
+      target      optional int64 (B*S, Ho, Wo) ((B*T, Ho, Wo) for video), nonzero = foreground: `.iu` int32 (., 2) then holds per-sample I and U
+      out_size    (Ho, Wo) of the mask, default = the network input size; via_size = (Hm, Wm): the two-stage interpolation of test_ytvos.py:249-253
+                  (network input size first, then the original frame size)
+      expressions_per_image   S: `image` holds B images, lang / l_mask B*S expressions (expression j of image i at i*S + j), mask sample i*S + j;
+                  patch embedding and the stage-0 Swin blocks run once per image
+    step() never synchronises: it returns the static mask tensor, the caller decides when to read it (EvalMeter.update(pred.iu) reads `.iu`)."""
+
+    def __init__(self, model, image, lang, l_mask, *, target=None, out_size=None, via_size=None, expressions_per_image=1, use_graph=True, context=None):
+        if model.training:
+            raise RuntimeError("Predictor: the model is in training mode -- call model.eval() first (BatchNorm is folded from the running statistics, DropPath is off)")
+        for name, t in (("image", image), ("lang", lang), ("l_mask", l_mask), ("target", target)):
+            if t is not None and not t.is_cuda:
+                raise RuntimeError(f"liblavt_hip operates on GPU memory only (got a CPU tensor for `{name}`); there is no CPU fallback")
+        if not hasattr(model, "forward_lowres"):
+            raise TypeError("Predictor: the model has no forward_lowres (LAVT, LAVTOne, LAVTVideo have)")
+        S = int(expressions_per_image)
+        if S < 1:
+            raise ValueError("Predictor: expressions_per_image must be >= 1")
+        if S > 1 and not getattr(model.backbone, "shares_stage0", False):
+            raise NotImplementedError(f"Predictor: expressions_per_image > 1 needs a backbone that shares stage 0 between expressions; {type(model.backbone).__name__} does not")
+        if lang.shape[0] != image.shape[0] * S:
+            raise ValueError(f"Predictor: {lang.shape[0]} expressions for {image.shape[0]} images x {S} expressions per image")
+        self.context = context if context is not None else ops.default_context()
+        self.model, self.x, self.l, self.m, self.t = model, image, lang, l_mask, target
+        self.S = S
+        self.in_size = (int(image.shape[-2]), int(image.shape[-1]))
+        self.out_size = (int(out_size[0]), int(out_size[1])) if out_size is not None else self.in_size
+        self.via_size = (int(via_size[0]), int(via_size[1])) if via_size is not None else None
+        self.use_graph = use_graph
+        self.graph = None
+        self.captured = False
+        self.mask = None                         # uint8 (samples, Ho, Wo): static once captured
+        self.iu = None                           # int32 (samples, 2) with a target, else None
+        # a replay runs no Python: neither the weight cache's version checks nor the BatchNorm fold's.  step() compares this stamp over parameters AND
+        # buffers (the running statistics are folded into weights) and re-casts / re-folds eagerly, into the same storage, when anything moved
+        self._state = [t for t in list(model.parameters()) + list(model.buffers())]
+        self._seen = None
+
+    def _stamp(self):
+        return sum(t._version for t in self._state), sum(t.data_ptr() for t in self._state)
+
+    @_in_context
+    def _body(self):
+        with torch.no_grad():
+            y = self.model.forward_lowres(self.x, self.l, self.m, folded=True, expand=self.S)
+            n, _, h, w = y.shape
+            from lib.mask_predictor import nchw_rows
+            self.mask, self.iu = ops.upsample_mask(nchw_rows(y, y.dtype), n, h, w, self.out_size, via_size=self.via_size, target=self.t)
+        return self.mask
+
+    @_in_context
+    def warmup_and_capture(self, eager_iters=2):
+        """eager_iters eager runs on a side stream (every compute copy and row map exists afterwards), then -- use_graph -- the body is captured into one
+        torch.cuda.CUDAGraph on that stream: a straight-line sequence, no forked branches.  A failed capture is reported and the eager path kept."""
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for it in range(max(int(eager_iters), 1)):
+                self._body()
+                if it == 0:
+                    ops.weights.build_multicast(compute_dtype())
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        self._seen = self._stamp()
+        if not self.use_graph:
+            return
+        self.captured = False
+        try:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                self._body()
+            self.graph, self.captured = g, True
+        except Exception as e:                                   # noqa: BLE001  (report and keep the eager path)
+            print(f"[lavt_hip.engine] hipGraph capture of the prediction step failed, running eagerly: {type(e).__name__}: {e}", file=sys.stderr)
+            self.graph = None
+            torch.cuda.synchronize()
+
+    @_in_context
+    def step(self):
+        """-> the mask tensor (static when captured).  No host synchronisation."""
+        if self.model.training:
+            raise RuntimeError("Predictor.step: the model was put back into training mode")
+        stamp = self._stamp()
+        if stamp != self._seen:
+            if self._seen is not None:
+                ops.weights.refresh_all()          # casts, LayerNorm folds and BatchNorm folds, eagerly, into the storage the graph reads
+            self._seen = stamp
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._body()
+        return self.mask

@@ -140,6 +140,35 @@ class _WeightCache:
         self.store[key] = (stamp, (Wg, wsum, biasp, [weakref.ref(p) for p in ps]), weakref.ref(w))
         return Wg, wsum, biasp
 
+    def get_bnfold(self, conv_weight, bn, dtype: torch.dtype):
+        """(w_packed `dtype` [Cout, taps * Cin], bias fp32 [Cout]) of a convolution whose output goes straight into the eval-mode BatchNorm `bn`
+        (lavt_conv_bn_fold): the normalisation is a per-channel constant, it lives in the weights.  Refreshed like every compute copy (refresh_all /
+        a version or address change of the weight, gamma, beta, running_mean or running_var), always into the same storage.  A BatchNorm without
+        running statistics has nothing to fold: ValueError, the caller keeps the unfolded path."""
+        if bn.running_mean is None or bn.running_var is None:
+            raise ValueError("get_bnfold: the BatchNorm keeps no running statistics (track_running_stats=False): nothing to fold")
+        key = (id(conv_weight), dtype, "bnfold")
+        ent = self.store.get(key)
+        if ent is not None and (ent[2]() is not conv_weight or ent[1][2]() is not bn):
+            ent = None
+        ps = (conv_weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        stamp = (tuple(-1 if p is None else p._version for p in ps), tuple(0 if p is None else p.data_ptr() for p in ps), self.epoch)
+        if ent is not None and ent[0] == stamp:
+            return ent[1][:2]
+        w = conv_weight.detach()
+        Cout, Cin = w.shape[0], w.shape[1]
+        taps = w.numel() // (Cout * Cin)
+        if ent is not None and tuple(ent[1][0].shape) == (Cout, taps * Cin):
+            Wp, bias = ent[1][:2]
+        else:
+            Wp = torch.empty(Cout, taps * Cin, dtype=dtype, device=w.device)
+            bias = torch.empty(Cout, dtype=torch.float32, device=w.device)
+            self.generation += 1
+        K.check(K.lib.lavt_conv_bn_fold(K.ptr(_f32(w.contiguous())), K.ptr(_f32(bn.weight)), K.ptr(_f32(bn.bias)), K.ptr(_f32(bn.running_mean)), K.ptr(_f32(bn.running_var)),
+                                        float(bn.eps), K.dt(dtype), K.ptr(Wp), K.ptr(bias), Cout, Cin, taps, K.stream()))
+        self.store[key] = (stamp, (Wp, bias, weakref.ref(bn)), weakref.ref(conv_weight))
+        return Wp, bias
+
     def get_cat(self, ps, dtype: torch.dtype) -> torch.Tensor:
         """[sum N_i, K] compute copy of several Linear weights stacked along N (BERT's query / key / value): the per-parameter 'lin' entries
         become row slices of ONE buffer, so the usual refresh (get / refresh_all's multi-cast) keeps the stacked matrix current for free."""
@@ -226,6 +255,12 @@ class _WeightCache:
                 bs = [r() for r in out[1]]
                 if all(b is not None for b in bs):
                     self.get_bias_cat(bs)
+                else:
+                    del self.store[k]
+            elif k[2] == "bnfold":
+                bn = out[2]()
+                if bn is not None and bn.running_mean is not None:
+                    self.get_bnfold(p, bn, k[1])
                 else:
                     del self.store[k]
             elif k[1] == "lnfold":
@@ -2730,12 +2765,13 @@ class _ConvTaps(torch.autograd.Function):
 _CONV_SPLIT_MAX_ROWS = 4096
 
 
-def _conv_split(dtype, M, N, Kc, C1, C2, taps, bias, act):
+def _conv_split(dtype, M, N, Kc, C1, C2, taps, bias, act, epilogue_in_reduce=False):
     """-> (pieces, over_channels): the number of pieces a convolution's reduction is cut into (0 = not split) and whether they are channel blocks
     (lavt_gemm_nt_t.conv_kc_split) or tap groups (conv_tap_split): bf16 tap-walking problems (channels % 64 == 0) without a fused epilogue, few rows
     (<= 2048: the fp32 partials are M x N x pieces x 4 bytes written and re-read) and a long reduction"""
     # (callers ask only for convolutions that stay bf16: in fp8 mode the e4m3 branches are tried first, and the maps they leave in bf16 -- decoder level 4 -- split like in bf16 mode)
-    if dtype != torch.bfloat16 or bias is not None or act != K.ACT_NONE or M > _CONV_SPLIT_MAX_ROWS or taps % 3 or taps > 27:
+    # epilogue_in_reduce: the caller reduces with lavt_splitk_reduce_epi, which adds the bias and applies the activation -- neither rules the split out
+    if dtype != torch.bfloat16 or ((bias is not None or act != K.ACT_NONE) and not epilogue_in_reduce) or M > _CONV_SPLIT_MAX_ROWS or taps % 3 or taps > 27:
         return 0, False
     if Kc % 64 or C1 % 64 or C2 % 64 or N % 8 or taps * Kc < 4096:
         return 0, False
@@ -2767,6 +2803,44 @@ def _kc_pieces(M, N, Kc):
 def conv3x3(x1, x2, weight, B, H, W):
     # under autograd (training) the launch also leaves the column statistics of its output for the BatchNorm that follows (ops.conv_stats)
     return _ConvTaps.apply(x1, x2, weight, None, B, 1, H, W, K.ACT_NONE, torch.is_grad_enabled())
+
+
+def conv3x3_bn_relu_folded(x1, x2, conv, bn, B, H, W):
+    """Inference only (no autograd node): relu(bn(conv([x1, x2]))) of an eval-mode `bn` as ONE convolution with the BatchNorm folded into the packed weight
+    (weights.get_bnfold) and `+ bias -> ReLU` in the GEMM epilogue (lib/mask_predictor.py:61-66 under eval()).  Where the plain convolution would split its
+    reduction (_conv_split) the folded one does too: the partials are summed by lavt_splitk_reduce_epi, which carries the bias and the ReLU."""
+    if bn.training:
+        raise RuntimeError("conv3x3_bn_relu_folded: the BatchNorm is in training mode (batch statistics cannot be folded)")
+    if conv.bias is not None:
+        raise NotImplementedError("conv3x3_bn_relu_folded: convolutions without bias (the decoder's)")
+    x1 = x1.contiguous()
+    dtype = x1.dtype
+    C1, C2 = x1.shape[1], 0
+    if x2 is not None:
+        x2 = x2.contiguous()
+        C2 = x2.shape[1]
+    weight = conv.weight
+    Cout, Cin = weight.shape[0], weight.shape[1]
+    kh, kw = weight.shape[2:]
+    taps = kh * kw
+    assert Cin == C1 + C2, f"conv: weight expects {Cin} input channels, got {C1}+{C2}"
+    Wp, bias = weights.get_bnfold(weight, bn, dtype)
+    M = B * H * W
+    y = torch.empty(M, Cout, dtype=dtype, device=x1.device)
+    geom = (H, W, Cin, 0, 1, 1, kh, kw)
+    sp, over_ch = _conv_split(dtype, M, Cout, Cin, C1, C2, taps, bias, K.ACT_RELU, epilogue_in_reduce=True)
+    if sp:
+        parts = torch.empty(sp, M, Cout, dtype=torch.float32, device=x1.device)
+        if over_ch:
+            gemm_nt(dtype, M, Cout, taps * (Cin // sp), x1, C1, Wp, taps * Cin, parts, Cout, A2=x2, lda2=C2, a_split=C1, conv=geom,
+                    batch=sp, strideC=M * Cout, c_f32=True, conv_kc_split=Cin // sp)
+        else:
+            gemm_nt(dtype, M, Cout, (taps // sp) * Cin, x1, C1, Wp, taps * Cin, parts, Cout, A2=x2, lda2=C2, a_split=C1, conv=geom,
+                    batch=sp, strideB=(taps // sp) * Cin, strideC=M * Cout, c_f32=True, conv_tap_split=taps // sp)
+        K.check(K.lib.lavt_splitk_reduce_epi(K.dt(dtype), K.ptr(parts), sp, M, Cout, K.ptr(bias), K.ACT_RELU, K.ptr(y), Cout, K.stream()))
+    else:
+        gemm_nt(dtype, M, Cout, taps * Cin, x1, C1, Wp, taps * Cin, y, Cout, A2=x2, lda2=C2, a_split=C1, conv=geom, bias=bias, act=K.ACT_RELU)
+    return y
 
 
 def conv3d(x, weight, bias, B, D, H, W, act=K.ACT_NONE):
@@ -2948,3 +3022,26 @@ class _UpsampleDice(torch.autograd.Function):
 
 def upsample_dice_loss(x, target, B, Hi, Wi, Ho, Wo):
     return _UpsampleDice.apply(x, target, B, Hi, Wi, Ho, Wo)
+
+
+# ------------------------------------------------------------------------------------------ fused upsample + argmax (+ I/U counts): inference
+def upsample_mask(rows, B, Hi, Wi, out_size, via_size=None, target=None):
+    """`F.interpolate(y, out_size, bilinear, align_corners=True).argmax(1)` (lib/_utils.py:21 + test.py:81-83) on the decoder's 2-class logit rows
+    [B*Hi*Wi, 2] without writing the upsampled logits: -> (mask uint8 [B, Ho, Wo], iu).  via_size = (Hm, Wm): the composition of two interpolations
+    (Hi, Wi) -> via_size -> out_size of test_ytvos.py:249-253.  target (int64 [B, Ho, Wo], nonzero = foreground): iu int32 [B, 2] = per-sample
+    (sum(pred & gt), sum(pred | gt)) of test.py:242-246, zeroed here in front of every launch (a fill node of a captured sequence); else iu is None."""
+    rows = rows.contiguous()
+    Ho, Wo = int(out_size[0]), int(out_size[1])
+    Hm, Wm = (int(via_size[0]), int(via_size[1])) if via_size is not None else (0, 0)
+    if rows.shape != (B * Hi * Wi, 2):
+        raise ValueError(f"upsample_mask: expected [{B * Hi * Wi}, 2] logit rows, got {tuple(rows.shape)}")
+    mask = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=rows.device)
+    iu = None
+    if target is not None:
+        if target.dtype != torch.int64 or tuple(target.shape) != (B, Ho, Wo):
+            raise ValueError(f"upsample_mask: target must be int64 [{B}, {Ho}, {Wo}], got {target.dtype} {tuple(target.shape)}")
+        target = target.contiguous()
+        iu = torch.zeros(B, 2, dtype=torch.int32, device=rows.device)
+    _note(f"upsample-mask {B}x{Hi}x{Wi}->{Ho}x{Wo}", nbytes=rows.numel() * rows.element_size() + mask.numel() + (8 * mask.numel() if target is not None else 0))
+    K.check(K.lib.lavt_upsample_mask(K.dt(rows.dtype), K.ptr(rows), B, Hi, Wi, Hm, Wm, Ho, Wo, K.ptr(mask), K.ptr(target), K.ptr(iu), K.stream()))
+    return mask, iu

@@ -38,16 +38,22 @@ def fused_dice_loss(y, target):
     return ops.upsample_dice_loss(nchw_rows(y, y.dtype), target, B, h, w, int(target.shape[-2]), int(target.shape[-1]))
 
 
+def _decode(classifier, folded, x_c4, x_c3, x_c2, x_c1):
+    return classifier.forward_folded(x_c4, x_c3, x_c2, x_c1) if folded else classifier(x_c4, x_c3, x_c2, x_c1)
+
+
 class _LAVTSimpleDecode(nn.Module):
     def __init__(self, backbone, classifier):
         super().__init__()
         self.backbone = backbone
         self.classifier = classifier
 
-    def forward_lowres(self, x, l_feats, l_mask):
-        """decoder output before the final upsample, (B, 2, H/4, W/4)-shaped: feed it to `fused_loss`"""
-        x_c1, x_c2, x_c3, x_c4 = self.backbone(x, l_feats, l_mask)
-        return self.classifier(x_c4, x_c3, x_c2, x_c1)
+    def forward_lowres(self, x, l_feats, l_mask, folded=False, expand=1):
+        """decoder output before the final upsample, (B, 2, H/4, W/4)-shaped: feed it to `fused_loss`.
+        Inference (lavt_hip.engine.Predictor): folded = the BatchNorm-folded decoder (eval mode); expand = S > 1 = S expressions per image (l_feats /
+        l_mask hold B * S of them), stage 0 of the backbone shared between the expressions of an image."""
+        x_c1, x_c2, x_c3, x_c4 = self.backbone(x, l_feats, l_mask, expand=expand) if expand != 1 else self.backbone(x, l_feats, l_mask)
+        return _decode(self.classifier, folded, x_c4, x_c3, x_c2, x_c1)
 
     def forward(self, x, l_feats, l_mask):
         return _upsample_logits(self.forward_lowres(x, l_feats, l_mask), x.shape[-2:])
@@ -85,16 +91,17 @@ class _LAVTOneSimpleDecode(nn.Module):
         self.text_encoder = _build_text_encoder(args)
         self.lazy_pred = bool(getattr(args, "lazy_pred", False))
 
-    def forward_lowres(self, x, text, l_mask):
-        """token ids (B, N_l) + attention mask (B, N_l) -> decoder logits at 1/4 resolution (what the fused upsample + CE kernel consumes)"""
+    def forward_lowres(self, x, text, l_mask, folded=False, expand=1):
+        """token ids (B, N_l) + attention mask (B, N_l) -> decoder logits at 1/4 resolution (what the fused upsample + CE kernel consumes).
+        folded / expand: see LAVT.forward_lowres (with expand = S the ids and the mask hold B * S expressions)."""
         l_feats = self.text_encoder(text, attention_mask=l_mask)[0].permute(0, 2, 1)      # (B, 768, N_l)
         l_mask = l_mask.unsqueeze(dim=-1)
-        features = self.backbone(x, l_feats, l_mask)
+        features = self.backbone(x, l_feats, l_mask, expand=expand) if expand != 1 else self.backbone(x, l_feats, l_mask)
         if self.lazy_pred:
             x_c1, (x_c2, x_c3, x_c4) = None, features
         else:
             x_c1, x_c2, x_c3, x_c4 = features
-        return self.classifier(x_c4, x_c3, x_c2, x_c1)
+        return _decode(self.classifier, folded, x_c4, x_c3, x_c2, x_c1)
 
     def forward(self, x, text, l_mask):
         return _upsample_logits(self.forward_lowres(x, text, l_mask), x.shape[-2:])
@@ -132,6 +139,17 @@ class _LAVTVideoSimpleDecode(nn.Module):
     def forward(self, x, text, l_mask):
         l_feats = self.text_encoder(text, attention_mask=l_mask)[0].permute(0, 2, 1)      # (B, 768, N_l)
         return self.forward_backbone(x, l_feats, l_mask.unsqueeze(dim=-1))
+
+    def forward_lowres(self, x, text, l_mask, folded=False, expand=1):
+        """clip (B, T, 3, H, W) + token ids + attention mask -> decoder logits (B*T, 2, H/4, W/4)-shaped, before the final upsample.
+        folded: the BatchNorm-folded decoder (eval mode).  The video backbone has no shared stage 0: expand > 1 raises NotImplementedError."""
+        l_feats = self.text_encoder(text, attention_mask=l_mask)[0].permute(0, 2, 1)
+        features = self.backbone(x.permute(0, 2, 1, 3, 4), l_feats, l_mask.unsqueeze(dim=-1), expand=expand)
+        if self.lazy_pred:
+            x_c1, (x_c2, x_c3, x_c4) = None, features
+        else:
+            x_c1, x_c2, x_c3, x_c4 = features
+        return _decode(self.classifier, folded, x_c4, x_c3, x_c2, x_c1)
 
     def forward_feats(self, x, text, l_mask):
         """Reference lib/_utils.py:110-131: -> (logits (B*T, 2, H, W) fp32, [x_c4, level-4, level-3, level-2 decoder features])."""

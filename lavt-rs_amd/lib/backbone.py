@@ -327,10 +327,18 @@ class MMBasicLayer(nn.Module):
         return []
 
     def forward(self, x, H, W, l, l_mask):
-        B, L, C = x.shape
+        return self.fuse_language(self.run_blocks(x, H, W), H, W, l, l_mask)
+
+    def run_blocks(self, x, H, W):
+        """first half of forward: the Swin blocks (they never see the language side)"""
         for blk in self.blocks:
             blk.H, blk.W = H, W
             x = blk(x)
+        return x
+
+    def fuse_language(self, x, H, W, l, l_mask):
+        """second half of forward: PWAM, language gate, PatchMerging on the blocks' output"""
+        B, L, C = x.shape
         x2 = xin = x.reshape(B * L, C)
         lang = _LangCtx.get(l, l_mask, x.dtype)
         with scope("pwam"):
@@ -355,6 +363,7 @@ class MMBasicLayer(nn.Module):
 
 class MultiModalSwinTransformer(nn.Module):
     """Reference: lib/backbone.py:334-520."""
+    shares_stage0 = True          # forward(expand=S): stage 0's blocks run once per image for S expressions (lavt_hip.engine.Predictor asks)
 
     def __init__(self, pretrain_img_size=224, patch_size=4, in_chans=3, embed_dim=96, depths=[2, 2, 6, 2],
                  num_heads=[3, 6, 12, 24], window_size=7, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop_rate=0.,
@@ -430,9 +439,19 @@ class MultiModalSwinTransformer(nn.Module):
         for i, d in enumerate(live):
             d._batched = [f[2 * i], f[2 * i + 1]]
 
-    def forward(self, x, l, l_mask):
+    def forward(self, x, l, l_mask, expand=1):
+        """expand = S > 1 (inference: test.py:73-79 runs the whole network once per sentence of an image): x holds B images, l / l_mask B * S
+        expressions, expression j of image i at index i * S + j.  Patch embedding and the Swin blocks of stage 0 do not depend on the sentence: they
+        run once per image, their rows are repeated S times in front of stage 0's PWAM, and everything after runs on B * S samples."""
         dtype = compute_dtype()
         B = x.shape[0]
+        S = int(expand)
+        if S < 1:
+            raise ValueError("expand must be >= 1")
+        if S > 1 and self.training:
+            raise RuntimeError("expand > 1 shares stage 0 across expressions: inference only (model.eval())")
+        if l.shape[0] != B * S:
+            raise ValueError(f"language batch {l.shape[0]} != image batch {B} x expand {S}")
         self._draw_drop_path(B, x.device)
         lang = _LangCtx.get(l, l_mask, dtype)
         lang.set_plan([(layer.fusion.image_lang_att.f_key[0], layer.fusion.image_lang_att.f_value[0]) for layer in self.layers])
@@ -440,7 +459,15 @@ class MultiModalSwinTransformer(nn.Module):
         t = t.view(B, Wh * Ww, self.embed_dim)
         outs = []
         for i, layer in enumerate(self.layers):
-            f, H, W, t, Wh, Ww = layer(t, Wh, Ww, l, l_mask)
+            if i == 0 and S > 1:
+                # each image's rows S times in a row (what repeat_interleave(S, 0) gives, written as expand + copy: no host synchronisation, so it can be
+                # captured); 14 400 x C elements per image at 480^2: not worth a kernel
+                t = layer.run_blocks(t, Wh, Ww)
+                t = t.unsqueeze(1).expand(B, S, t.shape[1], t.shape[2]).reshape(B * S, t.shape[1], t.shape[2])
+                B *= S
+                f, H, W, t, Wh, Ww = layer.fuse_language(t, Wh, Ww, l, l_mask)
+            else:
+                f, H, W, t, Wh, Ww = layer(t, Wh, Ww, l, l_mask)
             if i in self.out_indices:
                 nl = getattr(self, f"norm{i}")
                 C = self.num_features[i]

@@ -90,6 +90,35 @@ class SimpleDecoding(nn.Module):
     def forward(self, x_c4, x_c3, x_c2, x_c1):
         return self._run(x_c4, x_c3, x_c2, x_c1)[0]
 
+    def _level_folded(self, tag, x, xhw, skip, B, dtype):
+        H, W = skip.shape[-2:]
+        if xhw[0] < H or xhw[1] < W:
+            x = ops.bilinear(x, B, xhw[0], xhw[1], H, W)
+        elif xhw != (H, W):
+            raise ValueError("decoder: top-down map larger than the skip feature")
+        x = ops.conv3x3_bn_relu_folded(x, nchw_rows(skip, dtype), getattr(self, f"conv1_{tag}"), getattr(self, f"bn1_{tag}"), B, H, W)
+        x = ops.conv3x3_bn_relu_folded(x, None, getattr(self, f"conv2_{tag}"), getattr(self, f"bn2_{tag}"), B, H, W)
+        return x, (H, W)
+
+    def forward_folded(self, x_c4, x_c3, x_c2, x_c1):
+        """Inference form of forward (eval mode only): the wiring of _run_scoped with every conv -> bn -> relu triple as ONE convolution whose packed
+        weight carries the BatchNorm scale and whose epilogue adds the folded bias and applies the ReLU (ops.conv3x3_bn_relu_folded): 2 launches per
+        triple less, 3 where the reduction is split.  bf16 / exact-fp32 compute only; a SyncBatchNorm-converted decoder folds the same way (its
+        running statistics are ordinary buffers).  Not differentiable: call it under torch.no_grad()."""
+        if self.training:
+            raise RuntimeError("SimpleDecoding.forward_folded: BatchNorm can only be folded in eval mode (call model.eval())")
+        from lavt_hip._capi import scope
+        dtype = compute_dtype()
+        B = x_c4.shape[0]
+        with scope("decoder"), torch.no_grad():
+            x, hw = nchw_rows(x_c4, dtype), tuple(x_c4.shape[-2:])
+            x, hw = self._level_folded(4, x, hw, x_c3, B, dtype)
+            x, hw = self._level_folded(3, x, hw, x_c2, B, dtype)
+            if not self.lazy_pred:
+                x, hw = self._level_folded(2, x, hw, x_c1, B, dtype)
+            y = ops.cls_head(x, self.conv1_1.weight, self.conv1_1.bias)
+        return y.view(B, hw[0], hw[1], 2).permute(0, 3, 1, 2)
+
     def forward_feats(self, x_c4, x_c3, x_c2, x_c1):
         y, feats = self._run(x_c4, x_c3, x_c2, x_c1)
         return y, [x_c4] + feats

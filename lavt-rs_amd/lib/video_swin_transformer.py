@@ -374,8 +374,10 @@ class MultiModalSwinTransformer3D(nn.Module):
         for i, d in enumerate(live):
             d._batched = [f[2 * i], f[2 * i + 1]]
 
-    def forward(self, x, l, l_mask):
+    def forward(self, x, l, l_mask, expand=1):
         """x (B, 3, T, H, W) -> tuple of (B*T, C_i, H_i, W_i)-shaped maps (NHWC memory)"""
+        if expand != 1:
+            raise NotImplementedError("video backbone: several expressions per clip (expand > 1) are not supported")
         dtype = compute_dtype()
         B = x.shape[0]
         self._draw_drop_path(B, x.device)
