@@ -650,6 +650,26 @@ int lavt_upsample_mask(int dtype, const void* x, int B, int Hi, int Wi, int Hm, 
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Frame preprocessing (csrc/preprocess.hip; replaces the host-side transforms.py:20-31 (Resize), 83-87 (ToTensor), 106-113 (Normalize) and the
+ * per-frame loop of test_ytvos.py:236-243 for frames that are on the device as uint8).  New symbols only, added under ABI v7.
+ *
+ * lavt_resize_norm_u8: N uint8 HWC RGB frames of Hs x Ws, frame f at src + f * frame_stride (elements = bytes; >= Hs * Ws * 3, so the frames may be
+ *   a slice of a larger upload), -> out fp32 [N][3][Ho][Wo].  The resize is PIL's bilinear (antialiased) resample of 8-bit data, applied by ITS
+ *   fixed-point tables, which the caller builds (lavt_hip/preprocess.py: resample_tables) and passes per axis: coef int32 [out][ksize] and bounds
+ *   int32 [out][2] = (first source index, tap count), in device memory.  Width first, rounded to uint8, then height, each as
+ *   clip((2^21 + sum_k coef[k] * pix[first + k]) >> 22, 0, 255); then ((v / 255.f) - mean[c]) / std[c] in these three fp32 operations.
+ *   bounds_y_host is the bounds_y table in HOST memory: from it the entry picks the tile height TH (the largest of 16, 8, 4, 2, 1 whose source-row
+ *   span keeps the tile's LDS request, 192 bytes per source row, within 64 KB) without reading device memory; LAVT_ERR_INVALID when a single output
+ *   row does not fit (beyond ~170x downscale) or the table is not a non-decreasing sequence of row ranges inside the source.  One launch; N <= 65535.
+ * lavt_resize_nearest_u8: N uint8 single-channel masks (mask f at src + f * frame_stride, >= Hs * Ws) -> out int64 [N][Ho][Wo] =
+ *   src[idx_y[y]][idx_x[x]]: PIL's NEAREST with the caller's index tables (int32 [Ho], [Wo], device memory; lavt_hip/preprocess.py: nearest_table). */
+int lavt_resize_norm_u8(const uint8_t* src, int64_t frame_stride, int N, int Hs, int Ws, const int32_t* coef_x, const int32_t* bounds_x, int ksize_x,
+                        const int32_t* coef_y, const int32_t* bounds_y, int ksize_y, const int32_t* bounds_y_host, float* out, int Ho, int Wo,
+                        float mean0, float mean1, float mean2, float std0, float std1, float std2, void* stream);
+int lavt_resize_nearest_u8(const uint8_t* src, int64_t frame_stride, int N, int Hs, int Ws, const int32_t* idx_y, const int32_t* idx_x, int64_t* out, int Ho,
+                           int Wo, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Text side (lavt_one / lavt_video carry BERT inside the model: lib/_utils.py:38-52; train.py:595-602; the encoder is HF transformers
  * 3.0.2 `BertModel`, absent from the reference tree).  Its Linear / LayerNorm / GELU / attention GEMMs use the entry points above.
  * lavt_bert_embed_fwd: out[r] = word[ids[r]] + type[token_type ? token_type[r] : 0] + pos[r % N]  (BertEmbeddings.forward before LayerNorm;

@@ -1,0 +1,130 @@
+// Device-side frame preprocessing (reference transforms.py:20-31, 83-87, 106-113; the per-frame host loop of test_ytvos.py:236-243): PIL's bilinear
+// (antialiased) resize of uint8 RGB frames by its own fixed-point coefficient tables, finished as ((v / 255) - mean) / std into fp32 planes, and PIL's
+// nearest resize of uint8 masks into int64.  The tables come from the host (lavt_hip/preprocess.py): the integer stage equals PIL bit for bit.
+#include "common.h"
+
+namespace {
+
+#define ST reinterpret_cast<hipStream_t>(stream)
+constexpr int PP_TW = 64;                         // output pixels of a tile along x: one wave-width, the coalesced store
+constexpr int PP_ROW = 3 * PP_TW;                 // bytes of one horizontally resampled source row of a tile in LDS: [c][x]
+constexpr int PP_BITS = 22;                       // PIL's PRECISION_BITS for 8-bit data
+constexpr int PP_LDS_MAX = 64 * 1024;             // the default dynamic-LDS limit of a work-group
+
+struct Norm3 { float mean[3], std[3]; };
+
+__device__ __forceinline__ uint32_t pp_round_clip(uint32_t acc) {
+    const uint32_t v = acc >> PP_BITS;            // coefficients and pixels are non-negative: only the upper clip can act
+    return v > 255u ? 255u : v;
+}
+
+// One work-group = TH x 64 output pixels of one frame, 256 threads = 4 waves.  Lane = x within the tile in both passes.
+//   pass 1: source rows y0 .. y1 (what the tile's output rows read) resampled along x into LDS as uint8 [row][c][x]
+//   pass 2: output (row, channel) pairs, one per wave at a time, resampled along y out of LDS, normalised, stored along x
+__global__ __launch_bounds__(256) void resize_norm_u8_kernel(const uint8_t* __restrict__ src, int64_t frame_stride, int Hs, int Ws,
+                                                             const int32_t* __restrict__ coef_x, const int32_t* __restrict__ bounds_x, int ksize_x,
+                                                             const int32_t* __restrict__ coef_y, const int32_t* __restrict__ bounds_y, int ksize_y,
+                                                             float* __restrict__ out, int Ho, int Wo, int TH, int lds_rows, Norm3 nm) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t rows[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = blockIdx.x * PP_TW + lane;
+    const int r0 = blockIdx.y * TH, r1 = min(r0 + TH, Ho) - 1;          // first / last output row of the tile
+    const int y0 = bounds_y[2 * r0], y1 = bounds_y[2 * r1] + bounds_y[2 * r1 + 1];          // xmin and xmin + n are non-decreasing in the output index
+    const int span = y1 - y0;
+    if (span > lds_rows || y0 < 0 || y1 > Hs) return;          // tables that do not belong to this launch: nothing is written (block-uniform)
+    const uint8_t* frame = src + (int64_t)blockIdx.z * frame_stride;
+
+    if (x < Wo) {
+        const int xmin = bounds_x[2 * x], nx = bounds_x[2 * x + 1];
+        const int n = (xmin >= 0 && nx <= ksize_x && xmin + nx <= Ws) ? nx : 0;          // never read outside the frame or the table row
+        const int32_t* cx = coef_x + (int64_t)x * ksize_x;
+        for (int r = wave; r < span; r += 4) {
+            const uint8_t* p = frame + ((int64_t)(y0 + r) * Ws + xmin) * 3;
+            uint32_t a0 = 1u << (PP_BITS - 1), a1 = a0, a2 = a0;
+            for (int k = 0; k < n; ++k) {
+                const uint32_t c = (uint32_t)cx[k];
+                a0 += c * p[3 * k];
+                a1 += c * p[3 * k + 1];
+                a2 += c * p[3 * k + 2];
+            }
+            uint8_t* q = rows + r * PP_ROW + lane;
+            q[0] = (uint8_t)pp_round_clip(a0);
+            q[PP_TW] = (uint8_t)pp_round_clip(a1);
+            q[2 * PP_TW] = (uint8_t)pp_round_clip(a2);
+        }
+    }
+    __syncthreads();
+    if (x >= Wo) return;
+    const int nrows = r1 - r0 + 1;
+    float* plane = out + (int64_t)blockIdx.z * 3 * Ho * Wo;
+    for (int j = wave; j < nrows * 3; j += 4) {
+        const int ty = j / 3, c = j - ty * 3, y = r0 + ty;
+        const int ymin = bounds_y[2 * y], ny = bounds_y[2 * y + 1];
+        const int n = (ymin >= y0 && ny <= ksize_y && ymin + ny <= y1) ? ny : 0;          // never read outside the rows pass 1 wrote
+        const int32_t* cy = coef_y + (int64_t)y * ksize_y;
+        const uint8_t* q = rows + (ymin - y0) * PP_ROW + c * PP_TW + lane;
+        uint32_t a = 1u << (PP_BITS - 1);
+        for (int k = 0; k < n; ++k) a += (uint32_t)cy[k] * q[k * PP_ROW];
+        // the reference's three fp32 operations in its order: to_tensor's / 255, then normalize's subtraction and division (not one multiply-add)
+        const float v = (float)pp_round_clip(a) / 255.f;
+        plane[((int64_t)c * Ho + y) * Wo + x] = (v - nm.mean[c]) / nm.std[c];
+    }
+}
+
+__global__ __launch_bounds__(256) void resize_nearest_u8_kernel(const uint8_t* __restrict__ src, int64_t frame_stride, int Hs, int Ws, const int32_t* __restrict__ idx_y,
+                                                                const int32_t* __restrict__ idx_x, int64_t* __restrict__ out, int Ho, int Wo, int64_t total) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int xo = (int)(i % Wo), yo = (int)((i / Wo) % Ho);
+        const int64_t f = i / ((int64_t)Wo * Ho);
+        const int ys = min(max(idx_y[yo], 0), Hs - 1), xs = min(max(idx_x[xo], 0), Ws - 1);          // (the tables are clamped already: never read outside the mask)
+        out[i] = src[f * frame_stride + (int64_t)ys * Ws + xs];
+    }
+}
+
+}  // namespace
+
+extern "C" int lavt_resize_norm_u8(const uint8_t* src, int64_t frame_stride, int N, int Hs, int Ws, const int32_t* coef_x, const int32_t* bounds_x, int ksize_x,
+                                   const int32_t* coef_y, const int32_t* bounds_y, int ksize_y, const int32_t* bounds_y_host, float* out, int Ho, int Wo,
+                                   float mean0, float mean1, float mean2, float std0, float std1, float std2, void* stream) {
+    LAVT_CHECK_ARG(src && coef_x && bounds_x && coef_y && bounds_y && bounds_y_host && out, "lavt_resize_norm_u8: null pointer");
+    LAVT_CHECK_ARG(N > 0 && N <= 65535 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0 && ksize_x > 0 && ksize_y > 0, "lavt_resize_norm_u8: bad sizes (1 <= N <= 65535)");
+    LAVT_CHECK_ARG(frame_stride >= (int64_t)Hs * Ws * 3, "lavt_resize_norm_u8: frame_stride %lld is less than one %d x %d x 3 frame", (long long)frame_stride, Hs, Ws);
+    LAVT_CHECK_ARG(std0 != 0.f && std1 != 0.f && std2 != 0.f, "lavt_resize_norm_u8: std must be nonzero");
+    for (int y = 0; y < Ho; ++y) {
+        const int ymin = bounds_y_host[2 * y], n = bounds_y_host[2 * y + 1];
+        LAVT_CHECK_ARG(ymin >= 0 && n >= 0 && n <= ksize_y && ymin + n <= Hs && (y == 0 || (ymin >= bounds_y_host[2 * y - 2] && ymin + n >= bounds_y_host[2 * y - 2] + bounds_y_host[2 * y - 1])),
+                       "lavt_resize_norm_u8: bounds_y_host[%d] = (%d, %d) is not a row range of a %d-row source with %d taps", y, ymin, n, Hs, ksize_y);
+    }
+    // the largest tile height whose source-row span fits the LDS request
+    int TH = 0, lds_rows = 0;
+    for (int th = 16; th >= 1 && !TH; th >>= 1) {
+        int worst = 0;
+        for (int r0 = 0; r0 < Ho; r0 += th) {
+            const int r1 = (r0 + th < Ho ? r0 + th : Ho) - 1;
+            const int span = bounds_y_host[2 * r1] + bounds_y_host[2 * r1 + 1] - bounds_y_host[2 * r0];
+            worst = span > worst ? span : worst;
+        }
+        if ((int64_t)worst * PP_ROW <= PP_LDS_MAX) { TH = th; lds_rows = worst; }
+    }
+    LAVT_CHECK_ARG(TH > 0, "lavt_resize_norm_u8: %d -> %d rows: one output row reads more source rows than fit %d bytes of LDS (%d bytes each)", Hs, Ho, PP_LDS_MAX, PP_ROW);
+    const int gy = cdiv(Ho, TH);
+    LAVT_CHECK_ARG(gy <= 65535, "lavt_resize_norm_u8: too many output rows for one launch");
+    Norm3 nm;
+    nm.mean[0] = mean0; nm.mean[1] = mean1; nm.mean[2] = mean2; nm.std[0] = std0; nm.std[1] = std1; nm.std[2] = std2;
+    const size_t lds = (size_t)(lds_rows > 0 ? lds_rows : 1) * PP_ROW;
+    hipLaunchKernelGGL(resize_norm_u8_kernel, dim3(cdiv(Wo, PP_TW), gy, N), dim3(256), lds, ST, src, frame_stride, Hs, Ws, coef_x, bounds_x, ksize_x, coef_y, bounds_y,
+                       ksize_y, out, Ho, Wo, TH, lds_rows, nm);
+    LAVT_CHECK_LAUNCH("lavt_resize_norm_u8");
+    return LAVT_OK;
+}
+
+extern "C" int lavt_resize_nearest_u8(const uint8_t* src, int64_t frame_stride, int N, int Hs, int Ws, const int32_t* idx_y, const int32_t* idx_x, int64_t* out, int Ho,
+                                      int Wo, void* stream) {
+    LAVT_CHECK_ARG(src && idx_y && idx_x && out, "lavt_resize_nearest_u8: null pointer");
+    LAVT_CHECK_ARG(N > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, "lavt_resize_nearest_u8: bad sizes");
+    LAVT_CHECK_ARG(frame_stride >= (int64_t)Hs * Ws, "lavt_resize_nearest_u8: frame_stride %lld is less than one %d x %d mask", (long long)frame_stride, Hs, Ws);
+    const int64_t total = (int64_t)N * Ho * Wo, blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(resize_nearest_u8_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, ST, src, frame_stride, Hs, Ws, idx_y, idx_x, out, Ho, Wo, total);
+    LAVT_CHECK_LAUNCH("lavt_resize_nearest_u8");
+    return LAVT_OK;
+}

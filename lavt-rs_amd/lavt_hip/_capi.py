@@ -257,6 +257,8 @@ _PROTOTYPES = {
     "lavt_conv_bn_fold": [vp, vp, vp, vp, vp, f32, i32, vp, vp, i32, i32, i32, vp],
     "lavt_splitk_reduce_epi": [i32, vp, i32, i64, i32, vp, i32, vp, i64, vp],
     "lavt_upsample_mask": [i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "lavt_resize_norm_u8": [vp, i64, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, vp],
+    "lavt_resize_nearest_u8": [vp, i64, i32, i32, i32, vp, vp, vp, i32, i32, vp],
 }
 for _name, _args in _PROTOTYPES.items():
     _fn = getattr(_cdll, _name)          # AttributeError here = header/library mismatch: fail loudly

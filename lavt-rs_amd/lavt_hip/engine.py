@@ -301,6 +301,7 @@ class Predictor:
         self.captured = False
         self.mask = None                         # uint8 (samples, Ho, Wo): static once captured
         self.iu = None                           # int32 (samples, 2) with a target, else None
+        self.preprocessor = None                 # load_frames' FramePreprocessor(in_size), made on first use (assign one for another mean / std)
         # a replay runs no Python: neither the weight cache's version checks nor the BatchNorm fold's.  step() compares this stamp over parameters AND
         # buffers (the running statistics are folded into weights) and re-casts / re-folds eagerly, into the same storage, when anything moved
         self._state = [t for t in list(model.parameters()) + list(model.buffers())]
@@ -344,6 +345,35 @@ class Predictor:
             print(f"[lavt_hip.engine] hipGraph capture of the prediction step failed, running eagerly: {type(e).__name__}: {e}", file=sys.stderr)
             self.graph = None
             torch.cuda.synchronize()
+
+    def load_frames(self, frames_u8, targets_u8=None):
+        """Fill the static `image` buffer (and `target`) from uint8 frames: the reference's Resize -> ToTensor -> Normalize (test.py:70-76,
+        test_ytvos.py:236-243) on the device, with PIL's pixels (lavt_hip.preprocess.FramePreprocessor: what it accepts is accepted here).
+        frames_u8: (n, Hs, Ws, 3) RGB, n = the frames the image buffer holds (B, or B*T for LAVTVideo: the buffer is written as (B*T, 3, H, W));
+        targets_u8: (n', Hs, Ws) masks for a `target` of network-input size, resized with NEAREST.  Runs eagerly on the current stream in front of
+        step(): nothing of it is part of the captured graph, nothing synchronises the host (host input is uploaded first, in one copy)."""
+        from .preprocess import FramePreprocessor
+        if self.preprocessor is None:
+            self.preprocessor = FramePreprocessor(self.in_size)
+        H, W = self.in_size
+        n = self.x.numel() // (3 * H * W)
+        pp = self.preprocessor
+        frames = pp._to_device(frames_u8, 4)
+        if frames.shape[0] != n:
+            raise ValueError(f"Predictor.load_frames: {frames.shape[0]} frames for an image buffer of {n} ({tuple(self.x.shape)})")
+        masks = None
+        if targets_u8 is not None:
+            if self.t is None:
+                raise ValueError("Predictor.load_frames: targets given, but the predictor was built without a target buffer")
+            if tuple(self.t.shape[-2:]) != self.in_size:
+                raise ValueError(f"Predictor.load_frames: the target buffer is {tuple(self.t.shape[-2:])}, not the network input size {self.in_size} (the "
+                                 "via_size / out_size flow keeps targets at the original frame size): copy those into `target` yourself")
+            masks = pp._to_device(targets_u8, 3)
+            if masks.shape[0] != self.t.shape[0]:
+                raise ValueError(f"Predictor.load_frames: {masks.shape[0]} target masks for a target buffer of {self.t.shape[0]}")
+        pp.images(frames, out=self.x)
+        if masks is not None:
+            pp.targets(masks, out=self.t)
 
     @_in_context
     def step(self):

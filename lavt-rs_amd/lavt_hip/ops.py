@@ -3045,3 +3045,53 @@ def upsample_mask(rows, B, Hi, Wi, out_size, via_size=None, target=None):
     _note(f"upsample-mask {B}x{Hi}x{Wi}->{Ho}x{Wo}", nbytes=rows.numel() * rows.element_size() + mask.numel() + (8 * mask.numel() if target is not None else 0))
     K.check(K.lib.lavt_upsample_mask(K.dt(rows.dtype), K.ptr(rows), B, Hi, Wi, Hm, Wm, Ho, Wo, K.ptr(mask), K.ptr(target), K.ptr(iu), K.stream()))
     return mask, iu
+
+
+def _u8_frames(src, inner, what):
+    """(N, Hs, Ws[, 3]) uint8 on the GPU whose frames are contiguous (the frame stride is free) -> the tensor and that stride in elements"""
+    if not src.is_cuda:
+        raise RuntimeError(f"liblavt_hip operates on GPU memory only (got a CPU tensor for `{what}`); there is no CPU fallback")
+    if src.dtype != torch.uint8 or src.dim() != len(inner) + 1:
+        raise ValueError(f"{what}: expected uint8 with {len(inner) + 1} dimensions, got {src.dtype} {tuple(src.shape)}")
+    if src.shape[0] < 1 or min(src.shape[1:3]) < 1:
+        raise ValueError(f"{what}: empty input {tuple(src.shape)}")
+    if not src[0].is_contiguous() or (src.shape[0] > 1 and src.stride(0) < src[0].numel()):
+        src = src.contiguous()
+    return src, (src.stride(0) if src.shape[0] > 1 else src[0].numel())
+
+
+def resize_normalize_u8(src, out, mean, std):
+    """`Resize -> ToTensor -> Normalize` of the reference (transforms.py:20-31, 83-87, 106-113) on the device: src uint8 (N, Hs, Ws, 3) RGB frames (a
+    slice of a larger buffer is fine: any frame stride) -> out fp32 (N, 3, Ho, Wo), written in place; PIL's bilinear resize bit for bit, then
+    ((v / 255) - mean) / std.  The sizes come from the tensors, the tables from lavt_hip.preprocess's per-device cache."""
+    from . import preprocess as P
+    src, stride = _u8_frames(src, (0, 0, 3), "resize_normalize_u8")
+    if not out.is_cuda:
+        raise RuntimeError("liblavt_hip operates on GPU memory only (got a CPU tensor for `out`); there is no CPU fallback")
+    N, Hs, Ws, C = src.shape
+    if C != 3 or out.dtype != torch.float32 or out.dim() != 4 or out.shape[0] != N or out.shape[1] != 3 or not out.is_contiguous():
+        raise ValueError(f"resize_normalize_u8: src (N, Hs, Ws, 3) uint8 and out (N, 3, Ho, Wo) contiguous fp32, got {tuple(src.shape)} and {out.dtype} {tuple(out.shape)}")
+    Ho, Wo = int(out.shape[2]), int(out.shape[3])
+    cx, bx = P.device_resample_tables(Ws, Wo, src.device)
+    cy, by = P.device_resample_tables(Hs, Ho, src.device)
+    by_host = P.resample_tables(Hs, Ho)[1]
+    _note(f"resize-norm {N}x{Hs}x{Ws}->{Ho}x{Wo}", nbytes=N * (3 * Hs * Ws + 12 * Ho * Wo))
+    K.check(K.lib.lavt_resize_norm_u8(K.ptr(src), stride, N, Hs, Ws, K.ptr(cx), K.ptr(bx), cx.shape[1], K.ptr(cy), K.ptr(by), cy.shape[1], by_host.ctypes.data,
+                                      K.ptr(out), Ho, Wo, *(float(v) for v in mean), *(float(v) for v in std), K.stream()))
+    return out
+
+
+def resize_nearest_u8(src, out):
+    """The target half of transforms.py:20-31 + 83-87: src uint8 (N, Hs, Ws) masks -> out int64 (N, Ho, Wo), PIL's NEAREST resize, written in place"""
+    from . import preprocess as P
+    src, stride = _u8_frames(src, (0, 0), "resize_nearest_u8")
+    if not out.is_cuda:
+        raise RuntimeError("liblavt_hip operates on GPU memory only (got a CPU tensor for `out`); there is no CPU fallback")
+    N, Hs, Ws = src.shape
+    if out.dtype != torch.int64 or out.dim() != 3 or out.shape[0] != N or not out.is_contiguous():
+        raise ValueError(f"resize_nearest_u8: src (N, Hs, Ws) uint8 and out (N, Ho, Wo) contiguous int64, got {tuple(src.shape)} and {out.dtype} {tuple(out.shape)}")
+    Ho, Wo = int(out.shape[1]), int(out.shape[2])
+    iy, ix = P.device_nearest_table(Hs, Ho, src.device), P.device_nearest_table(Ws, Wo, src.device)
+    _note(f"resize-nearest {N}x{Hs}x{Ws}->{Ho}x{Wo}", nbytes=N * (Hs * Ws + 8 * Ho * Wo))
+    K.check(K.lib.lavt_resize_nearest_u8(K.ptr(src), stride, N, Hs, Ws, K.ptr(iy), K.ptr(ix), K.ptr(out), Ho, Wo, K.stream()))
+    return out

@@ -57,3 +57,18 @@ class Normalize:
 def get_transform(img_size):
     """train.py:37-47 `get_transform(args)`"""
     return Compose([Resize(img_size, img_size), ToTensor(), Normalize(mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225])])
+
+
+def get_device_transform(img_size):
+    """get_transform's result computed on the GPU (lavt_hip.preprocess: PIL's resize pixel for pixel, the same three fp32 operations): a callable
+    (image, target) -> (cuda fp32 (3, img_size, img_size), cuda int64 (img_size, img_size) or None).  image: PIL RGB image or uint8 (H, W, 3) array
+    or CUDA tensor; target: PIL 'L' / 'P' image, uint8 (H, W) array or CUDA tensor, or None.  There is no CPU fallback: without a GPU it raises."""
+    from lavt_hip.preprocess import FramePreprocessor
+    pp = FramePreprocessor(img_size)
+
+    def transform(image, target):
+        image = pp.images(image if isinstance(image, torch.Tensor) else np.asarray(image))[0]
+        if target is not None:
+            target = pp.targets(target if isinstance(target, torch.Tensor) else np.asarray(target))[0]
+        return image, target
+    return transform

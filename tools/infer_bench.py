@@ -11,7 +11,11 @@ on both sides (host wall clock: what an evaluation loop sees per sample).  Paths
   predictor_replay Predictor.step() replaying the captured graph + reading the two counts
   3 expressions    three batch-1 replays (one per sentence) against ONE replay of Predictor(expressions_per_image=3)
 
-and the decoder's launch count per call (profiler records in the "decoder" scope) before and after folding.  One JSON line per figure."""
+and the decoder's launch count per call (profiler records in the "decoder" scope) before and after folding.  One JSON line per figure.
+
+    --frames-u8 HxW   (opt-in) also time the input stage for one uint8 frame of that size, same frame on both paths, next to the replay time:
+  frames_cpu_pipeline   transforms.get_transform on the PIL image (resize, to-tensor, normalise on the host) + the fp32 upload into the predictor's image buffer
+  frames_load_frames    Predictor.load_frames: the uint8 upload (pinned staging) + the resize / normalise kernel into the same buffer"""
 import argparse
 import json
 import os
@@ -50,6 +54,7 @@ def main():
     ap.add_argument("--variant", default="base", choices=["base", "tiny"])
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--frames-u8", default=None, metavar="HxW", help="also time the input stage for a uint8 frame of this size: CPU pipeline vs Predictor.load_frames")
     a = ap.parse_args()
     if a.calls < 20:
         ap.error("--calls must be at least 20")
@@ -109,6 +114,32 @@ def main():
         report(path=name, batch=1, captured=p.captured, ms_median=round(med, 3), ms_min=round(lo, 3), ms_max=round(hi, 3), iu=iu,
                iu_eval_host=[int(base_iu[0]), int(base_iu[1])])
         single = p
+
+    # ---- input stage (opt-in): the parent's PIL path against load_frames, same frame, into the replay predictor's image buffer
+    if a.frames_u8:
+        from PIL import Image
+        import transforms
+        fh, fw = (int(v) for v in a.frames_u8.lower().split("x"))
+        frame = np.random.default_rng(7).integers(0, 256, (1, fh, fw, 3), dtype=np.uint8)
+        pil = Image.fromarray(frame[0], "RGB")
+        tf = transforms.get_transform(a.size)
+
+        def cpu_pipeline():
+            image, _ = tf(pil, None)
+            single.x.copy_(image.unsqueeze(0))
+        single.load_frames(frame)          # tables uploaded, preprocessor made
+        single.preprocessor.reserve_staging(frame.shape)
+
+        def load_frames():
+            single.load_frames(frame)
+        med_c, lo_c, hi_c = timed(cpu_pipeline, a.calls, a.warmup)
+        ref = single.x.clone()
+        med_d, lo_d, hi_d = timed(load_frames, a.calls, a.warmup)
+        err = float((single.x - ref).abs().max())
+        report(path="frames_cpu_pipeline", batch=1, frame=[fh, fw], ms_median=round(med_c, 3), ms_min=round(lo_c, 3), ms_max=round(hi_c, 3),
+               predictor_replay_ms=round(figures["predictor_replay"], 3))
+        report(path="frames_load_frames", batch=1, frame=[fh, fw], ms_median=round(med_d, 3), ms_min=round(lo_d, 3), ms_max=round(hi_d, 3),
+               predictor_replay_ms=round(figures["predictor_replay"], 3), max_abs_diff_vs_cpu_pipeline=err)
 
     # ---- three expressions of one image
     def three_replays():
