@@ -7,7 +7,7 @@
 // and spreads the key index j over its 64 lanes, so the softmax row reductions are wave shuffles.
 #include <stdlib.h>
 
-#include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -387,15 +387,6 @@ int launch_bwd(const void* qkv, const float* bias, int bias_ld, const int8_t* re
 
 }  // namespace
 
-int lavt_window_attn_fwd_mfma(const void* qkv, const float* table, const int8_t* region, int nw_img, void* out, float* lse,
-                              int wd, int wh, int ww, int nwin, int N, int heads, float scale, hipStream_t st);
-int lavt_window_attn_bwd_mfma(const void* qkv, const float* table, const int8_t* region, int nw_img, const void* out, const void* dout,
-                              const float* lse, void* dqkv, float* dtable, int bias_ld, float* ws, float* parts, int wd, int wh, int ww, int nwin, int N,
-                              int heads, float scale, hipStream_t st, const lavt_dtable_job_t* prev, lavt_dtable_job_t* mine);
-int lavt_attn_dtable_run_mfma(const lavt_dtable_job_t* jb, hipStream_t st);
-int lavt_attn_dtable_finish_multi_impl(const int64_t* desc, int n, int max_R, int max_heads, int total_heads, hipStream_t st);
-int lavt_window_attn_bwd_pieces_mfma(int nwin, int N, int heads);
-int64_t lavt_window_attn_bwd_ws_mfma(int nwin, int N, int heads, int bias_ld, int wd, int wh, int ww);
 static bool use_mfma(int dtype, int N, int bias_ld) {
     return dtype == LAVT_BF16 && N <= 400 && bias_ld >= (N <= 64 ? 64 : N <= 160 ? 160 : 416);
 }

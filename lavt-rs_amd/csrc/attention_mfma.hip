@@ -16,24 +16,12 @@
 
 #include <string.h>
 
-#include "common.h"
+#include "attn_common.h"
 #include "dtable_body.h"
+#include "internal.h"
 
 namespace {
 
-constexpr int HD = 32;
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-
-__device__ __forceinline__ bf16x8 join4(bf16x4 lo, bf16x4 hi) {
-    bf16x8 r;
-    r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-    r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-    return r;
-}
-// A/B fragment whose 8 k-values are contiguous in LDS: row `row`, elements k0..k0+7
-__device__ __forceinline__ bf16x8 lds_row8(const bf16* s, int ld, int row, int k0) {
-    return *reinterpret_cast<const bf16x8*>(s + row * ld + k0);
-}
 __device__ __forceinline__ bf16x8 zero8() {
     bf16x8 z;
 #pragma unroll
@@ -41,16 +29,6 @@ __device__ __forceinline__ bf16x8 zero8() {
     return z;
 }
 __device__ __forceinline__ bf16x8 ldg8(const bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
-// A lane holds two packed quadruples of one (token, head) row: channels 4g .. 4g+3 (p0) and 16+4g .. 16+4g+3 (p1), g = lane / 16.  Lanes g and
-// g ^ 1 swap one of them (ds_bpermute, no memory) so that every lane stores 16 contiguous bytes -- 64 contiguous bytes per row and
-// wave-instruction instead of 8-byte pieces.  Every lane of the wave must call (the partner of a valid lane is valid: same row).
-__device__ __forceinline__ void store_head_row16(bf16* row_head, int g, uint2 p0, uint2 p1, bool valid) {
-    const bool odd = g & 1;
-    const uint2 send = odd ? p0 : p1;
-    const uint2 got = make_uint2((unsigned)__shfl_xor((int)send.x, 16, 64), (unsigned)__shfl_xor((int)send.y, 16, 64));
-    const uint4 out = odd ? make_uint4(got.x, got.y, p1.x, p1.y) : make_uint4(p0.x, p0.y, got.x, got.y);
-    if (valid) *reinterpret_cast<uint4*>(row_head + (odd ? 16 + 4 * (g - 1) : 4 * g)) = out;
-}
 
 // ================================================================================================ forward
 // One workgroup (4 waves; 8 for the 25-tile windows) per (window, head).  Q, K, V are staged once into LDS by all threads (one round of 16-byte loads in
@@ -60,24 +38,14 @@ __device__ __forceinline__ void store_head_row16(bf16* row_head, int g, uint2 p0
 // S^T = K Q^T) and the V^T fragments (A operand of O^T = V^T P^T, transposing LDS read) in registers for all its tiles.
 // S^T puts one query per lane column: softmax reductions are in-register + two shuffles, and the un-normalised P^T accumulators of two
 // key tiles are directly the B operand of the second MFMA (no LDS round trip for P).
-// LDS rows of Q / K / V (/ dO): 64 bytes = four 16-byte chunks, UNPADDED, chunk c of row r stored at chunk c ^ swz(r) (round 6).  With the 80-byte padded rows of
-// rounds 2-5 the 16-byte row reads were conflict-free but the transposing 8-byte reads of 8 consecutive rows were 2-way (39 % of the LDS cycles of the 392-token
-// backward were bank conflicts).  swz takes bit 2 of the row into bit 1 of the chunk and bit 3 into bit 0: the 16 rows of a row-fragment read (same chunk) land in 16
-// different 16-byte bank groups, and the 8 rows x 2 chunks of a transposing read cover the 64 banks once.  Tile offsets are multiples of 16 rows: a lane's swizzle
-// is a constant of the lane.
+// LDS rows of Q / K / V (/ dO): 64 bytes = four 16-byte chunks, UNPADDED, chunk c of row r stored at chunk c ^ swz(r) (attn_common.h).
 constexpr int F_LD = 32;        // bf16 elements per LDS row
-__device__ __forceinline__ int swz(int row) { return (((row >> 2) & 1) << 1) | ((row >> 3) & 1); }
 
 // Arithmetic diet (the 392-token kernels are VALU-issue bound: rocprofv3 counters, profiles/r02_pmc_attention.json, r06_pmc_attn_392_tokens.json): scores live
 // in the log2 domain (table column and scale pre-multiplied by log2 e when staged, so the exponential is the bare v_exp_f32), the shift-mask compare is compiled
 // out for unshifted blocks (REGION), the padding tile of an odd tile count costs no arithmetic, and padded tokens need no bounds select in any tile: the
 // staged constants make their terms vanish (round 6, below).
-constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
-
-typedef __attribute__((address_space(3))) float lds_f32;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float lds_f32_at(uint32_t addr) { return *reinterpret_cast<lds_f32*>(addr); }
 
 // Round 6: the instruction diet of the backward below applied to the forward (before: 26 VALU instructions per MFMA in the 392-token launch, and ONE wave per
 // SIMD -- 112 KB of LDS, one 4-wave workgroup per CU; 39.8 -> 27.9 us for 16 x 16 units of 392 tokens, shifted 48.4 -> 31.7; 144- and 49-token windows +-1 us):
@@ -352,7 +320,7 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 8 && NT <= 10) ? 4 : 2) void 
             for (int e = tid; e < NP; e += NTHR) Rs[e] = e < N ? (uint8_t)region[(int64_t)(w % nw_img) * N + e] : 0;
         __syncthreads();
         // this (window, head)'s dS slab [N][slab_ld] behind a raw buffer descriptor (offsets at or beyond its size: the store is dropped)
-        const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(slab + ((int64_t)w * heads + h) * N * slab_ld, 0, N * slab_ld * 2, 0x00020000);
+        const buf_rsrc_t srs = buf_make_n(slab + ((int64_t)w * heads + h) * N * slab_ld, N * slab_ld * 2);
 
 #pragma unroll 1
         for (int t = t_lo + slot; t < t_hi; t += WAVES) {

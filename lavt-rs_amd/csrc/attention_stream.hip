@@ -17,44 +17,20 @@
 //   dK/dV kernel: one workgroup (4 waves) per (window, head, 64-key block); a wave owns 16 keys (K, V rows in registers) and sweeps the query tiles,
 //     which stream through an LDS ring (Q, dO rows + -lse, -delta) like K / V in the forward.
 // LDS rows of 64 bytes with the 16-byte chunk swizzle of attention_mfma.hip (chunk c of row r at c ^ swz(r)): row reads and transposing reads conflict-free.
-#include "common.h"
+#include "attn_common.h"
 
 namespace {
 
-constexpr int HD = 32;
 constexpr int SLD = 32;                 // bf16 elements per LDS row
 constexpr int TILE = 64;                // keys (forward) / queries (dK/dV) per ring stage
 constexpr int STREAM_MAX_N = 2048;
 constexpr int LDS_BUDGET = 160 * 1024;
-constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 constexpr float MASK_LOG2 = -100.0f * LOG2E;
 
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-typedef __attribute__((address_space(3))) float lds_f32;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int swz(int row) { return (((row >> 2) & 1) << 1) | ((row >> 3) & 1); }
-__device__ __forceinline__ bf16x8 join4(bf16x4 lo, bf16x4 hi) {
-    bf16x8 r;
-    r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-    r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-    return r;
-}
-__device__ __forceinline__ bf16x8 lds_row8(const bf16* s, int row, int k0) { return *reinterpret_cast<const bf16x8*>(s + row * SLD + k0); }
-__device__ __forceinline__ float lds_f32_at(uint32_t addr) { return *reinterpret_cast<lds_f32*>(addr); }
-__device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)reinterpret_cast<uintptr_t>((const lds_f32*)p); }
 // A^T fragment (k = 32 rows of a 32-row LDS block, m = 16 columns 16u .. 16u + 15) by two transposing reads
 __device__ __forceinline__ bf16x8 tr_frag(const bf16* blk, int rr, int tcol) {
     const bf16* p = blk + rr * SLD + tcol;
     return join4(__builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)p), __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p + 16 * SLD)));
-}
-// one (token, head) row of 32 bf16 from a lane pair's packed quadruples (see attention_mfma.hip: every lane stores 16 contiguous bytes)
-__device__ __forceinline__ void store_head_row16(bf16* row_head, int g, uint2 p0, uint2 p1, bool valid) {
-    const bool odd = g & 1;
-    const uint2 send = odd ? p0 : p1;
-    const uint2 got = make_uint2((unsigned)__shfl_xor((int)send.x, 16, 64), (unsigned)__shfl_xor((int)send.y, 16, 64));
-    const uint4 out = odd ? make_uint4(got.x, got.y, p1.x, p1.y) : make_uint4(p0.x, p0.y, got.x, got.y);
-    if (valid) *reinterpret_cast<uint4*>(row_head + (odd ? 16 + 4 * (g - 1) : 4 * g)) = out;
 }
 __device__ __forceinline__ uint2 pack4(f32x4 v, float s) { return make_uint2(pack_bf16x2(v[0] * s, v[1] * s), pack_bf16x2(v[2] * s, v[3] * s)); }
 
@@ -146,7 +122,7 @@ __global__ __launch_bounds__(256) void wattn_stream_fwd(const bf16* __restrict__
         float tmax = -1e30f;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row8(Ks, 16 * t + c16, kg), qf, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            const f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row8(Ks, SLD, 16 * t + c16, kg), qf, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
             const int j0 = kt * TILE + 16 * t + 4 * g;
             const u32x4 bj = *reinterpret_cast<const u32x4*>(bs + j0);
             const f32x4 bb = {lds_f32_at(bi - bj[0]), lds_f32_at(bi - bj[1]), lds_f32_at(bi - bj[2]), lds_f32_at(bi - bj[3])};
@@ -428,8 +404,8 @@ __global__ __launch_bounds__(256) void wattn_stream_dkv(const bf16* __restrict__
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
                 const int t = 2 * ks + half;                          // 16-query sub-tile of the stage
-                const f32x4 s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row8(Qs, 16 * t + c16, kg), kfr, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                const f32x4 dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row8(Os, 16 * t + c16, kg), vfr, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                const f32x4 s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row8(Qs, SLD, 16 * t + c16, kg), kfr, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                const f32x4 dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row8(Os, SLD, 16 * t + c16, kg), vfr, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
                 const int l0 = 16 * t + 4 * g, i0 = it * TILE + l0;     // lane: queries i0 + r, key j
                 const f32x4 nl4 = *reinterpret_cast<const f32x4*>(nls + l0), nd4 = *reinterpret_cast<const f32x4*>(nds + l0);
                 const u32x4 bi4 = *reinterpret_cast<const u32x4*>(bs + i0);

@@ -126,3 +126,12 @@ __device__ __forceinline__ float gelu_grad_f(float x) {
     const float pdf = 0.39894228040143267794f * __expf(-0.5f * x * x);
     return cdf + x * pdf;
 }
+
+// ---- bilinear resize (align_corners=True): source rows / columns i0, i1 and the weight of i1 for output index o ---------------------
+__device__ __forceinline__ void bl_coord(int o, float scale, int n_in, int& i0, int& i1, float& lam) {
+    const float src = scale * (float)o;
+    i0 = (int)src;
+    if (i0 > n_in - 1) i0 = n_in - 1;
+    i1 = min(i0 + 1, n_in - 1);
+    lam = src - (float)i0;
+}

@@ -43,9 +43,8 @@ struct CwArgs {
     const void* zeros;
 };
 
-// 32-byte slot swizzle of a 128-byte row by its POSITION (row bits 1 and 3: tn_swz<8>); any 4 consecutive positions in 4 blocks 8 apart --
+// 32-byte slot swizzle of a 128-byte row by its POSITION: tn_swz<8> (row bits 1 and 3); any 4 consecutive positions in 4 blocks 8 apart --
 // what one transposing read touches, whatever the tap shift -- spread over all bank groups
-__device__ __forceinline__ int cw_bswz(int pos) { return (((pos >> 1) & 1) | ((pos >> 2) & 2)) << 1; }
 
 // Fragment reads are ISSUED by one asm statement and WAITED FOR by another (cw_wait), with the MFMAs of the previous fragments in between: the
 // LDS latency of item n + 1 hides under the 12 MFMAs of item n inside a wave (the first form waited after every group of reads: the matrix pipe
@@ -120,7 +119,7 @@ __global__ __launch_bounds__(CW_THREADS) void conv_wgrad3x3_kernel(const CwArgs 
     bool b_ok[B_INSTR];
 #pragma unroll
     for (int i = 0; i < B_INSTR; ++i) {
-        const int q = (wave * B_INSTR + i) * 64 + lane, pos = 1 + (q >> 3), cc = (q & 7) ^ cw_bswz(pos);
+        const int q = (wave * B_INSTR + i) * 64 + lane, pos = 1 + (q >> 3), cc = (q & 7) ^ tn_swz<8>(pos);
         b_ok[i] = pos - 1 < W && j0 + cc * 8 < a.Cin;
         b_src[i] = X + (int64_t)(pos - 1) * ldx + cc * 8;
     }
@@ -151,7 +150,7 @@ __global__ __launch_bounds__(CW_THREADS) void conv_wgrad3x3_kernel(const CwArgs 
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int pos = row_off + 4 * h + d;                   // d = dx + 1
-            posoff[d][h] = (unsigned)(pos * (CW_BJ * 2) + (((wj * 2) ^ cw_bswz(pos)) + ((lane & 3) >> 1)) * 16 + (lane & 1) * 8);
+            posoff[d][h] = (unsigned)(pos * (CW_BJ * 2) + (((wj * 2) ^ tn_swz<8>(pos)) + ((lane & 3) >> 1)) * 16 + (lane & 1) * 8);
         }
 
     f32x4 acc[4][9];
@@ -291,7 +290,6 @@ bool cw_supported(int B, int H, int W, int Cout, int Cin, int c1) {
 // cut of a K step into image rows are address arithmetic as in the bf16 kernel.  A lane's 32 bytes of an operand are the pixels 32 g + 8 r + (0 .. 7)
 // (g = lane / 16, r = read) for BOTH operands: which K index the MFMA gives them is immaterial.  Per K step and wave: 16 + 36 transposing reads for 36
 // MFMAs of 32 cycles (bf16: 104 reads for 144 MFMAs of 16 cycles over the same pixels) and half the fill bytes.
-typedef __attribute__((__vector_size__(8 * sizeof(int)))) int cw_i32x8;
 typedef __attribute__((__vector_size__(4 * sizeof(u64)))) u64 cw_u64x4;
 
 template <int RPK> struct Cw8 {
@@ -329,9 +327,9 @@ __device__ __forceinline__ void cw8_issue4_rows(unsigned a, u64 (&d)[4]) {      
                  : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]) : "v"(a) : "memory");
 }
 __device__ __forceinline__ void cw8_wait4(u64 (&d)[4]) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(d[0]), "+v"(d[1]), "+v"(d[2]), "+v"(d[3])::"memory"); }
-__device__ __forceinline__ cw_i32x8 cw8_frag(const u64 (&d)[4]) {
+__device__ __forceinline__ i32x8 cw8_frag(const u64 (&d)[4]) {
     const cw_u64x4 v = {d[0], d[1], d[2], d[3]};
-    return __builtin_bit_cast(cw_i32x8, v);
+    return __builtin_bit_cast(i32x8, v);
 }
 
 template <int RPK>
@@ -432,7 +430,7 @@ __global__ __launch_bounds__(CW_THREADS) void conv_wgrad3x3_f8_kernel(const Cw8A
 #pragma unroll
         for (int i = 0; i < 4; ++i) cw8_wait4(af[i]);
         cw8_wait4(bf[0]);
-        cw_i32x8 fa[4];
+        i32x8 fa[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) fa[i] = cw8_frag(af[i]);
 #pragma unroll
@@ -442,7 +440,7 @@ __global__ __launch_bounds__(CW_THREADS) void conv_wgrad3x3_f8_kernel(const Cw8A
                 cw8_issue4(sb[d] + posoff[e][0], sb[d] + posoff[e][1], sb[d] + posoff[e][2], sb[d] + posoff[e][3], bf[(n + 1) & 1]);
             }
             __builtin_amdgcn_sched_barrier(0);
-            const cw_i32x8 fb = cw8_frag(bf[n & 1]);
+            const i32x8 fb = cw8_frag(bf[n & 1]);
 #pragma unroll
             for (int i = 0; i < 4; ++i) asm volatile("v_mfma_f32_16x16x128_f8f6f4 %0, %1, %2, %0" : "+v"(acc[i][n]) : "v"(fa[i]), "v"(fb));
             __builtin_amdgcn_sched_barrier(0);

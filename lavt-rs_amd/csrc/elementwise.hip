@@ -2,7 +2,8 @@
 #include <stdarg.h>
 #include <stdio.h>
 
-#include "common.h"
+#include "internal.h"
+#include "lds_prims.h"
 #include "adamw_body.h"
 #include "fp8_pack.h"
 
@@ -113,14 +114,7 @@ template <typename T> __global__ __launch_bounds__(256) void rowsoftmax_bwd_kern
 }
 
 // ---------------------------------------------------------------------------------------------- bilinear (align_corners=True)
-__device__ __forceinline__ void bl_coord(int o, float scale, int n_in, int& i0, int& i1, float& lam) {
-    const float src = scale * (float)o;
-    i0 = (int)src;
-    if (i0 > n_in - 1) i0 = n_in - 1;
-    i1 = min(i0 + 1, n_in - 1);
-    lam = src - (float)i0;
-}
-__host__ __device__ inline float bl_scale(int n_in, int n_out) { return n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f; }
+// coordinate arithmetic: bl_coord (common.h), bl_scale (internal.h)
 
 // Q8 (bf16; configs[4]): also writes the e4m3 twin of the output (the bytes of lavt_fp8_quantize(y)) and records its |max| (delayed scaling)
 template <typename T, bool Q8 = false>
@@ -163,8 +157,6 @@ __global__ __launch_bounds__(256) void bilinear_fwd_kernel(const T* x, T* y, int
 // 60 -> 120 upsample at 2.6 TB/s.  Here a workgroup owns ONE input row interval (rows y0, y0 + 1) of one image and one block of channels: the two rows
 // arrive in LDS by LDS-DMA (every input byte fetched twice, lane-linear image [row][pixel][16-byte chunk]), then every output row that samples the
 // interval is formed from LDS with the element-indexed kernel's own expression (bit-identical results) and stored.  grid (Hi, B, C / cblk).
-typedef __attribute__((address_space(3))) void ew_lds_void;
-typedef __attribute__((address_space(1))) const void ew_gbl_void;
 template <bool Q8>
 __global__ __launch_bounds__(256) void bilinear_rows_fwd_kernel(const bf16* __restrict__ x, bf16* __restrict__ y, int Hi, int Wi, int Ho, int Wo, int C, int cblk, float sh, float sw,
                                                                 unsigned char* __restrict__ q, const float* __restrict__ amax_prev, float* __restrict__ amax_cur) {
@@ -179,9 +171,9 @@ __global__ __launch_bounds__(256) void bilinear_rows_fwd_kernel(const bf16* __re
         const int qq = min(q0 + lane, total - 1);
         const int r = qq >= row_chunks ? 1 : 0, e = qq - r * row_chunks, xi = e / cpp, cc = e - xi * cpp;
         const bf16* src = x + (((int64_t)b * Hi + (r ? y1b : y0b)) * Wi + xi) * C + c0 + cc * 8;
-        __builtin_amdgcn_global_load_lds((ew_gbl_void*)src, (ew_lds_void*)(ew_smem + (size_t)q0 * 16), 16, 0, 0);
+        dma16(src, ew_smem + (size_t)q0 * 16);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
     const uint4* r0 = reinterpret_cast<const uint4*>(ew_smem);
     const uint4* r1 = r0 + row_chunks;

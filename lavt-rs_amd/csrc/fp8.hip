@@ -4,19 +4,11 @@
 //     is recorded on the way for the next one;
 //   weights: CURRENT scaling -- |max| over the tensor, computed when the compute copies are refreshed (with the optimizer step).
 // gfx950 converts with v_cvt_pk_fp8_f32 (OCP e4m3fn, round to nearest even); values are clamped to +-448 first (no NaN / inf encodings produced).
-#include "common.h"
+#include "fp8_pack.h"
 
 namespace {
 
 constexpr float E4M3_MAX = 448.f;
-
-__device__ __forceinline__ unsigned pack4_e4m3(float a, float b, float c, float d) {
-    int v = 0;
-    v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, v, false);
-    v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
-    return (unsigned)v;
-}
-__device__ __forceinline__ float clamp448(float x) { return fminf(fmaxf(x, -E4M3_MAX), E4M3_MAX); }
 
 // non-negative floats order like their bit patterns
 __device__ __forceinline__ void atomic_max_nonneg(float* dst, float v) { atomicMax(reinterpret_cast<unsigned*>(dst), __float_as_uint(v)); }
@@ -42,7 +34,7 @@ __global__ __launch_bounds__(256) void fp8_quantize_kernel(const T* __restrict__
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) m = fmaxf(m, fabsf(f[q * 4 + e]));
-            w[q] = pack4_e4m3(clamp448(f[q * 4] * s), clamp448(f[q * 4 + 1] * s), clamp448(f[q * 4 + 2] * s), clamp448(f[q * 4 + 3] * s));
+            w[q] = q8_pack4(q8_clamp(f[q * 4] * s), q8_clamp(f[q * 4 + 1] * s), q8_clamp(f[q * 4 + 2] * s), q8_clamp(f[q * 4 + 3] * s));
         }
         *reinterpret_cast<uint4*>(dst + i * 16) = make_uint4(w[0], w[1], w[2], w[3]);
     }
@@ -116,7 +108,7 @@ __global__ __launch_bounds__(256) void fp8_weight_kernel(const float* __restrict
         const int c4 = (int)(i % (cin / 4)), t = (int)((i / (cin / 4)) % taps), o = (int)(i / (cin / 4) / taps);
         const float* sp = src + ((int64_t)o * cin + c4 * 4) * taps + t;
         *reinterpret_cast<unsigned*>(dst + ((int64_t)o * taps + t) * cin + c4 * 4) =
-            pack4_e4m3(clamp448(sp[0] * s), clamp448(sp[taps] * s), clamp448(sp[2 * taps] * s), clamp448(sp[3 * taps] * s));
+            q8_pack4(q8_clamp(sp[0] * s), q8_clamp(sp[taps] * s), q8_clamp(sp[2 * taps] * s), q8_clamp(sp[3 * taps] * s));
     }
 }
 
@@ -130,7 +122,7 @@ __global__ __launch_bounds__(256) void fp8_weight_t_kernel(const float* __restri
         const int o4 = (int)(i % (cout / 4)), t = (int)((i / (cout / 4)) % taps), c = (int)(i / (cout / 4) / taps);
         const float* sp = src + ((int64_t)o4 * 4 * cin + c) * taps + t;
         *reinterpret_cast<unsigned*>(dst + ((int64_t)c * taps + t) * cout + o4 * 4) =
-            pack4_e4m3(clamp448(sp[0] * s), clamp448(sp[os] * s), clamp448(sp[2 * os] * s), clamp448(sp[3 * os] * s));
+            q8_pack4(q8_clamp(sp[0] * s), q8_clamp(sp[os] * s), q8_clamp(sp[2 * os] * s), q8_clamp(sp[3 * os] * s));
     }
 }
 

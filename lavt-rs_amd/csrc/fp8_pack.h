@@ -1,5 +1,5 @@
-// e4m3 packing shared by the producers that write a quantised twin of their bf16 output (norm.hip, elementwise.hip): the same arithmetic as
-// fp8_quantize_kernel (fp8.hip) applied to the bf16-ROUNDED value, so a twin holds exactly the bytes lavt_fp8_quantize would write for that output.
+// e4m3 packing shared by the quantiser (fp8.hip) and the producers that write a quantised twin of their bf16 output (norm.hip, elementwise.hip): the
+// twin applies fp8_quantize_kernel's arithmetic to the bf16-ROUNDED value, so it holds exactly the bytes lavt_fp8_quantize would write for that output.
 #pragma once
 #include "common.h"
 

@@ -16,6 +16,7 @@
 #include <stdlib.h>
 
 #include "gemm_common.h"
+#include "internal.h"
 
 using namespace lavt_gemm;
 
@@ -404,11 +405,6 @@ template <typename T> int dispatch_tn(const lavt_gemm_tn_t& p, hipStream_t st) {
 
 }  // namespace
 
-int lavt_gemm_nt_v2(const lavt_gemm_nt_t& p, hipStream_t st);
-int lavt_gemm_nt_pipe_tile(const lavt_gemm_nt_t& p, int* stages_out);          // gemm_nt_pipe.hip: software-pipelined K loop
-int lavt_gemm_nt_pipe(const lavt_gemm_nt_t& p, int tile, int stages, hipStream_t st);
-int lavt_gemm_tn_v2(const lavt_gemm_tn_t& p, hipStream_t st);
-
 extern "C" int lavt_gemm_nt(const lavt_gemm_nt_t* pp, void* stream) {
     LAVT_CHECK_ARG(pp != nullptr, "lavt_gemm_nt: null params");
     lavt_gemm_nt_t p = *pp;
@@ -423,7 +419,7 @@ extern "C" int lavt_gemm_nt(const lavt_gemm_nt_t* pp, void* stream) {
     LAVT_CHECK_ARG(!p.A2 || (p.a_split % epc == 0 && p.lda2 % epc == 0), "lavt_gemm_nt: bad a_split");
     LAVT_CHECK_ARG(!p.C2 || p.c_split % 4 == 0, "lavt_gemm_nt: bad c_split");
     if (p.conv_kc > 0) {
-        const int taps = (p.conv_kd > 0 ? p.conv_kd : 1) * (p.conv_kh > 0 ? p.conv_kh : 3) * (p.conv_kw > 0 ? p.conv_kw : 3);
+        const int taps = conv_taps_of(p);
         const int vox = (p.conv_d > 0 ? p.conv_d : 1) * p.conv_h * p.conv_w;
         if (p.conv_kc_split > 0) {
             int st_ = 0;
@@ -477,7 +473,7 @@ extern "C" int lavt_gemm_tn(const lavt_gemm_tn_t* pp, void* stream) {
     LAVT_CHECK_ARG(p.lda % epc == 0 && p.ldb % epc == 0, "lavt_gemm_tn: lda/ldb must be multiples of %d", epc);
     LAVT_CHECK_ARG(!p.B2 || (p.b_split % epc == 0 && p.ldb2 % epc == 0), "lavt_gemm_tn: bad b_split");
     if (p.conv_kc > 0)
-        LAVT_CHECK_ARG(p.J == (p.conv_kd > 0 ? p.conv_kd : 1) * (p.conv_kh > 0 ? p.conv_kh : 3) * (p.conv_kw > 0 ? p.conv_kw : 3) * p.conv_kc &&
+        LAVT_CHECK_ARG(p.J == conv_taps_of(p) * p.conv_kc &&
                        p.conv_kc % epc == 0 && p.conv_h > 0 && p.conv_w > 0, "lavt_gemm_tn: bad conv geometry");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int rc2 = lavt_gemm_tn_v2(p, st);          // bf16 LDS-DMA kernel (gemm_v2.hip); 1 = not applicable
@@ -498,17 +494,9 @@ extern "C" int lavt_gemm_tn_pieces(const lavt_gemm_tn_t* p) {
     return n < 1 ? 1 : n;
 }
 
-struct lavt_ln_rider_t { const void* dy; const void* x; const float* gamma; const float* mean; const float* rstd; void* dx; float* partials; const void* dres; int rows, C; };
-int lavt_gemm_tn_grouped_v2(const lavt_gemm_tn_t* probs, int n, hipStream_t st, const lavt_ln_rider_t* ln);
-int lavt_layernorm_bwd_partial_impl(int dtype, const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx, float* ws,
-                                    int64_t ws_floats, const void* dres, int rows, int C, void* stream);
-int lavt_ln_bwd_geometry(int dtype, int rows, int C, int* lpr, int* cpl, int* waves);
 // n independent weight-gradient problems issued together: one grouped launch without split-K when they qualify (bf16, plain / row-mapped
 // operands, >= 256 output tiles in total), else one lavt_gemm_tn call each.  Results are identical either way up to fp32 summation order.
-int64_t lavt_gemm_tn_grouped_sk_ws_v2(const lavt_gemm_tn_t* probs, int n);
-int lavt_gemm_tn_grouped_sk_v2(const lavt_gemm_tn_t* probs, int n, float* scratch, int64_t scratch_floats, hipStream_t st);
-// The stream-K form of the same launch (csrc/gemm_tn_v2.hip): 128x128 tiles, the K-tile iterations of all members dealt in equal runs to persistent
-// workgroups, split tiles through `scratch`.  _ws: floats of scratch the group wants, 0 = the group does not qualify (use lavt_gemm_tn_grouped).
+// The stream-K form of the same launch: lavt_gemm_tn_grouped_sk_ws_v2 / _sk_v2 (internal.h).
 extern "C" int64_t lavt_gemm_tn_grouped_sk_ws(const lavt_gemm_tn_t* probs, int n) {
     if (probs == nullptr || n < 1) return 0;
     for (int i = 0; i < n; ++i)

@@ -1,6 +1,6 @@
 // Shared tile / fragment helpers of the gather-GEMM kernels (gemm.hip: register-staged v1; gemm_v2.hip: LDS-DMA pipeline).
 #pragma once
-#include "common.h"
+#include "lds_prims.h"
 
 namespace lavt_gemm {
 
@@ -31,7 +31,6 @@ template <typename T> __device__ __forceinline__ typename FragT<T>::type frag_km
     if constexpr (std::is_same<T, bf16>::value) {
         const int k = ks * 32 + 8 * (lane >> 4) + ((lane & 15) >> 2);
         const bf16* p = s + k * ld + col0 + 4 * (lane & 3);
-        typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
         bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p));
         bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p + 4 * ld));
         bf16x8 r;
@@ -71,7 +70,6 @@ template <int N, int STRIDE> __device__ __forceinline__ void lds_read16_n(unsign
                      : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]) : "v"(addr), "n"(STRIDE) : "memory");
     __builtin_amdgcn_sched_barrier(0);
 }
-__device__ __forceinline__ unsigned lds_byte_addr(const void* p) { return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char*)p; }
 __device__ __forceinline__ uint4 zero16() { return make_uint4(0, 0, 0, 0); }
 
 template <bool FAST = false> __device__ __forceinline__ float apply_act(int act, float v) {

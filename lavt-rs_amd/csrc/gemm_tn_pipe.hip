@@ -25,60 +25,19 @@
 //   * a LayerNorm backward can ride as extra workgroups (two 256-thread units per 512-thread workgroup) on the CUs the 198 tiles leave idle.
 // Accumulators hold C^T fragments (B fragment as the first MFMA operand): a lane owns 4 consecutive j of one row i -- 16-byte stores.
 #include "gemm_v2_helpers.h"
+#include "internal.h"
 #include "ln_bwd_body.h"
 
 namespace {
 
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t tnp_rsrc_t;
-__device__ __forceinline__ tnp_rsrc_t tnp_buf(const void* base, unsigned bytes) {          // raw (stride 0) addressing, offsets >= bytes read zero
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void tnp_dma16(tnp_rsrc_t rs, void* lds_dst, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)lds_dst, 16, voff, 0, 0, 0);
-}
-#else
-struct tnp_rsrc_t { int unused; };
-__host__ __device__ inline tnp_rsrc_t tnp_buf(const void*, unsigned) { return tnp_rsrc_t{0}; }
-__host__ __device__ inline void tnp_dma16(tnp_rsrc_t, void*, unsigned) {}
-#endif
-
-typedef int tnp_i32x8 __attribute__((ext_vector_type(8)));
-typedef tnp_i32x8 __attribute__((aligned(4))) tnp_i32x8_u;          // (row maps are 4-byte aligned: s_load_dwordx8 needs no more)
+typedef i32x8 __attribute__((aligned(4))) tnp_i32x8_u;          // (row maps are 4-byte aligned: s_load_dwordx8 needs no more)
 typedef __attribute__((address_space(4))) const tnp_i32x8_u* tnp_cptr8;
 typedef __attribute__((address_space(4))) const int* tnp_cptr1;
 
-// transposing reads of NF fragments of one k-step (two reads per fragment: K rows r and r + 4 of the lane's 8-row block), issued only
-template <int NF, int HO, int KOFF> __device__ __forceinline__ void tnp_issue_tr(const unsigned (&a)[NF], u64 (&l)[NF], u64 (&h)[NF]) {
-    static_assert(NF == 2 || NF == 4, "NF");
-    if constexpr (NF == 4)
-        asm volatile("ds_read_b64_tr_b16 %0, %8 offset:%c13\n\tds_read_b64_tr_b16 %1, %8 offset:%c13+%c12\n\t"
-                     "ds_read_b64_tr_b16 %2, %9 offset:%c13\n\tds_read_b64_tr_b16 %3, %9 offset:%c13+%c12\n\t"
-                     "ds_read_b64_tr_b16 %4, %10 offset:%c13\n\tds_read_b64_tr_b16 %5, %10 offset:%c13+%c12\n\t"
-                     "ds_read_b64_tr_b16 %6, %11 offset:%c13\n\tds_read_b64_tr_b16 %7, %11 offset:%c13+%c12"
-                     : "=&v"(l[0]), "=&v"(h[0]), "=&v"(l[1]), "=&v"(h[1]), "=&v"(l[2]), "=&v"(h[2]), "=&v"(l[3]), "=&v"(h[3])
-                     : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "n"(HO), "n"(KOFF) : "memory");
-    else
-        asm volatile("ds_read_b64_tr_b16 %0, %4 offset:%c7\n\tds_read_b64_tr_b16 %1, %4 offset:%c7+%c6\n\t"
-                     "ds_read_b64_tr_b16 %2, %5 offset:%c7\n\tds_read_b64_tr_b16 %3, %5 offset:%c7+%c6"
-                     : "=&v"(l[0]), "=&v"(h[0]), "=&v"(l[1]), "=&v"(h[1]) : "v"(a[0]), "v"(a[1]), "n"(HO), "n"(KOFF) : "memory");
-}
 template <int OFF> __device__ __forceinline__ void tnp_rd1(unsigned a, u64& d) {
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%c2" : "=&v"(d) : "v"(a), "n"(OFF) : "memory");
 }
 __device__ __forceinline__ void tnp_tie1(u64& l, u64& h) { asm volatile("" : "+v"(l), "+v"(h)); }
-template <int CNT> __device__ __forceinline__ void tnp_wait() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(CNT) : "memory"); }
-// ties registers to the wait in front of it (consumers cannot be scheduled above this empty statement, which stays behind the wait)
-template <int N> __device__ __forceinline__ void tnp_tie(u64 (&l)[N], u64 (&h)[N]) {
-    if constexpr (N == 4) asm volatile("" : "+v"(l[0]), "+v"(h[0]), "+v"(l[1]), "+v"(h[1]), "+v"(l[2]), "+v"(h[2]), "+v"(l[3]), "+v"(h[3]));
-    else asm volatile("" : "+v"(l[0]), "+v"(h[0]), "+v"(l[1]), "+v"(h[1]));
-}
-template <int N, typename F> __device__ __forceinline__ void tnp_static_for(F&& f) {
-    if constexpr (N > 0) {
-        tnp_static_for<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
 
 constexpr int TNP_MAX = 6;
 enum { TNP_ACCUMULATE = 1, TNP_COLSUM_ATOMIC = 2, TNP_NO_B = 4, TNP_VEC4 = 8, TNP_PART_VEC4 = 16, TNP_WT = 32 };
@@ -136,8 +95,8 @@ __device__ __forceinline__ void tnp_tile(const TnpMember& m, const int local, ch
     const int32_t* const map_a = m.a_map;
     const int32_t* const map_b = m.b_map;
     const bool has_rs = m.a_rs != nullptr;
-    const tnp_rsrc_t rs_a = tnp_buf(m.A, (MAPS && map_a) ? 0x7fffffffu : (unsigned)Kd * (unsigned)lda2);
-    const tnp_rsrc_t rs_b = tnp_buf(has_b ? m.B : m.A, !has_b ? 0u : (MAPS && map_b) ? 0x7fffffffu : (unsigned)Kd * (unsigned)ldb2);
+    const buf_rsrc_t rs_a = buf_make_n(m.A, (MAPS && map_a) ? 0x7fffffffu : (unsigned)Kd * (unsigned)lda2);
+    const buf_rsrc_t rs_b = buf_make_n(has_b ? m.B : m.A, !has_b ? 0u : (MAPS && map_b) ? 0x7fffffffu : (unsigned)Kd * (unsigned)ldb2);
     unsigned a_vo[2], b_vo[2];          // MAPS: column byte offset (or TNP_OOB); else the running byte offset of the lane's chunk
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -172,7 +131,7 @@ __device__ __forceinline__ void tnp_tile(const TnpMember& m, const int local, ch
             }
         }
     }
-    tnp_i32x8 sa = {0, 0, 0, 0, 0, 0, 0, 0}, sb = {0, 0, 0, 0, 0, 0, 0, 0};
+    i32x8 sa = {0, 0, 0, 0, 0, 0, 0, 0}, sb = {0, 0, 0, 0, 0, 0, 0, 0};
     // rows of K tile t for this wave: entries [t * 64 + 8 wave, + 8) of either map (K % 8 == 0 on this path: a wave's eight rows are all inside K
     // or all beyond it; beyond K nothing is read -- entry 0 stands in and the rows are masked by k < K below)
     auto map_fetch = [&](int t) {
@@ -197,7 +156,7 @@ __device__ __forceinline__ void tnp_tile(const TnpMember& m, const int local, ch
             if (map_b) sb = *reinterpret_cast<tnp_cptr8>(reinterpret_cast<uintptr_t>(map_b + e));
         }
     };
-    auto sel4 = [&](const tnp_i32x8& s, int i) -> int {          // entry 4 i + lane / 16
+    auto sel4 = [&](const i32x8& s, int i) -> int {          // entry 4 i + lane / 16
         const int v0 = i ? s[4] : s[0], v1 = i ? s[5] : s[1], v2 = i ? s[6] : s[2], v3 = i ? s[7] : s[3];
         return g4 == 0 ? v0 : g4 == 1 ? v1 : g4 == 2 ? v2 : v3;
     };
@@ -211,9 +170,9 @@ __device__ __forceinline__ void tnp_tile(const TnpMember& m, const int local, ch
                 const int k = k_first + t * BK + wave * 8 + i * 4 + g4;
                 const int src = (sel4(sa, i) & amask) | (k & ~amask);
                 const bool ok = (src >= 0) & (k < Kd) & (((keep >> rs_s[i]) & 1ull) != 0ull);
-                tnp_dma16(rs_a, dst, ok ? (unsigned)src * (unsigned)lda2 + a_vo[i] : TNP_OOB);
+                buf_dma16(rs_a, dst, ok ? (unsigned)src * (unsigned)lda2 + a_vo[i] : TNP_OOB, 0);
             } else {
-                tnp_dma16(rs_a, dst, a_vo[i]);
+                buf_dma16(rs_a, dst, a_vo[i], 0);
                 a_vo[i] += a_adv;
             }
         } else {
@@ -222,9 +181,9 @@ __device__ __forceinline__ void tnp_tile(const TnpMember& m, const int local, ch
                 const int k = k_first + t * BK + wave * 8 + i * 4 + g4;
                 const int src = (sel4(sb, i) & bmask) | (k & ~bmask);
                 const bool ok = (src >= 0) & (k < Kd);
-                tnp_dma16(rs_b, dst, ok ? (unsigned)src * (unsigned)ldb2 + b_vo[i] : TNP_OOB);
+                buf_dma16(rs_b, dst, ok ? (unsigned)src * (unsigned)ldb2 + b_vo[i] : TNP_OOB, 0);
             } else {
-                tnp_dma16(rs_b, dst, b_vo[i]);
+                buf_dma16(rs_b, dst, b_vo[i], 0);
                 b_vo[i] += b_adv;
             }
         }
@@ -319,20 +278,20 @@ __device__ __forceinline__ void tnp_tile(const TnpMember& m, const int local, ch
 #define TNP_GROUP(CUR, NKS, nsoff, BARRIER, kt_)                                                                      \
     do {                                                                                                              \
         if constexpr (BARRIER) {                                                                                      \
-            tnp_wait<0>();                                                                                            \
-            tnp_tie<4>(fal[CUR], fah[CUR]); tnp_tie<2>(fbl[CUR], fbh[CUR]);                                           \
+            pipe_wait<0>();                                                                                           \
+            pipe_tie<4>(fal[CUR], fah[CUR]); pipe_tie<2>(fbl[CUR], fbh[CUR]);                                         \
             if constexpr (TNP_ABL & 4) wait_vmcnt<0>(); else wait_vmcnt<(STAGES - 2) * L>();                          \
             __builtin_amdgcn_s_barrier();                                                                             \
         } else {                                                                                                      \
-            tnp_wait<3>();                                                                                            \
-            tnp_tie<2>(fbl[CUR], fbh[CUR]); tnp_tie1(fal[CUR][0], fah[CUR][0]); tnp_tie1(fal[CUR][1], fah[CUR][1]);   \
+            pipe_wait<3>();                                                                                           \
+            pipe_tie<2>(fbl[CUR], fbh[CUR]); tnp_tie1(fal[CUR][0], fah[CUR][0]); tnp_tie1(fal[CUR][1], fah[CUR][1]);  \
         }                                                                                                             \
         rd_addr(nsoff);                                                                                               \
         __builtin_amdgcn_sched_barrier(0);                                                                            \
-        tnp_static_for<4>([&](auto c_) {                                                                              \
+        static_for<4>([&](auto c_) {                                                                                  \
             constexpr int ci_ = decltype(c_)::value;                                                                  \
             if constexpr (!(BARRIER) && ci_ == 2) {                                                                   \
-                tnp_wait<6>();                                                                                        \
+                pipe_wait<6>();                                                                                       \
                 tnp_tie1(fal[CUR][2], fah[CUR][2]); tnp_tie1(fal[CUR][3], fah[CUR][3]);                               \
             }                                                                                                         \
             rd(std::integral_constant<int, 3 * ci_>{}, std::integral_constant<int, NKS>{}, std::integral_constant<int, 1 - (CUR)>{});      \
@@ -355,13 +314,13 @@ __device__ __forceinline__ void tnp_tile(const TnpMember& m, const int local, ch
 #pragma unroll
     for (int t = 0; t < STAGES; ++t) {
         map_fetch(t);
-        tnp_static_for<L>([&](auto c) { issue_one(c, t, smem + t * STAGE_BYTES); });
+        static_for<L>([&](auto c) { issue_one(c, t, smem + t * STAGE_BYTES); });
         issue_end();
     }
     wait_vmcnt<(STAGES - 1) * L>();                                // tile 0 landed
     __builtin_amdgcn_s_barrier();
     rd_addr(0u);
-    tnp_static_for<12>([&](auto r) { rd(r, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}); });
+    static_for<12>([&](auto r) { rd(r, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}); });
     for (int kt = 0; kt < ktiles; ++kt) {
         const unsigned so = (unsigned)((kt % STAGES) * STAGE_BYTES);
         const unsigned sn = (unsigned)(((kt + 1) % STAGES) * STAGE_BYTES);
@@ -372,7 +331,7 @@ __device__ __forceinline__ void tnp_tile(const TnpMember& m, const int local, ch
         issue_end();
         __builtin_amdgcn_sched_barrier(0);
     }
-    tnp_wait<0>();                                                 // (the reads requested for the tile beyond K)
+    pipe_wait<0>();                                                 // (the reads requested for the tile beyond K)
     wait_vmcnt<0>();                                               // the tiles issued beyond K
 #undef TNP_GROUP
 #undef TNP_COLSUM
@@ -543,9 +502,6 @@ template <int STAGES, int LPR> void tnp_launch(const TnpGroup& g, const TnpRider
 
 }  // namespace
 
-struct lavt_ln_rider_t { const void* dy; const void* x; const float* gamma; const float* mean; const float* rstd; void* dx; float* partials; const void* dres; int rows, C; };
-int lavt_ln_bwd_geometry(int dtype, int rows, int C, int* lpr, int* cpl, int* waves);
-
 // The grouped weight-gradient launch on 128x128 pipelined tiles.  Returns 1 when the group does not qualify (the caller takes gemm_tn_v2.hip's
 // launch), LAVT_OK when it was launched (with the LayerNorm rider if `ln` was given), 3 when it was launched WITHOUT the rider it was offered.
 int lavt_gemm_tn_grouped_pipe(const lavt_gemm_tn_t* probs, int n, hipStream_t st, const lavt_ln_rider_t* ln) {
@@ -655,12 +611,12 @@ int lavt_gemm_tn_grouped_pipe(const lavt_gemm_tn_t* probs, int n, hipStream_t st
         } else lpr = 0;
     }
     const int stages = tun.tn_pipe_stages == 3 ? 3 : 4;
-#define TNP_GO(S_)                                                                  \
-    do {                                                                            \
-        if (lpr == 64) tnp_launch<S_, 64>(g, r, rider_wgs, st);                     \
-        else if (lpr == 32) tnp_launch<S_, 32>(g, r, rider_wgs, st);                \
-        else if (lpr == 16) tnp_launch<S_, 16>(g, r, rider_wgs, st);                \
-        else tnp_launch<S_, 0>(g, r, 0, st);                                        \
+#define TNP_GO(S_)                                                                                                    \
+    do {                                                                                                              \
+        if (lpr == 64) tnp_launch<S_, 64>(g, r, rider_wgs, st);                                                       \
+        else if (lpr == 32) tnp_launch<S_, 32>(g, r, rider_wgs, st);                                                  \
+        else if (lpr == 16) tnp_launch<S_, 16>(g, r, rider_wgs, st);                                                  \
+        else tnp_launch<S_, 0>(g, r, 0, st);                                                                          \
     } while (0)
     if (stages == 3) TNP_GO(3); else TNP_GO(4);
 #undef TNP_GO

@@ -1,6 +1,7 @@
 // Gather-GEMM, second generation (bf16), TN family: weight gradients (split from gemm_v2.hip so that the two families compile in parallel;
 // the design notes at the top of gemm_v2.hip apply).
 #include "gemm_v2_helpers.h"
+#include "internal.h"
 #include "ln_bwd_body.h"
 
 namespace {
@@ -626,10 +627,7 @@ static bool tn_v2_eligible(const lavt_gemm_tn_t& p) {
 }
 
 // returns 1 when the group cannot run as one launch (the caller then issues the problems one by one)
-struct lavt_ln_rider_t { const void* dy; const void* x; const float* gamma; const float* mean; const float* rstd; void* dx; float* partials; const void* dres; int rows, C; };
-int lavt_ln_bwd_geometry(int dtype, int rows, int C, int* lpr, int* cpl, int* waves);
 // ln != NULL: a LayerNorm backward to run as rider workgroups of the launch; returns 3 when the group was launched WITHOUT it (the caller launches it)
-int lavt_gemm_tn_grouped_pipe(const lavt_gemm_tn_t* probs, int n, hipStream_t st, const lavt_ln_rider_t* ln);
 int lavt_gemm_tn_grouped_v2(const lavt_gemm_tn_t* probs, int n, hipStream_t st, const lavt_ln_rider_t* ln) {
     if (n < 2 || n > TN_GROUP_MAX) return 1;
     {   // short reductions on enough 128x128 tiles (the Swin-block groups of stages 2 / 3): the software-pipelined launch of gemm_tn_pipe.hip

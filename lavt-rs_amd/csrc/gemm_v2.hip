@@ -18,6 +18,7 @@
 // belongs at its physical position); row gathers (window maps, 3x3 taps, concat) are per-lane source addresses too.
 // Rows / chunks that must read zero (padding, halo, tails) fetch from a caller-provided zero page (`p.zeros`).
 #include "gemm_v2_helpers.h"
+#include "internal.h"
 
 namespace {
 // SIMPLE = no conv taps, no concat source, K % 64 == 0: every lane's DMA source is a fixed pointer that advances by a constant per K tile,
@@ -26,7 +27,6 @@ namespace {
 // MODE 2 = convolution taps with Cin (and the concat split) a multiple of the 64-wide K tile: the tap of a K tile is wave-uniform and walks
 // forward with the K loop (no division), the lanes' voxel coordinates are computed once, so a neighbour fetch is three range checks and one
 // address add.  MODE 0 (anything else) decodes every K tile from scratch.
-typedef __attribute__((__vector_size__(8 * sizeof(int)))) int i32x8;
 // fp8 (F8): the operand tiles are the same BYTES as the bf16 ones (rows of 128 B = 128 e4m3 elements, 16 per 16-byte chunk), so the DMA ring,
 // the chunk swizzle and the fragment reads are unchanged; a lane feeds one v_mfma_scale_f32_16x16x128_f8f6f4 with the two chunks g and g + 4
 // (g = lane / 16) of its row -- which 32 k of the 128 a lane group holds is immaterial as long as A and B agree (unit block scales); these
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_nt_v2_kernel(const lavt_gemm_
             const bf16* tA = reinterpret_cast<const bf16*>(smem + (kt % STAGES) * STAGE_BYTES);
             const bf16x2_t ones2 = {(bf16)1.0f, (bf16)1.0f};
             uint4 sc[LN_SU];
-            lds_read16_n<LN_SU, WAVES * 8 * 128>(lds_byte_addr(tA) + (unsigned)tid * 16u, sc);      // chunk tid of rows tid / 8 + 8 WAVES u (any chunk order: sums only)
+            lds_read16_n<LN_SU, WAVES * 8 * 128>(lds_addr(tA) + (unsigned)tid * 16u, sc);      // chunk tid of rows tid / 8 + 8 WAVES u (any chunk order: sums only)
 #pragma unroll
             for (int u = 0; u < LN_SU; ++u) {
                 const uint4 c4 = sc[u];
@@ -412,9 +412,6 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_nt_v2_kernel(const lavt_gemm_
     }
 }
 
-static inline int conv_taps_of(const lavt_gemm_nt_t& p) {
-    return (p.conv_kd > 0 ? p.conv_kd : 1) * (p.conv_kh > 0 ? p.conv_kh : 3) * (p.conv_kw > 0 ? p.conv_kw : 3);
-}
 template <int BM, int BN, bool BKM, int STAGES, int WAVES, int MODE, bool DACT = false, bool F8 = false, bool LNA = false, bool GD = false, int LEAN = 0> int launch_nt_v2_(const lavt_gemm_nt_t& p, hipStream_t st) {
     if constexpr (LEAN == 0 && !DACT && !LNA && !F8 && MODE != 0) {      // epilogue instantiations without the features a launch does not use (gemm_common.h)
         if (p.act == 0 && !p.mul && !p.Cpre && !p.C2) {
@@ -495,7 +492,6 @@ template <int BM, int BN, bool BKM, int STAGES, int WAVES> int launch_nt_v2(cons
 
 }  // namespace
 
-// returns 1 when the problem is not for this kernel (caller falls back to gemm.hip), else a LAVT status
 int lavt_gemm_nt_v2(const lavt_gemm_nt_t& p, hipStream_t st) {
     if (p.dtype == LAVT_FP8) return launch_nt_v2_fp8(p, st);
     if (p.dtype != LAVT_BF16 || p.zeros == nullptr) return 1;

@@ -1,9 +1,11 @@
-// Helpers shared by the LDS-DMA GEMM generations (gemm_v2.hip: NT family; gemm_tn_v2.hip: TN family): DMA issue, counted waits, the
-// transposing LDS reads, slot swizzles.  Internal linkage (anonymous namespace) in each translation unit.
+// GEMM-specific helpers shared by the LDS-DMA GEMM generations (gemm_v2.hip, gemm_nt_pipe.hip: NT family; gemm_tn_v2.hip, gemm_tn_pipe.hip: TN family;
+// conv_wgrad.hip): dispatch constants, grouped vmcnt waits, the whole-tile transposing read, slot swizzles.  The family-neutral pipeline primitives
+// (DMA issue, counted waits, issue / tie) are in lds_prims.h.  Internal linkage (anonymous namespace) in each translation unit.
 #pragma once
 #include <stdlib.h>
 
 #include "gemm_common.h"
+#include "lds_prims.h"
 
 using namespace lavt_gemm;
 
@@ -15,14 +17,6 @@ constexpr long S2_MIN128 = 257;
 // Long reductions (K >= 4096) take the 128x128 tile from this many tiles up (below the general threshold of 200).
 constexpr long GEMM_BIG_LONG = 128;
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
-
-__device__ __forceinline__ void dma16(const void* src, void* lds_dst) {
-    __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)lds_dst, 16, 0, 0);
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 template <int G> __device__ __forceinline__ void wait_groups(int g) {      // leave g groups of G vector-memory ops in flight
     if (g <= 0) wait_vmcnt<0>();
     else if (g == 1) wait_vmcnt<G>();
@@ -33,7 +27,6 @@ template <int G> __device__ __forceinline__ void wait_groups(int g) {      // le
 // hipcc puts `s_waitcnt vmcnt(0)` in front of the ds_read_tr builtin while LDS-DMA is in flight (it cannot tell the stages
 // apart), which would serialise the pipeline.  Asm reads are invisible to that pass; we wait for them ourselves:
 // (cdna_hip_programming.md rule 18).
-typedef unsigned long long u64;
 // One statement = all transposing reads of a K tile (both k-steps) + the wait, early-clobber outputs: the compiler can neither copy a
 // destination before its data has landed nor schedule a consumer above the wait (5.7 form i).  One address VGPR per fragment (the slot
 // swizzle of the k-major tiles permutes the fragments' 32-byte slots differently in every lane, so they are not a compile-time stride
@@ -85,9 +78,6 @@ __device__ __forceinline__ bf16x8 frag_from(u64 lo, u64 hi) {
     typedef __attribute__((__vector_size__(2 * sizeof(u64)))) u64 u64x2;
     u64x2 v = {lo, hi};
     return __builtin_bit_cast(bf16x8, v);
-}
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char*)p;
 }
 
 }  // namespace

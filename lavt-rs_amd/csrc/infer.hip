@@ -1,6 +1,6 @@
 // Inference-only kernels (reference test.py / test_ytvos.py under model.eval()): BatchNorm folded into the packed convolution weight, the split-K
 // reduction with the folded bias + activation, and the final upsample fused with argmax and the I / U pixel counts.
-#include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -58,15 +58,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_epi_kernel(const float* __r
 }
 
 // ---------------------------------------------------------------------------------------------- upsample -> argmax mask (+ I / U)
-// coordinate arithmetic of lavt_logits_up_fwd (csrc/elementwise.hip: bl_coord / bl_scale), align_corners=True
-__device__ __forceinline__ void bl_coord(int o, float scale, int n_in, int& i0, int& i1, float& lam) {
-    const float src = scale * (float)o;
-    i0 = (int)src;
-    if (i0 > n_in - 1) i0 = n_in - 1;
-    i1 = min(i0 + 1, n_in - 1);
-    lam = src - (float)i0;
-}
-inline float bl_scale(int n_in, int n_out) { return n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f; }
+// coordinate arithmetic of lavt_logits_up_fwd (bl_coord: common.h, bl_scale: internal.h), align_corners=True
 
 template <typename T> __device__ __forceinline__ float2 ld_pair(const T* base, int64_t pix);
 template <> __device__ __forceinline__ float2 ld_pair<float>(const float* base, int64_t pix) { return *reinterpret_cast<const float2*>(base + pix * 2); }

@@ -2,7 +2,7 @@
 // normalisation kernels behind InstanceNorm1d (PWAM) and BatchNorm2d(+ReLU) (decoder).  All HBM-bound:
 // 16-byte accesses, one wave per LayerNorm row (row kept in registers, fp32 math), wave-shuffle reductions.
 #include <string.h>
-#include "common.h"
+#include "internal.h"
 #include "fp8_pack.h"
 #include "ln_bwd_body.h"
 #include "dtable_body.h"
@@ -596,8 +596,6 @@ static int ln_bwd_geometry(int dtype, int rows, int C, int* lpr_out, int* cpl_ou
 extern "C" int lavt_layernorm_bwd_blocks(int dtype, int rows, int C) { int a, b; return ln_bwd_geometry(dtype, rows, C, &a, &b, nullptr); }
 // geometry of the plain (no gather, no xn output) partial-sum form, for the grouped weight-gradient launch that runs it in rider workgroups
 int lavt_ln_bwd_geometry(int dtype, int rows, int C, int* lpr, int* cpl, int* waves) { return ln_bwd_geometry(dtype, rows, C, lpr, cpl, waves); }
-int lavt_layernorm_bwd_partial_impl(int dtype, const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx, float* ws,
-                                    int64_t ws_floats, const void* dres, int rows, int C, void* stream);
 
 static int layernorm_bwd_impl(int dtype, const void* dy, const void* x, const int32_t* gather, const float* gamma,
                               const float* mean, const float* rstd, void* dx, float* dgamma, float* dbeta, float* ws, int64_t ws_floats,

@@ -16,7 +16,7 @@
 // and three tiny language-side kernels on [32 x C] / [32 x 32] matrices.  tools/pwam_algebra_check.py proves the algebra against autograd.
 #include <stdlib.h>
 
-#include "common.h"
+#include "lds_prims.h"
 
 namespace {
 
@@ -27,7 +27,6 @@ __device__ __forceinline__ bf16x8 lds8(const bf16* p) { return *reinterpret_cast
 __device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
 __device__ __forceinline__ float bf16_round(float v) { return (float)(bf16)v; }
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char*)p; }
 
 // A lane of a C^T accumulator pair holds, for ONE row, elements 4g .. 4g+3 of a 16-wide tile (p0) and the same of the next tile (p1), g = lane / 16.
 // Lanes g and g ^ 1 swap one packed quadruple so that every lane moves 16 contiguous bytes (64 contiguous bytes per row and wave-instruction).

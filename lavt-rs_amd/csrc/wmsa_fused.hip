@@ -15,35 +15,14 @@
 // The [M, C] LayerNorm output, the LayerNorm launch, the qkv GEMM launch and the qkv re-read disappear from the forward pass.
 #include <stdlib.h>
 
+#include "attn_common.h"
 #include "gemm_common.h"
 
 using namespace lavt_gemm;
 
 namespace {
 
-constexpr int HD = 32;
 constexpr int F_LD = 40;        // bf16 elements per LDS row of Q / K / V (80 B)
-constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
-
-__device__ __forceinline__ void dma16(const void* src, void* lds_dst) { __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)lds_dst, 16, 0, 0); }
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ bf16x8 join4(bf16x4 lo, bf16x4 hi) {
-    bf16x8 r;
-    r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-    r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-    return r;
-}
-__device__ __forceinline__ bf16x8 lds_row8(const bf16* s, int ld, int row, int k0) { return *reinterpret_cast<const bf16x8*>(s + row * ld + k0); }
-__device__ __forceinline__ void store_head_row16(bf16* row_head, int g, uint2 p0, uint2 p1, bool valid) {
-    const bool odd = g & 1;
-    const uint2 send = odd ? p0 : p1;
-    const uint2 got = make_uint2((unsigned)__shfl_xor((int)send.x, 16, 64), (unsigned)__shfl_xor((int)send.y, 16, 64));
-    const uint4 out = odd ? make_uint4(got.x, got.y, p1.x, p1.y) : make_uint4(p0.x, p0.y, got.x, got.y);
-    if (valid) *reinterpret_cast<uint4*>(row_head + (odd ? 16 + 4 * (g - 1) : 4 * g)) = out;
-}
 
 struct WmsaArgs {
     const bf16* x;            // [tokens][C] residual stream (input of norm1)
@@ -172,7 +151,7 @@ __global__ __launch_bounds__(512, 4) void wmsa_fwd_fused_kernel(const WmsaArgs a
         // (v_dot2c_f32_bf16: one instruction per PAIR and sum -- exact bf16 products, fp32 accumulation.  The reads go through inline asm: in
         // front of a plain C++ LDS load hipcc put s_waitcnt vmcnt(0) here, serialising the ring.)
         uint4 sc[SU];
-        lds_read16_n<SU, 64 * 128>(lds_byte_addr(cA) + (unsigned)tid * 16u, sc);
+        lds_read16_n<SU, 64 * 128>(lds_addr(cA) + (unsigned)tid * 16u, sc);
 #pragma unroll
         for (int u = 0; u < SU; ++u) {
             const unsigned wv[4] = {sc[u].x, sc[u].y, sc[u].z, sc[u].w};
