@@ -677,10 +677,33 @@ def assign_partials(items, device):
                 off += nf
 
 
+def _ln_bwd_partial(dy, x, gamma, mean, rstd, dx, wsd, dres, rows, Cn, gather=None, beta=None, xn=None, carry=True):
+    """LayerNorm backward in its partial-sum form: dx (+ dres) now, the per-workgroup sums of the gamma / beta gradients into the arena slice `wsd`
+    (ln_deferred reduces them at the end of backward).  With `xn` (and beta) the kernel also writes the LayerNorm output (_LnMlp: its forward never
+    materialised it); `gather` is the PatchMerging row gather.  carry: a table-gradient binning job waiting in dtable_chain rides in this launch as
+    extra workgroups (the chained kernel has no gather form); the library answers 1 and launches nothing when this geometry has no rider form: the
+    job stays pending and the LayerNorm goes alone."""
+    dt = K.dt(x.dtype)
+    job = dtable_chain.take_for_layernorm() if carry and gather is None else None
+    if job is not None:
+        rc = K.lib.lavt_layernorm_bwd_partial_xn_dtable(dt, K.ptr(dy), K.ptr(x), K.ptr(gamma), K.ptr(beta), K.ptr(mean), K.ptr(rstd), K.ptr(dx), K.ptr(xn),
+                                                        K.ptr(wsd), wsd.numel(), K.ptr(dres), rows, Cn, C.byref(job), K.stream())
+        if rc == 0:
+            dtable_chain.done_by_layernorm()
+            return
+        if rc != 1:
+            K.check(rc)
+    if xn is not None:
+        K.check(K.lib.lavt_layernorm_bwd_partial_xn(dt, K.ptr(dy), K.ptr(x), K.ptr(gamma), K.ptr(beta), K.ptr(mean), K.ptr(rstd), K.ptr(dx), K.ptr(xn),
+                                                    K.ptr(wsd), wsd.numel(), K.ptr(dres), rows, Cn, K.stream()))
+    else:
+        K.check(K.lib.lavt_layernorm_bwd_partial(dt, K.ptr(dy), K.ptr(x), K.ptr(gather), K.ptr(gamma), K.ptr(mean), K.ptr(rstd), K.ptr(dx), K.ptr(wsd), wsd.numel(),
+                                                 K.ptr(dres), rows, Cn, K.stream()))
+
+
 def _launch_ln_partial(rider):
-    dy_, x_, g_, mean_, rstd_, dx_, ws_, dres_, rows_, C_ = rider
-    K.check(K.lib.lavt_layernorm_bwd_partial(K.dt(x_.dtype), K.ptr(dy_), K.ptr(x_), None, K.ptr(g_), K.ptr(mean_), K.ptr(rstd_), K.ptr(dx_), K.ptr(ws_), ws_.numel(),
-                                             K.ptr(dres_), rows_, C_, K.stream()))
+    """a rider (_WgradQueue.add) that did not ride: its LayerNorm backward as a launch of its own"""
+    _ln_bwd_partial(*rider, carry=False)
 
 
 class _WgradQueue:
@@ -753,6 +776,29 @@ class _WgradQueue:
 
 
 wgrads = _Proxy("wgrads")
+
+
+def _linear_wgrad(dtype, w, b, n, kd, rows, A, lda, Bm, ldb, grouped=None, **tn):
+    """The gradient hand-off of a Linear-shaped parameter pair, as ONE gemm_tn launch: dW[n, kd] = A[:, a_off:a_off + n]^T Bm over `rows` rows and db = the
+    column sums of that block of A.  -> (dW, db): the values backward returns for w and b (b = None: no bias gradient is produced, db is None).
+    THE grouping rule: the launch joins the block's grouped launch (_WgradQueue) iff the queue is active, every target is a sink, the dtype is bf16 and
+    the row scale is absent or binary.  Then the parameters are notified (the queue reports them ready once the group is enqueued) and both values are
+    None; otherwise the launch is issued at once and sinks.done decides.  Either way each parameter is fetched from sinks.buf exactly once.
+    tn: gemm_tn's a_rowmap, b_rowmap, a_rowscale, a_rowscale_div, a_rowscale_binary, alpha, a_off.  grouped: {"rows": ..., gemm_tn arguments} that
+    replace `rows` and entries of tn in a launch that joins a group (the token-order form of _Linear)."""
+    wbuf, wsink = sinks.buf(w, (n, kd))
+    bbuf, bsink = sinks.buf(b, (n,)) if b is not None else (None, True)
+    if wgrads.active() and wsink and bsink and dtype == torch.bfloat16 and (tn.get("a_rowscale") is None or tn.get("a_rowscale_binary", False)):
+        if grouped is not None:
+            tn = {**tn, **grouped}
+            rows = tn.pop("rows")
+        gemm_tn(dtype, n, kd, rows, A, lda, Bm, ldb, wbuf, kd, colsum=bbuf, defer=wgrads, **tn)
+        wgrads.notify(w)
+        if b is not None:
+            wgrads.notify(b)
+        return None, None
+    gemm_tn(dtype, n, kd, rows, A, lda, Bm, ldb, wbuf, kd, colsum=bbuf, **tn)
+    return sinks.done(w, wbuf, wsink), sinks.done(b, bbuf, bsink) if b is not None else None
 
 
 class _LnDeferred:
@@ -996,36 +1042,17 @@ class _Linear(torch.autograd.Function):
             gemm_nt(dtype, M, Kd, N, g, N, Wc, Kd, dx, Kd, a_rowmap=o.out_map, b_kmajor=True, row_scale=o.row_scale,
                     row_scale_div=o.row_scale_div, c_rowmap=o.in_map)
         if ctx.needs_input_grad[1]:
-            wbuf, wsink = sinks.buf(weight, (N, Kd))
-            bbuf = bsink = None
-            if bias is not None and ctx.needs_input_grad[2]:
-                bbuf, bsink = sinks.buf(bias, (N,))
             binary = o.row_scale is not None and o.row_scale_value != 0.0
-            grouped = wgrads.active() and wsink and (bbuf is None or bsink) and dtype == torch.bfloat16 and (o.row_scale is None or binary)
-            token_order = (o.out_inv is not None and o.out_map is not None and o.in_map is None and g.shape[0] < M and dtype == torch.bfloat16)
-            if token_order and grouped:
-                # windowed rows scattered back to tokens (proj): dW = sum over the TOKENS of dy[t]^T x[inv[t]] -- the padded window positions (dy = 0
-                # there) drop out of the reduction: K = tokens instead of window rows (1800 instead of 2592 at stage 2, 450 instead of 1152 at stage 3)
+            token_order = None
+            if o.out_inv is not None and o.out_map is not None and o.in_map is None and g.shape[0] < M:
+                # windowed rows scattered back to tokens (proj), when the launch joins a group: dW = sum over the TOKENS of dy[t]^T x[inv[t]] -- the padded
+                # window positions (dy = 0 there) drop out of the reduction: K = tokens instead of window rows (1800 instead of 2592 at stage 2, 450
+                # instead of 1152 at stage 3)
                 T_ = g.shape[0]
-                gemm_tn(dtype, N, Kd, T_, g, N, x, Kd, wbuf, Kd, a_rowscale=o.row_scale, a_rowscale_div=max(o.row_scale_div * T_ // M, 1) if o.row_scale is not None else 1,
-                        a_rowscale_binary=binary, alpha=o.row_scale_value if binary else 1.0, b_rowmap=o.out_inv, colsum=bbuf, defer=wgrads)
-                wgrads.notify(weight)
-                if bbuf is not None:
-                    wgrads.notify(bias)
-                dW = db = None
-            elif grouped:                         # joins the block's grouped launch; the parameters report ready when it is enqueued
-                gemm_tn(dtype, N, Kd, M, g, N, x, Kd, wbuf, Kd, a_rowmap=o.out_map, a_rowscale=o.row_scale, a_rowscale_div=o.row_scale_div,
-                        a_rowscale_binary=binary, alpha=o.row_scale_value if binary else 1.0, b_rowmap=o.in_map, colsum=bbuf, defer=wgrads)
-                wgrads.notify(weight)
-                if bbuf is not None:
-                    wgrads.notify(bias)
-                dW = db = None
-            else:
-                gemm_tn(dtype, N, Kd, M, g, N, x, Kd, wbuf, Kd, a_rowmap=o.out_map, a_rowscale=o.row_scale, a_rowscale_div=o.row_scale_div, a_rowscale_binary=binary,
-                        alpha=o.row_scale_value if binary else 1.0, b_rowmap=o.in_map, colsum=bbuf)
-                dW = sinks.done(weight, wbuf, wsink)
-                if bbuf is not None:
-                    db = sinks.done(bias, bbuf, bsink)
+                token_order = dict(rows=T_, a_rowmap=None, b_rowmap=o.out_inv, a_rowscale_div=max(o.row_scale_div * T_ // M, 1) if o.row_scale is not None else 1)
+            dW, db = _linear_wgrad(dtype, weight, bias if ctx.needs_input_grad[2] else None, N, Kd, M, g, N, x, Kd, grouped=token_order, a_rowmap=o.out_map,
+                                   a_rowscale=o.row_scale, a_rowscale_div=o.row_scale_div, a_rowscale_binary=binary, alpha=o.row_scale_value if binary else 1.0,
+                                   b_rowmap=o.in_map)
         d_res = dy if ctx.has_res and ctx.needs_input_grad[3] else None
         return dx, dW, db, d_res, None
 
@@ -1066,17 +1093,7 @@ class _LinearCat(torch.autograd.Function):
         off = 0
         for w, b in zip(ws, bs):
             n = w.shape[0]
-            wbuf, wsink = sinks.buf(w, (n, Kd))
-            bbuf, bsink = sinks.buf(b, (n,)) if b is not None else (None, True)
-            if wgrads.active() and wsink and bsink and dtype == torch.bfloat16:
-                gemm_tn(dtype, n, Kd, M, dy, Nt, x, Kd, wbuf, Kd, colsum=bbuf, a_off=off, defer=wgrads)
-                wgrads.notify(w)
-                if b is not None:
-                    wgrads.notify(b)
-                grads += [None, None]
-            else:
-                gemm_tn(dtype, n, Kd, M, dy, Nt, x, Kd, wbuf, Kd, colsum=bbuf, a_off=off)
-                grads += [sinks.done(w, wbuf, wsink), sinks.done(b, bbuf, bsink) if b is not None else None]
+            grads += _linear_wgrad(dtype, w, b, n, Kd, M, dy, Nt, x, Kd, a_off=off)
             off += n
         return (dx, *grads)
 
@@ -1098,6 +1115,17 @@ def linear(x, weight, bias=None, residual=None, **kw):
 # two exponentials per element (5 us of vector math on a 10 us GEMM at stage 2, tools/mlp_gemm_probe.py).  Only that launch is built with the
 # branch: compiled into every NT kernel's epilogue it made the whole step 0.16 ms slower (tools/ab_lib.sh).
 _GELU_FWD, _GELU_BWD = K.ACT_GELU_D, K.ACT_STORED
+
+
+def _mlp_wgrads(dtype, o, *, w1, b1, dpre, x1, w2, b2, dy, h):
+    """weight / bias gradients of the two layers of an MLP node, fc2 first (the order the block's grouped launch is built in): fc2 from dy -- under the
+    block's row scale (DropPath) -- and the hidden activation h, fc1 from d pre and the layer's input x1 -> (dw1, db1, dw2, db2)"""
+    M, Hd, Cin, Cout = x1.shape[0], h.shape[1], x1.shape[1], dy.shape[1]
+    binary = o.row_scale is not None and o.row_scale_value != 0.0
+    scale = dict(a_rowscale=o.row_scale, a_rowscale_div=o.row_scale_div, a_rowscale_binary=binary, alpha=o.row_scale_value if binary else 1.0) if o.row_scale is not None else {}
+    dw2, db2 = _linear_wgrad(dtype, w2, b2, Cout, Hd, M, dy, Cout, h, Hd, **scale)
+    dw1, db1 = _linear_wgrad(dtype, w1, b1, Hd, Cin, M, dpre, Hd, x1, Cin)
+    return dw1, db1, dw2, db2
 
 
 @K.scoped
@@ -1144,22 +1172,7 @@ class _Mlp(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             gemm_nt(dtype, M, Cin, Hd, dpre, Hd, W1, Cin, dx, Cin, b_kmajor=True)
-        binary = o.row_scale is not None and o.row_scale_value != 0.0
-        grads = []
-        for (w, b, g, inp, n, kd, rs) in ((w2, b2, dy, h, Cout, Hd, True), (w1, b1, dpre, x, Hd, Cin, False)):
-            wbuf, wsink = sinks.buf(w, (n, kd))
-            bbuf, bsink = sinks.buf(b, (n,)) if b is not None else (None, True)
-            kw = dict(a_rowscale=o.row_scale, a_rowscale_div=o.row_scale_div, a_rowscale_binary=binary, alpha=o.row_scale_value if binary else 1.0) if rs and o.row_scale is not None else {}
-            if wgrads.active() and wsink and bsink and (not kw or binary):
-                gemm_tn(dtype, n, kd, M, g, n, inp, kd, wbuf, kd, colsum=bbuf, defer=wgrads, **kw)
-                wgrads.notify(w)
-                if b is not None:
-                    wgrads.notify(b)
-                grads += [None, None]
-            else:
-                gemm_tn(dtype, n, kd, M, g, n, inp, kd, wbuf, kd, colsum=bbuf, **kw)
-                grads += [sinks.done(w, wbuf, wsink), sinks.done(b, bbuf, bsink) if b is not None else None]
-        dw2, db2, dw1, db1 = grads
+        dw1, db1, dw2, db2 = _mlp_wgrads(dtype, o, w1=w1, b1=b1, dpre=dpre, x1=x, w2=w2, b2=b2, dy=dy, h=h)
         return dx, dw1, db1, dw2, db2, (dy if ctx.has_res and ctx.needs_input_grad[5] else None), None
 
 
@@ -1215,18 +1228,8 @@ class _LnMlp(torch.autograd.Function):
             nblk = int(K.lib.lavt_layernorm_bwd_blocks(K.dt(dtype), M, Cin))
             wsd = ln_deferred.alloc(nblk * 2 * Cin, dev)
             if wsd is not None:
-                job = dtable_chain.take_for_layernorm()
-                rc = 1
-                if job is not None:          # the binning of the attention backward issued a few launches ago rides in this launch
-                    rc = K.lib.lavt_layernorm_bwd_partial_xn_dtable(K.dt(dtype), K.ptr(dxn), K.ptr(x), K.ptr(_f32(gamma)), K.ptr(_f32(beta)), K.ptr(st[0]), K.ptr(st[1]),
-                                                                    K.ptr(dx), K.ptr(xn), K.ptr(wsd), wsd.numel(), K.ptr(dy), M, Cin, C.byref(job), K.stream())
-                    if rc == 0:
-                        dtable_chain.done_by_layernorm()
-                    elif rc != 1:
-                        K.check(rc)
-                if rc == 1:
-                    K.check(K.lib.lavt_layernorm_bwd_partial_xn(K.dt(dtype), K.ptr(dxn), K.ptr(x), K.ptr(_f32(gamma)), K.ptr(_f32(beta)), K.ptr(st[0]), K.ptr(st[1]), K.ptr(dx),
-                                                                K.ptr(xn), K.ptr(wsd), wsd.numel(), K.ptr(dy), M, Cin, K.stream()))
+                # the job this launch carries, if any: the binning of the attention backward issued a few launches ago
+                _ln_bwd_partial(dxn, x, _f32(gamma), st[0], st[1], dx, wsd, dy, M, Cin, beta=_f32(beta), xn=xn)
                 ln_deferred.add(wsd, nblk, Cin, dg, db, (gamma, beta))
                 g_g = g_be = None
                 done = True
@@ -1235,22 +1238,7 @@ class _LnMlp(torch.autograd.Function):
             K.check(K.lib.lavt_layernorm_bwd_xn(K.dt(dtype), K.ptr(dxn), K.ptr(x), K.ptr(_f32(gamma)), K.ptr(_f32(beta)), K.ptr(st[0]), K.ptr(st[1]), K.ptr(dx), K.ptr(xn),
                                                 K.ptr(dg), K.ptr(db), K.ptr(wsl), wsl.numel(), K.ptr(dy), M, Cin, K.stream()))
             g_g, g_be = sinks.done(gamma, dg, gs), sinks.done(beta, db, bs_)
-        binary = o.row_scale is not None and o.row_scale_value != 0.0
-        grads = []
-        for (w, b, g, inp, n, kd, rs) in ((w2, b2, dy, h, Cout, Hd, True), (w1, b1, dpre, xn, Hd, Cin, False)):
-            wbuf, wsink = sinks.buf(w, (n, kd))
-            bbuf, bsink = sinks.buf(b, (n,)) if b is not None else (None, True)
-            kw = dict(a_rowscale=o.row_scale, a_rowscale_div=o.row_scale_div, a_rowscale_binary=binary, alpha=o.row_scale_value if binary else 1.0) if rs and o.row_scale is not None else {}
-            if wgrads.active() and wsink and bsink and (not kw or binary):
-                gemm_tn(dtype, n, kd, M, g, n, inp, kd, wbuf, kd, colsum=bbuf, defer=wgrads, **kw)
-                wgrads.notify(w)
-                if b is not None:
-                    wgrads.notify(b)
-                grads += [None, None]
-            else:
-                gemm_tn(dtype, n, kd, M, g, n, inp, kd, wbuf, kd, colsum=bbuf, **kw)
-                grads += [sinks.done(w, wbuf, wsink), sinks.done(b, bbuf, bsink) if b is not None else None]
-        dw2, db2, dw1, db1 = grads
+        dw1, db1, dw2, db2 = _mlp_wgrads(dtype, o, w1=w1, b1=b1, dpre=dpre, x1=xn, w2=w2, b2=b2, dy=dy, h=h)
         return dx, g_g, g_be, dw1, db1, dw2, db2, None, None
 
 
@@ -1313,18 +1301,8 @@ class _LayerNorm(torch.autograd.Function):
             wsd = ln_deferred.alloc(nblk * 2 * ctx.C, x.device)
             if wsd is not None:
                 _note(f"ln-bwd {ctx.rows}x{ctx.C}", nbytes=(4.0 if dres is not None else 3.0) * ctx.rows * ctx.C * x.element_size())
-                job = dtable_chain.take_for_layernorm() if gather is None else None
-                rc = 1
-                if job is not None:          # a pending table-gradient binning job rides in this launch (the last one of a backward pass: the patch embedding's norm)
-                    rc = K.lib.lavt_layernorm_bwd_partial_xn_dtable(K.dt(x.dtype), K.ptr(dy), K.ptr(x), K.ptr(_f32(gamma)), None, K.ptr(mean), K.ptr(rstd), K.ptr(dx), None,
-                                                                    K.ptr(wsd), wsd.numel(), K.ptr(dres), ctx.rows, ctx.C, C.byref(job), K.stream())
-                    if rc == 0:
-                        dtable_chain.done_by_layernorm()
-                    elif rc != 1:
-                        K.check(rc)
-                if rc == 1:
-                    K.check(K.lib.lavt_layernorm_bwd_partial(K.dt(x.dtype), K.ptr(dy), K.ptr(x), K.ptr(gather), K.ptr(_f32(gamma)), K.ptr(mean), K.ptr(rstd),
-                                                             K.ptr(dx), K.ptr(wsd), wsd.numel(), K.ptr(dres), ctx.rows, ctx.C, K.stream()))
+                # the job this launch carries, if any: the last one of a backward pass, at the patch embedding's norm
+                _ln_bwd_partial(dy, x, _f32(gamma), mean, rstd, dx, wsd, dres, ctx.rows, ctx.C, gather=gather)
                 ln_deferred.add(wsd, nblk, ctx.C, dg, db, (gamma, beta))
                 return dx, None, None, None, None, None, None, None
         ws = _scratch(int(K.lib.lavt_layernorm_bwd_blocks(K.dt(x.dtype), ctx.rows, ctx.C)) * 2 * ctx.C, x.device)     # (without it the kernel falls back to same-address atomics)
@@ -1598,7 +1576,7 @@ class _WmsaFused(torch.autograd.Function):
             wsd = ln_deferred.alloc(nblk * 2 * Cc, dev)
             if wsd is not None:
                 rider = (dxn, x, _f32(gamma), st[0], st[1], dx, wsd, dres, M, Cc)
-        # ---- qkv weight / bias gradient ----
+        # ---- qkv weight / bias gradient (not _linear_wgrad: two members, the LayerNorm rider, and notify BEFORE queueing because the member closes the group) ----
         wbuf, wsink = sinks.buf(wq, (3 * Cc, Cc))
         bbuf, bsink = sinks.buf(bq, (3 * Cc,))
         rode = False
@@ -2238,38 +2216,20 @@ class _PwamGate(torch.autograd.Function):
             gemm_nt(dtype, M, Cc, 2 * Cc, g, 2 * Cc, Wst, Cc, dx, Cc, b_kmajor=True, R=dxg, ldr=Cc)
         gemm_nt(dtype, B * KV_LD, Cc, Cc, dVW, Cc, Woc, Cc, dv, dv.stride(0), b_kmajor=True)          # dV = dVW Wo
         # ---- weight gradients (joined into grouped launches under the step harness) ----
-        grads = {}
-
-        def wgrad(w, b, A, lda, a_off, Bm, ldb, n, kd, rows):
-            wbuf, wsink = sinks.buf(w, (n, kd))
-            bbuf, bsink = sinks.buf(b, (n,)) if b is not None else (None, True)
-            if wgrads.active() and wsink and bsink:
-                gemm_tn(dtype, n, kd, rows, A, lda, Bm, ldb, wbuf, kd, colsum=bbuf, a_off=a_off, defer=wgrads)
-                wgrads.notify(w)
-                if b is not None:
-                    wgrads.notify(b)
-                grads[id(w)] = None
-                if b is not None:
-                    grads[id(b)] = None
-            else:
-                gemm_tn(dtype, n, kd, rows, A, lda, Bm, ldb, wbuf, kd, colsum=bbuf, a_off=a_off)
-                grads[id(w)] = sinks.done(w, wbuf, wsink)
-                if b is not None:
-                    grads[id(b)] = sinks.done(b, bbuf, bsink)
-
-        grads[id(W1)] = grads[id(W2)] = None
+        g_W1 = g_W2 = None
         if gate_live:
-            wgrad(W2, None, dg2, Cc, 0, g1, Cc, Cc, Cc, M)
-            wgrad(W1, None, dpre1, Cc, 0, r, Cc, Cc, Cc, M)
-        wgrad(Wm, bm, drpre, Cc, 0, mm, Cc, Cc, Cc, M)
-        wgrad(Wv, bv, g, 2 * Cc, 0, x, Cc, Cc, Cc, M)
-        wgrad(Wq, None, g, 2 * Cc, Cc, x, Cc, Cc, Cc, M)
-        wgrad(Wo, None, dVW, Cc, 0, v, kld, Cc, Cc, B * KV_LD)
+            g_W2, _ = _linear_wgrad(dtype, W2, None, Cc, Cc, M, dg2, Cc, g1, Cc)
+            g_W1, _ = _linear_wgrad(dtype, W1, None, Cc, Cc, M, dpre1, Cc, r, Cc)
+        g_Wm, g_bm = _linear_wgrad(dtype, Wm, bm, Cc, Cc, M, drpre, Cc, mm, Cc)
+        g_Wv, g_bv = _linear_wgrad(dtype, Wv, bv, Cc, Cc, M, g, 2 * Cc, x, Cc)                      # g = [d vpre | dq]
+        g_Wq, _ = _linear_wgrad(dtype, Wq, None, Cc, Cc, M, g, 2 * Cc, x, Cc, a_off=Cc)
+        g_Wo, _ = _linear_wgrad(dtype, Wo, None, Cc, Cc, B * KV_LD, dVW, Cc, v, kld)
+        g_zero = []
         for b0 in (bq, bo):                                                 # in front of an instance norm: exactly zero
             zb, zs = sinks.buf(b0, tuple(b0.shape))
-            grads[id(b0)] = sinks.done(b0, zb, zs)
-        gp = [grads[id(p)] for p in (Wv, bv, Wq, bq, Wo, bo, Wm, bm, W1, W2)]
-        return (dx, dk, dv, None, None, None, *gp)
+            g_zero.append(sinks.done(b0, zb, zs))
+        g_bq, g_bo = g_zero
+        return (dx, dk, dv, None, None, None, g_Wv, g_bv, g_Wq, g_bq, g_Wo, g_bo, g_Wm, g_bm, g_W1, g_W2)
 
 
 def pwam_gate(x, k, v, maskbias, kv_sinks, B, T, n_l, fusion, res_gate):
@@ -2338,17 +2298,7 @@ class _KvAll(torch.autograd.Function):
         out, off = [], 0
         for w, b in zip(ws, bs):
             n = w.shape[0]
-            wbuf, wsink = sinks.buf(w, (n, Kd))
-            bbuf, bsink = sinks.buf(b, (n,))
-            kw = dict(a_rowmap=kv.kv_map, a_rowscale=kv.mask_rows, a_rowscale_binary=True, alpha=1.0, colsum=bbuf, a_off=off)
-            if wgrads.active() and wsink and bsink and dtype == torch.bfloat16:
-                gemm_tn(dtype, n, Kd, M, G, Nt, lt, Kd, wbuf, Kd, defer=wgrads, **kw)
-                wgrads.notify(w)
-                wgrads.notify(b)
-                out += [None, None]
-            else:
-                gemm_tn(dtype, n, Kd, M, G, Nt, lt, Kd, wbuf, Kd, **kw)
-                out += [sinks.done(w, wbuf, wsink), sinks.done(b, bbuf, bsink)]
+            out += _linear_wgrad(dtype, w, b, n, Kd, M, G, Nt, lt, Kd, a_rowmap=kv.kv_map, a_rowscale=kv.mask_rows, a_rowscale_binary=True, alpha=1.0, a_off=off)
             off += n
         return (dlt, None, *out)
 

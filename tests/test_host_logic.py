@@ -375,6 +375,140 @@ def test_grad_buckets_zero_fill_skip_list():
     assert gb._zero_views is None
 
 
+class _WgradCase:
+    """ops._linear_wgrad driven on the CPU: n = 3 outputs, kd = 5 inputs, 7 rows (so that a transposed operand cannot pass), the A block at column 1
+    of a [7, 4] matrix.  ops.gemm_tn is replaced by a fake that records its keyword arguments (and its row count, as Kd) and writes A[:, a_off:a_off + n]^T B
+    and its column sums, over the rows it is given and through the row maps it is given."""
+    n, kd, rows, a_off = 3, 5, 7, 1
+
+    def __init__(self, monkeypatch, ops, dtype=torch.bfloat16, sink=True, enabled=False):
+        g = torch.Generator().manual_seed(3)
+        self.ops, self.dtype, self.calls, self.ready = ops, dtype, [], []
+        self.A = torch.randn(self.rows, self.n + 1, generator=g).to(dtype)
+        self.B = torch.randn(self.rows, self.kd, generator=g).to(dtype)
+        blk = self.A[:, self.a_off:self.a_off + self.n].float()
+        self.want_w, self.want_b = blk.T @ self.B.float(), blk.sum(0)
+        self.w, self.b = torch.nn.Parameter(torch.zeros(self.n, self.kd)), torch.nn.Parameter(torch.zeros(self.n))
+        if sink:
+            self.w.grad, self.b.grad = torch.zeros(self.n, self.kd), torch.zeros(self.n)
+            ops.sinks.set([self.w, self.b], on_ready=self.ready.append)
+        ops.wgrads.enabled = enabled
+        monkeypatch.setattr(ops, "gemm_tn", self.fake_tn)
+
+    def fake_tn(self, dtype, I, J, Kd, A, lda, B, ldb, Cout, ldc, **kw):
+        assert (I, J, lda, ldb, ldc) == (self.n, self.kd, self.n + 1, self.kd, self.kd) and Kd <= self.rows and Cout.shape == (I, J)
+        self.calls.append(dict(kw, Kd=Kd))
+        ra, rb = (kw.get(k) if kw.get(k) is not None else torch.arange(Kd) for k in ("a_rowmap", "b_rowmap"))       # Kd rows of each operand, through its map
+        blk = A[ra, kw.get("a_off", 0):kw.get("a_off", 0) + I].float()
+        Cout.copy_(blk.T @ B[rb].float())
+        if kw.get("colsum") is not None:
+            kw["colsum"].copy_(blk.sum(0))
+
+    def run(self, bias=True, **tn):
+        return self.ops._linear_wgrad(self.dtype, self.w, self.b if bias else None, self.n, self.kd, self.rows, self.A, self.n + 1, self.B, self.kd,
+                                      a_off=self.a_off, **tn)
+
+    def deferred(self):
+        (kw,) = self.calls
+        assert kw.get("defer") is None or kw["defer"] is self.ops.wgrads
+        return kw.get("defer") is not None
+
+    def ready_is(self, *params):
+        return len(self.ready) == len(params) and all(r is p for r, p in zip(self.ready, params))
+
+
+def test_linear_wgrad_without_sinks_returns_the_gradients(monkeypatch):
+    from lavt_hip import ops
+    with ops.use_context(ops.StepContext()):
+        c = _WgradCase(monkeypatch, ops, sink=False, enabled=True)
+        dW, db = c.run()
+        assert not c.deferred()
+        assert dW.shape == c.w.shape and db.shape == c.b.shape and torch.equal(dW, c.want_w) and torch.equal(db, c.want_b)
+        assert not ops.wgrads.pending and not c.ready
+
+
+def test_linear_wgrad_into_sinks_reports_each_parameter_once(monkeypatch):
+    """sinks without the grouped launch: backward returns None for both, the sink views hold the result, on_ready once per parameter, w before b"""
+    from lavt_hip import ops
+    with ops.use_context(ops.StepContext()):
+        c = _WgradCase(monkeypatch, ops, enabled=False)
+        assert c.run() == (None, None) and not c.deferred()
+        assert torch.equal(c.w.grad, c.want_w) and torch.equal(c.b.grad, c.want_b)
+        assert c.ready_is(c.w, c.b) and not ops.wgrads.pending
+        with pytest.raises(RuntimeError, match="second weight gradient for the same parameter"):       # _GradSinks.buf: one gradient per parameter per step
+            c.run()
+
+
+def test_linear_wgrad_grouped_holds_the_report_until_the_flush(monkeypatch):
+    """the grouped launch: the member is queued (defer = the queue), both parameters are pending and unreported until flush() has enqueued the group"""
+    from lavt_hip import ops
+    with ops.use_context(ops.StepContext()):
+        c = _WgradCase(monkeypatch, ops, enabled=True)
+        assert c.run() == (None, None) and c.deferred()
+        assert ops.wgrads.pending == {id(c.w), id(c.b)} and not c.ready
+        ops.wgrads.flush()                     # the fake queued nothing: no launch, only the reports
+        assert c.ready_is(c.w, c.b) and not ops.wgrads.pending
+        with pytest.raises(RuntimeError, match="second weight gradient for the same parameter"):
+            c.run()
+
+
+@pytest.mark.parametrize("dtype,tn,grouped", [(torch.float32, {}, False),
+                                              (torch.bfloat16, dict(a_rowscale=torch.ones(7), a_rowscale_binary=False), False),
+                                              (torch.bfloat16, dict(a_rowscale=torch.ones(7), a_rowscale_binary=True, alpha=0.5), True)],
+                         ids=["fp32", "rowscale", "binary-rowscale"])
+def test_linear_wgrad_grouping_rule(monkeypatch, dtype, tn, grouped):
+    """queue active + every target a sink is not enough: bf16 only, and a row scale only as a row mask"""
+    from lavt_hip import ops
+    with ops.use_context(ops.StepContext()):
+        c = _WgradCase(monkeypatch, ops, dtype=dtype, enabled=True)
+        assert c.run(**tn) == (None, None) and c.deferred() == grouped
+        assert all(c.calls[0][k] is v for k, v in tn.items())                     # handed through to the launch as given
+        assert torch.equal(c.w.grad, c.want_w) and torch.equal(c.b.grad, c.want_b)
+        if grouped:
+            assert ops.wgrads.pending == {id(c.w), id(c.b)} and not c.ready
+        else:
+            assert c.ready_is(c.w, c.b) and not ops.wgrads.pending
+
+
+@pytest.mark.parametrize("enabled", [False, True], ids=["immediate", "grouped"])
+def test_linear_wgrad_without_bias_touches_one_parameter(monkeypatch, enabled):
+    """b = None (no bias, or its gradient is not needed): one buffer, one notification, no column sum"""
+    from lavt_hip import ops
+    with ops.use_context(ops.StepContext()):
+        c = _WgradCase(monkeypatch, ops, enabled=enabled)
+        assert c.run(bias=False) == (None, None) and c.deferred() == enabled
+        assert c.calls[0]["colsum"] is None and ops.sinks.used == {id(c.w)}
+        assert torch.equal(c.w.grad, c.want_w) and not c.b.grad.any()
+        assert ops.wgrads.pending == ({id(c.w)} if enabled else set()) and c.ready_is(*(() if enabled else (c.w,)))
+        ops.wgrads.flush()
+        assert c.ready_is(c.w) and not ops.wgrads.pending
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["grouped", "immediate"])
+def test_linear_wgrad_grouped_arguments_replace_the_launch_only_in_a_group(monkeypatch, dtype):
+    """grouped= (the token-order form of _Linear): its row count and gemm_tn arguments replace the caller's in a launch that joins a group, and are
+    ignored in one that does not"""
+    from lavt_hip import ops
+    with ops.use_context(ops.StepContext()):
+        c = _WgradCase(monkeypatch, ops, dtype=dtype, enabled=True)
+        given = dict(a_rowmap=torch.arange(c.rows), b_rowmap=None, a_rowscale=torch.ones(c.rows), a_rowscale_div=4, a_rowscale_binary=True, alpha=0.5)
+        inv = torch.arange(c.rows - 1)
+        assert c.run(grouped=dict(rows=c.rows - 1, a_rowmap=None, b_rowmap=inv, a_rowscale_div=2), **given) == (None, None)
+        kw = c.calls[0]
+        if c.deferred():
+            assert dtype == torch.bfloat16
+            assert kw["Kd"] == c.rows - 1 and kw["a_rowmap"] is None and kw["b_rowmap"] is inv and kw["a_rowscale_div"] == 2
+            assert all(kw[k] is given[k] for k in ("a_rowscale", "a_rowscale_binary", "alpha"))      # what the group form does not name stays
+            blk = c.A[:c.rows - 1, c.a_off:c.a_off + c.n].float()
+            assert torch.equal(c.w.grad, blk.T @ c.B[:c.rows - 1].float()) and torch.equal(c.b.grad, blk.sum(0))
+            assert ops.wgrads.pending == {id(c.w), id(c.b)} and not c.ready
+        else:
+            assert dtype == torch.float32
+            assert kw["Kd"] == c.rows and all(kw[k] is v for k, v in given.items())
+            assert torch.equal(c.w.grad, c.want_w) and torch.equal(c.b.grad, c.want_b)
+            assert c.ready_is(c.w, c.b) and not ops.wgrads.pending
+
+
 def test_syncbn_rank_statistics_combination():
     """SyncBN forward: the ranks' (sum, centred M2) pairs, gathered with ONE collective, combine to the statistics of the whole batch --
     also when the channel means are large compared with the spread (no E[x^2] - E[x]^2 cancellation)"""
