@@ -550,6 +550,30 @@ int lavt_upsample_dice_fwd(int dtype, const void* x, const int64_t* target, floa
                            int B, int Hi, int Wi, int Ho, int Wo, void* stream);
 int lavt_upsample_dice_bwd(int dtype, const void* x, const int64_t* target, const float* stats, const float* dloss, void* dx,
                            int B, int Hi, int Wi, int Ho, int Wo, void* stream);
+/* Annotated-frame selection.  A2D-Sentences / JHMDB annotate one frame per clip, and the reference selects before it scores (train.py:282-285,
+ * 366-369; test.py:182-205): valid = [i * t + ind ...]; output_valid = index_select(output, 0, valid); criterion(output_valid, masks).
+ * The _sel_ pairs are the two fused criteria above with that indirection: x NHWC [B,Hi,Wi,2] holds all B frames, sel is a DEVICE int32 [nsel],
+ * target int64 [nsel,Ho,Wo]; sample j of the loss reads logits frame sel[j] and target j.  out4 / stats (2 + 6*nsel floats, per SELECTED sample; the
+ * Dice mean is over nsel samples and 2 classes) cover the nsel selected frames only; scratch as above with nsel in the place of B.
+ * Backward writes EVERY element of dx [B,Hi,Wi,2]: frames named by sel get the gradient, all others exactly +0.0 (both forms of the cross-entropy
+ * backward, the 8x8 LDS tile form and the wave-per-pixel form; every frame scans sel for its own index -- nsel is a handful -- no inverse table).
+ * Contract for sel: 0 < nsel <= B; the entries are distinct and lie in [0, B).  The kernels read sel on the device, so a replayed graph follows a
+ * changed buffer, and therefore they cannot raise: an entry outside [0, B) is never dereferenced and contributes nothing (no loss term, no counts,
+ * zero Dice sums; lavt_gather_samples zero-fills that sample); of two equal entries the first receives the gradient.  Distinctness and range are
+ * checked on the host wherever the indices arrive from the host (lavt_hip.engine: set_valid_indices). */
+int lavt_upsample_ce_sel_fwd(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, float w0, float w1, float* ws,
+                             int64_t ws_floats, float* out4, int B, int Hi, int Wi, int Ho, int Wo, void* stream);
+int lavt_upsample_ce_sel_bwd(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, float w0, float w1, const float* out4,
+                             const float* dloss, void* dx, int B, int Hi, int Wi, int Ho, int Wo, void* stream);
+int lavt_upsample_dice_sel_fwd(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, float* ws, int64_t ws_floats,
+                               float* stats, int B, int Hi, int Wi, int Ho, int Wo, void* stream);
+int lavt_upsample_dice_sel_bwd(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, const float* stats, const float* dloss,
+                               void* dx, int B, int Hi, int Wi, int Ho, int Wo, void* stream);
+/* dst[j] = src[sel[j]] for whole samples of sample_elems elements (dtype LAVT_F32 / LAVT_BF16; src holds B samples, dst nsel <= 65535): the gather of
+ * the backbone outputs in front of the BatchNorm-folded decoder when only the annotated frames are scored (test.py:182-205 selects behind the
+ * decoder; in eval mode the decoder is per-sample independent).  16-byte copies when the sample size and both bases are multiples of 16 bytes,
+ * element copies otherwise.  sel as above. */
+int lavt_gather_samples(int dtype, const void* src, const int32_t* sel, int nsel, int B, int64_t sample_elems, void* dst, void* stream);
 /* ---- fp8 (OCP e4m3) operand preparation for lavt_gemm_nt(dtype = LAVT_FP8) ----
  * lavt_fp8_quantize: activations, delayed scaling: dst[i] = e4m3(clamp(src[i] * s, +-448)), s = *amax_prev > 0 ? 448 / *amax_prev : 1 (the |max| seen
  *   in the PREVIOUS step; the GEMM reads the same float through deq_a); max |src| of THIS call is folded into *amax_cur (atomic max).

@@ -263,6 +263,23 @@ template <typename T> __global__ void bilinear_bwd_kernel(const T* dy, T* dx, in
 // cross-entropy (losses.py:7-11: F.cross_entropy(out, target, weight=[0.9, 1.1])) + the I / U pixel counts of train.py:64-76.
 // The (B, 2, H, W) logits are never written: every full-resolution pixel is recomputed from its four low-resolution neighbours.
 struct UpCe { float up0, up1, lse; };
+// ---- frame selection (train.py:282-285, 366-369; test.py:182-205 of the reference: `index_select(output, 0, valid_indices)` in front of the criterion):
+// with SEL the loss has nsel samples, sample j reads logits frame sel[j] of the nfr frames of x and target j.  sel is read on the device (a replayed
+// graph follows the buffer); an entry outside [0, nfr) is never dereferenced.  SEL = false is the plain kernel: frame = sample.
+template <bool SEL> __device__ __forceinline__ int sel_frame(const int32_t* __restrict__ sel, int j, int nfr) {          // frame read by sample j, -1 = none
+    if constexpr (!SEL) return j;
+    else { const int f = sel[j]; return (f >= 0 && f < nfr) ? f : -1; }
+}
+// Backward: the sample that frame b feeds, -1 = none (its dx is +0.0).  A scan of sel per frame -- nsel is a handful, b is uniform over a wave in both
+// cross-entropy forms (over the workgroup in the tile form), so the scan is a few scalar loads.
+template <bool SEL> __device__ __forceinline__ int sel_sample(const int32_t* __restrict__ sel, int nsel, int b) {
+    if constexpr (!SEL) return b;
+    else {
+        int j = -1;
+        for (int k = nsel - 1; k >= 0; --k) j = sel[k] == b ? k : j;          // (entries are distinct by contract; the first one wins otherwise)
+        return j;
+    }
+}
 template <typename T>
 __device__ __forceinline__ UpCe upce_at(const T* base, int Wi, int y0, int y1, float ly, int x0, int x1, float lx) {
     const T* r0 = base + ((int64_t)y0 * Wi) * 2;
@@ -277,13 +294,15 @@ __device__ __forceinline__ UpCe upce_at(const T* base, int Wi, int y0, int y1, f
     return u;
 }
 // partial[blk] = {sum w*nll, sum w, I, U}
-template <typename T>
-__global__ __launch_bounds__(256) void upsample_ce_fwd_kernel(const T* __restrict__ x, const int64_t* __restrict__ target, float w0, float w1,
-                                                              float* __restrict__ partial, int B, int Hi, int Wi, int Ho, int Wo, float sh, float sw) {
+template <typename T, bool SEL>
+__global__ __launch_bounds__(256) void upsample_ce_fwd_kernel(const T* __restrict__ x, const int32_t* __restrict__ sel, int nfr, const int64_t* __restrict__ target,
+                                                              float w0, float w1, float* __restrict__ partial, int B, int Hi, int Wi, int Ho, int Wo, float sh,
+                                                              float sw) {
     const int64_t n = (int64_t)B * Ho * Wo;
     float num = 0.f, den = 0.f, inter = 0.f, uni = 0.f;
     GRID_STRIDE(i, n) {
-        const int xo = (int)(i % Wo), yo = (int)((i / Wo) % Ho), b = (int)(i / Wo / Ho);
+        const int xo = (int)(i % Wo), yo = (int)((i / Wo) % Ho), b = sel_frame<SEL>(sel, (int)(i / Wo / Ho), nfr);
+        if (SEL && b < 0) continue;
         int y0, y1, x0, x1; float ly, lx;
         bl_coord(yo, sh, Hi, y0, y1, ly);
         bl_coord(xo, sw, Wi, x0, x1, lx);
@@ -330,10 +349,10 @@ __global__ __launch_bounds__(256) void upsample_ce_finish_kernel(const float* __
 // One WAVE per low-resolution pixel: its lanes share out the ~100 candidate full-resolution pixels (about 64 of them have a non-zero bilinear
 // weight at 4x upsampling) and meet in a wave reduction.  (A thread per pixel -- 28 800 threads = 113 workgroups on 256 CUs, each walking its
 // candidates serially -- took 55 us at 2x480x480.)
-template <typename T>
-__global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(const T* __restrict__ x, const int64_t* __restrict__ target, float w0, float w1,
-                                                              const float* __restrict__ stats, const float* __restrict__ dloss, T* __restrict__ dx,
-                                                              int B, int Hi, int Wi, int Ho, int Wo, float sh, float sw) {
+template <typename T, bool SEL>
+__global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(const T* __restrict__ x, const int32_t* __restrict__ sel, int nsel, const int64_t* __restrict__ target,
+                                                              float w0, float w1, const float* __restrict__ stats, const float* __restrict__ dloss,
+                                                              T* __restrict__ dx, int B, int Hi, int Wi, int Ho, int Wo, float sh, float sw) {
     const int64_t n = (int64_t)B * Hi * Wi;
     const float gscale = (stats[1] > 0.f ? 1.f / stats[1] : 0.f) * (dloss ? dloss[0] : 1.f);
     const int lane = threadIdx.x & 63;
@@ -343,7 +362,9 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(const T* __restric
         bl_range(yi, sh, Hi, Ho, ylo, yhi);
         bl_range(xi, sw, Wi, Wo, xlo, xhi);
         const T* base = x + (int64_t)b * Hi * Wi * 2;
-        const int nx = xhi - xlo + 1, cand = (yhi - ylo + 1) * nx;
+        const int js = sel_sample<SEL>(sel, nsel, b);
+        const int nx = xhi - xlo + 1, cand = js < 0 ? 0 : (yhi - ylo + 1) * nx;          // an unselected frame: no candidates, +0.0
+        const int64_t* tb = target + (int64_t)(js < 0 ? 0 : js) * Ho * Wo;
         float a0 = 0.f, a1 = 0.f;
         for (int c = lane; c < cand; c += 64) {
             const int yo = ylo + c / nx, xo = xlo + c % nx;
@@ -353,7 +374,7 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(const T* __restric
             const float wy = (y0 == yi ? 1.f - ly : 0.f) + (y1 == yi ? ly : 0.f);
             const float wx = (x0 == xi ? 1.f - lx : 0.f) + (x1 == xi ? lx : 0.f);
             if (wy == 0.f || wx == 0.f) continue;
-            const int64_t t = target[((int64_t)b * Ho + yo) * Wo + xo];
+            const int64_t t = tb[(int64_t)yo * Wo + xo];
             if (t != 0 && t != 1) continue;
             const UpCe u = upce_at<T>(base, Wi, y0, y1, ly, x0, x1, lx);
             const float w = (t ? w1 : w0) * wy * wx;
@@ -373,10 +394,10 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_kernel(const T* __restric
 // lanes per pixel.  The wave-per-pixel form above evaluates ~100 candidates per low-resolution pixel (every full-resolution pixel up to 4 x, plus the
 // zero-weight ring): 27.7 us at 2 x 480 x 480 -> 120 x 120 where this form evaluates ~27 per pixel.
 constexpr int UPCE_TL = 8;
-template <typename T>
-__global__ __launch_bounds__(256) void upsample_ce_bwd_tile_kernel(const T* __restrict__ x, const int64_t* __restrict__ target, float w0, float w1,
-                                                                   const float* __restrict__ stats, const float* __restrict__ dloss, T* __restrict__ dx,
-                                                                   int B, int Hi, int Wi, int Ho, int Wo, float sh, float sw, int lds_pixels) {
+template <typename T, bool SEL>
+__global__ __launch_bounds__(256) void upsample_ce_bwd_tile_kernel(const T* __restrict__ x, const int32_t* __restrict__ sel, int nsel, const int64_t* __restrict__ target,
+                                                                   float w0, float w1, const float* __restrict__ stats, const float* __restrict__ dloss,
+                                                                   T* __restrict__ dx, int B, int Hi, int Wi, int Ho, int Wo, float sh, float sw, int lds_pixels) {
     extern __shared__ __attribute__((aligned(16))) char upce_smem[];
     float2* g = reinterpret_cast<float2*>(upce_smem);
     const int tiles_x = (Wi + UPCE_TL - 1) / UPCE_TL, tiles_y = (Hi + UPCE_TL - 1) / UPCE_TL;
@@ -388,9 +409,20 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_tile_kernel(const T* __re
     const int nx = xhi - xlo + 1, ny = yhi - ylo + 1;
     const T* base = x + (int64_t)b * Hi * Wi * 2;
     const float gscale = (stats[1] > 0.f ? 1.f / stats[1] : 0.f) * (dloss ? dloss[0] : 1.f);
+    const int js = sel_sample<SEL>(sel, nsel, b);                  // uniform over the workgroup
+    if (SEL && js < 0) {                                           // an unselected frame: its tile of dx is +0.0
+        const int p = threadIdx.x, yi = yi0 + p / UPCE_TL, xi = xi0 + p % UPCE_TL;
+        if (p < UPCE_TL * UPCE_TL && yi < Hi && xi < Wi) {
+            const int64_t i = ((int64_t)b * Hi + yi) * Wi + xi;
+            dx[i * 2] = from_f<T>(0.f);
+            dx[i * 2 + 1] = from_f<T>(0.f);
+        }
+        return;
+    }
+    const int64_t* tb = target + (int64_t)js * Ho * Wo;
     for (int idx = threadIdx.x; idx < nx * ny && idx < lds_pixels; idx += 256) {
         const int yo = ylo + idx / nx, xo = xlo + idx % nx;
-        const int64_t t = target[((int64_t)b * Ho + yo) * Wo + xo];
+        const int64_t t = tb[(int64_t)yo * Wo + xo];
         float2 v = make_float2(0.f, 0.f);
         if (t == 0 || t == 1) {
             int y0, y1, x0, x1; float ly, lx;
@@ -872,21 +904,32 @@ extern "C" int lavt_logits_up_bwd(int dtype, const float* dy, void* dx, int B, i
     LAVT_CHECK_LAUNCH("lavt_logits_up_bwd");
     return LAVT_OK;
 }
-extern "C" int lavt_upsample_ce_fwd(int dtype, const void* x, const int64_t* target, float w0, float w1, float* ws, int64_t ws_floats,
-                                    float* out4, int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
-    LAVT_CHECK_ARG(x && target && ws && out4 && B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "lavt_upsample_ce_fwd: bad arguments");
-    const int64_t n = (int64_t)B * Ho * Wo;
+// SEL = false: B frames = B samples (sel, nsel unused); SEL = true: nsel samples out of the B frames of x / dx
+template <bool SEL>
+static int upsample_ce_fwd(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, float w0, float w1, float* ws, int64_t ws_floats,
+                           float* out4, int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
+    const int64_t n = (int64_t)(SEL ? nsel : B) * Ho * Wo;
     int blocks = (int)((n + 1023) / 1024);
     if (blocks > 2048) blocks = 2048;
     LAVT_CHECK_ARG(ws_floats >= (int64_t)blocks * 4, "lavt_upsample_ce_fwd: scratch of %d floats needed", blocks * 4);
-    DISPATCH_T(dtype, "lavt_upsample_ce_fwd", hipLaunchKernelGGL(upsample_ce_fwd_kernel<T>, dim3(blocks), dim3(256), 0, ST, (const T*)x, target, w0, w1, ws, B, Hi, Wi, Ho, Wo, bl_scale(Hi, Ho), bl_scale(Wi, Wo)));
+    DISPATCH_T(dtype, "lavt_upsample_ce_fwd", hipLaunchKernelGGL((upsample_ce_fwd_kernel<T, SEL>), dim3(blocks), dim3(256), 0, ST, (const T*)x, sel, B, target, w0, w1, ws, SEL ? nsel : B, Hi, Wi, Ho, Wo, bl_scale(Hi, Ho), bl_scale(Wi, Wo)));
     hipLaunchKernelGGL(upsample_ce_finish_kernel, dim3(1), dim3(256), 0, ST, ws, blocks, out4);
     LAVT_CHECK_LAUNCH("lavt_upsample_ce_fwd");
     return LAVT_OK;
 }
-extern "C" int lavt_upsample_ce_bwd(int dtype, const void* x, const int64_t* target, float w0, float w1, const float* out4, const float* dloss,
-                                    void* dx, int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
-    LAVT_CHECK_ARG(x && target && out4 && dx && B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "lavt_upsample_ce_bwd: bad arguments");
+extern "C" int lavt_upsample_ce_fwd(int dtype, const void* x, const int64_t* target, float w0, float w1, float* ws, int64_t ws_floats,
+                                    float* out4, int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
+    LAVT_CHECK_ARG(x && target && ws && out4 && B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "lavt_upsample_ce_fwd: bad arguments");
+    return upsample_ce_fwd<false>(dtype, x, nullptr, B, target, w0, w1, ws, ws_floats, out4, B, Hi, Wi, Ho, Wo, stream);
+}
+extern "C" int lavt_upsample_ce_sel_fwd(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, float w0, float w1, float* ws,
+                                        int64_t ws_floats, float* out4, int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
+    LAVT_CHECK_ARG(x && sel && target && ws && out4 && B > 0 && nsel > 0 && nsel <= B && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "lavt_upsample_ce_sel_fwd: bad arguments (0 < nsel <= B)");
+    return upsample_ce_fwd<true>(dtype, x, sel, nsel, target, w0, w1, ws, ws_floats, out4, B, Hi, Wi, Ho, Wo, stream);
+}
+template <bool SEL>
+static int upsample_ce_bwd(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, float w0, float w1, const float* out4, const float* dloss,
+                           void* dx, int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
     const int64_t n = (int64_t)B * Hi * Wi;
     // tiled form: the full-resolution region of a TL x TL tile must fit LDS (bl_range: (TL + 1) / scale + 5 rows / columns)
     const float sh = bl_scale(Hi, Ho), sw = bl_scale(Wi, Wo);
@@ -894,16 +937,26 @@ extern "C" int lavt_upsample_ce_bwd(int dtype, const void* x, const int64_t* tar
         const long ny = (long)((UPCE_TL + 1) / sh) + 6, nx = (long)((UPCE_TL + 1) / sw) + 6;
         const long tiles = (long)B * cdiv(Hi, UPCE_TL) * cdiv(Wi, UPCE_TL);
         if (ny * nx * 8 <= 48 * 1024 && tiles < (1L << 30)) {
-            DISPATCH_T(dtype, "lavt_upsample_ce_bwd", hipLaunchKernelGGL(upsample_ce_bwd_tile_kernel<T>, dim3((unsigned)tiles), dim3(256), (size_t)(ny * nx * 8), ST, (const T*)x, target, w0, w1, out4, dloss,
+            DISPATCH_T(dtype, "lavt_upsample_ce_bwd", hipLaunchKernelGGL((upsample_ce_bwd_tile_kernel<T, SEL>), dim3((unsigned)tiles), dim3(256), (size_t)(ny * nx * 8), ST, (const T*)x, sel, nsel, target, w0, w1, out4, dloss,
                                                                           (T*)dx, B, Hi, Wi, Ho, Wo, sh, sw, (int)(ny * nx)));
             LAVT_CHECK_LAUNCH("lavt_upsample_ce_bwd");
             return LAVT_OK;
         }
     }
     const int blocks = (int)((n + 3) / 4 > 8192 ? 8192 : (n + 3) / 4);          // a wave per low-resolution pixel
-    DISPATCH_T(dtype, "lavt_upsample_ce_bwd", hipLaunchKernelGGL(upsample_ce_bwd_kernel<T>, dim3(blocks), dim3(256), 0, ST, (const T*)x, target, w0, w1, out4, dloss, (T*)dx, B, Hi, Wi, Ho, Wo, bl_scale(Hi, Ho), bl_scale(Wi, Wo)));
+    DISPATCH_T(dtype, "lavt_upsample_ce_bwd", hipLaunchKernelGGL((upsample_ce_bwd_kernel<T, SEL>), dim3(blocks), dim3(256), 0, ST, (const T*)x, sel, nsel, target, w0, w1, out4, dloss, (T*)dx, B, Hi, Wi, Ho, Wo, bl_scale(Hi, Ho), bl_scale(Wi, Wo)));
     LAVT_CHECK_LAUNCH("lavt_upsample_ce_bwd");
     return LAVT_OK;
+}
+extern "C" int lavt_upsample_ce_bwd(int dtype, const void* x, const int64_t* target, float w0, float w1, const float* out4, const float* dloss,
+                                    void* dx, int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
+    LAVT_CHECK_ARG(x && target && out4 && dx && B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "lavt_upsample_ce_bwd: bad arguments");
+    return upsample_ce_bwd<false>(dtype, x, nullptr, B, target, w0, w1, out4, dloss, dx, B, Hi, Wi, Ho, Wo, stream);
+}
+extern "C" int lavt_upsample_ce_sel_bwd(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, float w0, float w1, const float* out4,
+                                        const float* dloss, void* dx, int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
+    LAVT_CHECK_ARG(x && sel && target && out4 && dx && B > 0 && nsel > 0 && nsel <= B && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "lavt_upsample_ce_sel_bwd: bad arguments (0 < nsel <= B)");
+    return upsample_ce_bwd<true>(dtype, x, sel, nsel, target, w0, w1, out4, dloss, dx, B, Hi, Wi, Ho, Wo, stream);
 }
 extern "C" int lavt_cls_head_fwd(int dtype, const void* x, const float* w, const float* b, void* y, int64_t rows, int C, void* stream) {
     LAVT_CHECK_ARG(x && w && b && y && rows > 0 && C % EPC_OF(dtype) == 0, "lavt_cls_head_fwd: bad arguments");
@@ -1054,20 +1107,21 @@ extern "C" int lavt_adamw_step_chunks(const int64_t* desc, const float* hyper, c
 // per sample b and class c:  I_bc = sum_pix p_c [t == c],  C_bc = sum_pix (p_c^2 + [t == c]),  loss = mean_{b,c} (1 - 2 I_bc / (C_bc + 1e-6)).
 // stats = {loss, 0, then per sample {I0, I1, Q0 = sum p0^2, Q1 = sum p1^2, N0 = #[t == 0], N1 = #[t == 1]}}; like the cross-entropy pair above the
 // (B, 2, H, W) logits are never written.
-template <typename T>
-__global__ __launch_bounds__(256) void upsample_dice_fwd_kernel(const T* __restrict__ x, const int64_t* __restrict__ target, float* __restrict__ partial,
-                                                                int Hi, int Wi, int Ho, int Wo, float sh, float sw) {
-    const int b = blockIdx.y;
-    const int64_t n = (int64_t)Ho * Wo;
+// (frame selection as in the cross-entropy pair: sample blockIdx.y reads frame sel[blockIdx.y]; a sample without a frame leaves zero sums)
+template <typename T, bool SEL>
+__global__ __launch_bounds__(256) void upsample_dice_fwd_kernel(const T* __restrict__ x, const int32_t* __restrict__ sel, int nfr, const int64_t* __restrict__ target,
+                                                                float* __restrict__ partial, int Hi, int Wi, int Ho, int Wo, float sh, float sw) {
+    const int b = blockIdx.y, fr = sel_frame<SEL>(sel, b, nfr);
+    const int64_t n = (SEL && fr < 0) ? 0 : (int64_t)Ho * Wo, npix = (int64_t)Ho * Wo;
     float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const int xo = (int)(i % Wo), yo = (int)(i / Wo);
         int y0, y1, x0, x1; float ly, lx;
         bl_coord(yo, sh, Hi, y0, y1, ly);
         bl_coord(xo, sw, Wi, x0, x1, lx);
-        const UpCe u = upce_at<T>(x + (int64_t)b * Hi * Wi * 2, Wi, y0, y1, ly, x0, x1, lx);
+        const UpCe u = upce_at<T>(x + (int64_t)fr * Hi * Wi * 2, Wi, y0, y1, ly, x0, x1, lx);
         const float p0 = expf(u.up0 - u.lse), p1 = expf(u.up1 - u.lse);
-        const int64_t t = target[(int64_t)b * n + i];
+        const int64_t t = target[(int64_t)b * npix + i];
         if (t == 0) { s[0] += p0; s[4] += 1.f; }
         if (t == 1) { s[1] += p1; s[5] += 1.f; }
         s[2] += p0 * p0; s[3] += p1 * p1;
@@ -1081,7 +1135,9 @@ __global__ __launch_bounds__(256) void upsample_dice_fwd_kernel(const T* __restr
     __syncthreads();
     if (threadIdx.x < 6) partial[((int64_t)b * gridDim.x + blockIdx.x) * 6 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
-__global__ __launch_bounds__(256) void upsample_dice_finish_kernel(const float* __restrict__ partial, int nblk, int B, float* __restrict__ stats) {
+// sel (NULL = none), nfr: a sample whose entry lies outside [0, nfr) adds no term to the loss (the mean stays over B samples)
+__global__ __launch_bounds__(256) void upsample_dice_finish_kernel(const float* __restrict__ partial, int nblk, int B, float* __restrict__ stats,
+                                                                   const int32_t* __restrict__ sel, int nfr) {
     __shared__ float red[4][6];
     __shared__ float loss_acc;
     if (threadIdx.x == 0) loss_acc = 0.f;
@@ -1101,23 +1157,31 @@ __global__ __launch_bounds__(256) void upsample_dice_finish_kernel(const float* 
             float v[6];
 #pragma unroll
             for (int j = 0; j < 6; ++j) { v[j] = red[0][j] + red[1][j] + red[2][j] + red[3][j]; stats[2 + b * 6 + j] = v[j]; }
-            loss_acc += (1.f - 2.f * v[0] / (v[2] + v[4] + 1e-6f)) + (1.f - 2.f * v[1] / (v[3] + v[5] + 1e-6f));
+            if (!sel || (sel[b] >= 0 && sel[b] < nfr))
+                loss_acc += (1.f - 2.f * v[0] / (v[2] + v[4] + 1e-6f)) + (1.f - 2.f * v[1] / (v[3] + v[5] + 1e-6f));
         }
     }
     if (threadIdx.x == 0) { stats[0] = loss_acc / (2.f * (float)B); stats[1] = 0.f; }
 }
 // dx[b, yi, xi, c]: with a_bc = -1 / (B (C_bc + eps)) and e_bc = I_bc / (B (C_bc + eps)^2),  d loss / d p_c(pix) = a_bc [t == c] + 2 p_c e_bc,
 // through the 2-class softmax (dz1 = p0 p1 (g1 - g0) = -dz0) and the bilinear weights, gathered per low-resolution pixel (no atomics)
-template <typename T>
-__global__ __launch_bounds__(256) void upsample_dice_bwd_kernel(const T* __restrict__ x, const int64_t* __restrict__ target, const float* __restrict__ stats,
-                                                                const float* __restrict__ dloss, T* __restrict__ dx, int B, int Hi, int Wi, int Ho, int Wo,
-                                                                float sh, float sw) {
+// B = frames of x / dx, nsel = samples of the loss (SEL = false: the same number); a frame that feeds no sample gets +0.0
+template <typename T, bool SEL>
+__global__ __launch_bounds__(256) void upsample_dice_bwd_kernel(const T* __restrict__ x, const int32_t* __restrict__ sel, int nsel, const int64_t* __restrict__ target,
+                                                                const float* __restrict__ stats, const float* __restrict__ dloss, T* __restrict__ dx, int B, int Hi,
+                                                                int Wi, int Ho, int Wo, float sh, float sw) {
     const int64_t n = (int64_t)B * Hi * Wi;
     const float g = dloss ? dloss[0] : 1.f;
     GRID_STRIDE(i, n) {
         const int xi = (int)(i % Wi), yi = (int)((i / Wi) % Hi), b = (int)(i / Wi / Hi);
-        const float* sb = stats + 2 + b * 6;
-        const float c0 = sb[2] + sb[4] + 1e-6f, c1 = sb[3] + sb[5] + 1e-6f, invB = 0.5f / (float)B;      // mean over (b, c): 1 / (2B)
+        const int js = sel_sample<SEL>(sel, nsel, b);
+        if (SEL && js < 0) {
+            dx[i * 2] = from_f<T>(0.f);
+            dx[i * 2 + 1] = from_f<T>(0.f);
+            continue;
+        }
+        const float* sb = stats + 2 + js * 6;
+        const float c0 = sb[2] + sb[4] + 1e-6f, c1 = sb[3] + sb[5] + 1e-6f, invB = 0.5f / (float)nsel;      // mean over (sample, c): 1 / (2 nsel)
         const float A0 = -2.f * invB / c0, A1 = -2.f * invB / c1, E0 = 2.f * invB * sb[0] / (c0 * c0), E1 = 2.f * invB * sb[1] / (c1 * c1);
         int ylo, yhi, xlo, xhi;
         bl_range(yi, sh, Hi, Ho, ylo, yhi);
@@ -1134,7 +1198,7 @@ __global__ __launch_bounds__(256) void upsample_dice_bwd_kernel(const T* __restr
                 bl_coord(xo, sw, Wi, x0, x1, lx);
                 const float wx = (x0 == xi ? 1.f - lx : 0.f) + (x1 == xi ? lx : 0.f);
                 if (wx == 0.f) continue;
-                const int64_t t = target[((int64_t)b * Ho + yo) * Wo + xo];
+                const int64_t t = target[((int64_t)js * Ho + yo) * Wo + xo];
                 const UpCe u = upce_at<T>(base, Wi, y0, y1, ly, x0, x1, lx);
                 const float p0 = expf(u.up0 - u.lse), p1 = expf(u.up1 - u.lse);
                 const float g0 = (t == 0 ? A0 : 0.f) + 2.f * p0 * E0, g1 = (t == 1 ? A1 : 0.f) + 2.f * p1 * E1;
@@ -1145,23 +1209,68 @@ __global__ __launch_bounds__(256) void upsample_dice_bwd_kernel(const T* __restr
         dx[i * 2 + 1] = from_f<T>(acc * g);
     }
 }
+template <bool SEL>
+static int upsample_dice_fwd(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, float* ws, int64_t ws_floats, float* stats,
+                             int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
+    const int64_t n = (int64_t)Ho * Wo;
+    const int ns = SEL ? nsel : B;
+    int blocks = (int)((n + 1023) / 1024);
+    if (blocks > 256) blocks = 256;
+    LAVT_CHECK_ARG(ws_floats >= (int64_t)blocks * 6 * ns, "lavt_upsample_dice_fwd: scratch of %d floats needed", blocks * 6 * ns);
+    DISPATCH_T(dtype, "lavt_upsample_dice_fwd", hipLaunchKernelGGL((upsample_dice_fwd_kernel<T, SEL>), dim3(blocks, ns), dim3(256), 0, ST, (const T*)x, sel, B, target, ws, Hi, Wi, Ho, Wo, bl_scale(Hi, Ho), bl_scale(Wi, Wo)));
+    hipLaunchKernelGGL(upsample_dice_finish_kernel, dim3(1), dim3(256), 0, ST, ws, blocks, ns, stats, sel, B);
+    LAVT_CHECK_LAUNCH("lavt_upsample_dice_fwd");
+    return LAVT_OK;
+}
 extern "C" int lavt_upsample_dice_fwd(int dtype, const void* x, const int64_t* target, float* ws, int64_t ws_floats, float* stats,
                                       int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
     LAVT_CHECK_ARG(x && target && ws && stats && B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "lavt_upsample_dice_fwd: bad arguments");
-    const int64_t n = (int64_t)Ho * Wo;
-    int blocks = (int)((n + 1023) / 1024);
-    if (blocks > 256) blocks = 256;
-    LAVT_CHECK_ARG(ws_floats >= (int64_t)blocks * 6 * B, "lavt_upsample_dice_fwd: scratch of %d floats needed", blocks * 6 * B);
-    DISPATCH_T(dtype, "lavt_upsample_dice_fwd", hipLaunchKernelGGL(upsample_dice_fwd_kernel<T>, dim3(blocks, B), dim3(256), 0, ST, (const T*)x, target, ws, Hi, Wi, Ho, Wo, bl_scale(Hi, Ho), bl_scale(Wi, Wo)));
-    hipLaunchKernelGGL(upsample_dice_finish_kernel, dim3(1), dim3(256), 0, ST, ws, blocks, B, stats);
-    LAVT_CHECK_LAUNCH("lavt_upsample_dice_fwd");
+    return upsample_dice_fwd<false>(dtype, x, nullptr, B, target, ws, ws_floats, stats, B, Hi, Wi, Ho, Wo, stream);
+}
+extern "C" int lavt_upsample_dice_sel_fwd(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, float* ws, int64_t ws_floats,
+                                          float* stats, int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
+    LAVT_CHECK_ARG(x && sel && target && ws && stats && B > 0 && nsel > 0 && nsel <= B && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "lavt_upsample_dice_sel_fwd: bad arguments (0 < nsel <= B)");
+    return upsample_dice_fwd<true>(dtype, x, sel, nsel, target, ws, ws_floats, stats, B, Hi, Wi, Ho, Wo, stream);
+}
+template <bool SEL>
+static int upsample_dice_bwd(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, const float* stats, const float* dloss, void* dx,
+                             int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
+    const int64_t n = (int64_t)B * Hi * Wi;
+    DISPATCH_T(dtype, "lavt_upsample_dice_bwd", hipLaunchKernelGGL((upsample_dice_bwd_kernel<T, SEL>), dim3(ew_grid(n)), dim3(256), 0, ST, (const T*)x, sel, SEL ? nsel : B, target, stats, dloss, (T*)dx, B, Hi, Wi, Ho, Wo, bl_scale(Hi, Ho), bl_scale(Wi, Wo)));
+    LAVT_CHECK_LAUNCH("lavt_upsample_dice_bwd");
     return LAVT_OK;
 }
 extern "C" int lavt_upsample_dice_bwd(int dtype, const void* x, const int64_t* target, const float* stats, const float* dloss, void* dx,
                                       int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
     LAVT_CHECK_ARG(x && target && stats && dx && B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "lavt_upsample_dice_bwd: bad arguments");
-    const int64_t n = (int64_t)B * Hi * Wi;
-    DISPATCH_T(dtype, "lavt_upsample_dice_bwd", hipLaunchKernelGGL(upsample_dice_bwd_kernel<T>, dim3(ew_grid(n)), dim3(256), 0, ST, (const T*)x, target, stats, dloss, (T*)dx, B, Hi, Wi, Ho, Wo, bl_scale(Hi, Ho), bl_scale(Wi, Wo)));
-    LAVT_CHECK_LAUNCH("lavt_upsample_dice_bwd");
+    return upsample_dice_bwd<false>(dtype, x, nullptr, B, target, stats, dloss, dx, B, Hi, Wi, Ho, Wo, stream);
+}
+extern "C" int lavt_upsample_dice_sel_bwd(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, const float* stats, const float* dloss,
+                                          void* dx, int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
+    LAVT_CHECK_ARG(x && sel && target && stats && dx && B > 0 && nsel > 0 && nsel <= B && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "lavt_upsample_dice_sel_bwd: bad arguments (0 < nsel <= B)");
+    return upsample_dice_bwd<true>(dtype, x, sel, nsel, target, stats, dloss, dx, B, Hi, Wi, Ho, Wo, stream);
+}
+
+// ---- dst[j] = src[sel[j]] for whole samples: the gather of the backbone outputs in front of the folded decoder when only the annotated frames of a
+// clip are scored (test.py:182-205 of the reference selects after the decoder; in eval mode the folded decoder is per-sample independent).
+// V = uint4 when the sample size and both bases are multiples of 16 bytes, else the element type.  A sample whose entry lies outside [0, B) is zero-filled.
+template <typename V>
+__global__ __launch_bounds__(256) void gather_samples_kernel(const V* __restrict__ src, const int32_t* __restrict__ sel, int B, int64_t per, V* __restrict__ dst) {
+    const int j = blockIdx.y, f = sel[j];
+    const bool ok = f >= 0 && f < B;
+    const V* s = src + (int64_t)(ok ? f : 0) * per;
+    V* d = dst + (int64_t)j * per;
+    GRID_STRIDE(i, per) d[i] = ok ? s[i] : V{};
+}
+extern "C" int lavt_gather_samples(int dtype, const void* src, const int32_t* sel, int nsel, int B, int64_t sample_elems, void* dst, void* stream) {
+    LAVT_CHECK_ARG(src && sel && dst && nsel > 0 && nsel <= 65535 && B > 0 && sample_elems > 0 && (dtype | 1) == 1, "lavt_gather_samples: bad arguments");
+    const int64_t bytes = sample_elems * (dtype == LAVT_F32 ? 4 : 2);
+    if (bytes % 16 == 0 && ((uintptr_t)src | (uintptr_t)dst) % 16 == 0)
+        hipLaunchKernelGGL(gather_samples_kernel<uint4>, dim3(ew_grid(bytes / 16), nsel), dim3(256), 0, ST, (const uint4*)src, sel, B, bytes / 16, (uint4*)dst);
+    else if (dtype == LAVT_F32)
+        hipLaunchKernelGGL(gather_samples_kernel<float>, dim3(ew_grid(sample_elems), nsel), dim3(256), 0, ST, (const float*)src, sel, B, sample_elems, (float*)dst);
+    else
+        hipLaunchKernelGGL(gather_samples_kernel<uint16_t>, dim3(ew_grid(sample_elems), nsel), dim3(256), 0, ST, (const uint16_t*)src, sel, B, sample_elems, (uint16_t*)dst);
+    LAVT_CHECK_LAUNCH("lavt_gather_samples");
     return LAVT_OK;
 }

@@ -238,6 +238,11 @@ _PROTOTYPES = {
     "lavt_upsample_ce_bwd": [i32, vp, vp, f32, f32, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "lavt_upsample_dice_fwd": [i32, vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, vp],
     "lavt_upsample_dice_bwd": [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "lavt_upsample_ce_sel_fwd": [i32, vp, vp, i32, vp, f32, f32, vp, i64, vp, i32, i32, i32, i32, i32, vp],
+    "lavt_upsample_ce_sel_bwd": [i32, vp, vp, i32, vp, f32, f32, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "lavt_upsample_dice_sel_fwd": [i32, vp, vp, i32, vp, vp, i64, vp, i32, i32, i32, i32, i32, vp],
+    "lavt_upsample_dice_sel_bwd": [i32, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "lavt_gather_samples": [i32, vp, vp, i32, i32, i64, vp, vp],
     "lavt_fp8_quantize": [i32, vp, vp, i64, vp, vp, vp],
     "lavt_fp8_advance": [vp, vp, i32, vp],
     "lavt_fp8_quantize_weight": [vp, vp, vp, i32, i32, i32, vp],

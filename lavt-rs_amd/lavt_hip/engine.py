@@ -41,11 +41,67 @@ def _in_context(fn):
     return wrapped
 
 
-class TrainStep:
-    def __init__(self, model, image, l_feats, l_mask, target, world=1, use_graph=True, bucket_mib=32.0, fused_loss=True, refresh_weights_in_step=False, context=None):
+def flat_valid_indices(per_clip, frames_per_clip, n_frames, count=None):
+    """`[i * t + ind for i, ind in enumerate(valid_indices)]` of the reference (train.py:283, test.py:182-205): the annotated frame `ind` of clip i as
+    a row of the (B*T, ...) model output.  Host integers in, a list out; ValueError unless there are `count` entries (when given), every flat index
+    lies in [0, n_frames) and no two are equal -- the checks the kernels cannot make (include/lavt_hip.h: the contract of sel)."""
+    per_clip = [int(v) for v in per_clip]
+    T = int(frames_per_clip)
+    if T < 1:
+        raise ValueError(f"valid indices: frames_per_clip must be >= 1, got {T}")
+    if count is not None and len(per_clip) != count:
+        raise ValueError(f"valid indices: {len(per_clip)} entries for an index buffer of {count}")
+    flat = [i * T + ind for i, ind in enumerate(per_clip)]
+    bad = [(i, ind) for i, (ind, f) in enumerate(zip(per_clip, flat)) if ind < 0 or not 0 <= f < n_frames]
+    if bad:
+        raise ValueError(f"valid indices: (clip, frame) {bad} outside the {n_frames} frames of the batch ({T} per clip)")
+    if len(set(flat)) != len(flat):
+        raise ValueError(f"valid indices: {per_clip} with {T} frames per clip name a frame twice (flat {flat})")
+    return flat
+
+
+def _check_index_buffer(who, valid_indices, target, n_frames):
+    if not isinstance(valid_indices, torch.Tensor) or not valid_indices.is_cuda:
+        raise RuntimeError("liblavt_hip operates on GPU memory only (got a CPU tensor for `valid_indices`); there is no CPU fallback")
+    if valid_indices.dtype != torch.int32 or valid_indices.dim() != 1 or not valid_indices.is_contiguous() or not 1 <= valid_indices.numel() <= n_frames:
+        raise ValueError(f"{who}: valid_indices must be a contiguous int32 vector of 1..{n_frames} frame numbers, got {valid_indices.dtype} {tuple(valid_indices.shape)}")
+    if target is not None and target.shape[0] != valid_indices.numel():
+        raise ValueError(f"{who}: {valid_indices.numel()} valid indices need a target of as many samples, got {tuple(target.shape)}")
+
+
+class _ValidIndices:
+    """set_valid_indices of TrainStep and Predictor: `valid_indices` is a static device buffer like image and target"""
+
+    def _n_frames(self):
+        return self.x.numel() // (3 * int(self.x.shape[-2]) * int(self.x.shape[-1]))          # B, or B*T for a clip batch (B, T, 3, H, W)
+
+    def set_valid_indices(self, per_clip, frames_per_clip):
+        """per_clip[i] = the annotated frame of clip i (host integers): writes `i * frames_per_clip + per_clip[i]` (train.py:283) into the static
+        index buffer after checking count, range and distinctness (ValueError).  An asynchronous copy on the current stream, nothing synchronises;
+        usable between replays -- the captured kernels read the buffer on the device."""
+        if self.valid_indices is None:
+            raise ValueError(f"{type(self).__name__}.set_valid_indices: built without a valid_indices buffer")
+        flat = torch.tensor(flat_valid_indices(per_clip, frames_per_clip, self._n_frames(), count=self.valid_indices.numel()), dtype=torch.int32)
+        if self.valid_indices.is_cuda:
+            flat = flat.pin_memory()
+        self.valid_indices.copy_(flat, non_blocking=True)
+
+
+class TrainStep(_ValidIndices):
+    def __init__(self, model, image, l_feats, l_mask, target, world=1, use_graph=True, bucket_mib=32.0, fused_loss=True, refresh_weights_in_step=False, context=None,
+                 *, loss="ce", valid_indices=None):
         """context: the ops.StepContext this harness keeps its state in (gradient sinks, deferred-launch queues, weight copies, scratch).  None = the
         process-wide default context -- what the drop-in path and a single harness use.  Give every further model in the process its own
-        `ops.StepContext()` (and its optimizer the same one: FusedAdamW(..., context=)): their steps can then alternate freely."""
+        `ops.StepContext()` (and its optimizer the same one: FusedAdamW(..., context=)): their steps can then alternate freely.
+        loss: "ce" (losses.py:7-11, the default) or "mc_dice" (MultiClassDiceLoss, losses.py:38-77; `--loss mc_dice` of train.py:703-704).
+        valid_indices: device int32 [nsel], a static buffer like image and target -- the flat numbers of the annotated frames (A2D-Sentences / JHMDB:
+        one per clip, train.py:282-285); target is then (nsel, H, W) and the criterion (and `stats`) covers `index_select(output, 0, valid_indices)`.
+        Fill it with set_valid_indices(per_clip, frames_per_clip), before capture or between replays."""
+        if loss not in ("ce", "mc_dice"):
+            raise ValueError(f"TrainStep: loss must be 'ce' or 'mc_dice', got {loss!r}")
+        if valid_indices is not None:
+            _check_index_buffer("TrainStep", valid_indices, target, image.numel() // (3 * int(image.shape[-2]) * int(image.shape[-1])))
+        self.criterion, self.valid_indices = loss, valid_indices
         self.context = context if context is not None else ops.default_context()
         with ops.use_context(self.context):
             self._init(model, image, l_feats, l_mask, target, world, use_graph, bucket_mib, fused_loss, refresh_weights_in_step)
@@ -124,12 +180,22 @@ class TrainStep:
         ops.dtable_chain.job, ops.dtable_chain.keep = None, None          # (a backward that raised mid-way must not leave its binning job to the next step)
         if fp8_enabled():
             ops.fp8.advance()                    # delayed scaling: last step's |max| values become this step's quantisation scales
-        if self.fused_loss:                       # upsample + weighted CE (+ I/U) fused: the (B,2,H,W) logits are never written
-            from lib._utils import fused_loss
-            loss, self.stats = fused_loss(self.model.forward_lowres(self.x, self.l, self.m), self.t, (0.9, 1.1))
+        if self.fused_loss:                       # upsample + criterion (+ I/U) fused: the (B,2,H,W) logits are never written
+            from lib._utils import fused_dice_loss, fused_loss
+            y = self.model.forward_lowres(self.x, self.l, self.m)
+            if self.criterion == "ce":
+                loss, self.stats = fused_loss(y, self.t, (0.9, 1.1), valid_indices=self.valid_indices)
+            else:
+                loss, self.stats = fused_dice_loss(y, self.t, valid_indices=self.valid_indices)
         else:
             out = self.model(self.x, self.l, self.m)
-            loss = F.cross_entropy(out, self.t, weight=self.w)
+            if self.valid_indices is not None:
+                out = torch.index_select(out, 0, self.valid_indices)          # train.py:284, literally
+            if self.criterion == "ce":
+                loss = F.cross_entropy(out, self.t, weight=self.w)
+            else:
+                from losses import MultiClassDiceLoss
+                loss = MultiClassDiceLoss()(out, self.t)
         if self._one is None or self._one.shape != loss.shape or self._one.dtype != loss.dtype:
             self._one = torch.ones_like(loss)    # (first eager step) the root gradient as a persistent tensor: `loss.backward()` fills a fresh ones_like every step,
         loss.backward(self._one)                 # one more 4.5 us launch on the captured chain
@@ -257,7 +323,7 @@ class TrainStep:
         return self.loss
 
 
-class Predictor:
+class Predictor(_ValidIndices):
     """The inference sibling of TrainStep: the reference's evaluation loop body (test.py:60-83, test_ytvos.py:230-260)
 
         model.eval(); with torch.no_grad(): out = model(image, l, l_mask); mask = out.argmax(1); I, U = computeIoU(mask, target)
@@ -273,9 +339,13 @@ class Predictor:
                   (network input size first, then the original frame size)
       expressions_per_image   S: `image` holds B images, lang / l_mask B*S expressions (expression j of image i at i*S + j), mask sample i*S + j;
                   patch embedding and the stage-0 Swin blocks run once per image
+      valid_indices   optional device int32 [nsel], a static buffer: the flat numbers of the annotated frames of the clips (A2D-Sentences / JHMDB,
+                  test.py:182-205).  The backbone runs on all frames, the decoder and the mask kernel on the nsel selected ones: mask (nsel, Ho, Wo),
+                  target (if given) (nsel, Ho, Wo), iu (nsel, 2).  set_valid_indices(per_clip, frames_per_clip) fills it, also between replays.
     step() never synchronises: it returns the static mask tensor, the caller decides when to read it (EvalMeter.update(pred.iu) reads `.iu`)."""
 
-    def __init__(self, model, image, lang, l_mask, *, target=None, out_size=None, via_size=None, expressions_per_image=1, use_graph=True, context=None):
+    def __init__(self, model, image, lang, l_mask, *, target=None, out_size=None, via_size=None, expressions_per_image=1, use_graph=True, context=None,
+                 valid_indices=None):
         if model.training:
             raise RuntimeError("Predictor: the model is in training mode -- call model.eval() first (BatchNorm is folded from the running statistics, DropPath is off)")
         for name, t in (("image", image), ("lang", lang), ("l_mask", l_mask), ("target", target)):
@@ -286,6 +356,11 @@ class Predictor:
         S = int(expressions_per_image)
         if S < 1:
             raise ValueError("Predictor: expressions_per_image must be >= 1")
+        if valid_indices is not None:
+            if S > 1:
+                raise ValueError("Predictor: valid_indices selects frames of clips; it cannot be combined with expressions_per_image > 1")
+            _check_index_buffer("Predictor", valid_indices, target, image.numel() // (3 * int(image.shape[-2]) * int(image.shape[-1])))
+        self.valid_indices = valid_indices
         if S > 1 and not getattr(model.backbone, "shares_stage0", False):
             raise NotImplementedError(f"Predictor: expressions_per_image > 1 needs a backbone that shares stage 0 between expressions; {type(model.backbone).__name__} does not")
         if lang.shape[0] != image.shape[0] * S:
@@ -313,7 +388,10 @@ class Predictor:
     @_in_context
     def _body(self):
         with torch.no_grad():
-            y = self.model.forward_lowres(self.x, self.l, self.m, folded=True, expand=self.S)
+            if self.valid_indices is None:
+                y = self.model.forward_lowres(self.x, self.l, self.m, folded=True, expand=self.S)
+            else:
+                y = self.model.forward_lowres(self.x, self.l, self.m, folded=True, frames=self.valid_indices)
             n, _, h, w = y.shape
             from lib.mask_predictor import nchw_rows
             self.mask, self.iu = ops.upsample_mask(nchw_rows(y, y.dtype), n, h, w, self.out_size, via_size=self.via_size, target=self.t)

@@ -2898,17 +2898,25 @@ def logits_upsample(x, B, Hi, Wi, Ho, Wo):
 class _UpsampleCE(torch.autograd.Function):
     """loss = F.cross_entropy(F.interpolate(y, (Ho, Wo), bilinear, align_corners=True), target, weight=(w0, w1)) on the low-resolution
     2-class logits rows x [B*Hi*Wi, 2] (lib/_utils.py:21 + losses.py:7-11) without materialising the upsampled logits.
-    Returns (loss, stats) with stats = [loss, sum of weights, I, U] (train.py:64-76 pixel counts of the argmax mask)."""
+    Returns (loss, stats) with stats = [loss, sum of weights, I, U] (train.py:64-76 pixel counts of the argmax mask).
+    sel (device int32 [nsel], see _frame_sel): the loss of `index_select(logits, 0, sel)` against target [nsel, Ho, Wo] (train.py:282-285); the
+    gradient of the unselected frames is +0.0."""
 
     @staticmethod
-    def forward(ctx, x, target, B, Hi, Wi, Ho, Wo, w0, w1):
+    def forward(ctx, x, target, B, Hi, Wi, Ho, Wo, w0, w1, sel=None):
         x = x.contiguous()
         target = target.contiguous()
-        assert target.dtype == torch.int64 and target.numel() == B * Ho * Wo
+        ns = B if sel is None else sel.numel()
+        assert target.dtype == torch.int64 and target.numel() == ns * Ho * Wo
         out4 = torch.empty(4, dtype=torch.float32, device=x.device)
         ws = _scratch(4 * 2048, x.device)
-        K.check(K.lib.lavt_upsample_ce_fwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), float(w0), float(w1), K.ptr(ws), ws.numel(), K.ptr(out4),
-                                           B, Hi, Wi, Ho, Wo, K.stream()))
+        if sel is None:
+            K.check(K.lib.lavt_upsample_ce_fwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), float(w0), float(w1), K.ptr(ws), ws.numel(), K.ptr(out4),
+                                               B, Hi, Wi, Ho, Wo, K.stream()))
+        else:
+            K.check(K.lib.lavt_upsample_ce_sel_fwd(K.dt(x.dtype), K.ptr(x), K.ptr(sel), ns, K.ptr(target), float(w0), float(w1), K.ptr(ws), ws.numel(),
+                                                   K.ptr(out4), B, Hi, Wi, Ho, Wo, K.stream()))
+        ctx.sel = sel                            # (an index buffer, not a tensor autograd tracks: the backward reads what it holds THEN, as a replay does)
         ctx.dims = (B, Hi, Wi, Ho, Wo, float(w0), float(w1))
         ctx.set_materialize_grads(False)         # (the statistics receive no gradient: None instead of a zero fill per step)
         if wgrads.active():
@@ -2931,30 +2939,56 @@ class _UpsampleCE(torch.autograd.Function):
         B, Hi, Wi, Ho, Wo, w0, w1 = ctx.dims
         dx = torch.empty_like(x)
         if dloss is None:                        # (nothing downstream of the loss)
-            return None, None, None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None, None, None
         dl = dloss.contiguous().float().reshape(1)
-        K.check(K.lib.lavt_upsample_ce_bwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), w0, w1, K.ptr(out4), K.ptr(dl), K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
-        return dx, None, None, None, None, None, None, None, None
+        if ctx.sel is None:
+            K.check(K.lib.lavt_upsample_ce_bwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), w0, w1, K.ptr(out4), K.ptr(dl), K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
+        else:
+            K.check(K.lib.lavt_upsample_ce_sel_bwd(K.dt(x.dtype), K.ptr(x), K.ptr(ctx.sel), ctx.sel.numel(), K.ptr(target), w0, w1, K.ptr(out4), K.ptr(dl),
+                                                   K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
+        return dx, None, None, None, None, None, None, None, None, None
 
 
-def upsample_cross_entropy(x, target, B, Hi, Wi, Ho, Wo, weight=(0.9, 1.1)):
-    return _UpsampleCE.apply(x, target, B, Hi, Wi, Ho, Wo, weight[0], weight[1])
+def _frame_sel(sel, B, what):
+    """the frame-selection buffer of the _sel_ entry points (include/lavt_hip.h): a contiguous int32 vector of 1..B entries ON THE DEVICE.  Its values are
+    not read here (that would synchronise, and a captured step reads the buffer at replay time): range and distinctness are the caller's, checked
+    on the host where the indices come from the host (engine.TrainStep / Predictor.set_valid_indices)."""
+    if sel is None:
+        return None
+    if not isinstance(sel, torch.Tensor) or not sel.is_cuda:
+        raise RuntimeError(f"liblavt_hip operates on GPU memory only (got {type(sel).__name__} for the frame selection of `{what}`); there is no CPU fallback")
+    if sel.dtype != torch.int32 or sel.dim() != 1 or not sel.is_contiguous() or not 1 <= sel.numel() <= B:
+        raise ValueError(f"{what}: the frame selection must be a contiguous int32 vector of 1..{B} entries, got {sel.dtype} {tuple(sel.shape)}")
+    return sel
+
+
+def upsample_cross_entropy(x, target, B, Hi, Wi, Ho, Wo, weight=(0.9, 1.1), sel=None):
+    if sel is None:
+        return _UpsampleCE.apply(x, target, B, Hi, Wi, Ho, Wo, weight[0], weight[1])
+    return _UpsampleCE.apply(x, target, B, Hi, Wi, Ho, Wo, weight[0], weight[1], _frame_sel(sel, B, "upsample_cross_entropy"))
 
 
 @K.scoped
 class _UpsampleDice(torch.autograd.Function):
     """MultiClassDiceLoss()(F.interpolate(y, (Ho, Wo), bilinear, align_corners=True), target) on the low-resolution 2-class logits rows
     x [B*Hi*Wi, 2] (reference losses.py:38-77 after lib/_utils.py:21), the upsampled logits never written.
-    Returns (loss, stats) with stats = [loss, 0, per sample {I0, I1, sum p0^2, sum p1^2, #t==0, #t==1}]."""
+    Returns (loss, stats) with stats = [loss, 0, per sample {I0, I1, sum p0^2, sum p1^2, #t==0, #t==1}].
+    sel (device int32 [nsel], see _frame_sel): the loss of `index_select(logits, 0, sel)` against target [nsel, Ho, Wo]; stats per SELECTED sample."""
 
     @staticmethod
-    def forward(ctx, x, target, B, Hi, Wi, Ho, Wo):
+    def forward(ctx, x, target, B, Hi, Wi, Ho, Wo, sel=None):
         x = x.contiguous()
         target = target.contiguous()
-        assert target.dtype == torch.int64 and target.numel() == B * Ho * Wo
-        stats = torch.empty(2 + 6 * B, dtype=torch.float32, device=x.device)
-        ws = _scratch(6 * 256 * B, x.device)
-        K.check(K.lib.lavt_upsample_dice_fwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), K.ptr(ws), ws.numel(), K.ptr(stats), B, Hi, Wi, Ho, Wo, K.stream()))
+        ns = B if sel is None else sel.numel()
+        assert target.dtype == torch.int64 and target.numel() == ns * Ho * Wo
+        stats = torch.empty(2 + 6 * ns, dtype=torch.float32, device=x.device)
+        ws = _scratch(6 * 256 * ns, x.device)
+        if sel is None:
+            K.check(K.lib.lavt_upsample_dice_fwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), K.ptr(ws), ws.numel(), K.ptr(stats), B, Hi, Wi, Ho, Wo, K.stream()))
+        else:
+            K.check(K.lib.lavt_upsample_dice_sel_fwd(K.dt(x.dtype), K.ptr(x), K.ptr(sel), ns, K.ptr(target), K.ptr(ws), ws.numel(), K.ptr(stats),
+                                                     B, Hi, Wi, Ho, Wo, K.stream()))
+        ctx.sel = sel
         ctx.save_for_backward(x, target, stats)
         ctx.dims = (B, Hi, Wi, Ho, Wo)
         ctx.mark_non_differentiable(stats)
@@ -2966,12 +3000,40 @@ class _UpsampleDice(torch.autograd.Function):
         B, Hi, Wi, Ho, Wo = ctx.dims
         dx = torch.empty_like(x)
         dl = dloss.contiguous().float().reshape(1)
-        K.check(K.lib.lavt_upsample_dice_bwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), K.ptr(stats), K.ptr(dl), K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
-        return dx, None, None, None, None, None, None
+        if ctx.sel is None:
+            K.check(K.lib.lavt_upsample_dice_bwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), K.ptr(stats), K.ptr(dl), K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
+        else:
+            K.check(K.lib.lavt_upsample_dice_sel_bwd(K.dt(x.dtype), K.ptr(x), K.ptr(ctx.sel), ctx.sel.numel(), K.ptr(target), K.ptr(stats), K.ptr(dl),
+                                                     K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
+        return dx, None, None, None, None, None, None, None
 
 
-def upsample_dice_loss(x, target, B, Hi, Wi, Ho, Wo):
-    return _UpsampleDice.apply(x, target, B, Hi, Wi, Ho, Wo)
+def upsample_dice_loss(x, target, B, Hi, Wi, Ho, Wo, sel=None):
+    if sel is None:
+        return _UpsampleDice.apply(x, target, B, Hi, Wi, Ho, Wo)
+    return _UpsampleDice.apply(x, target, B, Hi, Wi, Ho, Wo, _frame_sel(sel, B, "upsample_dice_loss"))
+
+
+def gather_samples(x, sel):
+    """`torch.index_select(x, 0, sel)` for whole samples with sel on the device (int32 [nsel], see _frame_sel), no layout change: x is a dense tensor in
+    ANY dimension order (an NCHW-shaped view of NHWC memory, as the backbone returns its feature maps, included) whose samples are contiguous blocks;
+    the result has x's strides with nsel samples.  Not differentiable (the inference path: lib._utils forward_lowres(frames=))."""
+    if not x.is_cuda:
+        raise RuntimeError("liblavt_hip operates on GPU memory only (got a CPU tensor for `gather_samples`); there is no CPU fallback")
+    B = int(x.shape[0])
+    sel = _frame_sel(sel, B, "gather_samples")
+    per = x[0].numel()
+    inner, expect = sorted((st, sz) for st, sz in zip(x.stride()[1:], x.shape[1:]) if sz > 1), 1
+    for st, sz in inner:                         # a sample is a dense block when its strides, sorted, are the running products of its sizes
+        if st != expect:
+            break
+        expect *= sz
+    if expect != per or (B > 1 and x.stride(0) != per):
+        x = x.contiguous()
+    out = torch.empty_strided((sel.numel(),) + tuple(x.shape[1:]), (per,) + tuple(x.stride()[1:]), dtype=x.dtype, device=x.device)
+    _note(f"gather-samples {sel.numel()}/{B}x{per}", nbytes=2 * sel.numel() * per * x.element_size())
+    K.check(K.lib.lavt_gather_samples(K.dt(x.dtype), K.ptr(x), K.ptr(sel), sel.numel(), B, per, K.ptr(out), K.stream()))
+    return out
 
 
 # ------------------------------------------------------------------------------------------ fused upsample + argmax (+ I/U counts): inference

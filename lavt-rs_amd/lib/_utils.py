@@ -23,22 +23,40 @@ def _upsample_logits(y, size):
     return ops.logits_upsample(nchw_rows(y, y.dtype), B, h, w, int(size[0]), int(size[1]))
 
 
-def fused_loss(y, target, weight=(0.9, 1.1)):
+def fused_loss(y, target, weight=(0.9, 1.1), valid_indices=None):
     """The caller's `criterion(model(...), target)` (train.py:221-224; losses.py:7-11) on the LOW-resolution decoder output y
     ((B, 2, h, w)-shaped): bilinear upsample to target.shape[-2:] + weighted cross-entropy + I/U counts in one kernel pair.
-    -> (loss, stats[loss, sum of weights, I, U])"""
+    -> (loss, stats[loss, sum of weights, I, U])
+    valid_indices (device int32 [nsel]: the flat frame numbers `i * t + ind` of train.py:283): the clips of A2D-Sentences / JHMDB carry one annotated
+    frame each -- `criterion(torch.index_select(output, 0, valid_indices), masks)` of train.py:282-285 with target (nsel, H, W); the statistics are
+    over the selected frames, the gradient of every other frame of y is exactly zero."""
     B, _, h, w = y.shape
-    return ops.upsample_cross_entropy(nchw_rows(y, y.dtype), target, B, h, w, int(target.shape[-2]), int(target.shape[-1]), weight)
+    return ops.upsample_cross_entropy(nchw_rows(y, y.dtype), target, B, h, w, int(target.shape[-2]), int(target.shape[-1]), weight, sel=valid_indices)
 
 
-def fused_dice_loss(y, target):
+def fused_dice_loss(y, target, valid_indices=None):
     """`MultiClassDiceLoss()(model(...), target)` (train.py:703-704; losses.py:38-77) on the LOW-resolution decoder output y: bilinear upsample
-    + softmax + per-sample Dice sums in one kernel pair.  -> (loss, stats)"""
+    + softmax + per-sample Dice sums in one kernel pair.  -> (loss, stats)
+    valid_indices: as for fused_loss; the Dice mean is over the selected samples and the 2 classes."""
     B, _, h, w = y.shape
-    return ops.upsample_dice_loss(nchw_rows(y, y.dtype), target, B, h, w, int(target.shape[-2]), int(target.shape[-1]))
+    return ops.upsample_dice_loss(nchw_rows(y, y.dtype), target, B, h, w, int(target.shape[-2]), int(target.shape[-1]), sel=valid_indices)
 
 
-def _decode(classifier, folded, x_c4, x_c3, x_c2, x_c1):
+def _check_frames(module, folded, frames):
+    if frames is not None and (module.training or not folded):
+        raise ValueError("forward_lowres: frames= needs the BatchNorm-folded decoder (folded=True, model.eval()); in training mode select in the "
+                         "loss: fused_loss(y, target, valid_indices=frames)")
+
+
+def _decode(classifier, folded, x_c4, x_c3, x_c2, x_c1, frames=None):
+    """frames (device int32 [nsel]): decode only those samples -- test.py:182-205 of the reference selects the annotated frame of every clip behind
+    the decoder; the BatchNorm-folded decoder is per-sample independent, so the backbone outputs are gathered in front of it instead
+    (ops.gather_samples: the 3 maps a lazy_pred decoder reads, else 4) and the result is (nsel, 2, H/4, W/4)-shaped.  Eval mode + folded only: the
+    train-mode BatchNorm of the decoder takes its statistics over ALL frames in the reference, there the selection belongs to the loss
+    (fused_loss(valid_indices=))."""
+    if frames is not None:
+        _check_frames(classifier, folded, frames)
+        x_c4, x_c3, x_c2, x_c1 = (None if f is None else ops.gather_samples(f, frames) for f in (x_c4, x_c3, x_c2, x_c1))
     return classifier.forward_folded(x_c4, x_c3, x_c2, x_c1) if folded else classifier(x_c4, x_c3, x_c2, x_c1)
 
 
@@ -48,12 +66,13 @@ class _LAVTSimpleDecode(nn.Module):
         self.backbone = backbone
         self.classifier = classifier
 
-    def forward_lowres(self, x, l_feats, l_mask, folded=False, expand=1):
+    def forward_lowres(self, x, l_feats, l_mask, folded=False, expand=1, frames=None):
         """decoder output before the final upsample, (B, 2, H/4, W/4)-shaped: feed it to `fused_loss`.
         Inference (lavt_hip.engine.Predictor): folded = the BatchNorm-folded decoder (eval mode); expand = S > 1 = S expressions per image (l_feats /
-        l_mask hold B * S of them), stage 0 of the backbone shared between the expressions of an image."""
+        l_mask hold B * S of them), stage 0 of the backbone shared between the expressions of an image; frames: see _decode."""
+        _check_frames(self, folded, frames)          # (raises in front of the backbone)
         x_c1, x_c2, x_c3, x_c4 = self.backbone(x, l_feats, l_mask, expand=expand) if expand != 1 else self.backbone(x, l_feats, l_mask)
-        return _decode(self.classifier, folded, x_c4, x_c3, x_c2, x_c1)
+        return _decode(self.classifier, folded, x_c4, x_c3, x_c2, x_c1, frames)
 
     def forward(self, x, l_feats, l_mask):
         return _upsample_logits(self.forward_lowres(x, l_feats, l_mask), x.shape[-2:])
@@ -91,9 +110,10 @@ class _LAVTOneSimpleDecode(nn.Module):
         self.text_encoder = _build_text_encoder(args)
         self.lazy_pred = bool(getattr(args, "lazy_pred", False))
 
-    def forward_lowres(self, x, text, l_mask, folded=False, expand=1):
+    def forward_lowres(self, x, text, l_mask, folded=False, expand=1, frames=None):
         """token ids (B, N_l) + attention mask (B, N_l) -> decoder logits at 1/4 resolution (what the fused upsample + CE kernel consumes).
-        folded / expand: see LAVT.forward_lowres (with expand = S the ids and the mask hold B * S expressions)."""
+        folded / expand / frames: see LAVT.forward_lowres (with expand = S the ids and the mask hold B * S expressions)."""
+        _check_frames(self, folded, frames)
         l_feats = self.text_encoder(text, attention_mask=l_mask)[0].permute(0, 2, 1)      # (B, 768, N_l)
         l_mask = l_mask.unsqueeze(dim=-1)
         features = self.backbone(x, l_feats, l_mask, expand=expand) if expand != 1 else self.backbone(x, l_feats, l_mask)
@@ -101,7 +121,7 @@ class _LAVTOneSimpleDecode(nn.Module):
             x_c1, (x_c2, x_c3, x_c4) = None, features
         else:
             x_c1, x_c2, x_c3, x_c4 = features
-        return _decode(self.classifier, folded, x_c4, x_c3, x_c2, x_c1)
+        return _decode(self.classifier, folded, x_c4, x_c3, x_c2, x_c1, frames)
 
     def forward(self, x, text, l_mask):
         return _upsample_logits(self.forward_lowres(x, text, l_mask), x.shape[-2:])
@@ -140,16 +160,18 @@ class _LAVTVideoSimpleDecode(nn.Module):
         l_feats = self.text_encoder(text, attention_mask=l_mask)[0].permute(0, 2, 1)      # (B, 768, N_l)
         return self.forward_backbone(x, l_feats, l_mask.unsqueeze(dim=-1))
 
-    def forward_lowres(self, x, text, l_mask, folded=False, expand=1):
+    def forward_lowres(self, x, text, l_mask, folded=False, expand=1, frames=None):
         """clip (B, T, 3, H, W) + token ids + attention mask -> decoder logits (B*T, 2, H/4, W/4)-shaped, before the final upsample.
-        folded: the BatchNorm-folded decoder (eval mode).  The video backbone has no shared stage 0: expand > 1 raises NotImplementedError."""
+        folded: the BatchNorm-folded decoder (eval mode).  The video backbone has no shared stage 0: expand > 1 raises NotImplementedError.
+        frames (device int32 [nsel], flat numbers i * T + ind): only the annotated frames are decoded, -> (nsel, 2, H/4, W/4)-shaped; see _decode."""
+        _check_frames(self, folded, frames)
         l_feats = self.text_encoder(text, attention_mask=l_mask)[0].permute(0, 2, 1)
         features = self.backbone(x.permute(0, 2, 1, 3, 4), l_feats, l_mask.unsqueeze(dim=-1), expand=expand)
         if self.lazy_pred:
             x_c1, (x_c2, x_c3, x_c4) = None, features
         else:
             x_c1, x_c2, x_c3, x_c4 = features
-        return _decode(self.classifier, folded, x_c4, x_c3, x_c2, x_c1)
+        return _decode(self.classifier, folded, x_c4, x_c3, x_c2, x_c1, frames)
 
     def forward_feats(self, x, text, l_mask):
         """Reference lib/_utils.py:110-131: -> (logits (B*T, 2, H, W) fp32, [x_c4, level-4, level-3, level-2 decoder features])."""

@@ -6,6 +6,9 @@
 
 Both run on liblavt_hip (the fused upsample + loss kernels with an identity upsample); the step harness uses the same kernels directly on
 the decoder's low-resolution output (lib._utils.fused_loss / fused_dice_loss) so that the (B, 2, H, W) logits are never materialised.
+Clips with one annotated frame (A2D-Sentences / JHMDB, train.py:282-285: `criterion(torch.index_select(output, 0, valid_indices), masks)`) keep
+working as written here on the selected logits; the fused forms take the indices themselves (fused_loss / fused_dice_loss(..., valid_indices=),
+engine.TrainStep(loss="ce" | "mc_dice", valid_indices=)) and leave the unselected frames a zero gradient.
 DiceFocalLoss / DiceBoundaryLoss (ablation criteria) are outside the hot path and raise.
 """
 import torch

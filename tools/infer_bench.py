@@ -15,7 +15,12 @@ and the decoder's launch count per call (profiler records in the "decoder" scope
 
     --frames-u8 HxW   (opt-in) also time the input stage for one uint8 frame of that size, same frame on both paths, next to the replay time:
   frames_cpu_pipeline   transforms.get_transform on the PIL image (resize, to-tensor, normalise on the host) + the fp32 upload into the predictor's image buffer
-  frames_load_frames    Predictor.load_frames: the uint8 upload (pinned staging) + the resize / normalise kernel into the same buffer"""
+  frames_load_frames    Predictor.load_frames: the uint8 upload (pinned staging) + the resize / normalise kernel into the same buffer
+
+    --video-select IND   (opt-in, runs ONLY this) annotated-frame selection on the geometry of `bench.py --workload video_swin_b_t8_384` (Video-Swin-B, one clip
+                         of T = 8 frames at 384^2, batch 1; A2D-Sentences / JHMDB annotate one frame per clip), two captured predictors in one process:
+  video_all_frames_then_index   the all-frame Predictor replay followed by mask[sel] / iu[sel] (what a caller does without selection)
+  video_valid_indices           Predictor(valid_indices=[IND]): the decoder and the mask kernel run on the one annotated frame"""
 import argparse
 import json
 import os
@@ -46,6 +51,60 @@ def timed(fn, calls, warmup):
     return statistics.median(ts), min(ts), max(ts)
 
 
+def video_select(a, report):
+    import lavt_hip
+    from lavt_hip import ops
+    from lavt_hip.detweights import det_inputs, fill_state_dict_
+    from lavt_hip.engine import Predictor
+    from lib._utils import LAVTVideo
+    from lib.mask_predictor import SimpleDecoding
+    from lib.video_swin_transformer import MultiModalSwinTransformer3D
+    dev, T, size, ind = "cuda:0", 8, 384, int(a.video_select)
+    if not 0 <= ind < T:
+        raise SystemExit(f"--video-select: the annotated frame must lie in [0, {T})")
+    lavt_hip.set_compute_dtype(torch.bfloat16 if a.dtype == "bf16" else torch.float32)
+    args = SimpleNamespace()
+    bb = MultiModalSwinTransformer3D(patch_size=(1, 4, 4), embed_dim=128, depths=[2, 2, 18, 2], num_heads=[4, 8, 16, 32], window_size=(8, 7, 7),
+                                     drop_path_rate=0.3, patch_norm=True, out_indices=(0, 1, 2, 3), num_heads_fusion=[1, 1, 1, 1], args=args)
+    parts = torch.nn.ModuleDict({"backbone": bb, "classifier": SimpleDecoding(1024, args)})
+    fill_state_dict_(parts)
+    parts.to(dev)
+    clip, l, m, tgt = det_inputs(1, size, 20, seed=1234, frames=T)
+    clip, l, m, tgt = clip.to(dev), l.to(dev), m.to(dev), tgt.to(dev)
+
+    class _Text(torch.nn.Module):          # language features are the input, as for bench.py's video workload: BERT is outside the comparison
+        def forward(self, ids, attention_mask=None):
+            return (l.permute(0, 2, 1),)
+
+    model = LAVTVideo.__new__(LAVTVideo)
+    torch.nn.Module.__init__(model)
+    model.backbone, model.classifier, model.text_encoder = parts["backbone"], parts["classifier"], _Text()
+    model.lazy_pred, model.seg_last = False, False
+    model.eval()
+    ids, am = torch.zeros(1, 20, dtype=torch.long, device=dev), m.squeeze(-1).contiguous()
+    sel = torch.tensor([ind], device=dev)
+    p_all = Predictor(model, clip, ids, am, target=tgt, context=ops.StepContext())
+    p_all.warmup_and_capture()
+    p_sel = Predictor(model, clip, ids, am, target=tgt[sel].contiguous(), valid_indices=sel.int(), context=ops.StepContext())
+    p_sel.warmup_and_capture()
+
+    def all_then_index():
+        p_all.step()
+        return p_all.mask[sel], p_all.iu[sel].tolist()
+
+    def selected():
+        p_sel.step()
+        return p_sel.mask, p_sel.iu.tolist()
+    med_a, lo_a, hi_a = timed(all_then_index, a.calls, a.warmup)
+    med_s, lo_s, hi_s = timed(selected, a.calls, a.warmup)
+    (mask_a, iu_a), (mask_s, iu_s) = all_then_index(), selected()
+    differ = int((mask_a != mask_s).sum())
+    common = dict(variant="video_swin_b", size=size, frames=T, batch=1, annotated_frame=ind)
+    report(path="video_all_frames_then_index", captured=p_all.captured, ms_median=round(med_a, 3), ms_min=round(lo_a, 3), ms_max=round(hi_a, 3), iu=iu_a[0], **common)
+    report(path="video_valid_indices", captured=p_sel.captured, ms_median=round(med_s, 3), ms_min=round(lo_s, 3), ms_max=round(hi_s, 3), iu=iu_s[0],
+           mask_pixels_differing_from_all_frames=differ, speedup=round(med_a / med_s, 3), **common)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=30)
@@ -55,9 +114,22 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("--frames-u8", default=None, metavar="HxW", help="also time the input stage for a uint8 frame of this size: CPU pipeline vs Predictor.load_frames")
+    ap.add_argument("--video-select", default=None, metavar="IND", help="run ONLY the annotated-frame comparison on Video-Swin-B, T=8, 384^2: all frames + index vs valid_indices=[IND]")
     a = ap.parse_args()
     if a.calls < 20:
         ap.error("--calls must be at least 20")
+    if a.video_select is not None:
+        lines = []
+
+        def report_video(**kw):
+            kw.update(dtype=a.dtype, calls=a.calls)
+            lines.append(json.dumps(kw))
+            print(lines[-1], flush=True)
+        video_select(a, report_video)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     import lavt_hip
     from lavt_hip import _capi as K
     from lavt_hip import ops
