@@ -569,6 +569,31 @@ int lavt_upsample_dice_sel_fwd(int dtype, const void* x, const int32_t* sel, int
                                float* stats, int B, int Hi, int Wi, int Ho, int Wo, void* stream);
 int lavt_upsample_dice_sel_bwd(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, const float* stats, const float* dloss,
                                void* dx, int B, int Hi, int Wi, int Ho, int Wo, void* stream);
+/* Fused bilinear upsample (align_corners) + DiceBoundaryLoss (reference losses.py:142-244, `--loss dice_boundary`, train.py:709-711; the rates are
+ * args.py:83-84: dice_rate 1, boundary_rate 0.05) on the 2-class low-resolution logits x NHWC [B,Hi,Wi,2]; target int64 [B,Ho,Wo] in {0,1}.
+ *   loss = dice_rate * dice + boundary_rate * boundary; dice is the criterion of lavt_upsample_dice_*; boundary = mean over (sample, class c) of 1 - BF1:
+ *   a = 1 - p_c, h = 1 - [t == c]; pred_b = maxpool3(a) - a, gt_b = maxpool3(h) - h, pred_b_ext = maxpool5(pred_b), gt_b_ext = maxpool5(gt_b) (stride 1, windows
+ *   clipped at the border); S1 = sum pred_b gt_b_ext, S2 = sum pred_b, S3 = sum pred_b_ext gt_b, S4 = sum gt_b; P = S1 / (S2 + 1e-7), R = S3 / (S4 + 1e-7),
+ *   BF1 = 2 P R / (P + R + 1e-7)                                                                                                 (losses.py:191-244).
+ * stats (device fp32, 3 + 14*n floats, n = samples) = {loss, dice, boundary, then per sample {I0, I1, sum p0^2, sum p1^2, #[t==0], #[t==1],
+ * S1..S4 of class 0, S1..S4 of class 1}}.  One workgroup per 32x32 output tile recomputes the probabilities of the tile and its halo in LDS: the
+ * [B,2,Ho,Wo] probabilities are never written.  No floating-point atomics anywhere: results are identical from run to run.
+ * ws: lavt_upsample_dice_boundary_ws(n, Ho, Wo) floats of scratch -- the forward's partial rows (14 per tile and sample), then the backward's
+ * fp32 map dz [n,Ho,Wo] = d loss / d (z1 - z0); forward and backward may be lent the same buffer or different ones of that size.
+ * Backward: dx NHWC [B,Hi,Wi,2] = dloss[0] (device scalar, NULL = 1) * d loss / d x in two launches: the dz map per tile (the gradient passes both
+ * max-pools by arg-max, torch's choice: window scanned row-major, the first maximum wins), then its transposed bilinear in gather form.
+ * With Hi == Ho and Wi == Wo the upsample is the identity (lavt-rs_amd/losses.py: DiceBoundaryLoss on full-resolution logits).
+ * _sel_: annotated-frame selection exactly as for the pairs above (sel DEVICE int32 [nsel], target [nsel,Ho,Wo], stats / ws with n = nsel). */
+int64_t lavt_upsample_dice_boundary_ws(int n, int Ho, int Wo);
+int lavt_upsample_dice_boundary_fwd(int dtype, const void* x, const int64_t* target, float dice_rate, float boundary_rate, float* ws, int64_t ws_floats,
+                                    float* stats, int B, int Hi, int Wi, int Ho, int Wo, void* stream);
+int lavt_upsample_dice_boundary_bwd(int dtype, const void* x, const int64_t* target, float dice_rate, float boundary_rate, const float* stats,
+                                    const float* dloss, float* ws, int64_t ws_floats, void* dx, int B, int Hi, int Wi, int Ho, int Wo, void* stream);
+int lavt_upsample_dice_boundary_sel_fwd(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, float dice_rate, float boundary_rate,
+                                        float* ws, int64_t ws_floats, float* stats, int B, int Hi, int Wi, int Ho, int Wo, void* stream);
+int lavt_upsample_dice_boundary_sel_bwd(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, float dice_rate, float boundary_rate,
+                                        const float* stats, const float* dloss, float* ws, int64_t ws_floats, void* dx, int B, int Hi, int Wi, int Ho,
+                                        int Wo, void* stream);
 /* dst[j] = src[sel[j]] for whole samples of sample_elems elements (dtype LAVT_F32 / LAVT_BF16; src holds B samples, dst nsel <= 65535): the gather of
  * the backbone outputs in front of the BatchNorm-folded decoder when only the annotated frames are scored (test.py:182-205 selects behind the
  * decoder; in eval mode the decoder is per-sample independent).  16-byte copies when the sample size and both bases are multiples of 16 bytes,

@@ -135,3 +135,43 @@ __device__ __forceinline__ void bl_coord(int o, float scale, int n_in, int& i0, 
     i1 = min(i0 + 1, n_in - 1);
     lam = src - (float)i0;
 }
+// gather form of the transpose: the output rows / columns [lo, hi] that can have sampled input index i (a generous candidate range; bl_coord decides)
+__device__ __forceinline__ void bl_range(int i, float scale, int n_in, int n_out, int& lo, int& hi) {
+    if (scale <= 0.f) { lo = 0; hi = n_out - 1; return; }
+    lo = max(0, (int)floorf((float)(i - 1) / scale) - 1);
+    hi = min(n_out - 1, (int)ceilf((float)(i + 1) / scale) + 1);
+}
+
+// ---- the fused upsample + criterion kernels (elementwise.hip, boundary_loss.hip): one full-resolution pixel of the 2-class logits from its four
+// low-resolution neighbours (x NHWC [.,Hi,Wi,2]) and its log-sum-exp
+struct UpCe { float up0, up1, lse; };
+// ---- frame selection (train.py:282-285, 366-369; test.py:182-205 of the reference: `index_select(output, 0, valid_indices)` in front of the criterion):
+// with SEL the loss has nsel samples, sample j reads logits frame sel[j] of the nfr frames of x and target j.  sel is read on the device (a replayed
+// graph follows the buffer); an entry outside [0, nfr) is never dereferenced.  SEL = false is the plain kernel: frame = sample.
+template <bool SEL> __device__ __forceinline__ int sel_frame(const int32_t* __restrict__ sel, int j, int nfr) {          // frame read by sample j, -1 = none
+    if constexpr (!SEL) return j;
+    else { const int f = sel[j]; return (f >= 0 && f < nfr) ? f : -1; }
+}
+// Backward: the sample that frame b feeds, -1 = none (its dx is +0.0).  A scan of sel per frame -- nsel is a handful, b is uniform over a wave in both
+// cross-entropy forms (over the workgroup in the tile form), so the scan is a few scalar loads.
+template <bool SEL> __device__ __forceinline__ int sel_sample(const int32_t* __restrict__ sel, int nsel, int b) {
+    if constexpr (!SEL) return b;
+    else {
+        int j = -1;
+        for (int k = nsel - 1; k >= 0; --k) j = sel[k] == b ? k : j;          // (entries are distinct by contract; the first one wins otherwise)
+        return j;
+    }
+}
+template <typename T>
+__device__ __forceinline__ UpCe upce_at(const T* base, int Wi, int y0, int y1, float ly, int x0, int x1, float lx) {
+    const T* r0 = base + ((int64_t)y0 * Wi) * 2;
+    const T* r1 = base + ((int64_t)y1 * Wi) * 2;
+    const float a0 = to_f<T>(r0[x0 * 2]), a1 = to_f<T>(r0[x0 * 2 + 1]), b0 = to_f<T>(r0[x1 * 2]), b1 = to_f<T>(r0[x1 * 2 + 1]);
+    const float c0 = to_f<T>(r1[x0 * 2]), c1 = to_f<T>(r1[x0 * 2 + 1]), d0 = to_f<T>(r1[x1 * 2]), d1 = to_f<T>(r1[x1 * 2 + 1]);
+    UpCe u;
+    u.up0 = (1.f - ly) * ((1.f - lx) * a0 + lx * b0) + ly * ((1.f - lx) * c0 + lx * d0);
+    u.up1 = (1.f - ly) * ((1.f - lx) * a1 + lx * b1) + ly * ((1.f - lx) * c1 + lx * d1);
+    const float m = fmaxf(u.up0, u.up1);
+    u.lse = m + logf(expf(u.up0 - m) + expf(u.up1 - m));
+    return u;
+}

@@ -243,6 +243,11 @@ _PROTOTYPES = {
     "lavt_upsample_dice_sel_fwd": [i32, vp, vp, i32, vp, vp, i64, vp, i32, i32, i32, i32, i32, vp],
     "lavt_upsample_dice_sel_bwd": [i32, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "lavt_gather_samples": [i32, vp, vp, i32, i32, i64, vp, vp],
+    "lavt_upsample_dice_boundary_ws": [i32, i32, i32],
+    "lavt_upsample_dice_boundary_fwd": [i32, vp, vp, f32, f32, vp, i64, vp, i32, i32, i32, i32, i32, vp],
+    "lavt_upsample_dice_boundary_bwd": [i32, vp, vp, f32, f32, vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, vp],
+    "lavt_upsample_dice_boundary_sel_fwd": [i32, vp, vp, i32, vp, f32, f32, vp, i64, vp, i32, i32, i32, i32, i32, vp],
+    "lavt_upsample_dice_boundary_sel_bwd": [i32, vp, vp, i32, vp, f32, f32, vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, vp],
     "lavt_fp8_quantize": [i32, vp, vp, i64, vp, vp, vp],
     "lavt_fp8_advance": [vp, vp, i32, vp],
     "lavt_fp8_quantize_weight": [vp, vp, vp, i32, i32, i32, vp],
@@ -279,8 +284,9 @@ _cdll.lavt_window_attn_stream_bwd_ws.restype = C.c_int64
 _cdll.lavt_conv3x3_wgrad_ws.restype = C.c_int64
 _cdll.lavt_gemm_tn_grouped_sk_ws.restype = C.c_int64
 _cdll.lavt_grad_norm_ws.restype = C.c_int64
+_cdll.lavt_upsample_dice_boundary_ws.restype = C.c_int64
 _cdll.lavt_last_error.argtypes = []
-for _name in ("lavt_last_error", "lavt_window_attn_bwd_ws", "lavt_window_attn_stream_ok", "lavt_window_attn_stream_bwd_ws", "lavt_attn_uses_table", "lavt_abi_version", "lavt_layernorm_bwd_blocks", "lavt_window_attn_bwd_pieces", "lavt_gemm_tn_pieces", "lavt_pwam_q_parts", "lavt_pwam_words_records", "lavt_pwam_mix1_records", "lavt_adamw_chunk_elems", "lavt_tuning_reload", "lavt_conv3x3_wgrad_ws", "lavt_conv3x3_wgrad_f8_ok", "lavt_gemm_tn_grouped_sk_ws", "lavt_gemm_nt_colstats_plan", "lavt_cls_head_bwd_blocks", "lavt_reduce_partials_column_blocks", "lavt_grad_norm_ws"):      # queries, not launches: never timed
+for _name in ("lavt_last_error", "lavt_window_attn_bwd_ws", "lavt_window_attn_stream_ok", "lavt_window_attn_stream_bwd_ws", "lavt_attn_uses_table", "lavt_abi_version", "lavt_layernorm_bwd_blocks", "lavt_window_attn_bwd_pieces", "lavt_gemm_tn_pieces", "lavt_pwam_q_parts", "lavt_pwam_words_records", "lavt_pwam_mix1_records", "lavt_adamw_chunk_elems", "lavt_tuning_reload", "lavt_conv3x3_wgrad_ws", "lavt_conv3x3_wgrad_f8_ok", "lavt_gemm_tn_grouped_sk_ws", "lavt_gemm_nt_colstats_plan", "lavt_cls_head_bwd_blocks", "lavt_reduce_partials_column_blocks", "lavt_grad_norm_ws", "lavt_upsample_dice_boundary_ws"):      # queries, not launches: never timed
     setattr(lib, _name, getattr(_cdll, _name))
 
 EXPORTED = tuple(_PROTOTYPES) + ("lavt_last_error",)

@@ -89,19 +89,22 @@ class _ValidIndices:
 
 class TrainStep(_ValidIndices):
     def __init__(self, model, image, l_feats, l_mask, target, world=1, use_graph=True, bucket_mib=32.0, fused_loss=True, refresh_weights_in_step=False, context=None,
-                 *, loss="ce", valid_indices=None):
+                 *, loss="ce", valid_indices=None, dice_rate=1.0, boundary_rate=0.05):
         """context: the ops.StepContext this harness keeps its state in (gradient sinks, deferred-launch queues, weight copies, scratch).  None = the
         process-wide default context -- what the drop-in path and a single harness use.  Give every further model in the process its own
         `ops.StepContext()` (and its optimizer the same one: FusedAdamW(..., context=)): their steps can then alternate freely.
-        loss: "ce" (losses.py:7-11, the default) or "mc_dice" (MultiClassDiceLoss, losses.py:38-77; `--loss mc_dice` of train.py:703-704).
+        loss: "ce" (losses.py:7-11, the default), "mc_dice" (MultiClassDiceLoss, losses.py:38-77; `--loss mc_dice` of train.py:703-704) or
+        "dice_boundary" (DiceBoundaryLoss(boundary_rate, dice_rate), losses.py:142-244; `--loss dice_boundary` of train.py:709-711 with the
+        `--dice_rate` / `--boundary_rate` of args.py:83-84; the other criteria ignore the two rates).
         valid_indices: device int32 [nsel], a static buffer like image and target -- the flat numbers of the annotated frames (A2D-Sentences / JHMDB:
         one per clip, train.py:282-285); target is then (nsel, H, W) and the criterion (and `stats`) covers `index_select(output, 0, valid_indices)`.
         Fill it with set_valid_indices(per_clip, frames_per_clip), before capture or between replays."""
-        if loss not in ("ce", "mc_dice"):
-            raise ValueError(f"TrainStep: loss must be 'ce' or 'mc_dice', got {loss!r}")
+        if loss not in ("ce", "mc_dice", "dice_boundary"):
+            raise ValueError(f"TrainStep: loss must be 'ce', 'mc_dice' or 'dice_boundary', got {loss!r}")
         if valid_indices is not None:
             _check_index_buffer("TrainStep", valid_indices, target, image.numel() // (3 * int(image.shape[-2]) * int(image.shape[-1])))
         self.criterion, self.valid_indices = loss, valid_indices
+        self.dice_rate, self.boundary_rate = float(dice_rate), float(boundary_rate)
         self.context = context if context is not None else ops.default_context()
         with ops.use_context(self.context):
             self._init(model, image, l_feats, l_mask, target, world, use_graph, bucket_mib, fused_loss, refresh_weights_in_step)
@@ -181,21 +184,26 @@ class TrainStep(_ValidIndices):
         if fp8_enabled():
             ops.fp8.advance()                    # delayed scaling: last step's |max| values become this step's quantisation scales
         if self.fused_loss:                       # upsample + criterion (+ I/U) fused: the (B,2,H,W) logits are never written
-            from lib._utils import fused_dice_loss, fused_loss
+            from lib._utils import fused_dice_boundary_loss, fused_dice_loss, fused_loss
             y = self.model.forward_lowres(self.x, self.l, self.m)
             if self.criterion == "ce":
                 loss, self.stats = fused_loss(y, self.t, (0.9, 1.1), valid_indices=self.valid_indices)
-            else:
+            elif self.criterion == "mc_dice":
                 loss, self.stats = fused_dice_loss(y, self.t, valid_indices=self.valid_indices)
+            else:
+                loss, self.stats = fused_dice_boundary_loss(y, self.t, valid_indices=self.valid_indices, dice_rate=self.dice_rate, boundary_rate=self.boundary_rate)
         else:
             out = self.model(self.x, self.l, self.m)
             if self.valid_indices is not None:
                 out = torch.index_select(out, 0, self.valid_indices)          # train.py:284, literally
             if self.criterion == "ce":
                 loss = F.cross_entropy(out, self.t, weight=self.w)
-            else:
+            elif self.criterion == "mc_dice":
                 from losses import MultiClassDiceLoss
                 loss = MultiClassDiceLoss()(out, self.t)
+            else:
+                from losses import DiceBoundaryLoss
+                loss = DiceBoundaryLoss(self.boundary_rate, self.dice_rate)(out, self.t)
         if self._one is None or self._one.shape != loss.shape or self._one.dtype != loss.dtype:
             self._one = torch.ones_like(loss)    # (first eager step) the root gradient as a persistent tensor: `loss.backward()` fills a fresh ones_like every step,
         loss.backward(self._one)                 # one more 4.5 us launch on the captured chain

@@ -3014,6 +3014,56 @@ def upsample_dice_loss(x, target, B, Hi, Wi, Ho, Wo, sel=None):
     return _UpsampleDice.apply(x, target, B, Hi, Wi, Ho, Wo, _frame_sel(sel, B, "upsample_dice_loss"))
 
 
+@K.scoped
+class _UpsampleDiceBoundary(torch.autograd.Function):
+    """DiceBoundaryLoss(boundary_rate, dice_rate)(F.interpolate(y, (Ho, Wo), bilinear, align_corners=True), target) on the low-resolution 2-class
+    logits rows x [B*Hi*Wi, 2] (reference losses.py:142-244 after lib/_utils.py:21), neither the upsampled logits nor their probabilities written.
+    Returns (loss, stats) with stats = [loss, dice, boundary, per sample {I0, I1, sum p0^2, sum p1^2, #t==0, #t==1, S1..S4 of class 0, S1..S4 of class 1}].
+    sel (device int32 [nsel], see _frame_sel): the loss of `index_select(logits, 0, sel)` against target [nsel, Ho, Wo]; stats per SELECTED sample."""
+
+    @staticmethod
+    def forward(ctx, x, target, B, Hi, Wi, Ho, Wo, dice_rate, boundary_rate, sel=None):
+        x = x.contiguous()
+        target = target.contiguous()
+        ns = B if sel is None else sel.numel()
+        assert target.dtype == torch.int64 and target.numel() == ns * Ho * Wo
+        stats = torch.empty(3 + 14 * ns, dtype=torch.float32, device=x.device)
+        ws = _scratch(K.lib.lavt_upsample_dice_boundary_ws(ns, Ho, Wo), x.device)
+        if sel is None:
+            K.check(K.lib.lavt_upsample_dice_boundary_fwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), dice_rate, boundary_rate, K.ptr(ws), ws.numel(),
+                                                          K.ptr(stats), B, Hi, Wi, Ho, Wo, K.stream()))
+        else:
+            K.check(K.lib.lavt_upsample_dice_boundary_sel_fwd(K.dt(x.dtype), K.ptr(x), K.ptr(sel), ns, K.ptr(target), dice_rate, boundary_rate, K.ptr(ws),
+                                                              ws.numel(), K.ptr(stats), B, Hi, Wi, Ho, Wo, K.stream()))
+        ctx.sel = sel
+        ctx.save_for_backward(x, target, stats)
+        ctx.dims = (B, Hi, Wi, Ho, Wo, dice_rate, boundary_rate)
+        ctx.mark_non_differentiable(stats)
+        return stats[0].clone(), stats
+
+    @staticmethod
+    def backward(ctx, dloss, _dstats):
+        x, target, stats = ctx.saved_tensors
+        B, Hi, Wi, Ho, Wo, dice_rate, boundary_rate = ctx.dims
+        dx = torch.empty_like(x)
+        dl = dloss.contiguous().float().reshape(1)
+        ns = B if ctx.sel is None else ctx.sel.numel()
+        ws = _scratch(K.lib.lavt_upsample_dice_boundary_ws(ns, Ho, Wo), x.device)          # (the dz map lives from launch A to launch B only)
+        if ctx.sel is None:
+            K.check(K.lib.lavt_upsample_dice_boundary_bwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), dice_rate, boundary_rate, K.ptr(stats), K.ptr(dl), K.ptr(ws),
+                                                          ws.numel(), K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
+        else:
+            K.check(K.lib.lavt_upsample_dice_boundary_sel_bwd(K.dt(x.dtype), K.ptr(x), K.ptr(ctx.sel), ns, K.ptr(target), dice_rate, boundary_rate, K.ptr(stats),
+                                                              K.ptr(dl), K.ptr(ws), ws.numel(), K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
+        return dx, None, None, None, None, None, None, None, None, None
+
+
+def upsample_dice_boundary_loss(x, target, B, Hi, Wi, Ho, Wo, sel=None, dice_rate=1.0, boundary_rate=0.05):
+    if sel is None:
+        return _UpsampleDiceBoundary.apply(x, target, B, Hi, Wi, Ho, Wo, float(dice_rate), float(boundary_rate))
+    return _UpsampleDiceBoundary.apply(x, target, B, Hi, Wi, Ho, Wo, float(dice_rate), float(boundary_rate), _frame_sel(sel, B, "upsample_dice_boundary_loss"))
+
+
 def gather_samples(x, sel):
     """`torch.index_select(x, 0, sel)` for whole samples with sel on the device (int32 [nsel], see _frame_sel), no layout change: x is a dense tensor in
     ANY dimension order (an NCHW-shaped view of NHWC memory, as the backbone returns its feature maps, included) whose samples are contiguous blocks;

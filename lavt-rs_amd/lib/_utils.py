@@ -42,6 +42,15 @@ def fused_dice_loss(y, target, valid_indices=None):
     return ops.upsample_dice_loss(nchw_rows(y, y.dtype), target, B, h, w, int(target.shape[-2]), int(target.shape[-1]), sel=valid_indices)
 
 
+def fused_dice_boundary_loss(y, target, valid_indices=None, dice_rate=1.0, boundary_rate=0.05):
+    """`DiceBoundaryLoss(boundary_rate, dice_rate)(model(...), target)` (train.py:709-711; losses.py:142-244) on the LOW-resolution decoder output y:
+    bilinear upsample + softmax + the Dice sums + the boundary F1 stencil (3x3 and 5x5 max-pools) per output tile in LDS.  -> (loss, stats)
+    valid_indices: as for fused_loss; both means are over the selected samples and the 2 classes."""
+    B, _, h, w = y.shape
+    return ops.upsample_dice_boundary_loss(nchw_rows(y, y.dtype), target, B, h, w, int(target.shape[-2]), int(target.shape[-1]), sel=valid_indices,
+                                           dice_rate=dice_rate, boundary_rate=boundary_rate)
+
+
 def _check_frames(module, folded, frames):
     if frames is not None and (module.training or not folded):
         raise ValueError("forward_lowres: frames= needs the BatchNorm-folded decoder (folded=True, model.eval()); in training mode select in the "
