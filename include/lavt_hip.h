@@ -637,11 +637,12 @@ int lavt_pack_conv3x3(const float* w, int dtype, void* packed, int Cout, int Cin
 int lavt_unpack_conv_grad(const float* packed, float* dw, int Cout, int Cin, int taps, void* stream);
 /* many small fp32 -> dtype casts in one launch: desc = int64 triples (src_ptr, dst_ptr, n) on the DEVICE */
 int lavt_cast_multi(const int64_t* desc, int count, int dst_dtype, void* stream);
-/* The caller's optimizer step (train.py:688-700: torch.optim.AdamW, amsgrad off, + LambdaLR((1 - it/T)^0.9)) as one
+/* The caller's optimizer step (train.py:688-700: torch.optim.AdamW + LambdaLR((1 - it/T)^0.9)) as one
  * multi-tensor launch.  desc: int64 [count][5] = {param, grad, exp_avg, exp_avg_sq (fp32 device pointers), numel}; hyper: fp32 [count][5] =
  * {base lr, weight decay, beta1, beta2, eps} (both tables in device memory); step: device fp32 scalar = optimizer steps taken so far,
  * incremented by the call (so a captured hipGraph keeps advancing its schedule); lr = base lr * (1 - step/total_steps)^power, or the
- * base lr when total_steps <= 0.  Update rule identical to torch.optim.AdamW (decoupled decay, bias-corrected moments). */
+ * base lr when total_steps <= 0.  Update rule identical to torch.optim.AdamW (decoupled decay, bias-corrected moments) with amsgrad off;
+ * amsgrad on: lavt_adamw_step_chunks_amsgrad below. */
 int lavt_adamw_step(const int64_t* desc, const float* hyper, int count, float* step, float total_steps, float power, void* stream);
 /* The same update driven by a chunk table (ABI v4): desc int64 [count][6] = {param, grad, exp_avg, exp_avg_sq, numel, copy} -- a non-zero `copy` is the
  * parameter's bf16 compute copy in the same layout, written by the same kernel (the mixed-precision trainer's re-cast of the weights the next
@@ -673,6 +674,16 @@ int64_t lavt_grad_norm_ws(int nchunks);
 int lavt_grad_norm(const int64_t* desc, const int32_t* chunks, int nchunks, float* ws, float* ctl, float max_norm, int skip_nonfinite, void* stream);
 int lavt_adamw_step_chunks_guarded(const int64_t* desc, const float* hyper, const int32_t* chunks, int nchunks, float* step, float total_steps, float power,
                                    float* ctl, void* stream);
+/* AMSGrad (train.py:689-693, --amsgrad; a new symbol under ABI v7): the chunked update with a fifth fp32 stream x = max_exp_avg_sq.
+ * torch.optim.AdamW(amsgrad=True), single-tensor form:
+ *   m = b1*m + (1-b1)*g;  v = b2*v + (1-b2)*g*g;  x = max(x, v)   (the UNcorrected second moment, after its update; a NaN stays)
+ *   p = p*(1 - lr*wd) - (lr/bc1) * m / (sqrt(x)/sqrt(bc2) + eps)
+ * desc, hyper, chunks, step and the schedule are those of lavt_adamw_step_chunks (desc keeps its six columns, so lavt_grad_norm reads the same
+ * table); vmax: device int64 [count] = the fp32 device pointer of x for every desc row.  ctl == NULL: the unguarded update and tick of
+ * lavt_adamw_step_chunks.  ctl != NULL: the control block above, obeyed as by lavt_adamw_step_chunks_guarded -- g is multiplied by ctl[1] first;
+ * on skip or hold nothing is stored (x included), the step counter does not advance, and ctl[3] += ctl[2] unless on hold (hence non-const). */
+int lavt_adamw_step_chunks_amsgrad(const int64_t* desc, const int64_t* vmax, const float* hyper, const int32_t* chunks, int nchunks, float* step, float total_steps,
+                                   float power, float* ctl /* NULL: unguarded */, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Inference path (csrc/infer.hip; reference test.py:60-110 and test_ytvos.py:230-260: batch-1 forward under model.eval() / torch.no_grad(), argmax,

@@ -13,9 +13,13 @@ constexpr int ADAMW_CE = 8192;            // elements per chunk: 256 threads x 2
 // GUARD: ctl is the fp32[8] control block of lavt_grad_norm (wave-uniform, read once per workgroup): the workgroup returns before its first
 // store when ctl[2] (skip) or ctl[4] (hold) is set, and gradients are scaled by ctl[1] (the clip coefficient; x * 1.0f is exact, so a
 // coefficient of 1 gives the unguarded bits).
-template <bool GUARD>
-__device__ __forceinline__ void adamw_chunk_update(const int64_t* __restrict__ desc, const float* __restrict__ hyper, const int2* __restrict__ chunks,
-                                                   const float* __restrict__ step, float total_steps, float power, const float* __restrict__ ctl) {
+// AMSGRAD: a fifth fp32 stream x = max_exp_avg_sq, addressed by vmax: int64 [count], one pointer per desc row (desc keeps its six columns: the norm
+// kernel and the plain entry points read that layout).  torch.optim.AdamW(amsgrad=True), single-tensor form: x = max(x, v) with the UNcorrected v
+// after its update, and x takes v's place in the denominator.  With AMSGRAD off, vmax is never read and the code is the four-stream update.
+template <bool GUARD, bool AMSGRAD>
+__device__ __forceinline__ void adamw_chunk_update(const int64_t* __restrict__ desc, const int64_t* __restrict__ vmax, const float* __restrict__ hyper,
+                                                   const int2* __restrict__ chunks, const float* __restrict__ step, float total_steps, float power,
+                                                   const float* __restrict__ ctl) {
     float coef = 1.f;
     if constexpr (GUARD) {
         if (ctl[2] != 0.f || ctl[4] != 0.f) return;
@@ -35,38 +39,51 @@ __device__ __forceinline__ void adamw_chunk_update(const int64_t* __restrict__ d
     const float lr = hyper[5 * t] * sched;
     const float bc1 = 1.f - powf(b1, k + 1.f), bc2 = 1.f - powf(b2, k + 1.f);
     const float step_size = lr / bc1, rbc2 = rsqrtf(bc2), decay = 1.f - lr * wd;
-    auto upd = [&](float& pp, float gg, float& mm, float& vv) {
+    float unused = 0.f;                        // what the x arguments bind to when AMSGRAD is off: never read, never stored
+    float* x = nullptr;
+    if constexpr (AMSGRAD) x = reinterpret_cast<float*>(vmax[t]);
+    auto upd = [&](float& pp, float gg, float& mm, float& vv, float& xx) {
         if constexpr (GUARD) gg *= coef;
         pp *= decay;
         mm = b1 * mm + (1.f - b1) * gg;
         vv = b2 * vv + (1.f - b2) * gg * gg;
-        pp -= step_size * mm / (sqrtf(vv) * rbc2 + eps);
+        if constexpr (AMSGRAD) {
+            xx = (vv > xx || vv != vv) ? vv : xx;          // torch.maximum: a NaN on either side stays (fmaxf would drop it)
+            pp -= step_size * mm / (sqrtf(xx) * rbc2 + eps);
+        } else {
+            pp -= step_size * mm / (sqrtf(vv) * rbc2 + eps);
+        }
     };
     const int64_t e0 = (int64_t)ch.y * ADAMW_CE, e1 = min(n, e0 + ADAMW_CE);
-    const bool vec = ((desc[6 * t] | desc[6 * t + 1] | desc[6 * t + 2] | desc[6 * t + 3]) & 15) == 0 && (desc[6 * t + 5] & 7) == 0;
+    bool vec = ((desc[6 * t] | desc[6 * t + 1] | desc[6 * t + 2] | desc[6 * t + 3]) & 15) == 0 && (desc[6 * t + 5] & 7) == 0;
+    if constexpr (AMSGRAD) vec = vec && (vmax[t] & 15) == 0;
     if (vec && e1 - e0 == ADAMW_CE) {          // a whole chunk: no per-element conditions (a conditional load costs a branch and a full wait each)
 #pragma unroll
         for (int round = 0; round < 2; ++round) {
-            float4 pp[4], gg[4], mm[4], vv[4];
+            float4 pp[4], gg[4], mm[4], vv[4], xx[AMSGRAD ? 4 : 1];
             const int64_t base = e0 + (int64_t)round * 4096 + threadIdx.x * 4;
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int64_t i = base + u * 1024;
                 pp[u] = *reinterpret_cast<const float4*>(p + i); gg[u] = *reinterpret_cast<const float4*>(g + i);
                 mm[u] = *reinterpret_cast<const float4*>(m + i); vv[u] = *reinterpret_cast<const float4*>(v + i);
+                if constexpr (AMSGRAD) xx[u] = *reinterpret_cast<const float4*>(x + i);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int64_t i = base + u * 1024;
-                upd(pp[u].x, gg[u].x, mm[u].x, vv[u].x); upd(pp[u].y, gg[u].y, mm[u].y, vv[u].y);
-                upd(pp[u].z, gg[u].z, mm[u].z, vv[u].z); upd(pp[u].w, gg[u].w, mm[u].w, vv[u].w);
+                float4& xu = xx[AMSGRAD ? u : 0];          // (AMSGRAD off: bound, never read or stored)
+                upd(pp[u].x, gg[u].x, mm[u].x, vv[u].x, xu.x); upd(pp[u].y, gg[u].y, mm[u].y, vv[u].y, xu.y);
+                upd(pp[u].z, gg[u].z, mm[u].z, vv[u].z, xu.z); upd(pp[u].w, gg[u].w, mm[u].w, vv[u].w, xu.w);
                 *reinterpret_cast<float4*>(p + i) = pp[u]; *reinterpret_cast<float4*>(m + i) = mm[u]; *reinterpret_cast<float4*>(v + i) = vv[u];
+                if constexpr (AMSGRAD) *reinterpret_cast<float4*>(x + i) = xu;
                 if (cp) *reinterpret_cast<uint2*>(cp + i) = make_uint2(pack_bf16x2(pp[u].x, pp[u].y), pack_bf16x2(pp[u].z, pp[u].w));
             }
         }
     } else {                                   // a tensor's last chunk / unaligned tensors
         for (int64_t i = e0 + threadIdx.x; i < e1; i += 256) {
-            upd(p[i], g[i], m[i], v[i]);
+            if constexpr (AMSGRAD) upd(p[i], g[i], m[i], v[i], x[i]);
+            else upd(p[i], g[i], m[i], v[i], unused);
             if (cp) cp[i] = from_f<bf16>(p[i]);
         }
     }

@@ -682,7 +682,7 @@ __global__ void adamw_tick_kernel(float* step) { step[0] += 1.f; }
 // The same update over a CHUNK table (adamw_body.h: shared with the guarded kernel of optim_guard.hip).
 __global__ __launch_bounds__(256) void adamw_chunks_kernel(const int64_t* __restrict__ desc, const float* __restrict__ hyper, const int2* __restrict__ chunks,
                                                            const float* __restrict__ step, float total_steps, float power) {
-    adamw_chunk_update<false>(desc, hyper, chunks, step, total_steps, power, nullptr);
+    adamw_chunk_update<false, false>(desc, nullptr, hyper, chunks, step, total_steps, power, nullptr);
 }
 
 template <typename D> __global__ void cast_multi_kernel(const int64_t* desc, int count) {

@@ -58,8 +58,17 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(const float* __re
 
 __global__ __launch_bounds__(256) void adamw_chunks_guarded_kernel(const int64_t* __restrict__ desc, const float* __restrict__ hyper, const int2* __restrict__ chunks,
                                                                    const float* __restrict__ step, float total_steps, float power, const float* __restrict__ ctl) {
-    adamw_chunk_update<true>(desc, hyper, chunks, step, total_steps, power, ctl);
+    adamw_chunk_update<true, false>(desc, nullptr, hyper, chunks, step, total_steps, power, ctl);
 }
+
+// AMSGrad (adamw_body.h: AMSGRAD): the same body with the max_exp_avg_sq stream behind vmax; GUARD = a control block was given
+template <bool GUARD>
+__global__ __launch_bounds__(256) void adamw_chunks_amsgrad_kernel(const int64_t* __restrict__ desc, const int64_t* __restrict__ vmax, const float* __restrict__ hyper,
+                                                                   const int2* __restrict__ chunks, const float* __restrict__ step, float total_steps, float power,
+                                                                   const float* __restrict__ ctl) {
+    adamw_chunk_update<GUARD, true>(desc, vmax, hyper, chunks, step, total_steps, power, ctl);
+}
+__global__ void adamw_tick_kernel(float* step) { step[0] += 1.f; }          // the unguarded tick, as behind lavt_adamw_step_chunks
 
 // the step counter advances only when the update ran; a skipped step is counted unless the optimizer is on hold
 __global__ void adamw_tick_guarded_kernel(float* step, float* ctl) {
@@ -88,5 +97,19 @@ extern "C" int lavt_adamw_step_chunks_guarded(const int64_t* desc, const float* 
     hipLaunchKernelGGL(adamw_chunks_guarded_kernel, dim3(nchunks), dim3(256), 0, ST, desc, hyper, reinterpret_cast<const int2*>(chunks), step, total_steps, power, ctl);
     hipLaunchKernelGGL(adamw_tick_guarded_kernel, dim3(1), dim3(1), 0, ST, step, ctl);
     LAVT_CHECK_LAUNCH("lavt_adamw_step_chunks_guarded");
+    return LAVT_OK;
+}
+
+extern "C" int lavt_adamw_step_chunks_amsgrad(const int64_t* desc, const int64_t* vmax, const float* hyper, const int32_t* chunks, int nchunks, float* step, float total_steps,
+                                              float power, float* ctl, void* stream) {
+    LAVT_CHECK_ARG(desc && vmax && hyper && chunks && step && nchunks > 0, "lavt_adamw_step_chunks_amsgrad: bad arguments");
+    if (ctl) {
+        hipLaunchKernelGGL(adamw_chunks_amsgrad_kernel<true>, dim3(nchunks), dim3(256), 0, ST, desc, vmax, hyper, reinterpret_cast<const int2*>(chunks), step, total_steps, power, ctl);
+        hipLaunchKernelGGL(adamw_tick_guarded_kernel, dim3(1), dim3(1), 0, ST, step, ctl);
+    } else {
+        hipLaunchKernelGGL(adamw_chunks_amsgrad_kernel<false>, dim3(nchunks), dim3(256), 0, ST, desc, vmax, hyper, reinterpret_cast<const int2*>(chunks), step, total_steps, power, nullptr);
+        hipLaunchKernelGGL(adamw_tick_kernel, dim3(1), dim3(1), 0, ST, step);
+    }
+    LAVT_CHECK_LAUNCH("lavt_adamw_step_chunks_amsgrad");
     return LAVT_OK;
 }

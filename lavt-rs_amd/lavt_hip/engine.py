@@ -145,7 +145,7 @@ class TrainStep(_ValidIndices):
     def make_optimizer(self, param_groups=None, **adamw_kwargs):
         """Build a FusedAdamW on THIS step's context, attach it and return it.  param_groups=None: lavt_param_groups(model) when the model has a
         `backbone` and a `classifier` (the reference's groups), else all its parameters.  adamw_kwargs go to FusedAdamW (lr, weight_decay,
-        total_steps, power, max_grad_norm, skip_nonfinite, ...).  Before warmup_and_capture() only."""
+        total_steps, power, max_grad_norm, skip_nonfinite, amsgrad, ...).  Before warmup_and_capture() only."""
         from .optim import FusedAdamW, lavt_param_groups
         self._check_attach_window()
         if "context" in adamw_kwargs:

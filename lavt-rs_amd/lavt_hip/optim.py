@@ -7,7 +7,11 @@
 `torch.optim.Optimizer`-shaped (param_groups, state_dict / load_state_dict in torch.optim.AdamW's layout) so that the reference's
 checkpoint code (train.py:749-763) keeps working.  The step counter and the schedule live on the device: the optimizer step can be
 captured into the same hipGraph as forward/backward and still follows (1 - it/T)^0.9 on every replay (a LambdaLR on the host would be
-frozen at capture time): engine.TrainStep.make_optimizer() does exactly that.  amsgrad (off by default in the reference) is not implemented.
+frozen at capture time): engine.TrainStep.make_optimizer() does exactly that.
+
+amsgrad=True (train.py:689-693, --amsgrad) is torch.optim.AdamW's rule: a third flat fp32 buffer holds state[p]["max_exp_avg_sq"], the running maximum
+of the uncorrected second moment, which replaces it in the denominator (lavt_adamw_step_chunks_amsgrad, guarded or not).  The flag is optimizer-wide:
+every group carries the constructor's value, and a checkpoint written with the other value is refused rather than half-loaded.
 
 The guard (opt-in: max_grad_norm > 0, skip_nonfinite=True, or hold()): a device fp32[8] control block `opt.guard` = [global gradient norm, clip
 coefficient, skip flag, skipped-step count, hold flag, 0, 0, 0].  lavt_grad_norm fills the first three from the gradients the update is about to
@@ -22,18 +26,31 @@ import torch
 from . import _capi as K
 
 
-def lavt_param_groups(model, text_encoder_layers: int = 10):
-    """The reference's parameter groups (train.py:615-660): backbone tensors whose name contains 'norm', 'absolute_pos_embed' or
-    'relative_position_bias_table' get weight_decay 0; the rest of the backbone, the classifier and (if the model carries one) the first
-    `text_encoder_layers` BERT encoder layers use the default."""
+LANG_ENC_PARAMS = ("encoder-10", "encoder-all", "embeddings+encoder-10", "embeddings+encoder-all")
+
+
+def lavt_param_groups(model, text_encoder_layers: int = 10, *, lang_enc_params: str = "encoder-10", text_encoder=None):
+    """The reference's parameter groups (train.py:615-686): backbone tensors whose name contains 'norm', 'absolute_pos_embed' or
+    'relative_position_bias_table' get weight_decay 0; the rest of the backbone and the classifier use the default; then the language encoder's
+    groups (only tensors with requires_grad), chosen by `lang_enc_params` (--lang_enc_params):
+      'encoder-10'  the first `text_encoder_layers` BERT encoder layers        'encoder-all'  encoder.parameters()
+      'embeddings+encoder-10' / 'embeddings+encoder-all'  a group of embeddings.parameters() in front of that encoder group.
+    text_encoder: the separate `bert_model` of --model lavt (train.py:623-632); default model.text_encoder (a model without one gets no language group)."""
+    if lang_enc_params not in LANG_ENC_PARAMS:
+        raise ValueError(f"lavt_param_groups: lang_enc_params must be one of {LANG_ENC_PARAMS}, not {lang_enc_params!r}")
     no_decay, decay = [], []
     for name, p in model.backbone.named_parameters():
         (no_decay if ("norm" in name or "absolute_pos_embed" in name or "relative_position_bias_table" in name) else decay).append(p)
     groups = [{"params": no_decay, "weight_decay": 0.0}, {"params": decay},
               {"params": [p for p in model.classifier.parameters() if p.requires_grad]}]
-    enc = getattr(model, "text_encoder", None)
+    enc = text_encoder if text_encoder is not None else getattr(model, "text_encoder", None)
     if enc is not None and hasattr(enc, "encoder"):
-        groups.append({"params": [p for i in range(text_encoder_layers) for p in enc.encoder.layer[i].parameters() if p.requires_grad]})
+        if lang_enc_params.startswith("embeddings+"):
+            groups.append({"params": [p for p in enc.embeddings.parameters() if p.requires_grad]})
+        if lang_enc_params.endswith("encoder-all"):
+            groups.append({"params": [p for p in enc.encoder.parameters() if p.requires_grad]})
+        else:
+            groups.append({"params": [p for i in range(text_encoder_layers) for p in enc.encoder.layer[i].parameters() if p.requires_grad]})
     return groups
 
 
@@ -54,9 +71,8 @@ class FusedAdamW(torch.optim.Optimizer):
         engine.TrainStep when the model runs in a private context)"""
         from . import ops
         self.context = context if context is not None else ops.default_context()
-        if amsgrad:
-            raise NotImplementedError("FusedAdamW: amsgrad is not implemented (the reference's default is off)")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False))
+        self.amsgrad = bool(amsgrad)          # optimizer-wide (one kernel for the whole chunk table): add_param_group reads it during super().__init__
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=self.amsgrad))
         self.total_steps, self.power = float(total_steps), float(power)
         self.fuse_copies = os.environ.get("LAVT_ADAMW_FUSE_COPIES", "1") != "0"
         self._tables = None
@@ -67,6 +83,12 @@ class FusedAdamW(torch.optim.Optimizer):
         self._norm_ws = None       # lavt_grad_norm's per-chunk partial sums
         if self._wants_norm():
             self._make_guard()
+
+    def add_param_group(self, param_group):
+        if isinstance(param_group, dict) and "amsgrad" in param_group and bool(param_group["amsgrad"]) != self.amsgrad:
+            raise ValueError(f"FusedAdamW: amsgrad is optimizer-wide: a group with amsgrad={param_group['amsgrad']} cannot join an optimizer built with "
+                             f"amsgrad={self.amsgrad}")
+        super().add_param_group(param_group)
 
     # ---- the guard ----
     def _wants_norm(self):
@@ -115,15 +137,21 @@ class FusedAdamW(torch.optim.Optimizer):
             self._step = torch.zeros(1, dtype=torch.float32, device=dev)
         if not all("exp_avg" in self.state[p] for _, p in ps):
             flat_m, flat_v = torch.zeros(total, dtype=torch.float32, device=dev), torch.zeros(total, dtype=torch.float32, device=dev)
+            flat_x = torch.zeros(total, dtype=torch.float32, device=dev) if self.amsgrad else None
             off = 0
             for _, p in ps:
                 n = p.numel()
                 st = self.state[p]
                 st.setdefault("step", self._step)
                 st["exp_avg"], st["exp_avg_sq"] = flat_m[off:off + n].view_as(p), flat_v[off:off + n].view_as(p)
+                if self.amsgrad:
+                    st["max_exp_avg_sq"] = flat_x[off:off + n].view_as(p)
                 off += n
+        if self.amsgrad and not all("max_exp_avg_sq" in self.state[p] for _, p in ps):
+            raise ValueError("FusedAdamW(amsgrad=True): a parameter's state has exp_avg but no max_exp_avg_sq (it was written without amsgrad); the running "
+                             "maximum is not started at zero silently")
         from . import ops
-        desc, hyper, missing, chunks, fused = [], [], [], [], {}
+        desc, hyper, missing, chunks, fused, vmax = [], [], [], [], {}, []
         ce = int(K.lib.lavt_adamw_chunk_elems())
         for g, p in ps:
             if p.grad is None:
@@ -143,13 +171,16 @@ class FusedAdamW(torch.optim.Optimizer):
                 chunks.append([len(desc), c])
             desc.append([p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(), copy])
             hyper.append([g["lr"], g["weight_decay"], g["betas"][0], g["betas"][1], g["eps"]])
+            if self.amsgrad:
+                vmax.append(st["max_exp_avg_sq"].data_ptr())
         # (the copies' addresses are baked into the table: ops.weights.generation moves whenever one of them gets a new buffer)
         key = tuple(d[1] for d in desc) + tuple(tuple(h) for h in hyper) + (ops_generation(),)
         # (every described parameter with the gradient address the table holds: step(check_tables=False) compares them all -- integer work on the host,
         # no device synchronisation; three probed addresses missed a single re-created .grad)
         self._probe = [(p, p.grad.data_ptr()) for _, p in ps if p.grad is not None]
         self._tables = (key, torch.tensor(desc, dtype=torch.int64).to(dev), torch.tensor(hyper, dtype=torch.float32).to(dev), len(desc),
-                        torch.tensor(chunks, dtype=torch.int32).to(dev), len(chunks), dict(fused))
+                        torch.tensor(chunks, dtype=torch.int32).to(dev), len(chunks), dict(fused),
+                        torch.tensor(vmax, dtype=torch.int64).to(dev) if self.amsgrad else None)          # [7]: one max_exp_avg_sq address per desc row
         if self._wants_norm():
             need = int(K.lib.lavt_grad_norm_ws(len(chunks)))
             if self._norm_ws is None or self._norm_ws.numel() < need:
@@ -177,7 +208,7 @@ class FusedAdamW(torch.optim.Optimizer):
         loss = closure() if closure is not None else None
         if self._tables is None or (check_tables and self._tables[0] != self._current_key()):
             self._build()
-        _, desc, hyper, n, chunks, nchunks, fused = self._tables
+        _, desc, hyper, n, chunks, nchunks, fused, vmax = self._tables
         if not check_tables and (self._tables[0][-1] != ops_generation()
                                  or any(p.grad is None or p.grad.data_ptr() != a for p, a in self._probe)):
             # (captured steps skip the host-side scan, but a copy that moved since the table was built would be written at its OLD address, and a
@@ -185,11 +216,14 @@ class FusedAdamW(torch.optim.Optimizer):
             # read at its OLD offsets)
             raise RuntimeError("FusedAdamW.step(check_tables=False): a compute copy was re-allocated or the flat gradient buffer was laid out again "
                                "after the descriptor table was built; call step() once with check_tables=True (outside a capture) first")
-        if self.guard is None:
+        if self.guard is not None and self._wants_norm():
+            K.check(K.lib.lavt_grad_norm(K.ptr(desc), K.ptr(chunks), nchunks, K.ptr(self._norm_ws), K.ptr(self.guard), self.max_grad_norm, int(self.skip_nonfinite), K.stream()))
+        if self.amsgrad:
+            K.check(K.lib.lavt_adamw_step_chunks_amsgrad(K.ptr(desc), K.ptr(vmax), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(self._step), self.total_steps, self.power,
+                                                         K.ptr(self.guard), K.stream()))
+        elif self.guard is None:
             K.check(K.lib.lavt_adamw_step_chunks(K.ptr(desc), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(self._step), self.total_steps, self.power, K.stream()))
         else:
-            if self._wants_norm():
-                K.check(K.lib.lavt_grad_norm(K.ptr(desc), K.ptr(chunks), nchunks, K.ptr(self._norm_ws), K.ptr(self.guard), self.max_grad_norm, int(self.skip_nonfinite), K.stream()))
             K.check(K.lib.lavt_adamw_step_chunks_guarded(K.ptr(desc), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(self._step), self.total_steps, self.power,
                                                          K.ptr(self.guard), K.stream()))
         # The kernel writes the parameters through raw pointers: p._version does not move, so the cached compute copies (bf16 Linear weights,
@@ -217,6 +251,11 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def load_state_dict(self, state_dict):
         sched = state_dict.get("lavt_schedule")
+        theirs = {bool(g.get("amsgrad", False)) for g in state_dict["param_groups"]}
+        if theirs != {self.amsgrad}:
+            # (a plain checkpoint would start max_exp_avg_sq at zero, an AMSGrad one would lose it: neither silently)
+            raise ValueError(f"FusedAdamW.load_state_dict: the checkpoint's param_groups have amsgrad={sorted(theirs)} but this optimizer was built with "
+                             f"amsgrad={self.amsgrad}")
         super().load_state_dict({k: v for k, v in state_dict.items() if k != "lavt_schedule"})
         steps = None
         if sched is not None:
@@ -226,6 +265,10 @@ class FusedAdamW(torch.optim.Optimizer):
                 if "step" in st:
                     steps = int(st["step"].item()) if torch.is_tensor(st["step"]) else int(st["step"])
                     break
+            if self.total_steps > 0:
+                for g in self.param_groups:          # a LambdaLR left its scheduled lr in the group and the base in 'initial_lr': (1 - it/T)^power is applied here
+                    if "initial_lr" in g:
+                        g["lr"] = g["initial_lr"]
         dev = self.param_groups[0]["params"][0].device
         self._step = torch.full((1,), float(steps or 0), dtype=torch.float32, device=dev)
         for st in self.state.values():

@@ -26,7 +26,7 @@ def timeit(fn, n=10):
     for _ in range(n): fn()
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / n
-_, desc, hyper, n, chunks, nchunks, fused = opt._tables
+_, desc, hyper, n, chunks, nchunks, fused = opt._tables[:7]
 nparam = sum(p.numel() for g in opt.param_groups for p in g["params"])
 print("tensors", n, "parameters %.1f M" % (nparam / 1e6))
 t_all = timeit(lambda: opt.step(check_tables=False))

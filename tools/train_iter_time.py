@@ -69,7 +69,7 @@ def main():
     sa, oa = harness(False)
     sb, ob = harness(True)
     sc, oc = harness(True, max_grad_norm=1.0, skip_nonfinite=True)
-    _, desc, _, _, chunks, nchunks, _ = oc._tables
+    _, desc, _, _, chunks, nchunks, _ = oc._tables[:7]
     ctl = torch.tensor([0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0]).to(dev)
     ws = torch.empty(int(K.lib.lavt_grad_norm_ws(nchunks)), dtype=torch.float32, device=dev)
     flat = sc.buckets.flat
