@@ -470,7 +470,7 @@ int lavt_wmsa_fwd_rider(const void* x, const int32_t* wmap, const void* Wg, cons
  * Fused PWAM (ABI v4, bf16).  Replaces, with the GEMMs above, PWAM.forward (lib/backbone.py:1265-1278),
  * SpatialImageLanguageAttention.forward (:1329-1372) and the language gate (:604-611, :669) and their autograd backward.
  * The instance norm of the query folds into the keys and the W projection collapses onto the <= 32 word probabilities
- * (w = P (V Wo^T) + bo, so IN(w) = (P - Pbar) VW' from the word statistics alone): see csrc/pwam.hip and tools/pwam_algebra_check.py.
+ * (w = P (V Wo^T) + bo, so IN(w) = (P - Pbar) VW' from the word statistics alone): see csrc/pwam.hip; tests/pwam_stages.py states every kernel in fp64.
  * Word axes are padded to 32 slots; B samples of T pixels each, rows [B*T]; C % 32 == 0.
  *   lavt_pwam_words_fwd: P[row][32] = softmax_{j < n_l}(alpha * IN_T(q) K^T + maskbias)   (q raw, mean / rstd [B][C] of q over the T pixels)
  *   lavt_pwam_lang_fwd:  from V [B][32][ldv], Wo [C][C] (bf16 compute copy), PP = P^T P [B][32][32], sumP [B][32]:

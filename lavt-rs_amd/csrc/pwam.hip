@@ -13,7 +13,7 @@
 //   pwam_words_kernel: [T x C] x [C x 32] -> per-row word vectors (forward: S -> softmax -> P; backward: dP -> softmax' -> dS)
 //   pwam_mix_kernel:   [T x 32] x [32 x C] -> per-row channel vectors fused with the element-wise neighbours
 //                      (forward: mm = GELU(vpre) * what; backward A: d vpre, d what; backward C: dq = dS K'' + c0 - q c1)
-// and three tiny language-side kernels on [32 x C] / [32 x 32] matrices.  tools/pwam_algebra_check.py proves the algebra against autograd.
+// and three tiny language-side kernels on [32 x C] / [32 x 32] matrices.  tests/test_pwam_stages_host.py proves the algebra against autograd.
 #include <stdlib.h>
 
 #include "lds_prims.h"
