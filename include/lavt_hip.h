@@ -743,6 +743,44 @@ int lavt_bert_embed_bwd(int dtype, const void* dy, const int64_t* ids, const int
                         int rows, int N, int H, void* stream);
 int lavt_dropout(int dtype, const void* x, const uint8_t* keep, float scale, const void* residual, void* y, int64_t n, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Deterministic forms (DESIGN.md "Deterministic mode"; new symbols only: no existing prototype or struct changed, lavt_abi_version() stays 7).
+ * Every entry point below computes what its sibling above computes WITHOUT float atomics: the same bits on every run from the same inputs.  The
+ * library keeps no mode: the host calls these instead of the siblings (lavt_hip.ops.deterministic()).  The weight-gradient GEMMs need no new entry
+ * point: a caller that lends `partials` to every launch that may split, or asks for split_k = 1, never reaches their atomic branches (one addend
+ * per output element; a colsum_atomic vector shared by exactly two members of a launch receives 0 + a + b, which does not depend on the order).
+ * lavt_reduce_partials_det: partials [nblk][W] (W = groups * 2 * C: per group C "sum-1" values, then C "sum-2" values) are ADDED into o1 / o2 [groups][C].
+ *   Two-level: the row slices of the atomic form store their sums to `stage` (lavt_reduce_partials_det_stage(W) floats), a second launch adds them in
+ *   slice order.  stage NULL / too small: one slice walks all rows.  lavt_layernorm_bwd_partial(_xn) / lavt_cls_head_bwd_partial + this call replace
+ *   lavt_layernorm_bwd(_xn) / lavt_cls_head_bwd.
+ * lavt_reduce_partials_multi_det: lavt_reduce_partials_multi's compact launch (n <= 64 sets, total_column_blocks as there) with the eight row slices of
+ *   every column block stored to stage (>= total_column_blocks * 8 * 128 floats) and added in slice order by a second launch.
+ * lavt_norm_bwd_stats_det: lavt_norm_bwd_stats with scratch REQUIRED (the block sums) and reduced as lavt_reduce_partials_det does; with
+ *   lavt_reduce_partials_det_stage(groups * 2 * C) floats more in ws the reduction is two-level.
+ * lavt_window_attn_bwd_det: lavt_window_attn_bwd's arguments; ws of lavt_window_attn_bwd_det_ws floats is REQUIRED.  bf16 MFMA path: the table gradient
+ *   is GATHERED -- one thread per (table entry, head) walks the query rows in ascending order, takes the one key whose offset is its entry and sums the
+ *   slab values over the windows in window order; the per-workgroup records (same count and layout as the histogram form: lavt_window_attn_bwd_pieces)
+ *   are added in record order by one thread per entry (dtable), or left in parts for lavt_attn_dtable_finish_multi.  Exact-fp32 kernel: dS goes to
+ *   per-(window, head) fp32 slabs, summed over the windows (lavt_attn_dbias_sum's kernel) and binned (lavt_relpos_reduce's); the waves of a workgroup add
+ *   their dK / dV tiles in wave order; no deferred (parts) form.
+ * lavt_bert_embed_bwd_det: lavt_bert_embed_bwd with one writer per target row: the first token row that names a word / position / type row adds the dy
+ *   rows of all token rows naming it, in ascending row order, to that row's running sum.
+ * lavt_gemm_tn_v2_eligible: 1 when lavt_gemm_tn runs the problem on the bf16 LDS-DMA kernels, the ones that honour `partials`; a query, nothing is launched. */
+int lavt_gemm_tn_v2_eligible(const lavt_gemm_tn_t* p);
+int64_t lavt_reduce_partials_det_stage(int W);
+int lavt_reduce_partials_det(const float* partials, int nblk, int W, int C, float* o1, float* o2, float* stage, int64_t stage_floats, void* stream);
+int lavt_reduce_partials_multi_det(const int64_t* desc, int n, int total_column_blocks, float* stage, int64_t stage_floats, void* stream);
+int lavt_norm_bwd_stats_det(int dtype, const void* dy, const void* x, const void* y, const float* mean, const float* rstd,
+                            const float* gamma, const float* beta, const void* mul, int relu, float* s1, float* s2,
+                            float* ws, int64_t ws_floats, int groups, int rows, int C, void* stream);
+int64_t lavt_window_attn_bwd_det_ws(int dtype, int nwin, int N, int heads, int bias_ld, int wd, int wh, int ww);
+int lavt_window_attn_bwd_det(int dtype, const void* qkv, const float* bias, int bias_ld, const int8_t* region, int nw_img,
+                             const void* out, const void* dout, const float* lse, void* dqkv, const float* table, float* dtable,
+                             float* ws, int64_t ws_floats, float* parts, int wd, int wh, int ww, int nwin, int N, int heads, int head_dim, float scale,
+                             void* stream);
+int lavt_bert_embed_bwd_det(int dtype, const void* dy, const int64_t* ids, const int64_t* token_type, float* dword, float* dpos, float* dtype_,
+                            int rows, int N, int H, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

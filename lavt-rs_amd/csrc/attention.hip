@@ -98,13 +98,15 @@ __device__ __forceinline__ int relpos_index(int i, int j, int wd, int wh, int ww
     const int dj = j / (wh * ww), hj = (j / ww) % wh, wj = j % ww;
     return ((di - dj + wd - 1) * (2 * wh - 1) + (hi - hj + wh - 1)) * (2 * ww - 1) + (wi - wj + ww - 1);
 }
-template <typename T, int NJ>
+// DET (lavt_window_attn_bwd_det): no float atomics.  dS goes to this (window, head)'s own fp32 slab dslab[w][h][N][bias_ld] as plain stores (summed over
+// the windows by attn_dbias_sum_kernel, binned by relpos_reduce_kernel), and the waves add their dK / dV tiles into LDS one after the other, in wave order.
+template <typename T, int NJ, bool DET = false>
 __global__ __launch_bounds__(256) void window_attn_bwd_kernel(const T* __restrict__ qkv, const float* __restrict__ bias,
                                                               const int8_t* __restrict__ region, int nw_img,
                                                               const T* __restrict__ out, const T* __restrict__ dout,
                                                               const float* __restrict__ lse, T* __restrict__ dqkv,
                                                               float* __restrict__ dbias, int N, int heads, float scale, int bias_ld,
-                                                              float* __restrict__ dtable, int wd, int wh, int ww) {
+                                                              float* __restrict__ dtable, int wd, int wh, int ww, float* __restrict__ dslab = nullptr) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* Ks = reinterpret_cast<float*>(smem_raw);
     float* Vs = Ks + N * KV_LD;
@@ -163,8 +165,10 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(const T* __restric
                 if (rid_j[t] != rid_i) a += -100.0f;
                 const float pj = __expf(a - l);
                 ds = pj * (dp - dl);
+                if constexpr (!DET) {
                 if (dtable) atomicAdd(dtable + (int64_t)relpos_index(i, j, wd, wh, ww) * heads + h, ds);      // parity path: plain global atomics
                 else atomicAdd(dbh + (int64_t)i * bias_ld + j, ds);
+                }
 #pragma unroll
                 for (int d = 0; d < HD; ++d) {
                     dv[t][d] = fmaf(pj, dOr[d], dv[t][d]);
@@ -172,6 +176,10 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(const T* __restric
                 }
             }
             dS[j] = ds;
+            if constexpr (DET) {
+                if (j < bias_ld) dslab[((int64_t)blockIdx.x * N + i) * bias_ld + j] = ds;          // (a padding column a lane reaches holds 0, one beyond 64 NJ stays unwritten: attn_dbias_sum_kernel sums both into padding columns of the dense
+                // gradient, which relpos_reduce_kernel -- j < N -- never reads)
+            }
         }
         __builtin_amdgcn_wave_barrier();
         // dQ[i][d] = scale * sum_j dS[j] K[j][d]
@@ -183,6 +191,24 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(const T* __restric
         __builtin_amdgcn_wave_barrier();
     }
     // cross-wave reduction of dK, dV through LDS, then store
+    if constexpr (DET) {
+        for (int wv = 0; wv < 4; ++wv) {          // a lane owns its keys j within its wave: plain adds, the waves take turns
+            if (wave == wv) {
+#pragma unroll
+                for (int t = 0; t < NJ; ++t) {
+                    const int j = lane + 64 * t;
+                    if (j < N) {
+#pragma unroll
+                        for (int d = 0; d < HD; ++d) {
+                            dKs[j * KV_LD + d] += dk[t][d];
+                            dVs[j * KV_LD + d] += dv[t][d];
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    } else {
 #pragma unroll
     for (int t = 0; t < NJ; ++t) {
         const int j = lane + 64 * t;
@@ -195,6 +221,7 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(const T* __restric
         }
     }
     __syncthreads();
+    }
     for (int e = threadIdx.x; e < N * HD; e += blockDim.x) {
         const int j = e / HD, d = e % HD;
         T* r = dqkv + (row0 + j) * (int64_t)(3 * C) + h * HD + d;
@@ -371,6 +398,20 @@ int launch_fwd(const void* qkv, const float* bias, int bias_ld, const int8_t* re
     return LAVT_OK;
 }
 template <typename T>
+int launch_bwd_det(const void* qkv, const float* bias, int bias_ld, const int8_t* region, int nw_img, const void* out, const void* dout,
+                   const float* lse, void* dqkv, float* dslab, int nwin, int N, int heads, float scale, hipStream_t st) {
+    const int NJ = (N + 63) / 64;
+    const size_t lds = (size_t)(5 * N * KV_LD + 4 * NJ * 64 + 4 * HD) * sizeof(float);
+    dim3 grid(nwin * heads);
+#define L(NJ_)                                                                                                                   \
+    hipLaunchKernelGGL((window_attn_bwd_kernel<T, NJ_, true>), grid, dim3(256), lds, st, (const T*)qkv, bias, region, nw_img,    \
+                       (const T*)out, (const T*)dout, lse, (T*)dqkv, (float*)nullptr, N, heads, scale, bias_ld, (float*)nullptr, 1, 1, 1, dslab)
+    if (NJ == 1) L(1); else if (NJ == 2) L(2); else if (NJ == 3) L(3); else { lavt_set_error("lavt_window_attn_bwd_det: N=%d > 192 not supported by this kernel", N); return LAVT_ERR_INVALID; }
+#undef L
+    LAVT_CHECK_LAUNCH("lavt_window_attn_bwd_det");
+    return LAVT_OK;
+}
+template <typename T>
 int launch_bwd(const void* qkv, const float* bias, int bias_ld, const int8_t* region, int nw_img, const void* out, const void* dout,
                const float* lse, void* dqkv, float* dbias, float* dtable, int wd, int wh, int ww, int nwin, int N, int heads, float scale, hipStream_t st) {
     const int NJ = (N + 63) / 64;
@@ -438,6 +479,36 @@ extern "C" int lavt_window_attn_bwd_chained(int dtype, const void* qkv, int bias
                    "lavt_window_attn_bwd_chained: bf16 MFMA path only (N <= 400, scratch of lavt_window_attn_bwd_ws floats)");
     return lavt_window_attn_bwd_mfma(qkv, table, region, nw_img, out, dout, lse, dqkv, nullptr, bias_ld, ws, parts, wd, wh, ww, nwin, N, heads, scale,
                                      reinterpret_cast<hipStream_t>(stream), prev, mine);
+}
+// Deterministic mode (no float atomics; the same arguments as lavt_window_attn_bwd).  bf16 MFMA path: the gather form of the binning
+// (attention_mfma.hip).  Exact-fp32 kernel: per-(window, head) dS slabs -> lavt_attn_dbias_sum's kernel -> lavt_relpos_reduce's kernel; needs
+// ws of lavt_window_attn_bwd_det_ws floats and has no deferred (parts) form.
+extern "C" int64_t lavt_window_attn_bwd_det_ws(int dtype, int nwin, int N, int heads, int bias_ld, int wd, int wh, int ww) {
+    if (use_mfma(dtype, N, bias_ld)) return lavt_window_attn_bwd_ws_mfma(nwin, N, heads, bias_ld, wd, wh, ww);
+    return ((int64_t)nwin + 1) * heads * N * bias_ld;
+}
+extern "C" int lavt_window_attn_bwd_det(int dtype, const void* qkv, const float* bias, int bias_ld, const int8_t* region, int nw_img,
+                                        const void* out, const void* dout, const float* lse, void* dqkv, const float* table, float* dtable,
+                                        float* ws, int64_t ws_floats, float* parts, int wd, int wh, int ww, int nwin, int N, int heads, int head_dim,
+                                        float scale, void* stream) {
+    LAVT_CHECK_ARG(head_dim == HD, "lavt_window_attn_bwd_det: head_dim %d != 32", head_dim);
+    LAVT_CHECK_ARG(qkv && out && dout && lse && dqkv && table && (dtable || parts) && ws && nwin > 0 && N > 0 && heads > 0, "lavt_window_attn_bwd_det: bad arguments");
+    LAVT_CHECK_ARG(wd > 0 && wh > 0 && ww > 0 && N <= wd * wh * ww, "lavt_window_attn_bwd_det: window shape (wd, wh, ww) must cover N tokens");
+    LAVT_CHECK_ARG(ws_floats >= lavt_window_attn_bwd_det_ws(dtype, nwin, N, heads, bias_ld, wd, wh, ww), "lavt_window_attn_bwd_det: scratch of lavt_window_attn_bwd_det_ws floats needed");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (use_mfma(dtype, N, bias_ld))
+        return lavt_window_attn_bwd_det_mfma(qkv, table, region, nw_img, out, dout, lse, dqkv, dtable, bias_ld, ws, parts, wd, wh, ww, nwin, N, heads, scale, st);
+    LAVT_CHECK_ARG(parts == nullptr && dtable, "lavt_window_attn_bwd_det: the deferred table-gradient form exists on the bf16 MFMA path only");
+    LAVT_CHECK_ARG(bias && bias_ld >= N && bias_ld % 4 == 0, "lavt_window_attn_bwd_det: the exact-fp32 kernel needs the dense bias (lavt_relpos_expand), bias_ld %% 4 == 0");
+    int rc;
+    if (dtype == LAVT_F32) rc = launch_bwd_det<float>(qkv, bias, bias_ld, region, nw_img, out, dout, lse, dqkv, ws, nwin, N, heads, scale, st);
+    else if (dtype == LAVT_BF16) rc = launch_bwd_det<bf16>(qkv, bias, bias_ld, region, nw_img, out, dout, lse, dqkv, ws, nwin, N, heads, scale, st);
+    else { lavt_set_error("lavt_window_attn_bwd_det: bad dtype %d", dtype); return LAVT_ERR_INVALID; }
+    if (rc != LAVT_OK) return rc;
+    float* ddense = ws + (int64_t)nwin * heads * N * bias_ld;
+    rc = lavt_attn_dbias_sum(LAVT_F32, ws, ddense, nwin, heads, N, N, bias_ld, stream);
+    if (rc != LAVT_OK) return rc;
+    return lavt_relpos_reduce(ddense, dtable, wd, wh, ww, N, heads, bias_ld, stream);
 }
 extern "C" int lavt_attn_dtable_run(const lavt_dtable_job_t* job, void* stream) {
     LAVT_CHECK_ARG(job && job->slab && job->part && job->gx > 0 && job->gz > 0 && job->heads > 0, "lavt_attn_dtable_run: bad job");

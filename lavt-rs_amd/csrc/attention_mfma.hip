@@ -480,6 +480,35 @@ __global__ void wattn_dtable_finish(const float* __restrict__ part, float* __res
     else dtable[(int64_t)e * heads + h] += a;
 }
 
+// Gather form of the binning (deterministic mode: no float atomics).  The grid and the records are those of wattn_dtable_kernel -- (row chunks, heads,
+// window groups) -> part[(z * chunks + chunk) * heads + h][R] -- but a THREAD owns a table entry: it walks the query rows i of its chunk in ascending
+// order, takes the one key j with relpos_index(i, j) == entry (none for most rows), sums slab[w][h][i][j] over the group's windows in window order and
+// adds the rows' sums in row order.  Strided 2-byte reads: several times the time of the histogram form, and the same bits on every run.
+__global__ __launch_bounds__(256) void wattn_dtable_gather_kernel(const bf16* __restrict__ slab, float* __restrict__ part, int slab_ld, int wd, int wh, int ww, int nwin,
+                                                                  int N, int heads, int rows_per_block, int win_per_group) {
+    const int R = (2 * wd - 1) * (2 * wh - 1) * (2 * ww - 1);
+    const int h = blockIdx.y;
+    const int r0 = blockIdx.x * rows_per_block, r1 = min(N, r0 + rows_per_block);
+    const int w0 = blockIdx.z * win_per_group, w1 = min(nwin, w0 + win_per_group);
+    const int64_t wstride = (int64_t)heads * N * slab_ld;
+    float* dst = part + (((int64_t)blockIdx.z * gridDim.x + blockIdx.x) * heads + h) * R;
+    for (int e = threadIdx.x; e < R; e += 256) {
+        const int dw = e % (2 * ww - 1) - (ww - 1), dh = (e / (2 * ww - 1)) % (2 * wh - 1) - (wh - 1), dd = e / ((2 * ww - 1) * (2 * wh - 1)) - (wd - 1);
+        float acc = 0.f;
+        for (int i = r0; i < r1; ++i) {
+            const int zj = i / (wh * ww) - dd, yj = (i / ww) % wh - dh, xj = i % ww - dw;
+            if (zj < 0 || zj >= wd || yj < 0 || yj >= wh || xj < 0 || xj >= ww) continue;
+            const int j = (zj * wh + yj) * ww + xj;
+            if (j >= N) continue;
+            const bf16* q = slab + ((int64_t)w0 * heads + h) * N * slab_ld + (int64_t)i * slab_ld + j;
+            float sw = 0.f;
+            for (int w = w0; w < w1; ++w, q += wstride) sw += __uint_as_float((uint32_t)(*reinterpret_cast<const uint16_t*>(q)) << 16);
+            acc += sw;
+        }
+        dst[e] = acc;
+    }
+}
+
 template <int NT> size_t bwd_lds_bytes(int R) {
     constexpr int NP = ((NT + 1) / 2) * 32;
     return (size_t)4 * NP * R_LD * 2 + (size_t)3 * NP * 4 + NP + (size_t)R * 4 + 16;
@@ -612,6 +641,24 @@ int lavt_attn_dtable_run_mfma(const lavt_dtable_job_t* jb, hipStream_t st) {
     hipLaunchKernelGGL(wattn_dtable_kernel, dim3(jb->gx, jb->heads, jb->gz), dim3(256), (size_t)(R + jb->N) * 4, st, reinterpret_cast<const bf16*>(jb->slab), jb->part,
                        jb->slab_ld, jb->wd, jb->wh, jb->ww, jb->nwin, jb->N, jb->heads, jb->rows_per_block, jb->win_per_group);
     LAVT_CHECK_LAUNCH("lavt_attn_dtable_run");
+    return LAVT_OK;
+}
+// Deterministic table gradient: the attention backward with its binning left undone (`mine`), then the gather form of the binning, then -- dtable != NULL --
+// the records added into dtable by ONE thread per entry in record order (wattn_dtable_finish with a single piece group); parts != NULL: the records are the
+// caller's, for lavt_attn_dtable_finish_multi (one writer per entry there too).
+int lavt_window_attn_bwd_det_mfma(const void* qkv, const float* table, const int8_t* region, int nw_img, const void* out, const void* dout, const float* lse,
+                                  void* dqkv, float* dtable, int bias_ld, float* ws, float* parts, int wd, int wh, int ww, int nwin, int N, int heads, float scale,
+                                  hipStream_t st) {
+    lavt_dtable_job_t jb;
+    const int rc = lavt_window_attn_bwd_mfma(qkv, table, region, nw_img, out, dout, lse, dqkv, dtable, bias_ld, ws, parts, wd, wh, ww, nwin, N, heads, scale, st, nullptr, &jb);
+    if (rc != LAVT_OK) return rc;
+    hipLaunchKernelGGL(wattn_dtable_gather_kernel, dim3(jb.gx, jb.heads, jb.gz), dim3(256), 0, st, reinterpret_cast<const bf16*>(jb.slab), jb.part, jb.slab_ld, jb.wd, jb.wh,
+                       jb.ww, jb.nwin, jb.N, jb.heads, jb.rows_per_block, jb.win_per_group);
+    if (!parts) {
+        const int R = (2 * wd - 1) * (2 * wh - 1) * (2 * ww - 1), pieces = jb.gx * jb.gz;
+        hipLaunchKernelGGL(wattn_dtable_finish, dim3(cdiv(R, 256), heads, 1), dim3(256), 0, st, jb.part, dtable, pieces, pieces, heads, R);
+    }
+    LAVT_CHECK_LAUNCH("lavt_window_attn_bwd_det(table gradient)");
     return LAVT_OK;
 }
 // prev: the binning job of an EARLIER launch to run inside this one (8-wave variants; launched on its own in front otherwise); mine != NULL: this

@@ -626,6 +626,10 @@ static bool tn_v2_eligible(const lavt_gemm_tn_t& p) {
     return true;
 }
 
+// 1 when lavt_gemm_tn runs this problem on the LDS-DMA kernels of this file -- the only ones that honour a lent `partials` scratch.  Deterministic mode asks
+// before it lends one (lavt_hip.ops.gemm_tn): a problem that falls to gemm_tn_kernel must be told split_k = 1 instead.
+extern "C" int lavt_gemm_tn_v2_eligible(const lavt_gemm_tn_t* p) { return p != nullptr && tn_v2_eligible(*p) ? 1 : 0; }
+
 // returns 1 when the group cannot run as one launch (the caller then issues the problems one by one)
 // ln != NULL: a LayerNorm backward to run as rider workgroups of the launch; returns 3 when the group was launched WITHOUT it (the caller launches it)
 int lavt_gemm_tn_grouped_v2(const lavt_gemm_tn_t* probs, int n, hipStream_t st, const lavt_ln_rider_t* ln) {

@@ -49,6 +49,9 @@ int lavt_window_attn_bwd_mfma(const void* qkv, const float* table, const int8_t*
                               const float* lse, void* dqkv, float* dtable, int bias_ld, float* ws, float* parts, int wd, int wh, int ww, int nwin, int N,
                               int heads, float scale, hipStream_t st, const lavt_dtable_job_t* prev, lavt_dtable_job_t* mine);
 int lavt_attn_dtable_run_mfma(const lavt_dtable_job_t* jb, hipStream_t st);
+int lavt_window_attn_bwd_det_mfma(const void* qkv, const float* table, const int8_t* region, int nw_img, const void* out, const void* dout, const float* lse,
+                                  void* dqkv, float* dtable, int bias_ld, float* ws, float* parts, int wd, int wh, int ww, int nwin, int N, int heads, float scale,
+                                  hipStream_t st);
 int lavt_attn_dtable_finish_multi_impl(const int64_t* desc, int n, int max_R, int max_heads, int total_heads, hipStream_t st);
 int lavt_window_attn_bwd_pieces_mfma(int nwin, int N, int heads);
 int64_t lavt_window_attn_bwd_ws_mfma(int nwin, int N, int heads, int bias_ld, int wd, int wh, int ww);

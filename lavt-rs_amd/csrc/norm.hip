@@ -212,6 +212,98 @@ __global__ __launch_bounds__(256) void reduce_partials_multi_kernel(const int64_
 }
 static inline dim3 reduce_partials_grid(int nblk, int W) { return dim3(cdiv(W, 32), nblk >= 768 ? 16 : nblk >= 384 ? 8 : nblk >= 128 ? 4 : (nblk >= 48 ? 2 : 1)); }
 
+// Deterministic form of reduce_partials_kernel (lavt_reduce_partials_det and the *_det entry points): the same walk, but a row slice STORES its sum
+// to stage[slice][W] (stage != NULL) instead of meeting the other slices in the output through atomics.  A second launch of this kernel over the
+// stage rows with gridDim.y == 1 and stage == NULL then adds them to the output: one writer per column, one fixed order of additions.
+__global__ __launch_bounds__(256) void reduce_partials_det_kernel(const float* __restrict__ partials, int nblk, int W, int C, float* __restrict__ stage,
+                                                                  float* __restrict__ o1, float* __restrict__ o2) {
+    __shared__ float red[8][33];
+    const int col = threadIdx.x & 31, slice = threadIdx.x >> 5;
+    const int w = blockIdx.x * 32 + col;
+    const int per = (nblk + gridDim.y - 1) / gridDim.y, k0 = blockIdx.y * per, k1 = min(nblk, k0 + per);
+    float a = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    if (w < W) {
+        int k = k0 + slice;
+        for (; k + 24 < k1; k += 32) {
+            a += partials[(int64_t)k * W + w]; a1 += partials[(int64_t)(k + 8) * W + w];
+            a2 += partials[(int64_t)(k + 16) * W + w]; a3 += partials[(int64_t)(k + 24) * W + w];
+        }
+        for (; k < k1; k += 8) a += partials[(int64_t)k * W + w];
+    }
+    red[slice][col] = (a + a1) + (a2 + a3);
+    __syncthreads();
+    if (slice == 0 && w < W) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) t += red[k][col];
+        if (stage) { stage[(int64_t)blockIdx.y * W + w] = t; return; }          // (an empty slice stores its 0: the second launch reads every stage row)
+        const int g2 = w / C, c = w - g2 * C;          // g2 = 2*g + which
+        float* dst = (g2 & 1) ? o2 : o1;
+        dst[(int64_t)(g2 >> 1) * C + c] += t;          // gridDim.y == 1: the only writer of this column
+    }
+}
+// stage: slices * W floats, or NULL (then one slice walks all rows: slower, the same guarantee)
+static void reduce_partials_det(const float* partials, int nblk, int W, int C, float* o1, float* o2, float* stage, hipStream_t st) {
+    const dim3 g = reduce_partials_grid(nblk, W);
+    if (g.y > 1 && stage) {
+        hipLaunchKernelGGL(reduce_partials_det_kernel, g, dim3(256), 0, st, partials, nblk, W, C, stage, o1, o2);
+        hipLaunchKernelGGL(reduce_partials_det_kernel, dim3(g.x, 1), dim3(256), 0, st, stage, (int)g.y, W, C, (float*)nullptr, o1, o2);
+    } else {
+        hipLaunchKernelGGL(reduce_partials_det_kernel, dim3(g.x, 1), dim3(256), 0, st, partials, nblk, W, C, (float*)nullptr, o1, o2);
+    }
+}
+constexpr int RP_DET_MAX_SLICES = 16;          // the most row slices reduce_partials_grid cuts
+
+// Deterministic form of reduce_partials_multi_kernel<true>.  FINAL = false: the (column block, row slice) workgroups of the atomic form store their
+// sums to stage[column block][slice][RPM_COLS]; FINAL = true: one workgroup per column block adds its slices in slice order into the outputs.
+template <bool FINAL>
+__global__ __launch_bounds__(256) void reduce_partials_multi_det_kernel(const int64_t* __restrict__ desc, int nsets, float* __restrict__ stage, int slices) {
+    const int ln = threadIdx.x & 63;
+    int nb = ln < nsets ? (2 * (int)desc[(int64_t)ln * 5 + 2] + RPM_COLS - 1) / RPM_COLS : 0;
+    int pre = nb;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(pre, o, 64);
+        if (ln >= o) pre += up;
+    }
+    const unsigned long long hit = __ballot(pre > (int)blockIdx.x);
+    const int set = hit ? __ffsll((long long)hit) - 1 : nsets - 1;
+    const int cb = (int)blockIdx.x - __shfl(pre - nb, set, 64);
+    const int64_t* d = desc + (int64_t)set * 5;
+    const float* partials = reinterpret_cast<const float*>(d[0]);
+    const int nblk = (int)d[1], C = (int)d[2], W = 2 * C;
+    if (cb * RPM_COLS >= W) return;
+    if constexpr (FINAL) {
+        const int w = cb * RPM_COLS + (int)threadIdx.x;
+        if (threadIdx.x >= RPM_COLS || w >= W) return;
+        const float* q = stage + (int64_t)blockIdx.x * slices * RPM_COLS + threadIdx.x;
+        float t = 0.f;
+        for (int s = 0; s < slices; ++s) t += q[s * RPM_COLS];
+        float* dst = w >= C ? reinterpret_cast<float*>(d[4]) + (w - C) : reinterpret_cast<float*>(d[3]) + w;
+        *dst += t;
+    } else {
+        __shared__ float red[8][RPM_COLS + 1];
+        const int col = threadIdx.x & 31, slice = threadIdx.x >> 5;
+        const int per = (nblk + gridDim.y - 1) / gridDim.y, k0 = blockIdx.y * per, k1 = min(nblk, k0 + per);
+        float a[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int k = k0 + slice; k < k1; k += 8)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int w = cb * RPM_COLS + 4 * col + i;
+                if (w < W) a[i] += partials[(int64_t)k * W + w];
+            }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) red[slice][4 * col + i] = a[i];
+        __syncthreads();
+        if (threadIdx.x < RPM_COLS) {
+            float t = 0.f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) t += red[k][threadIdx.x];
+            stage[((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * RPM_COLS + threadIdx.x] = t;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- column statistics
 // grid: (row blocks, groups).  Thread t owns chunk column t % cpr and walks rows t / cpr, + 256/cpr, ...
 template <typename T, bool BWD>
@@ -680,6 +772,27 @@ extern "C" int lavt_reduce_partials_multi(const int64_t* desc, int n, int total_
     LAVT_CHECK_LAUNCH("lavt_reduce_partials_multi");
     return LAVT_OK;
 }
+// Deterministic forms (no float atomics: the same bits from run to run).  lavt_reduce_partials_det: partials [nblk][W] (W = groups * 2 * C, laid out as
+// the second-stage comment above says) are ADDED into o1 / o2; stage = scratch of lavt_reduce_partials_det_stage(W) floats for the two-level form (NULL or
+// too small: one slice walks all rows).  lavt_reduce_partials_multi_det: the compact launch of lavt_reduce_partials_multi (n <= 64 sets) with
+// stage >= total_column_blocks * 8 * 128 floats.
+extern "C" int64_t lavt_reduce_partials_det_stage(int W) { return (int64_t)RP_DET_MAX_SLICES * W; }
+extern "C" int lavt_reduce_partials_det(const float* partials, int nblk, int W, int C, float* o1, float* o2, float* stage, int64_t stage_floats, void* stream) {
+    LAVT_CHECK_ARG(partials && o1 && o2 && nblk > 0 && C > 0 && W > 0 && W % (2 * C) == 0, "lavt_reduce_partials_det: bad arguments");
+    reduce_partials_det(partials, nblk, W, C, o1, o2, stage_floats >= (int64_t)RP_DET_MAX_SLICES * W ? stage : nullptr, reinterpret_cast<hipStream_t>(stream));
+    LAVT_CHECK_LAUNCH("lavt_reduce_partials_det");
+    return LAVT_OK;
+}
+extern "C" int lavt_reduce_partials_multi_det(const int64_t* desc, int n, int total_column_blocks, float* stage, int64_t stage_floats, void* stream) {
+    constexpr int slices = 8;
+    LAVT_CHECK_ARG(desc && n > 0 && n <= 64 && total_column_blocks > 0 && stage && stage_floats >= (int64_t)total_column_blocks * slices * RPM_COLS,
+                   "lavt_reduce_partials_multi_det: n <= 64 sets, their column-block total and a stage of total_column_blocks * 8 * 128 floats required");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(reduce_partials_multi_det_kernel<false>, dim3(total_column_blocks, slices), dim3(256), 0, st, desc, n, stage, slices);
+    hipLaunchKernelGGL(reduce_partials_multi_det_kernel<true>, dim3(total_column_blocks), dim3(RPM_COLS), 0, st, desc, n, stage, slices);
+    LAVT_CHECK_LAUNCH("lavt_reduce_partials_multi_det");
+    return LAVT_OK;
+}
 
 // Row blocks of the column-statistics kernels: a thread walks t rows of its chunk column (t = 8, or 4 / 2 when that is what it takes to reach
 // ~256 workgroups; the loads of a thread's rows are independent, the loop is unrolled).  The first version used 64-row blocks whatever the
@@ -796,9 +909,9 @@ extern "C" int lavt_norm_apply(int dtype, const void* x, const float* mean, cons
     return LAVT_OK;
 }
 
-extern "C" int lavt_norm_bwd_stats(int dtype, const void* dy, const void* x, const void* y, const float* mean, const float* rstd,
-                                   const float* gamma, const float* beta, const void* mul, int relu, float* s1, float* s2,
-                                   float* ws, int64_t ws_floats, int groups, int rows, int C, void* stream) {
+static int norm_bwd_stats_impl(int dtype, const void* dy, const void* x, const void* y, const float* mean, const float* rstd,
+                               const float* gamma, const float* beta, const void* mul, int relu, float* s1, float* s2,
+                               float* ws, int64_t ws_floats, int groups, int rows, int C, void* stream, bool det) {
     const int zero_out = 1;          // with scratch (two-stage form) s1 / s2 are cleared by this call; without it they must arrive zeroed (atomics)
     const int epc = dtype == LAVT_F32 ? 4 : 8;
     LAVT_CHECK_ARG(dy && x && mean && rstd && s1 && s2 && (!relu || y) && groups > 0 && rows > 0 && C % epc == 0 && (gamma == nullptr) == (beta == nullptr), "lavt_norm_bwd_stats: bad arguments");
@@ -806,12 +919,28 @@ extern "C" int lavt_norm_bwd_stats(int dtype, const void* dy, const void* x, con
     int rpb;
     const int blocks = stats_launch_geometry(rows, groups, C, epc, &rpb);
     float* partials = (ws && ws_floats >= (int64_t)blocks * groups * 2 * C) ? ws : nullptr;
+    LAVT_CHECK_ARG(!det || partials, "lavt_norm_bwd_stats_det: scratch of %ld floats needed", (long)blocks * groups * 2 * C);
     DISPATCH_T(dtype, "lavt_norm_bwd_stats",
                hipLaunchKernelGGL((colstats_kernel<T, true>), dim3(blocks, groups), dim3(256), 256 * 2 * Chunk<T>::N * sizeof(float), st,
                                   (const T*)dy, (const T*)x, (const T*)y, mean, rstd, (const T*)mul, relu, s1, s2, partials, rows, C, rpb, zero_out, gamma, beta));
-    if (partials) hipLaunchKernelGGL(reduce_partials_kernel, reduce_partials_grid(blocks, groups * 2 * C), dim3(256), 0, st, partials, blocks, groups * 2 * C, C, s1, s2);
+    if (det) {
+        const int64_t W = (int64_t)groups * 2 * C, used = (int64_t)blocks * W;
+        reduce_partials_det(partials, blocks, (int)W, C, s1, s2, ws_floats >= used + RP_DET_MAX_SLICES * W ? ws + used : nullptr, st);
+    } else if (partials) hipLaunchKernelGGL(reduce_partials_kernel, reduce_partials_grid(blocks, groups * 2 * C), dim3(256), 0, st, partials, blocks, groups * 2 * C, C, s1, s2);
     LAVT_CHECK_LAUNCH("lavt_norm_bwd_stats");
     return LAVT_OK;
+}
+extern "C" int lavt_norm_bwd_stats(int dtype, const void* dy, const void* x, const void* y, const float* mean, const float* rstd,
+                                   const float* gamma, const float* beta, const void* mul, int relu, float* s1, float* s2,
+                                   float* ws, int64_t ws_floats, int groups, int rows, int C, void* stream) {
+    return norm_bwd_stats_impl(dtype, dy, x, y, mean, rstd, gamma, beta, mul, relu, s1, s2, ws, ws_floats, groups, rows, C, stream, false);
+}
+// the same with the row blocks summed in a fixed order (no float atomics): ws must hold the block sums (<= 1024 * groups * 2 * C floats), and with
+// lavt_reduce_partials_det_stage(groups * 2 * C) floats more the reduction keeps its row slices (two-level form)
+extern "C" int lavt_norm_bwd_stats_det(int dtype, const void* dy, const void* x, const void* y, const float* mean, const float* rstd,
+                                       const float* gamma, const float* beta, const void* mul, int relu, float* s1, float* s2,
+                                       float* ws, int64_t ws_floats, int groups, int rows, int C, void* stream) {
+    return norm_bwd_stats_impl(dtype, dy, x, y, mean, rstd, gamma, beta, mul, relu, s1, s2, ws, ws_floats, groups, rows, C, stream, true);
 }
 
 extern "C" int lavt_norm_bwd_apply(int dtype, const void* dy, const void* x, const void* y, const float* mean, const float* rstd,

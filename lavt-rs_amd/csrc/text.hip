@@ -42,6 +42,27 @@ __global__ __launch_bounds__(256) void bert_embed_bwd_kernel(const T* __restrict
     }
 }
 
+// The same sums without atomics (lavt_bert_embed_bwd_det): workgroup (r, which) serves target `which` (0 word, 1 position, 2 token type) of token row r.
+// It owns the target row key(r) iff no earlier token row names the same one; the owner then adds the dy rows of every token row with that key in ascending
+// row order and adds the total to the target row -- one writer per target row, one fixed order.  rows = B * N_l is a few hundred: the quadratic scan over
+// the keys is a few thousand uniform loads.
+template <typename T>
+__global__ __launch_bounds__(256) void bert_embed_bwd_det_kernel(const T* __restrict__ dy, const int64_t* __restrict__ ids, const int64_t* __restrict__ tt,
+                                                                 float* __restrict__ dword, float* __restrict__ dpos, float* __restrict__ dtype_, int rows, int N, int H) {
+    const int r = blockIdx.x, which = blockIdx.y;
+    auto key = [&](int q) -> int64_t { return which == 0 ? ids[q] : (which == 1 ? (int64_t)(q % N) : (tt ? tt[q] : 0)); };
+    const int64_t mine = key(r);
+    for (int q = 0; q < r; ++q)
+        if (key(q) == mine) return;                    // (uniform over the workgroup)
+    float* dst = (which == 0 ? dword : (which == 1 ? dpos : dtype_)) + mine * (int64_t)H;
+    for (int c = threadIdx.x; c < H; c += 256) {
+        float a = 0.f;
+        for (int q = r; q < rows; ++q)
+            if (key(q) == mine) a += to_f<T>(dy[(int64_t)q * H + c]);
+        dst[c] += a;
+    }
+}
+
 // y = x * keep * scale (+ r)   (nn.Dropout in training: keep ~ Bernoulli(1 - p) drawn by the caller, scale = 1 / (1 - p); the optional r is
 // the residual BertSelfOutput / BertOutput add before their LayerNorm; backward of x is the same map without r)
 template <typename T>
@@ -74,6 +95,14 @@ extern "C" int lavt_bert_embed_bwd(int dtype, const void* dy, const int64_t* ids
     LAVT_CHECK_ARG(dy && ids && dword && dpos && dtype_ && rows > 0 && N > 0 && H > 0, "lavt_bert_embed_bwd: bad arguments");
     DISPATCH_T(dtype, "lavt_bert_embed_bwd", hipLaunchKernelGGL(bert_embed_bwd_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, ST, (const T*)dy, ids, token_type, dword, dpos, dtype_, rows, N, H));
     LAVT_CHECK_LAUNCH("lavt_bert_embed_bwd");
+    return LAVT_OK;
+}
+
+extern "C" int lavt_bert_embed_bwd_det(int dtype, const void* dy, const int64_t* ids, const int64_t* token_type, float* dword, float* dpos, float* dtype_,
+                                       int rows, int N, int H, void* stream) {
+    LAVT_CHECK_ARG(dy && ids && dword && dpos && dtype_ && rows > 0 && N > 0 && H > 0, "lavt_bert_embed_bwd_det: bad arguments");
+    DISPATCH_T(dtype, "lavt_bert_embed_bwd_det", hipLaunchKernelGGL(bert_embed_bwd_det_kernel<T>, dim3(rows, 3), dim3(256), 0, ST, (const T*)dy, ids, token_type, dword, dpos, dtype_, rows, N, H));
+    LAVT_CHECK_LAUNCH("lavt_bert_embed_bwd_det");
     return LAVT_OK;
 }
 

@@ -270,6 +270,15 @@ _PROTOTYPES = {
     "lavt_upsample_mask": [i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "lavt_resize_norm_u8": [vp, i64, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, vp],
     "lavt_resize_nearest_u8": [vp, i64, i32, i32, i32, vp, vp, vp, i32, i32, vp],
+    # deterministic forms (no float atomics): the host calls them instead of their siblings in deterministic mode
+    "lavt_gemm_tn_v2_eligible": [C.POINTER(GemmTN)],
+    "lavt_reduce_partials_det_stage": [i32],
+    "lavt_reduce_partials_det": [vp, i32, i32, i32, vp, vp, vp, i64, vp],
+    "lavt_reduce_partials_multi_det": [vp, i32, i32, vp, i64, vp],
+    "lavt_norm_bwd_stats_det": [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i64, i32, i32, i32, vp],
+    "lavt_window_attn_bwd_det_ws": [i32, i32, i32, i32, i32, i32, i32, i32],
+    "lavt_window_attn_bwd_det": [i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
+    "lavt_bert_embed_bwd_det": [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
 }
 for _name, _args in _PROTOTYPES.items():
     _fn = getattr(_cdll, _name)          # AttributeError here = header/library mismatch: fail loudly
@@ -286,8 +295,10 @@ _cdll.lavt_conv3x3_wgrad_ws.restype = C.c_int64
 _cdll.lavt_gemm_tn_grouped_sk_ws.restype = C.c_int64
 _cdll.lavt_grad_norm_ws.restype = C.c_int64
 _cdll.lavt_upsample_dice_boundary_ws.restype = C.c_int64
+_cdll.lavt_reduce_partials_det_stage.restype = C.c_int64
+_cdll.lavt_window_attn_bwd_det_ws.restype = C.c_int64
 _cdll.lavt_last_error.argtypes = []
-for _name in ("lavt_last_error", "lavt_window_attn_bwd_ws", "lavt_window_attn_stream_ok", "lavt_window_attn_stream_bwd_ws", "lavt_attn_uses_table", "lavt_abi_version", "lavt_layernorm_bwd_blocks", "lavt_window_attn_bwd_pieces", "lavt_gemm_tn_pieces", "lavt_pwam_q_parts", "lavt_pwam_words_records", "lavt_pwam_mix1_records", "lavt_adamw_chunk_elems", "lavt_tuning_reload", "lavt_conv3x3_wgrad_ws", "lavt_conv3x3_wgrad_f8_ok", "lavt_gemm_tn_grouped_sk_ws", "lavt_gemm_nt_colstats_plan", "lavt_cls_head_bwd_blocks", "lavt_reduce_partials_column_blocks", "lavt_grad_norm_ws", "lavt_upsample_dice_boundary_ws"):      # queries, not launches: never timed
+for _name in ("lavt_last_error", "lavt_window_attn_bwd_ws", "lavt_window_attn_stream_ok", "lavt_window_attn_stream_bwd_ws", "lavt_attn_uses_table", "lavt_abi_version", "lavt_layernorm_bwd_blocks", "lavt_window_attn_bwd_pieces", "lavt_gemm_tn_pieces", "lavt_pwam_q_parts", "lavt_pwam_words_records", "lavt_pwam_mix1_records", "lavt_adamw_chunk_elems", "lavt_tuning_reload", "lavt_conv3x3_wgrad_ws", "lavt_conv3x3_wgrad_f8_ok", "lavt_gemm_tn_grouped_sk_ws", "lavt_gemm_nt_colstats_plan", "lavt_cls_head_bwd_blocks", "lavt_reduce_partials_column_blocks", "lavt_grad_norm_ws", "lavt_upsample_dice_boundary_ws", "lavt_reduce_partials_det_stage", "lavt_window_attn_bwd_det_ws", "lavt_gemm_tn_v2_eligible"):      # queries, not launches: never timed
     setattr(lib, _name, getattr(_cdll, _name))
 
 EXPORTED = tuple(_PROTOTYPES) + ("lavt_last_error",)

@@ -89,7 +89,7 @@ class _ValidIndices:
 
 class TrainStep(_ValidIndices):
     def __init__(self, model, image, l_feats, l_mask, target, world=1, use_graph=True, bucket_mib=32.0, fused_loss=True, refresh_weights_in_step=False, context=None,
-                 *, loss="ce", valid_indices=None, dice_rate=1.0, boundary_rate=0.05):
+                 *, loss="ce", valid_indices=None, dice_rate=1.0, boundary_rate=0.05, deterministic=None):
         """context: the ops.StepContext this harness keeps its state in (gradient sinks, deferred-launch queues, weight copies, scratch).  None = the
         process-wide default context -- what the drop-in path and a single harness use.  Give every further model in the process its own
         `ops.StepContext()` (and its optimizer the same one: FusedAdamW(..., context=)): their steps can then alternate freely.
@@ -98,7 +98,11 @@ class TrainStep(_ValidIndices):
         `--dice_rate` / `--boundary_rate` of args.py:83-84; the other criteria ignore the two rates).
         valid_indices: device int32 [nsel], a static buffer like image and target -- the flat numbers of the annotated frames (A2D-Sentences / JHMDB:
         one per clip, train.py:282-285); target is then (nsel, H, W) and the criterion (and `stats`) covers `index_select(output, 0, valid_indices)`.
-        Fill it with set_valid_indices(per_clip, frames_per_clip), before capture or between replays."""
+        Fill it with set_valid_indices(per_clip, frames_per_clip), before capture or between replays.
+        deterministic: True / False sets the mode of the step's context, None keeps it (a context starts with LAVT_DETERMINISTIC).  In deterministic mode
+        two steps from identical state (parameters, optimizer state, BatchNorm buffers, DropPath generator) on identical inputs give identical bits --
+        loss, gradients, updated parameters, moments, running statistics -- eagerly and under graph replay, on ONE GPU (LAVT_FP8=1 included: its |max| history
+        is part of the state): world > 1 and collectives forced in a 1-rank group raise NotImplementedError (DESIGN.md "Deterministic mode")."""
         if loss not in ("ce", "mc_dice", "dice_boundary"):
             raise ValueError(f"TrainStep: loss must be 'ce', 'mc_dice' or 'dice_boundary', got {loss!r}")
         if valid_indices is not None:
@@ -106,6 +110,8 @@ class TrainStep(_ValidIndices):
         self.criterion, self.valid_indices = loss, valid_indices
         self.dice_rate, self.boundary_rate = float(dice_rate), float(boundary_rate)
         self.context = context if context is not None else ops.default_context()
+        self._warmed = False
+        self.set_deterministic(deterministic, world=world)
         with ops.use_context(self.context):
             self._init(model, image, l_feats, l_mask, target, world, use_graph, bucket_mib, fused_loss, refresh_weights_in_step)
 
@@ -139,7 +145,22 @@ class TrainStep(_ValidIndices):
         self._seen = None
         self._one = None
         self.opt = None                          # the owned optimizer (make_optimizer / attach_optimizer): its step ends _body
-        self._warmed = False
+
+    def set_deterministic(self, deterministic, world=None):
+        """Set the mode of the step's context (None: keep it).  Before warmup_and_capture() only: the captured launch sequence is frozen.  Raises
+        NotImplementedError, naming it, for what the mode does not cover."""
+        if self._warmed:
+            raise RuntimeError("TrainStep: the deterministic mode must be set before warmup_and_capture() (the captured launch sequence is frozen)")
+        mode = self.context.deterministic if deterministic is None else bool(deterministic)
+        world = self.world if world is None else world
+        if mode:
+            if world > 1:
+                raise NotImplementedError("TrainStep(deterministic=True): world > 1 is not covered (the reduction order of the gradient all-reduce is RCCL's)")
+            from .ddp import FORCE_COLLECTIVES
+            if FORCE_COLLECTIVES and torch.distributed.is_available() and torch.distributed.is_initialized():
+                raise NotImplementedError("TrainStep(deterministic=True): collectives forced in a 1-rank group (LAVT_FORCE_COLLECTIVES=1, the LAVT_DDP_MODE "
+                                          "routes at world 1) are not covered")
+        self.context.deterministic = mode
 
     # ---- owned optimizer ----
     def make_optimizer(self, param_groups=None, **adamw_kwargs):

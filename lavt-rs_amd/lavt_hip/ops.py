@@ -19,6 +19,7 @@ from typing import Optional
 import torch
 
 from . import _capi as K
+from . import runtime as _runtime
 from .runtime import fp8_enabled
 
 KV_LD = 32          # padded word axis of PWAM keys/values (N_l <= 32)
@@ -497,6 +498,24 @@ def _scratch(n_floats, device):
 _TN_PARTIALS_MINK = 2048          # shortest reduction (rows) whose single weight-gradient launch is lent a partial-tile scratch
 
 
+_TN_PARTIALS_MAX = 16 << 20       # floats: a larger partial-tile scratch is not lent
+
+
+def tn_plan(dtype, Kd, batch, conv, deferred, v2_eligible, need_floats, det, lend_enabled=True):
+    """How a weight-gradient launch (gemm_tn) may split its reduction: -> (floats of partial-tile scratch to lend, or 0; lavt_gemm_tn_t.split_k).
+    need_floats: batch * lavt_gemm_tn_pieces * (I * J + I), the scratch the most pieces the launchers cut would fill.  A pure function of its arguments.
+    Default mode: scratch for long bf16 reductions only (the pieces of every other split launch meet in C through fp32 atomics), split_k = -1 for a member
+    of a grouped launch (its zeroed C may be cut into up to 4 atomic pieces), else 0 = the launcher's choice.
+    det (deterministic mode): NO launch may split through atomics.  A launch the bf16 LDS-DMA kernels are sure to take (v2_eligible: only they honour the
+    scratch) is lent scratch whatever its length, and split_k = 0 (never -1: a grouped member is then cut through its scratch or not at all); every other
+    launch -- fp32, convolutions, batched group members, a scratch beyond _TN_PARTIALS_MAX -- gets split_k = 1: one addend per output element."""
+    lend = (dtype == torch.bfloat16 and conv is None and (batch == 1 or not deferred) and lend_enabled and 0 < need_floats <= _TN_PARTIALS_MAX
+            and ((det and v2_eligible) or (not det and Kd >= (_TN_PARTIALS_MINK if batch == 1 else 128))))
+    if det:
+        return (need_floats, 0) if lend else (0, 1)
+    return (need_floats if lend else 0), (-1 if deferred else 0)
+
+
 def _tn_parts(n_floats, device):
     """One persistent fp32 buffer per device for the partial tiles of split weight-gradient reductions: a launch's pieces are consumed by its own
     reduction kernel before the next launch of the stream writes them again (stream order), so consecutive launches share it."""
@@ -642,19 +661,21 @@ def gemm_tn(dtype, I, J, Kd, A, lda, B, ldb, Cout, ldc, *, batch=1, strideA=0, s
         if len(conv) > 3:
             p.conv_d, p.conv_kd, p.conv_kh, p.conv_kw = conv[3:7]
     p.alpha, p.C, p.ldc, p.strideC = alpha, K.ptr(Cout) + c_off * 4, ldc, strideC
-    p.c_conv_permute, p.split_k = int(c_conv_permute), (-1 if defer is not None else 0)     # deferred = into the zeroed flat gradient buffer: a grouped launch may split K
+    p.c_conv_permute = int(c_conv_permute)          # (split_k: tn_plan below -- deferred = into the zeroed flat gradient buffer: a grouped launch may split K)
     p.colsum, p.strideColsum, p.colsum_atomic = K.ptr(colsum), strideColsum, int(colsum_atomic)
     # rows a row map may name (the pipelined grouped kernel bounds its 32-bit descriptor offsets with them)
     p.a_src_rows = (A.shape[0] if A.dim() >= 2 else A.numel() // max(lda, 1)) if a_rowmap is not None else 0
     p.b_src_rows = (B.shape[0] if B.dim() >= 2 else B.numel() // max(ldb, 1)) if b_rowmap is not None else 0
     p.zeros = _zero_page(A.device)
-    if dtype == torch.bfloat16 and conv is None and (batch == 1 or defer is None) and Kd >= (_TN_PARTIALS_MINK if batch == 1 else 128) and os.environ.get("LAVT_TN_PARTIALS", "1") != "0":      # (one scratch per device: every launch of a step is on ONE stream)
-        # scratch for split reductions through partial tiles (long-K weight gradients on few output tiles: PWAM's 1x1 convolutions over 28 800 rows;
-        # batched: the per-sample word-side matrices of the fused PWAM node -- plain stores + a fixed-order sum, so the result is run-to-run identical)
-        need = batch * int(K.lib.lavt_gemm_tn_pieces(C.byref(p))) * (I * J + I)
-        if need <= (16 << 20):
-            scr = _tn_parts(need, A.device)
-            p.partials, p.partials_floats = K.ptr(scr), (need if defer is not None else scr.numel())     # queued: flush() hands every member its own region
+    det = deterministic()
+    v2_ok = bool(K.lib.lavt_gemm_tn_v2_eligible(C.byref(p))) if det else False          # the launches that honour a lent scratch: the library's own rule
+    # scratch for split reductions through partial tiles (long-K weight gradients on few output tiles: PWAM's 1x1 convolutions over 28 800 rows;
+    # batched: the per-sample word-side matrices of the fused PWAM node -- plain stores + a fixed-order sum, so the result is run-to-run identical)
+    need, p.split_k = tn_plan(dtype, Kd, batch, conv, defer is not None, v2_ok, batch * int(K.lib.lavt_gemm_tn_pieces(C.byref(p))) * (I * J + I), det,
+                              os.environ.get("LAVT_TN_PARTIALS", "1") != "0")
+    if need:          # (one scratch per device: every launch of a step is on ONE stream)
+        scr = _tn_parts(need, A.device)
+        p.partials, p.partials_floats = K.ptr(scr), (need if defer is not None else scr.numel())     # queued: flush() hands every member its own region
     if defer is not None:
         if rider is not None:
             defer.add(p, (A, B, Cout, a_rowmap, a_rowscale, b_rowmap, colsum) + tuple(t for t in rider if torch.is_tensor(t)), extra=extra, rider=rider)
@@ -699,6 +720,74 @@ def _ln_bwd_partial(dy, x, gamma, mean, rstd, dx, wsd, dres, rows, Cn, gather=No
     else:
         K.check(K.lib.lavt_layernorm_bwd_partial(dt, K.ptr(dy), K.ptr(x), K.ptr(gather), K.ptr(gamma), K.ptr(mean), K.ptr(rstd), K.ptr(dx), K.ptr(wsd), wsd.numel(),
                                                  K.ptr(dres), rows, Cn, K.stream()))
+
+
+_RP_DET_SLICES = 16          # lavt_reduce_partials_det_stage(W) / W: the most row slices the second-stage reduction cuts
+_RP_MULTI_SLICES, _RP_MULTI_COLS = 8, 128          # lavt_reduce_partials_multi: row slices per column block, columns per block
+# kind -> (what the default mode calls, what deterministic mode calls instead)
+_RP_ENTRIES = {"layernorm": (("lavt_layernorm_bwd",), ("lavt_layernorm_bwd_partial", "lavt_reduce_partials_det")),
+               "layernorm_xn": (("lavt_layernorm_bwd_xn",), ("lavt_layernorm_bwd_partial_xn", "lavt_reduce_partials_det")),
+               "norm_stats": (("lavt_norm_bwd_stats",), ("lavt_norm_bwd_stats_det",)),
+               "cls_head": (("lavt_cls_head_bwd",), ("lavt_cls_head_bwd_partial", "lavt_reduce_partials_det")),
+               "multi": (("lavt_reduce_partials_multi",), ("lavt_reduce_partials_multi_det",))}
+
+
+def reduce_partials_slices(nblk):
+    """row slices of the second-stage reduction over nblk partial rows (reduce_partials_grid of csrc/norm.hip)"""
+    return 16 if nblk >= 768 else 8 if nblk >= 384 else 4 if nblk >= 128 else 2 if nblk >= 48 else 1
+
+
+def reduce_partials_plan(kind, nblk, W, det, column_blocks=0):
+    """How the per-workgroup partial sums [nblk][W] of a norm / classifier-head backward reach their outputs: -> (entry points to call, row slices that
+    meet in the output through float atomics, floats of stage scratch to lend).  A pure function of its arguments; kind names the caller (_RP_ENTRIES).
+    Default mode: the one-call entry points, whose reduction cuts reduce_partials_slices(nblk) row slices that meet through atomics (none below 48 row
+    blocks; the multi-set launch always eight); the classifier head adds from every workgroup.  det (deterministic mode): never an atomic slice -- the
+    *_det forms with a stage of _RP_DET_SLICES * W floats (multi: every column block's eight slices), added in slice order by a second launch."""
+    default, dets = _RP_ENTRIES[kind]
+    if det:
+        return dets, 0, (column_blocks * _RP_MULTI_SLICES * _RP_MULTI_COLS if kind == "multi" else _RP_DET_SLICES * W)
+    sl = _RP_MULTI_SLICES if kind == "multi" else (nblk if kind == "cls_head" else reduce_partials_slices(nblk))
+    return default, (sl if sl > 1 else 0), 0
+
+
+def _reduce_partials_multi(desc, items):
+    """the end-of-backward reduction of the parked partial sets: desc = device int64 [n][5] rows {partials, nblk, C, o1, o2} of `items`"""
+    ncb = [int(K.lib.lavt_reduce_partials_column_blocks(it[2])) for it in items]
+    if not deterministic():
+        K.check(K.lib.lavt_reduce_partials_multi(K.ptr(desc), len(items), sum(ncb), K.stream()))
+        return
+    for i in range(0, len(items), 64):          # the compact deterministic launch takes <= 64 sets: rows i .. i + 63 of the table
+        n, cb = len(items[i:i + 64]), sum(ncb[i:i + 64])
+        (entry,), _, nstage = reduce_partials_plan("multi", 0, 0, True, column_blocks=cb)
+        stage = _scratch(nstage, desc.device)
+        K.check(getattr(K.lib, entry)(K.ptr(desc[i:i + 64]), n, cb, K.ptr(stage), stage.numel(), K.stream()))
+
+
+def _ln_bwd_now(dy, x, gather, gamma, beta, mean, rstd, dx, xn, dg, db, dres, rows, Cn):
+    """LayerNorm backward whose gamma / beta sums are reduced at once (not parked in ln_deferred) and ADDED into dg / db; xn (with beta): the LayerNorm
+    output is written on the way.  Deterministic mode: the partial-sum launch + lavt_reduce_partials_det (row slices stored, then added in slice order)
+    instead of lavt_layernorm_bwd(_xn), whose row slices meet in dg / db through atomics from 48 row blocks on."""
+    dt = K.dt(x.dtype)
+    nparts = int(K.lib.lavt_layernorm_bwd_blocks(dt, rows, Cn)) * 2 * Cn
+    if not deterministic():
+        ws = _scratch(nparts, x.device)     # (without it the kernel falls back to same-address atomics)
+        if xn is not None:
+            K.check(K.lib.lavt_layernorm_bwd_xn(dt, K.ptr(dy), K.ptr(x), K.ptr(gamma), K.ptr(beta), K.ptr(mean), K.ptr(rstd), K.ptr(dx), K.ptr(xn),
+                                                K.ptr(dg), K.ptr(db), K.ptr(ws), ws.numel(), K.ptr(dres), rows, Cn, K.stream()))
+        else:
+            K.check(K.lib.lavt_layernorm_bwd(dt, K.ptr(dy), K.ptr(x), K.ptr(gather), K.ptr(gamma), K.ptr(mean), K.ptr(rstd),
+                                             K.ptr(dx), K.ptr(dg), K.ptr(db), K.ptr(ws), ws.numel(), K.ptr(dres), rows, Cn, K.stream()))
+        return
+    _, _, nstage = reduce_partials_plan("layernorm_xn" if xn is not None else "layernorm", nparts // (2 * Cn), 2 * Cn, True)
+    ws = _scratch(nparts + nstage, x.device)
+    parts, stage = ws[:nparts], ws[nparts:]
+    if xn is not None:
+        K.check(K.lib.lavt_layernorm_bwd_partial_xn(dt, K.ptr(dy), K.ptr(x), K.ptr(gamma), K.ptr(beta), K.ptr(mean), K.ptr(rstd), K.ptr(dx), K.ptr(xn),
+                                                    K.ptr(parts), parts.numel(), K.ptr(dres), rows, Cn, K.stream()))
+    else:
+        K.check(K.lib.lavt_layernorm_bwd_partial(dt, K.ptr(dy), K.ptr(x), K.ptr(gather), K.ptr(gamma), K.ptr(mean), K.ptr(rstd), K.ptr(dx), K.ptr(parts), parts.numel(),
+                                                 K.ptr(dres), rows, Cn, K.stream()))
+    K.check(K.lib.lavt_reduce_partials_det(K.ptr(parts), nparts // (2 * Cn), 2 * Cn, Cn, K.ptr(dg), K.ptr(db), K.ptr(stage), stage.numel(), K.stream()))
 
 
 def _launch_ln_partial(rider):
@@ -858,7 +947,7 @@ class _LnDeferred:
                     raise RuntimeError("deferred LayerNorm reductions: the step being captured differs from the warm-up steps (descriptor table would need a host copy)")
                 self.desc = torch.tensor(self.items, dtype=torch.int64).to(self.arena.device)
                 self.desc_key = key
-            K.check(K.lib.lavt_reduce_partials_multi(K.ptr(self.desc), len(self.items), sum(int(K.lib.lavt_reduce_partials_column_blocks(it[2])) for it in self.items), K.stream()))
+            _reduce_partials_multi(self.desc, self.items)
         params = self.params
         self.items, self.params, self.off = [], [], 0
         for p in params:
@@ -1234,9 +1323,7 @@ class _LnMlp(torch.autograd.Function):
                 g_g = g_be = None
                 done = True
         if not done:
-            wsl = _scratch(int(K.lib.lavt_layernorm_bwd_blocks(K.dt(dtype), M, Cin)) * 2 * Cin, dev)
-            K.check(K.lib.lavt_layernorm_bwd_xn(K.dt(dtype), K.ptr(dxn), K.ptr(x), K.ptr(_f32(gamma)), K.ptr(_f32(beta)), K.ptr(st[0]), K.ptr(st[1]), K.ptr(dx), K.ptr(xn),
-                                                K.ptr(dg), K.ptr(db), K.ptr(wsl), wsl.numel(), K.ptr(dy), M, Cin, K.stream()))
+            _ln_bwd_now(dxn, x, None, _f32(gamma), _f32(beta), st[0], st[1], dx, xn, dg, db, dy, M, Cin)
             g_g, g_be = sinks.done(gamma, dg, gs), sinks.done(beta, db, bs_)
         dw1, db1, dw2, db2 = _mlp_wgrads(dtype, o, w1=w1, b1=b1, dpre=dpre, x1=xn, w2=w2, b2=b2, dy=dy, h=h)
         return dx, g_g, g_be, dw1, db1, dw2, db2, None, None
@@ -1305,9 +1392,7 @@ class _LayerNorm(torch.autograd.Function):
                 _ln_bwd_partial(dy, x, _f32(gamma), mean, rstd, dx, wsd, dres, ctx.rows, ctx.C, gather=gather)
                 ln_deferred.add(wsd, nblk, ctx.C, dg, db, (gamma, beta))
                 return dx, None, None, None, None, None, None, None
-        ws = _scratch(int(K.lib.lavt_layernorm_bwd_blocks(K.dt(x.dtype), ctx.rows, ctx.C)) * 2 * ctx.C, x.device)     # (without it the kernel falls back to same-address atomics)
-        K.check(K.lib.lavt_layernorm_bwd(K.dt(x.dtype), K.ptr(dy), K.ptr(x), K.ptr(gather), K.ptr(_f32(gamma)), K.ptr(mean), K.ptr(rstd),
-                                         K.ptr(dx), K.ptr(dg), K.ptr(db), K.ptr(ws), ws.numel(), K.ptr(dres), ctx.rows, ctx.C, K.stream()))
+        _ln_bwd_now(dy, x, gather, _f32(gamma), None, mean, rstd, dx, None, dg, db, dres, ctx.rows, ctx.C)
         return dx, sinks.done(gamma, dg, gs), sinks.done(beta, db, bs), None, None, None, None, None
 
 
@@ -1368,14 +1453,19 @@ class _WindowAttn(torch.autograd.Function):
         wd, wh, ww = win
         dout = dout.contiguous()
         dqkv = torch.empty_like(qkv)
-        nws = int(K.lib.lavt_window_attn_bwd_ws(K.dt(qkv.dtype), nwin, N, heads, ld, wd, wh, ww))
+        det = deterministic()
+        nws = int((K.lib.lavt_window_attn_bwd_det_ws if det else K.lib.lavt_window_attn_bwd_ws)(K.dt(qkv.dtype), nwin, N, heads, ld, wd, wh, ww))
         ws = torch.empty(nws, dtype=torch.float32, device=qkv.device) if nws > 0 else None                      # dS slabs + table histograms
         R = (2 * wd - 1) * (2 * wh - 1) * (2 * ww - 1)
         dtable, ts = sinks.buf(table, (R, heads))
         pieces = int(K.lib.lavt_window_attn_bwd_pieces(K.dt(qkv.dtype), nwin, N, heads, ld)) if (ts and ln_deferred.active()) else 0
         parts = ln_deferred.alloc(pieces * heads * R, qkv.device) if pieces > 0 else None
         _note(f"wattn-bwd {nwin * N}x{Cc} N{N}", 10.0 * nwin * heads * N * N * 32)
-        if parts is not None and ws is not None:
+        if det:          # the table gradient gathered (bf16) / reduced from per-window dS slabs (fp32): no atomics, no chained or rider binning
+            K.check(K.lib.lavt_window_attn_bwd_det(K.dt(qkv.dtype), K.ptr(qkv), K.ptr(dense), ld, K.ptr(region), nw_img, K.ptr(out), K.ptr(dout),
+                                                   K.ptr(lse), K.ptr(dqkv), K.ptr(_f32(table)), None if parts is not None else K.ptr(dtable), K.ptr(ws),
+                                                   ws.numel(), K.ptr(parts), wd, wh, ww, nwin, N, heads, Cc // heads, scale, K.stream()))
+        elif parts is not None and ws is not None:
             dtable_chain.launch(qkv.dtype, qkv, ld, region, nw_img, out, dout, lse, dqkv, table, ws, parts, wd, wh, ww, nwin, N, heads, Cc // heads, scale)
         else:
             K.check(K.lib.lavt_window_attn_bwd(K.dt(qkv.dtype), K.ptr(qkv), K.ptr(dense), ld, K.ptr(region), nw_img, K.ptr(out), K.ptr(dout),
@@ -1542,7 +1632,11 @@ class _WmsaFused(torch.autograd.Function):
         pieces = int(K.lib.lavt_window_attn_bwd_pieces(K.dt(dtype), nwin, N, heads, ld)) if (ts and ln_deferred.active()) else 0
         parts = ln_deferred.alloc(pieces * heads * R, dev) if pieces > 0 else None
         _note(f"wattn-bwd {Mw}x{Cc} N{N}", 10.0 * nwin * heads * N * N * 32)
-        if parts is not None and wsb is not None:
+        if deterministic():          # (as _WindowAttn.backward: the gather form of the table gradient)
+            K.check(K.lib.lavt_window_attn_bwd_det(K.dt(dtype), K.ptr(qkv), None, ld, K.ptr(region), nw_img, K.ptr(out), K.ptr(dout), K.ptr(lse), K.ptr(dqkv), K.ptr(_f32(table)),
+                                                   None if parts is not None else K.ptr(dtable), K.ptr(wsb), wsb.numel(), K.ptr(parts), 1, ws_, ws_,
+                                                   nwin, N, heads, Cc // heads, scale, K.stream()))
+        elif parts is not None and wsb is not None:
             dtable_chain.launch(dtype, qkv, ld, region, nw_img, out, dout, lse, dqkv, table, wsb, parts, 1, ws_, ws_, nwin, N, heads, Cc // heads, scale)
         else:
             K.check(K.lib.lavt_window_attn_bwd(K.dt(dtype), K.ptr(qkv), None, ld, K.ptr(region), nw_img, K.ptr(out), K.ptr(dout), K.ptr(lse), K.ptr(dqkv), K.ptr(_f32(table)),
@@ -1608,9 +1702,7 @@ class _WmsaFused(torch.autograd.Function):
             ln_deferred.add(wsd, nblk, Cc, dg, db, (gamma, beta))
             g_g = g_be = None
         else:
-            wsl = _scratch(int(K.lib.lavt_layernorm_bwd_blocks(K.dt(dtype), M, Cc)) * 2 * Cc, dev)
-            K.check(K.lib.lavt_layernorm_bwd(K.dt(dtype), K.ptr(dxn), K.ptr(x), None, K.ptr(_f32(gamma)), K.ptr(st[0]), K.ptr(st[1]), K.ptr(dx), K.ptr(dg), K.ptr(db),
-                                             K.ptr(wsl), wsl.numel(), K.ptr(dres), M, Cc, K.stream()))
+            _ln_bwd_now(dxn, x, None, _f32(gamma), None, st[0], st[1], dx, None, dg, db, dres, M, Cc)
             g_g, g_be = sinks.done(gamma, dg, gs), sinks.done(beta, db, bs_)
         return dx, g_g, g_be, g_w, g_b, g_table, None, None, None, None, None, None
 
@@ -1649,6 +1741,13 @@ def window_attention(qkv, table, region, win, heads, N=None):
 
 
 # ------------------------------------------------------------------------------------------ Instance / Batch norm
+def _norm_bwd_stats(W):
+    """the column sums of a norm backward over rows of W = groups * 2 * C partial floats: -> (entry point, its scratch).  Deterministic mode adds the row
+    blocks in a fixed order (reduce_partials_plan): the scratch holds the stage behind the <= 1024 block sums."""
+    (entry,), _, nstage = reduce_partials_plan("norm_stats", 1024, W, deterministic())
+    return getattr(K.lib, entry), 1025 * W + nstage
+
+
 def _stats(x, groups, rows, Cc):
     s = torch.empty(2, groups, Cc, dtype=torch.float32, device=x.device)       # cleared by the kernel (two-stage form)
     ws = _scratch(1025 * groups * 2 * Cc, x.device)
@@ -1683,8 +1782,9 @@ class _InstanceNorm(torch.autograd.Function):
         dy = dy.contiguous()
         s = torch.empty(2, B, Cc, dtype=torch.float32, device=x.device)         # cleared by lavt_norm_bwd_stats (two-stage form)
         d = K.dt(x.dtype)
-        ws = _scratch(1025 * B * 2 * Cc, x.device)
-        K.check(K.lib.lavt_norm_bwd_stats(d, K.ptr(dy), K.ptr(x), None, K.ptr(mean), K.ptr(rstd), None, None, K.ptr(mul), 0,
+        bwd_stats, nws = _norm_bwd_stats(B * 2 * Cc)
+        ws = _scratch(nws, x.device)
+        K.check(bwd_stats(d, K.ptr(dy), K.ptr(x), None, K.ptr(mean), K.ptr(rstd), None, None, K.ptr(mul), 0,
                                           K.ptr(s[0]), K.ptr(s[1]), K.ptr(ws), ws.numel(), B, T, Cc, K.stream()))
         dx = torch.empty_like(x)
         dmul = torch.empty_like(x) if mul is not None else None
@@ -1766,7 +1866,10 @@ class StepContext:
     see the context of the thread that called `backward()` inside the `with` block (and that thread is blocked meanwhile).  Harnesses in private contexts
     can therefore alternate freely, but two host threads must not run forward / backward passes at the same time."""
 
-    def __init__(self):
+    def __init__(self, deterministic=None):
+        # deterministic: None = LAVT_DETERMINISTIC.  Decided here, before the first launch: every float-atomic site asks ops.deterministic(), and a captured
+        # launch sequence keeps the forms it was captured with
+        self.deterministic = _runtime.deterministic() if deterministic is None else bool(deterministic)
         self.weights = _WeightCache()
         self.fp8 = _Fp8State()
         self.sinks = _GradSinks()
@@ -1801,6 +1904,12 @@ def default_context():
 
 def current_context():
     return _ctx
+
+
+def deterministic() -> bool:
+    """Is the current context in deterministic mode (DESIGN.md "Deterministic mode")?  THE question of every site that has a float-atomic form: it then
+    takes the atomic-free sibling -- lent scratch, a fixed-order second stage, a gather instead of a scatter -- or raises NotImplementedError."""
+    return _ctx.deterministic
 
 
 def use_context(ctx):
@@ -1880,8 +1989,9 @@ class _HipBnKernels:
         if out is None:
             s = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
             out = (s[0], s[1])
-        ws = _scratch(1025 * 2 * Cc, x.device)
-        K.check(K.lib.lavt_norm_bwd_stats(K.dt(x.dtype), K.ptr(dy), K.ptr(x), K.ptr(y), K.ptr(mean), K.ptr(rstd), K.ptr(_f32(gamma)), K.ptr(_f32(beta)),
+        bwd_stats, nws = _norm_bwd_stats(2 * Cc)
+        ws = _scratch(nws, x.device)
+        K.check(bwd_stats(K.dt(x.dtype), K.ptr(dy), K.ptr(x), K.ptr(y), K.ptr(mean), K.ptr(rstd), K.ptr(_f32(gamma)), K.ptr(_f32(beta)),
                                           None, 1, K.ptr(out[0]), K.ptr(out[1]), K.ptr(ws), ws.numel(), 1, R, Cc, K.stream()))
         return out
 
@@ -2346,7 +2456,7 @@ class _BertEmbed(torch.autograd.Function):
         dw, ws = sinks.buf(word, tuple(word.shape))
         dp, ps = sinks.buf(pos, tuple(pos.shape))
         dt_, ts = sinks.buf(typ, tuple(typ.shape))
-        K.check(K.lib.lavt_bert_embed_bwd(K.dt(dy.dtype), K.ptr(dy), K.ptr(ids), K.ptr(tt), K.ptr(dw), K.ptr(dp), K.ptr(dt_), ids.numel(), ctx.N,
+        K.check((K.lib.lavt_bert_embed_bwd_det if deterministic() else K.lib.lavt_bert_embed_bwd)(K.dt(dy.dtype), K.ptr(dy), K.ptr(ids), K.ptr(tt), K.ptr(dw), K.ptr(dp), K.ptr(dt_), ids.numel(), ctx.N,
                                           word.shape[1], K.stream()))
         return None, None, sinks.done(word, dw, ws), sinks.done(pos, dp, ps), sinks.done(typ, dt_, ts), None, None
 
@@ -2859,6 +2969,14 @@ class _ClsHead(torch.autograd.Function):
                 ln_deferred.add(pw, nblk, Cc, dw[0], dw[1], (weight,))
                 ln_deferred.add(pb, nblk, 1, db[0:1], db[1:2], (bias,))
                 return dx, None, None
+        if deterministic():          # always the records form: per-workgroup sums, added in a fixed order (lavt_cls_head_bwd adds them through atomics)
+            nblk = int(K.lib.lavt_cls_head_bwd_blocks(K.dt(x.dtype), R, Cc))
+            pw, pb = _scratch(nblk * 2 * Cc, x.device), _scratch(nblk * 2, x.device)
+            stage = _scratch(reduce_partials_plan("cls_head", nblk, 2 * Cc, True)[2], x.device)
+            K.check(K.lib.lavt_cls_head_bwd_partial(K.dt(x.dtype), K.ptr(x), K.ptr(dy), K.ptr(_f32(weight)), K.ptr(dx), K.ptr(pw), K.ptr(pb), R, Cc, K.stream()))
+            K.check(K.lib.lavt_reduce_partials_det(K.ptr(pw), nblk, 2 * Cc, Cc, K.ptr(dw[0]), K.ptr(dw[1]), K.ptr(stage), stage.numel(), K.stream()))
+            K.check(K.lib.lavt_reduce_partials_det(K.ptr(pb), nblk, 2, 1, K.ptr(db[0:1]), K.ptr(db[1:2]), K.ptr(stage), stage.numel(), K.stream()))
+            return dx, sinks.done(weight, dw, wsink), sinks.done(bias, db, bsink)
         K.check(K.lib.lavt_cls_head_bwd(K.dt(x.dtype), K.ptr(x), K.ptr(dy), K.ptr(_f32(weight)), K.ptr(dx), K.ptr(dw), K.ptr(db), R, Cc, K.stream()))
         return dx, sinks.done(weight, dw, wsink), sinks.done(bias, db, bsink)
 

@@ -1,4 +1,4 @@
-"""Process-wide switches of the HIP path (compute dtype)."""
+"""Process-wide switches of the HIP path (compute dtype, fp8, deterministic mode)."""
 import contextlib
 import os
 import warnings
@@ -55,6 +55,13 @@ def compute_dtype() -> torch.dtype:
 def fp8_enabled() -> bool:
     """BASELINE.json configs[4]: e4m3 weights / activations on the CDNA4 fp8 MFMA for the forward contractions (bf16 everywhere else)."""
     return _state["fp8"] and _state["dtype"] == torch.bfloat16
+
+
+def deterministic() -> bool:
+    """LAVT_DETERMINISTIC=1: the mode a new ops.StepContext (and engine.TrainStep) starts in when not told otherwise -- every kernel with a float-atomic
+    form is replaced by its atomic-free sibling, so two runs from identical state give identical bits (DESIGN.md "Deterministic mode").  Default 0:
+    the atomic forms are the faster ones."""
+    return os.environ.get("LAVT_DETERMINISTIC", "0") == "1"
 
 
 @contextlib.contextmanager
