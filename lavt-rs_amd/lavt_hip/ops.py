@@ -698,6 +698,11 @@ def assign_partials(items, device):
                 off += nf
 
 
+def _ln_bwd_note(x, rows, Cn, dres, xn):
+    """profiler note of a LayerNorm-backward launch: dy, x and dx, plus the residual gradient and the LayerNorm output where the launch has them"""
+    _note(f"ln-bwd {rows}x{Cn}", nbytes=(3.0 + (dres is not None) + (xn is not None)) * rows * Cn * x.element_size())
+
+
 def _ln_bwd_partial(dy, x, gamma, mean, rstd, dx, wsd, dres, rows, Cn, gather=None, beta=None, xn=None, carry=True):
     """LayerNorm backward in its partial-sum form: dx (+ dres) now, the per-workgroup sums of the gamma / beta gradients into the arena slice `wsd`
     (ln_deferred reduces them at the end of backward).  With `xn` (and beta) the kernel also writes the LayerNorm output (_LnMlp: its forward never
@@ -705,6 +710,7 @@ def _ln_bwd_partial(dy, x, gamma, mean, rstd, dx, wsd, dres, rows, Cn, gather=No
     extra workgroups (the chained kernel has no gather form); the library answers 1 and launches nothing when this geometry has no rider form: the
     job stays pending and the LayerNorm goes alone."""
     dt = K.dt(x.dtype)
+    _ln_bwd_note(x, rows, Cn, dres, xn)
     job = dtable_chain.take_for_layernorm() if carry and gather is None else None
     if job is not None:
         rc = K.lib.lavt_layernorm_bwd_partial_xn_dtable(dt, K.ptr(dy), K.ptr(x), K.ptr(gamma), K.ptr(beta), K.ptr(mean), K.ptr(rstd), K.ptr(dx), K.ptr(xn),
@@ -771,6 +777,7 @@ def _ln_bwd_now(dy, x, gather, gamma, beta, mean, rstd, dx, xn, dg, db, dres, ro
     nparts = int(K.lib.lavt_layernorm_bwd_blocks(dt, rows, Cn)) * 2 * Cn
     if not deterministic():
         ws = _scratch(nparts, x.device)     # (without it the kernel falls back to same-address atomics)
+        _ln_bwd_note(x, rows, Cn, dres, xn)
         if xn is not None:
             K.check(K.lib.lavt_layernorm_bwd_xn(dt, K.ptr(dy), K.ptr(x), K.ptr(gamma), K.ptr(beta), K.ptr(mean), K.ptr(rstd), K.ptr(dx), K.ptr(xn),
                                                 K.ptr(dg), K.ptr(db), K.ptr(ws), ws.numel(), K.ptr(dres), rows, Cn, K.stream()))
@@ -781,18 +788,50 @@ def _ln_bwd_now(dy, x, gather, gamma, beta, mean, rstd, dx, xn, dg, db, dres, ro
     _, _, nstage = reduce_partials_plan("layernorm_xn" if xn is not None else "layernorm", nparts // (2 * Cn), 2 * Cn, True)
     ws = _scratch(nparts + nstage, x.device)
     parts, stage = ws[:nparts], ws[nparts:]
-    if xn is not None:
-        K.check(K.lib.lavt_layernorm_bwd_partial_xn(dt, K.ptr(dy), K.ptr(x), K.ptr(gamma), K.ptr(beta), K.ptr(mean), K.ptr(rstd), K.ptr(dx), K.ptr(xn),
-                                                    K.ptr(parts), parts.numel(), K.ptr(dres), rows, Cn, K.stream()))
-    else:
-        K.check(K.lib.lavt_layernorm_bwd_partial(dt, K.ptr(dy), K.ptr(x), K.ptr(gather), K.ptr(gamma), K.ptr(mean), K.ptr(rstd), K.ptr(dx), K.ptr(parts), parts.numel(),
-                                                 K.ptr(dres), rows, Cn, K.stream()))
+    _ln_bwd_partial(dy, x, gamma, mean, rstd, dx, parts, dres, rows, Cn, gather=gather, beta=beta, xn=xn, carry=False)      # (this path never carries a table-gradient job)
     K.check(K.lib.lavt_reduce_partials_det(K.ptr(parts), nparts // (2 * Cn), 2 * Cn, Cn, K.ptr(dg), K.ptr(db), K.ptr(stage), stage.numel(), K.stream()))
 
 
 def _launch_ln_partial(rider):
     """a rider (_WgradQueue.add) that did not ride: its LayerNorm backward as a launch of its own"""
     _ln_bwd_partial(*rider, carry=False)
+
+
+class _LnBwd:
+    """The hand-off of a LayerNorm backward's gamma / beta gradients, for every node that has one (_LayerNorm, _LnMlp, _WmsaFused).  The constructor
+    DECIDES: each parameter is fetched from sinks.buf once, and the partial sums are parked in ln_deferred's arena iff both targets are sinks, the step
+    harness is active and the arena has nblk * 2 * C floats left.  `rider` is then the ten-field tuple _WgradQueue.add(rider=) expects (the positional
+    arguments of _ln_bwd_partial), else None.  close() COMPLETES: parked -- the partial-sum launch (unless the rider rode on a grouped launch), the
+    arena slice registered with ln_deferred, None for both gradients; otherwise the launch that reduces at once and what sinks.done says.
+    xn (with beta) as in _ln_bwd_partial / _ln_bwd_now."""
+
+    def __init__(self, dy, x, gamma, beta, mean, rstd, dx, dres, rows, Cn, gather=None, xn=None):
+        self.gamma, self.beta, self.gather, self.xn = gamma, beta, gather, xn
+        self.dg, self.gs = sinks.buf(gamma, (Cn,))
+        self.db, self.bs = sinks.buf(beta, (Cn,))
+        self.nblk, wsd = 0, None
+        if self.gs and self.bs and ln_deferred.active():
+            self.nblk = int(K.lib.lavt_layernorm_bwd_blocks(K.dt(x.dtype), rows, Cn))
+            wsd = ln_deferred.alloc(self.nblk * 2 * Cn, x.device)
+        self.args = (dy, x, _f32(gamma), mean, rstd, dx, wsd, dres, rows, Cn)
+        self.rider = self.args if wsd is not None else None
+
+    def close(self, rode=False, carry=True):
+        """-> the values backward returns for gamma and beta.  carry: _ln_bwd_partial's (a launch that follows a grouped launch carries no job)"""
+        dy, x, g, mean, rstd, dx, wsd, dres, rows, Cn = self.args
+        bt = _f32(self.beta) if self.xn is not None else None
+        if wsd is None:
+            _ln_bwd_now(dy, x, self.gather, g, bt, mean, rstd, dx, self.xn, self.dg, self.db, dres, rows, Cn)
+            return sinks.done(self.gamma, self.dg, self.gs), sinks.done(self.beta, self.db, self.bs)
+        if not rode:
+            _ln_bwd_partial(*self.args, gather=self.gather, beta=bt, xn=self.xn, carry=carry)
+        ln_deferred.add(wsd, self.nblk, Cn, self.dg, self.db, (self.gamma, self.beta))
+        return None, None
+
+
+def _ln_bwd(*args, **kw):
+    """decision and completion in one call (the nodes whose LayerNorm backward is a launch of its own)"""
+    return _LnBwd(*args, **kw).close()
 
 
 class _WgradQueue:
@@ -1309,22 +1348,8 @@ class _LnMlp(torch.autograd.Function):
         # LayerNorm backward: dx = LN'(dxn) + dy (the residual branch), xn written on the way
         dx = torch.empty_like(x)
         xn = torch.empty_like(x)
-        dg, gs = sinks.buf(gamma, (Cin,))
-        db, bs_ = sinks.buf(beta, (Cin,))
-        done = False
-        _note(f"ln-bwd {M}x{Cin}", nbytes=5.0 * M * Cin * x.element_size())
-        if gs and bs_ and ln_deferred.active():
-            nblk = int(K.lib.lavt_layernorm_bwd_blocks(K.dt(dtype), M, Cin))
-            wsd = ln_deferred.alloc(nblk * 2 * Cin, dev)
-            if wsd is not None:
-                # the job this launch carries, if any: the binning of the attention backward issued a few launches ago
-                _ln_bwd_partial(dxn, x, _f32(gamma), st[0], st[1], dx, wsd, dy, M, Cin, beta=_f32(beta), xn=xn)
-                ln_deferred.add(wsd, nblk, Cin, dg, db, (gamma, beta))
-                g_g = g_be = None
-                done = True
-        if not done:
-            _ln_bwd_now(dxn, x, None, _f32(gamma), _f32(beta), st[0], st[1], dx, xn, dg, db, dy, M, Cin)
-            g_g, g_be = sinks.done(gamma, dg, gs), sinks.done(beta, db, bs_)
+        # (parked: the job this launch carries, if any, is the binning of the attention backward issued a few launches ago)
+        g_g, g_be = _ln_bwd(dxn, x, gamma, beta, st[0], st[1], dx, dy, M, Cin, xn=xn)
         dw1, db1, dw2, db2 = _mlp_wgrads(dtype, o, w1=w1, b1=b1, dpre=dpre, x1=xn, w2=w2, b2=b2, dy=dy, h=h)
         return dx, g_g, g_be, dw1, db1, dw2, db2, None, None
 
@@ -1381,19 +1406,9 @@ class _LayerNorm(torch.autograd.Function):
         if dres is not None:
             dres = dres.contiguous()
         dx = torch.empty_like(x)
-        dg, gs = sinks.buf(gamma, (ctx.C,))
-        db, bs = sinks.buf(beta, (ctx.C,))
-        if gs and bs and ln_deferred.active():
-            nblk = int(K.lib.lavt_layernorm_bwd_blocks(K.dt(x.dtype), ctx.rows, ctx.C))
-            wsd = ln_deferred.alloc(nblk * 2 * ctx.C, x.device)
-            if wsd is not None:
-                _note(f"ln-bwd {ctx.rows}x{ctx.C}", nbytes=(4.0 if dres is not None else 3.0) * ctx.rows * ctx.C * x.element_size())
-                # the job this launch carries, if any: the last one of a backward pass, at the patch embedding's norm
-                _ln_bwd_partial(dy, x, _f32(gamma), mean, rstd, dx, wsd, dres, ctx.rows, ctx.C, gather=gather)
-                ln_deferred.add(wsd, nblk, ctx.C, dg, db, (gamma, beta))
-                return dx, None, None, None, None, None, None, None
-        _ln_bwd_now(dy, x, gather, _f32(gamma), None, mean, rstd, dx, None, dg, db, dres, ctx.rows, ctx.C)
-        return dx, sinks.done(gamma, dg, gs), sinks.done(beta, db, bs), None, None, None, None, None
+        # (parked: the job this launch carries, if any, is the last one of a backward pass, at the patch embedding's norm)
+        g_g, g_be = _ln_bwd(dy, x, gamma, beta, mean, rstd, dx, dres, ctx.rows, ctx.C, gather=gather)
+        return dx, g_g, g_be, None, None, None, None, None
 
 
 def layer_norm(x, gamma, beta, eps=1e-5, gather=None):
@@ -1416,6 +1431,40 @@ def _win3(win):
 
 FUSED_ATTN_MAX_N = 160          # exact-fp32 fused kernels: one window's K/V (and P for backward) up to 12x12 = 144 (+pad) tokens
 FUSED_ATTN_MAX_N_BF16 = 400     # bf16 MFMA kernels: Q/K/V(/dO) of a whole window in LDS up to 25 key tiles (Video-Swin 8x7x7 = 392 tokens)
+
+
+def _wattn_core_bwd(qkv, dense, region, nw_img, out, lse, dout, table, ld, win, nwin, N, heads, Cc, scale):
+    """Backward of the fused window-attention core, for both nodes that have one (_WindowAttn; _WmsaFused, whose forward kernel leaves the same qkv / out /
+    lse: dense = None, win = (1, ws, ws)) -> (dqkv, the value backward returns for the bias table).  Under the step harness the table gradient's
+    per-workgroup histograms are parked in ln_deferred's arena and finished with the other layers' at the end of backward (None is returned); the
+    binning of the dS slabs is then chained onto a later launch (dtable_chain) where the kernel leaves slabs.  Deterministic mode: the table gradient
+    gathered (bf16) / reduced from per-window dS slabs (fp32) -- no atomics, no chained or rider binning; its scratch is lavt_window_attn_bwd_det_ws
+    for every caller (for bf16, all the fused node computes in, the two queries agree: tests/test_deterministic_host.py)."""
+    wd, wh, ww = win
+    dt, dev = K.dt(qkv.dtype), qkv.device
+    dout = dout.contiguous()
+    dqkv = torch.empty_like(qkv)
+    det = deterministic()
+    nws = int((K.lib.lavt_window_attn_bwd_det_ws if det else K.lib.lavt_window_attn_bwd_ws)(dt, nwin, N, heads, ld, wd, wh, ww))
+    ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws > 0 else None                      # dS slabs + table histograms
+    R = (2 * wd - 1) * (2 * wh - 1) * (2 * ww - 1)
+    dtable, ts = sinks.buf(table, (R, heads))
+    pieces = int(K.lib.lavt_window_attn_bwd_pieces(dt, nwin, N, heads, ld)) if (ts and ln_deferred.active()) else 0
+    parts = ln_deferred.alloc(pieces * heads * R, dev) if pieces > 0 else None
+    args = (dt, K.ptr(qkv), K.ptr(dense), ld, K.ptr(region), nw_img, K.ptr(out), K.ptr(dout), K.ptr(lse), K.ptr(dqkv), K.ptr(_f32(table)),
+            None if parts is not None else K.ptr(dtable), K.ptr(ws), ws.numel() if ws is not None else 0, K.ptr(parts), wd, wh, ww, nwin, N, heads,
+            Cc // heads, scale, K.stream())
+    _note(f"wattn-bwd {nwin * N}x{Cc} N{N}", 10.0 * nwin * heads * N * N * 32)
+    if det:
+        K.check(K.lib.lavt_window_attn_bwd_det(*args))
+    elif parts is not None and ws is not None:
+        dtable_chain.launch(qkv.dtype, qkv, ld, region, nw_img, out, dout, lse, dqkv, table, ws, parts, wd, wh, ww, nwin, N, heads, Cc // heads, scale)
+    else:
+        K.check(K.lib.lavt_window_attn_bwd(*args))
+    if parts is not None:          # table gradient finished with the other layers' in one launch at the end of backward
+        ln_deferred.add_table(parts, pieces, heads, R, dtable, table)
+        return dqkv, None
+    return dqkv, sinks.done(table, dtable, ts)
 
 
 @K.scoped
@@ -1450,31 +1499,8 @@ class _WindowAttn(torch.autograd.Function):
     def backward(ctx, dout):
         qkv, dense, region, out, lse, table = ctx.saved_tensors
         win, heads, nwin, N, Cc, nw_img, scale, ld = ctx.dims
-        wd, wh, ww = win
-        dout = dout.contiguous()
-        dqkv = torch.empty_like(qkv)
-        det = deterministic()
-        nws = int((K.lib.lavt_window_attn_bwd_det_ws if det else K.lib.lavt_window_attn_bwd_ws)(K.dt(qkv.dtype), nwin, N, heads, ld, wd, wh, ww))
-        ws = torch.empty(nws, dtype=torch.float32, device=qkv.device) if nws > 0 else None                      # dS slabs + table histograms
-        R = (2 * wd - 1) * (2 * wh - 1) * (2 * ww - 1)
-        dtable, ts = sinks.buf(table, (R, heads))
-        pieces = int(K.lib.lavt_window_attn_bwd_pieces(K.dt(qkv.dtype), nwin, N, heads, ld)) if (ts and ln_deferred.active()) else 0
-        parts = ln_deferred.alloc(pieces * heads * R, qkv.device) if pieces > 0 else None
-        _note(f"wattn-bwd {nwin * N}x{Cc} N{N}", 10.0 * nwin * heads * N * N * 32)
-        if det:          # the table gradient gathered (bf16) / reduced from per-window dS slabs (fp32): no atomics, no chained or rider binning
-            K.check(K.lib.lavt_window_attn_bwd_det(K.dt(qkv.dtype), K.ptr(qkv), K.ptr(dense), ld, K.ptr(region), nw_img, K.ptr(out), K.ptr(dout),
-                                                   K.ptr(lse), K.ptr(dqkv), K.ptr(_f32(table)), None if parts is not None else K.ptr(dtable), K.ptr(ws),
-                                                   ws.numel(), K.ptr(parts), wd, wh, ww, nwin, N, heads, Cc // heads, scale, K.stream()))
-        elif parts is not None and ws is not None:
-            dtable_chain.launch(qkv.dtype, qkv, ld, region, nw_img, out, dout, lse, dqkv, table, ws, parts, wd, wh, ww, nwin, N, heads, Cc // heads, scale)
-        else:
-            K.check(K.lib.lavt_window_attn_bwd(K.dt(qkv.dtype), K.ptr(qkv), K.ptr(dense), ld, K.ptr(region), nw_img, K.ptr(out), K.ptr(dout),
-                                               K.ptr(lse), K.ptr(dqkv), K.ptr(_f32(table)), None if parts is not None else K.ptr(dtable), K.ptr(ws),
-                                               ws.numel() if ws is not None else 0, K.ptr(parts), wd, wh, ww, nwin, N, heads, Cc // heads, scale, K.stream()))
-        if parts is not None:          # table gradient finished with the other layers' in one launch at the end of backward
-            ln_deferred.add_table(parts, pieces, heads, R, dtable, table)
-            return dqkv, None, None, None, None, None
-        return dqkv, sinks.done(table, dtable, ts), None, None, None, None
+        dqkv, g_table = _wattn_core_bwd(qkv, dense, region, nw_img, out, lse, dout, table, ld, win, nwin, N, heads, Cc, scale)
+        return dqkv, g_table, None, None, None, None
 
 
 @K.scoped
@@ -1622,31 +1648,7 @@ class _WmsaFused(torch.autograd.Function):
         dtype, dev = x.dtype, x.device
         M = x.shape[0]
         ld = 64 if N <= 64 else 160
-        # ---- attention core (as _WindowAttn.backward) ----
-        dout = dout.contiguous()
-        dqkv = torch.empty_like(qkv)
-        nws = int(K.lib.lavt_window_attn_bwd_ws(K.dt(dtype), nwin, N, heads, ld, 1, ws_, ws_))
-        wsb = torch.empty(nws, dtype=torch.float32, device=dev) if nws > 0 else None
-        R = (2 * ws_ - 1) * (2 * ws_ - 1)
-        dtable, ts = sinks.buf(table, (R, heads))
-        pieces = int(K.lib.lavt_window_attn_bwd_pieces(K.dt(dtype), nwin, N, heads, ld)) if (ts and ln_deferred.active()) else 0
-        parts = ln_deferred.alloc(pieces * heads * R, dev) if pieces > 0 else None
-        _note(f"wattn-bwd {Mw}x{Cc} N{N}", 10.0 * nwin * heads * N * N * 32)
-        if deterministic():          # (as _WindowAttn.backward: the gather form of the table gradient)
-            K.check(K.lib.lavt_window_attn_bwd_det(K.dt(dtype), K.ptr(qkv), None, ld, K.ptr(region), nw_img, K.ptr(out), K.ptr(dout), K.ptr(lse), K.ptr(dqkv), K.ptr(_f32(table)),
-                                                   None if parts is not None else K.ptr(dtable), K.ptr(wsb), wsb.numel(), K.ptr(parts), 1, ws_, ws_,
-                                                   nwin, N, heads, Cc // heads, scale, K.stream()))
-        elif parts is not None and wsb is not None:
-            dtable_chain.launch(dtype, qkv, ld, region, nw_img, out, dout, lse, dqkv, table, wsb, parts, 1, ws_, ws_, nwin, N, heads, Cc // heads, scale)
-        else:
-            K.check(K.lib.lavt_window_attn_bwd(K.dt(dtype), K.ptr(qkv), None, ld, K.ptr(region), nw_img, K.ptr(out), K.ptr(dout), K.ptr(lse), K.ptr(dqkv), K.ptr(_f32(table)),
-                                               None if parts is not None else K.ptr(dtable), K.ptr(wsb), wsb.numel() if wsb is not None else 0, K.ptr(parts), 1, ws_, ws_,
-                                               nwin, N, heads, Cc // heads, scale, K.stream()))
-        if parts is not None:
-            ln_deferred.add_table(parts, pieces, heads, R, dtable, table)
-            g_table = None
-        else:
-            g_table = sinks.done(table, dtable, ts)
+        dqkv, g_table = _wattn_core_bwd(qkv, None, region, nw_img, out, lse, dout, table, ld, (1, ws_, ws_), nwin, N, heads, Cc, scale)
         # ---- qkv projection: data gradient scattered back to token order, weight / bias gradient over the windowed rows ----
         Wc = weights.get(wq, dtype, "lin")
         dxn = torch.empty_like(x)
@@ -1662,14 +1664,7 @@ class _WmsaFused(torch.autograd.Function):
         if dres is not None:
             dres = dres.contiguous()
         dx = torch.empty_like(x)
-        dg, gs = sinks.buf(gamma, (Cc,))
-        db, bs_ = sinks.buf(beta, (Cc,))
-        rider, nblk, wsd = None, 0, None
-        if gs and bs_ and ln_deferred.active():
-            nblk = int(K.lib.lavt_layernorm_bwd_blocks(K.dt(dtype), M, Cc))
-            wsd = ln_deferred.alloc(nblk * 2 * Cc, dev)
-            if wsd is not None:
-                rider = (dxn, x, _f32(gamma), st[0], st[1], dx, wsd, dres, M, Cc)
+        ln = _LnBwd(dxn, x, gamma, beta, st[0], st[1], dx, dres, M, Cc)
         # ---- qkv weight / bias gradient (not _linear_wgrad: two members, the LayerNorm rider, and notify BEFORE queueing because the member closes the group) ----
         wbuf, wsink = sinks.buf(wq, (3 * Cc, Cc))
         bbuf, bsink = sinks.buf(bq, (3 * Cc,))
@@ -1683,27 +1678,19 @@ class _WmsaFused(torch.autograd.Function):
             wgrads.notify(wq)          # (before the member is queued: it closes the group, and the flush reports what has been notified)
             wgrads.notify(bq)
             gemm_tn(dtype, 3 * Cc, 8, padrows.numel(), dqkv, 3 * Cc, zp, 0, dummy, 8, a_rowmap=padrows, colsum=bbuf, colsum_atomic=True, defer=wgrads, extra=True)
-            gemm_tn(dtype, 3 * Cc, Cc, M, dqkv, 3 * Cc, xn, Cc, wbuf, Cc, a_rowmap=inv, colsum=bbuf, colsum_atomic=True, defer=wgrads, rider=rider)
-            rode = rider is not None
+            gemm_tn(dtype, 3 * Cc, Cc, M, dqkv, 3 * Cc, xn, Cc, wbuf, Cc, a_rowmap=inv, colsum=bbuf, colsum_atomic=True, defer=wgrads, rider=ln.rider)
+            rode = ln.rider is not None
             g_w = g_b = None
         elif wgrads.active() and wsink and bsink:
             wgrads.notify(wq)
             wgrads.notify(bq)
-            gemm_tn(dtype, 3 * Cc, Cc, Mw, dqkv, 3 * Cc, xn, Cc, wbuf, Cc, b_rowmap=wmap, colsum=bbuf, defer=wgrads, rider=rider)
-            rode = rider is not None
+            gemm_tn(dtype, 3 * Cc, Cc, Mw, dqkv, 3 * Cc, xn, Cc, wbuf, Cc, b_rowmap=wmap, colsum=bbuf, defer=wgrads, rider=ln.rider)
+            rode = ln.rider is not None
             g_w = g_b = None
         else:
             gemm_tn(dtype, 3 * Cc, Cc, Mw, dqkv, 3 * Cc, xn, Cc, wbuf, Cc, b_rowmap=wmap, colsum=bbuf)
             g_w, g_b = sinks.done(wq, wbuf, wsink), sinks.done(bq, bbuf, bsink)
-        if rider is not None:
-            if not rode:
-                _note(f"ln-bwd {M}x{Cc}", nbytes=(4.0 if dres is not None else 3.0) * M * Cc * x.element_size())
-                _launch_ln_partial(rider)
-            ln_deferred.add(wsd, nblk, Cc, dg, db, (gamma, beta))
-            g_g = g_be = None
-        else:
-            _ln_bwd_now(dxn, x, None, _f32(gamma), None, st[0], st[1], dx, None, dg, db, dres, M, Cc)
-            g_g, g_be = sinks.done(gamma, dg, gs), sinks.done(beta, db, bs_)
+        g_g, g_be = ln.close(rode=rode, carry=False)          # (a rider that did not ride is launched on its own, after the group it closed)
         return dx, g_g, g_be, g_w, g_b, g_table, None, None, None, None, None, None
 
 
@@ -2696,22 +2683,12 @@ class _ConvTaps(torch.autograd.Function):
                 ctx.fp8_x_amax = a_ptr          # the e4m3 copies stay alive for the weight gradient (half the bytes of the bf16 tensors beside them)
             else:
                 x1q = x2q = None
-        elif _conv_split(dtype, M, Cout, Cin, C1, C2, taps, bias, act)[0]:
-            # few pixels, long reduction (decoder level 4: 1 800 rows x K = 13 824 = 60-232 tiles walking 72-216 K tiles each): the reduction is cut
-            # at tap boundaries over the batch index into fp32 partial outputs, a second small kernel adds them
-            sp, over_ch = _conv_split(dtype, M, Cout, Cin, C1, C2, taps, bias, act)
-            parts = torch.empty(sp, M, Cout, dtype=torch.float32, device=x1.device)
-            if over_ch:
-                gemm_nt(dtype, M, Cout, taps * (Cin // sp), x1, C1, Wp, taps * Cin, parts, Cout, A2=x2, lda2=C2, a_split=C1, conv=(H, W, Cin, 0, D, kd, kh, kw),
-                        batch=sp, strideC=M * Cout, c_f32=True, conv_kc_split=Cin // sp)
-            else:
-                gemm_nt(dtype, M, Cout, (taps // sp) * Cin, x1, C1, Wp, taps * Cin, parts, Cout, A2=x2, lda2=C2, a_split=C1, conv=(H, W, Cin, 0, D, kd, kh, kw),
-                        batch=sp, strideB=(taps // sp) * Cin, strideC=M * Cout, c_f32=True, conv_tap_split=taps // sp)
-            K.check(K.lib.lavt_splitk_reduce(K.dt(dtype), K.ptr(parts), sp, M, Cout, K.ptr(y), Cout, K.stream()))
         else:
-            st = gemm_nt(dtype, M, Cout, taps * Cin, x1, C1, Wp, taps * Cin, y, Cout, A2=x2, lda2=C2, a_split=C1,
-                         conv=(H, W, Cin, 0, D, kd, kh, kw), bias=_f32(bias), act=act, Cpre=pre, ldcpre=Cout,
-                         want_colstats=stats and bias is None and act == K.ACT_NONE)
+            # few pixels, long reduction (decoder level 4: 1 800 rows x K = 13 824 = 60-232 tiles walking 72-216 K tiles each): _conv_split cuts the
+            # reduction (_conv_contract); a split launch carries no epilogue and leaves no column statistics
+            st = _conv_contract(dtype, _conv_split(dtype, M, Cout, Cin, C1, C2, taps, bias, act), M, Cout, Cin, taps, x1, C1, Wp, taps * Cin, y,
+                                (H, W, Cin, 0, D, kd, kh, kw), bias=_f32(bias), act=act, A2=x2, lda2=C2, a_split=C1, Cpre=pre, ldcpre=Cout,
+                                want_colstats=stats and bias is None and act == K.ACT_NONE)
             if st is not None:
                 conv_stats.put(y, st)
         ctx.save_for_backward(x1, x2, weight, bias, pre, x1q if ctx.fp8_x_amax else None, x2q if ctx.fp8_x_amax else None)
@@ -2746,37 +2723,23 @@ class _ConvTaps(torch.autograd.Function):
                 for dxo, Cn, roff in ((dx1, C1, 0),) + (((dx2, C2, C1),) if x2 is not None else ()):
                     gemm_nt(torch.uint8, M, Cn, taps * Cout, dyq, Cout, WqT, taps * Cout, dxo, Cn, conv=(H, W, Cout, 1, D, kd, kh, kw),
                             b_off=roff * taps * Cout, deq=(a_ptr, w_amax.data_ptr()))
-            elif x2 is not None and C1 % 256 == 0 and C2 % 64 == 0 and dtype == torch.bfloat16:
-                # concat convolution (conv1_2: 512 + 128 input channels): N = 640 is not a multiple of the 256-wide tile, so the whole data gradient
-                # fell back to 128x128 tiles (239 us at 2x120x120).  As two launches over column blocks of the packed weight the 512-channel part
-                # runs on the 256x256 tile and the skip part on its own.
-                for dxo, Cn, boff in ((dx1, C1, 0), (dx2, C2, C1)):
-                    sp, over_ch = _conv_split(dtype, M, Cn, Cout, Cout, 0, taps, None, K.ACT_NONE)
-                    if sp:
-                        parts = torch.empty(sp, M, Cn, dtype=torch.float32, device=dy.device)
-                        if over_ch:
-                            gemm_nt(dtype, M, Cn, taps * (Cout // sp), dy, Cout, Wp, taps * Cin, parts, Cn, conv=(H, W, Cout, 1, D, kd, kh, kw), b_kmajor=True,
-                                    b_tap_stride=Cin, b_off=boff, batch=sp, strideC=M * Cn, c_f32=True, conv_kc_split=Cout // sp)
-                        else:
-                            gemm_nt(dtype, M, Cn, (taps // sp) * Cout, dy, Cout, Wp, taps * Cin, parts, Cn, conv=(H, W, Cout, 1, D, kd, kh, kw), b_kmajor=True,
-                                    b_tap_stride=Cin, b_off=boff, batch=sp, strideC=M * Cn, c_f32=True, conv_tap_split=taps // sp)
-                        K.check(K.lib.lavt_splitk_reduce(K.dt(dtype), K.ptr(parts), sp, M, Cn, K.ptr(dxo), Cn, K.stream()))
-                    else:
-                        gemm_nt(dtype, M, Cn, taps * Cout, dy, Cout, Wp, taps * Cin, dxo, Cn, conv=(H, W, Cout, 1, D, kd, kh, kw), b_kmajor=True, b_tap_stride=Cin,
-                                b_off=boff)
-            elif x2 is None and _conv_split(dtype, M, Cin, Cout, Cout, 0, taps, None, K.ACT_NONE)[0]:
-                sp, over_ch = _conv_split(dtype, M, Cin, Cout, Cout, 0, taps, None, K.ACT_NONE)
-                parts = torch.empty(sp, M, Cin, dtype=torch.float32, device=dy.device)
-                if over_ch:
-                    gemm_nt(dtype, M, Cin, taps * (Cout // sp), dy, Cout, Wp, taps * Cin, parts, Cin, conv=(H, W, Cout, 1, D, kd, kh, kw), b_kmajor=True,
-                            b_tap_stride=Cin, batch=sp, strideC=M * Cin, c_f32=True, conv_kc_split=Cout // sp)
-                else:
-                    gemm_nt(dtype, M, Cin, (taps // sp) * Cout, dy, Cout, Wp, taps * Cin, parts, Cin, conv=(H, W, Cout, 1, D, kd, kh, kw), b_kmajor=True,
-                            b_tap_stride=Cin, batch=sp, strideC=M * Cin, c_f32=True, conv_tap_split=taps // sp)
-                K.check(K.lib.lavt_splitk_reduce(K.dt(dtype), K.ptr(parts), sp, M, Cin, K.ptr(dx1), Cin, K.stream()))
             else:
-                gemm_nt(dtype, M, Cin, taps * Cout, dy, Cout, Wp, taps * Cin, dx1, C1, conv=(H, W, Cout, 1, D, kd, kh, kw), b_kmajor=True,
-                        b_tap_stride=Cin, C2=dx2, ldc2=C2, c_split=C1)
+                blocks = ()
+                if x2 is not None and C1 % 256 == 0 and C2 % 64 == 0 and dtype == torch.bfloat16:
+                    # concat convolution (conv1_2: 512 + 128 input channels): N = 640 is not a multiple of the 256-wide tile, so the whole data gradient
+                    # fell back to 128x128 tiles (239 us at 2x120x120).  As two launches over column blocks of the packed weight the 512-channel part
+                    # runs on the 256x256 tile and the skip part on its own.
+                    blocks = ((dx1, C1, 0), (dx2, C2, C1))
+                elif x2 is None:
+                    blocks = ((dx1, Cin, 0),)
+                splits = [_conv_split(dtype, M, Cn, Cout, Cout, 0, taps, None, K.ACT_NONE) for _, Cn, _ in blocks]
+                if len(blocks) == 2 or (blocks and splits[0][0]):          # (a single source goes through here only where its reduction is cut)
+                    for (dxo, Cn, boff), split in zip(blocks, splits):
+                        _conv_contract(dtype, split, M, Cn, Cout, taps, dy, Cout, Wp, taps * Cin, dxo, (H, W, Cout, 1, D, kd, kh, kw), b_kmajor=True,
+                                       b_tap_stride=Cin, b_off=boff)
+                else:
+                    gemm_nt(dtype, M, Cin, taps * Cout, dy, Cout, Wp, taps * Cin, dx1, C1, conv=(H, W, Cout, 1, D, kd, kh, kw), b_kmajor=True,
+                            b_tap_stride=Cin, C2=dx2, ldc2=C2, c_split=C1)
         dW, wsink = sinks.buf(weight, (Cout, Cin * taps))
         db = bsink = None
         if bias is not None:
@@ -2860,6 +2823,33 @@ def _kc_pieces(M, N, Kc):
     return best if best and tiles * best > min(tiles * 3, 256) * 0.9 else 0          # (not worse filled than the 3 tap groups it replaces)
 
 
+def _conv_contract(dtype, split, M, N, Kc, taps, A, lda, Wp, ldb, out, conv, *, bias=None, act=K.ACT_NONE, b_kmajor=False, **nt):
+    """out[M, N] = the convolution contraction of A over taps x Kc channels with the packed weight Wp (rows of ldb elements), its reduction cut where
+    _conv_split said: split = that function's answer (pieces, over_channels), asked by the caller once.  Not split: ONE gemm_nt with the epilogue (bias, act
+    and nt's Cpre / ldcpre / want_colstats) -> what it returns (the column statistics, if it left any).  Split: ONE gemm_nt over batch = pieces into fp32
+    partial outputs [pieces, M, N] -- channel blocks (conv_kc_split) or tap groups (conv_tap_split; in the weight-major layout a group's weights start
+    strideB further on, in the k-major one the kernel finds them through b_tap_stride) -- with no epilogue and no statistics, then lavt_splitk_reduce, or
+    lavt_splitk_reduce_epi where there is a bias or an activation to apply -> None.
+    Weight-major callers (forward, folded forward) pass A2 / lda2 / a_split in nt; k-major ones (the data gradient onto the column block of N channels
+    at b_off) b_kmajor=True, b_tap_stride and b_off."""
+    sp, over_ch = split
+    if not sp:
+        return gemm_nt(dtype, M, N, taps * Kc, A, lda, Wp, ldb, out, N, conv=conv, bias=bias, act=act, b_kmajor=b_kmajor, **nt)
+    for k in ("Cpre", "ldcpre", "want_colstats"):
+        nt.pop(k, None)
+    parts = torch.empty(sp, M, N, dtype=torch.float32, device=A.device)
+    if over_ch:
+        gemm_nt(dtype, M, N, taps * (Kc // sp), A, lda, Wp, ldb, parts, N, conv=conv, b_kmajor=b_kmajor, batch=sp, strideC=M * N, c_f32=True,
+                conv_kc_split=Kc // sp, **nt)
+    else:
+        gemm_nt(dtype, M, N, (taps // sp) * Kc, A, lda, Wp, ldb, parts, N, conv=conv, b_kmajor=b_kmajor, batch=sp, strideB=0 if b_kmajor else (taps // sp) * Kc,
+                strideC=M * N, c_f32=True, conv_tap_split=taps // sp, **nt)
+    if bias is not None or act != K.ACT_NONE:
+        K.check(K.lib.lavt_splitk_reduce_epi(K.dt(dtype), K.ptr(parts), sp, M, N, K.ptr(bias), act, K.ptr(out), N, K.stream()))
+    else:
+        K.check(K.lib.lavt_splitk_reduce(K.dt(dtype), K.ptr(parts), sp, M, N, K.ptr(out), N, K.stream()))
+
+
 def conv3x3(x1, x2, weight, B, H, W):
     # under autograd (training) the launch also leaves the column statistics of its output for the BatchNorm that follows (ops.conv_stats)
     return _ConvTaps.apply(x1, x2, weight, None, B, 1, H, W, K.ACT_NONE, torch.is_grad_enabled())
@@ -2887,19 +2877,8 @@ def conv3x3_bn_relu_folded(x1, x2, conv, bn, B, H, W):
     Wp, bias = weights.get_bnfold(weight, bn, dtype)
     M = B * H * W
     y = torch.empty(M, Cout, dtype=dtype, device=x1.device)
-    geom = (H, W, Cin, 0, 1, 1, kh, kw)
-    sp, over_ch = _conv_split(dtype, M, Cout, Cin, C1, C2, taps, bias, K.ACT_RELU, epilogue_in_reduce=True)
-    if sp:
-        parts = torch.empty(sp, M, Cout, dtype=torch.float32, device=x1.device)
-        if over_ch:
-            gemm_nt(dtype, M, Cout, taps * (Cin // sp), x1, C1, Wp, taps * Cin, parts, Cout, A2=x2, lda2=C2, a_split=C1, conv=geom,
-                    batch=sp, strideC=M * Cout, c_f32=True, conv_kc_split=Cin // sp)
-        else:
-            gemm_nt(dtype, M, Cout, (taps // sp) * Cin, x1, C1, Wp, taps * Cin, parts, Cout, A2=x2, lda2=C2, a_split=C1, conv=geom,
-                    batch=sp, strideB=(taps // sp) * Cin, strideC=M * Cout, c_f32=True, conv_tap_split=taps // sp)
-        K.check(K.lib.lavt_splitk_reduce_epi(K.dt(dtype), K.ptr(parts), sp, M, Cout, K.ptr(bias), K.ACT_RELU, K.ptr(y), Cout, K.stream()))
-    else:
-        gemm_nt(dtype, M, Cout, taps * Cin, x1, C1, Wp, taps * Cin, y, Cout, A2=x2, lda2=C2, a_split=C1, conv=geom, bias=bias, act=K.ACT_RELU)
+    _conv_contract(dtype, _conv_split(dtype, M, Cout, Cin, C1, C2, taps, bias, K.ACT_RELU, epilogue_in_reduce=True), M, Cout, Cin, taps, x1, C1, Wp, taps * Cin, y,
+                   (H, W, Cin, 0, 1, 1, kh, kw), bias=bias, act=K.ACT_RELU, A2=x2, lda2=C2, a_split=C1)
     return y
 
 
@@ -3012,6 +2991,15 @@ def logits_upsample(x, B, Hi, Wi, Ho, Wo):
 
 
 # ------------------------------------------------------------------------------------------ fused upsample + weighted CE (+ I/U counts)
+def _criterion_entry(crit, which, sel):
+    """The entry point of pass `which` ("fwd" | "bwd") of the fused criterion `crit` ("ce" | "dice" | "dice_boundary") and the arguments to insert
+    directly after x: lavt_upsample_<crit>_<which> and nothing without a frame selection; with one (see _frame_sel) the _sel_ form, whose prototype
+    is the plain one with (selection pointer, its length) after x -- for all six pairs (include/lavt_hip.h)."""
+    if sel is None:
+        return getattr(K.lib, f"lavt_upsample_{crit}_{which}"), ()
+    return getattr(K.lib, f"lavt_upsample_{crit}_sel_{which}"), (K.ptr(sel), sel.numel())
+
+
 @K.scoped
 class _UpsampleCE(torch.autograd.Function):
     """loss = F.cross_entropy(F.interpolate(y, (Ho, Wo), bilinear, align_corners=True), target, weight=(w0, w1)) on the low-resolution
@@ -3028,12 +3016,8 @@ class _UpsampleCE(torch.autograd.Function):
         assert target.dtype == torch.int64 and target.numel() == ns * Ho * Wo
         out4 = torch.empty(4, dtype=torch.float32, device=x.device)
         ws = _scratch(4 * 2048, x.device)
-        if sel is None:
-            K.check(K.lib.lavt_upsample_ce_fwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), float(w0), float(w1), K.ptr(ws), ws.numel(), K.ptr(out4),
-                                               B, Hi, Wi, Ho, Wo, K.stream()))
-        else:
-            K.check(K.lib.lavt_upsample_ce_sel_fwd(K.dt(x.dtype), K.ptr(x), K.ptr(sel), ns, K.ptr(target), float(w0), float(w1), K.ptr(ws), ws.numel(),
-                                                   K.ptr(out4), B, Hi, Wi, Ho, Wo, K.stream()))
+        entry, frames = _criterion_entry("ce", "fwd", sel)
+        K.check(entry(K.dt(x.dtype), K.ptr(x), *frames, K.ptr(target), float(w0), float(w1), K.ptr(ws), ws.numel(), K.ptr(out4), B, Hi, Wi, Ho, Wo, K.stream()))
         ctx.sel = sel                            # (an index buffer, not a tensor autograd tracks: the backward reads what it holds THEN, as a replay does)
         ctx.dims = (B, Hi, Wi, Ho, Wo, float(w0), float(w1))
         ctx.set_materialize_grads(False)         # (the statistics receive no gradient: None instead of a zero fill per step)
@@ -3059,11 +3043,8 @@ class _UpsampleCE(torch.autograd.Function):
         if dloss is None:                        # (nothing downstream of the loss)
             return None, None, None, None, None, None, None, None, None, None
         dl = dloss.contiguous().float().reshape(1)
-        if ctx.sel is None:
-            K.check(K.lib.lavt_upsample_ce_bwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), w0, w1, K.ptr(out4), K.ptr(dl), K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
-        else:
-            K.check(K.lib.lavt_upsample_ce_sel_bwd(K.dt(x.dtype), K.ptr(x), K.ptr(ctx.sel), ctx.sel.numel(), K.ptr(target), w0, w1, K.ptr(out4), K.ptr(dl),
-                                                   K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
+        entry, frames = _criterion_entry("ce", "bwd", ctx.sel)
+        K.check(entry(K.dt(x.dtype), K.ptr(x), *frames, K.ptr(target), w0, w1, K.ptr(out4), K.ptr(dl), K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
         return dx, None, None, None, None, None, None, None, None, None
 
 
@@ -3081,8 +3062,6 @@ def _frame_sel(sel, B, what):
 
 
 def upsample_cross_entropy(x, target, B, Hi, Wi, Ho, Wo, weight=(0.9, 1.1), sel=None):
-    if sel is None:
-        return _UpsampleCE.apply(x, target, B, Hi, Wi, Ho, Wo, weight[0], weight[1])
     return _UpsampleCE.apply(x, target, B, Hi, Wi, Ho, Wo, weight[0], weight[1], _frame_sel(sel, B, "upsample_cross_entropy"))
 
 
@@ -3101,11 +3080,8 @@ class _UpsampleDice(torch.autograd.Function):
         assert target.dtype == torch.int64 and target.numel() == ns * Ho * Wo
         stats = torch.empty(2 + 6 * ns, dtype=torch.float32, device=x.device)
         ws = _scratch(6 * 256 * ns, x.device)
-        if sel is None:
-            K.check(K.lib.lavt_upsample_dice_fwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), K.ptr(ws), ws.numel(), K.ptr(stats), B, Hi, Wi, Ho, Wo, K.stream()))
-        else:
-            K.check(K.lib.lavt_upsample_dice_sel_fwd(K.dt(x.dtype), K.ptr(x), K.ptr(sel), ns, K.ptr(target), K.ptr(ws), ws.numel(), K.ptr(stats),
-                                                     B, Hi, Wi, Ho, Wo, K.stream()))
+        entry, frames = _criterion_entry("dice", "fwd", sel)
+        K.check(entry(K.dt(x.dtype), K.ptr(x), *frames, K.ptr(target), K.ptr(ws), ws.numel(), K.ptr(stats), B, Hi, Wi, Ho, Wo, K.stream()))
         ctx.sel = sel
         ctx.save_for_backward(x, target, stats)
         ctx.dims = (B, Hi, Wi, Ho, Wo)
@@ -3118,17 +3094,12 @@ class _UpsampleDice(torch.autograd.Function):
         B, Hi, Wi, Ho, Wo = ctx.dims
         dx = torch.empty_like(x)
         dl = dloss.contiguous().float().reshape(1)
-        if ctx.sel is None:
-            K.check(K.lib.lavt_upsample_dice_bwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), K.ptr(stats), K.ptr(dl), K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
-        else:
-            K.check(K.lib.lavt_upsample_dice_sel_bwd(K.dt(x.dtype), K.ptr(x), K.ptr(ctx.sel), ctx.sel.numel(), K.ptr(target), K.ptr(stats), K.ptr(dl),
-                                                     K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
+        entry, frames = _criterion_entry("dice", "bwd", ctx.sel)
+        K.check(entry(K.dt(x.dtype), K.ptr(x), *frames, K.ptr(target), K.ptr(stats), K.ptr(dl), K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
         return dx, None, None, None, None, None, None, None
 
 
 def upsample_dice_loss(x, target, B, Hi, Wi, Ho, Wo, sel=None):
-    if sel is None:
-        return _UpsampleDice.apply(x, target, B, Hi, Wi, Ho, Wo)
     return _UpsampleDice.apply(x, target, B, Hi, Wi, Ho, Wo, _frame_sel(sel, B, "upsample_dice_loss"))
 
 
@@ -3147,12 +3118,8 @@ class _UpsampleDiceBoundary(torch.autograd.Function):
         assert target.dtype == torch.int64 and target.numel() == ns * Ho * Wo
         stats = torch.empty(3 + 14 * ns, dtype=torch.float32, device=x.device)
         ws = _scratch(K.lib.lavt_upsample_dice_boundary_ws(ns, Ho, Wo), x.device)
-        if sel is None:
-            K.check(K.lib.lavt_upsample_dice_boundary_fwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), dice_rate, boundary_rate, K.ptr(ws), ws.numel(),
-                                                          K.ptr(stats), B, Hi, Wi, Ho, Wo, K.stream()))
-        else:
-            K.check(K.lib.lavt_upsample_dice_boundary_sel_fwd(K.dt(x.dtype), K.ptr(x), K.ptr(sel), ns, K.ptr(target), dice_rate, boundary_rate, K.ptr(ws),
-                                                              ws.numel(), K.ptr(stats), B, Hi, Wi, Ho, Wo, K.stream()))
+        entry, frames = _criterion_entry("dice_boundary", "fwd", sel)
+        K.check(entry(K.dt(x.dtype), K.ptr(x), *frames, K.ptr(target), dice_rate, boundary_rate, K.ptr(ws), ws.numel(), K.ptr(stats), B, Hi, Wi, Ho, Wo, K.stream()))
         ctx.sel = sel
         ctx.save_for_backward(x, target, stats)
         ctx.dims = (B, Hi, Wi, Ho, Wo, dice_rate, boundary_rate)
@@ -3167,18 +3134,13 @@ class _UpsampleDiceBoundary(torch.autograd.Function):
         dl = dloss.contiguous().float().reshape(1)
         ns = B if ctx.sel is None else ctx.sel.numel()
         ws = _scratch(K.lib.lavt_upsample_dice_boundary_ws(ns, Ho, Wo), x.device)          # (the dz map lives from launch A to launch B only)
-        if ctx.sel is None:
-            K.check(K.lib.lavt_upsample_dice_boundary_bwd(K.dt(x.dtype), K.ptr(x), K.ptr(target), dice_rate, boundary_rate, K.ptr(stats), K.ptr(dl), K.ptr(ws),
-                                                          ws.numel(), K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
-        else:
-            K.check(K.lib.lavt_upsample_dice_boundary_sel_bwd(K.dt(x.dtype), K.ptr(x), K.ptr(ctx.sel), ns, K.ptr(target), dice_rate, boundary_rate, K.ptr(stats),
-                                                              K.ptr(dl), K.ptr(ws), ws.numel(), K.ptr(dx), B, Hi, Wi, Ho, Wo, K.stream()))
+        entry, frames = _criterion_entry("dice_boundary", "bwd", ctx.sel)
+        K.check(entry(K.dt(x.dtype), K.ptr(x), *frames, K.ptr(target), dice_rate, boundary_rate, K.ptr(stats), K.ptr(dl), K.ptr(ws), ws.numel(), K.ptr(dx), B, Hi, Wi, Ho, Wo,
+                      K.stream()))
         return dx, None, None, None, None, None, None, None, None, None
 
 
 def upsample_dice_boundary_loss(x, target, B, Hi, Wi, Ho, Wo, sel=None, dice_rate=1.0, boundary_rate=0.05):
-    if sel is None:
-        return _UpsampleDiceBoundary.apply(x, target, B, Hi, Wi, Ho, Wo, float(dice_rate), float(boundary_rate))
     return _UpsampleDiceBoundary.apply(x, target, B, Hi, Wi, Ho, Wo, float(dice_rate), float(boundary_rate), _frame_sel(sel, B, "upsample_dice_boundary_loss"))
 
 

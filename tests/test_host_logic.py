@@ -509,6 +509,232 @@ def test_linear_wgrad_grouped_arguments_replace_the_launch_only_in_a_group(monke
             assert c.ready_is(c.w, c.b) and not ops.wgrads.pending
 
 
+class _LnCase:
+    """ops._LnBwd / ops._ln_bwd driven on the CPU: 7 rows x 8 channels, the two leaf launchers replaced by fakes that record their arguments, the
+    parking arena shrunk to `arena` floats"""
+    rows, C = 7, 8
+
+    def __init__(self, monkeypatch, ops, sink=True, enabled=True, arena=1 << 12):
+        g = torch.Generator().manual_seed(5)
+        self.ops, self.partial, self.now, self.ready = ops, [], [], []
+        self.gamma, self.beta = torch.nn.Parameter(torch.ones(self.C)), torch.nn.Parameter(torch.zeros(self.C))
+        if sink:
+            self.gamma.grad, self.beta.grad = torch.zeros(self.C), torch.zeros(self.C)
+            ops.sinks.set([self.gamma, self.beta], on_ready=self.ready.append)
+        ops.wgrads.enabled = enabled
+        monkeypatch.setattr(ops._LnDeferred, "ARENA_FLOATS", arena)
+        monkeypatch.setattr(ops, "_ln_bwd_partial", lambda *a, **kw: self.partial.append((a, kw)))
+        monkeypatch.setattr(ops, "_ln_bwd_now", lambda *a: self.now.append(a))
+        self.dy, self.x, self.dx, self.dres, self.xn = (torch.randn(self.rows, self.C, generator=g) for _ in range(5))
+        self.mean, self.rstd = torch.randn(self.rows, generator=g), torch.rand(self.rows, generator=g)
+        self.nblk = int(ops.K.lib.lavt_layernorm_bwd_blocks(ops.K.dt(torch.float32), self.rows, self.C))
+        assert self.nblk >= 1
+
+    def args(self):
+        return self.dy, self.x, self.gamma, self.beta, self.mean, self.rstd, self.dx, self.dres, self.rows, self.C
+
+    def is_rider(self, t, ws_floats):
+        """the ten fields _WgradQueue.add(rider=) / flush() unpack: (dy, x, gamma, mean, rstd, dx, ws, dres, rows, C)"""
+        dy_, x_, g_, mean_, rstd_, dx_, ws_, dres_, rows_, C_ = t
+        same = all(a is b for a, b in ((dy_, self.dy), (x_, self.x), (mean_, self.mean), (rstd_, self.rstd), (dx_, self.dx), (dres_, self.dres)))
+        return (same and g_.data_ptr() == self.gamma.data_ptr() and not g_.requires_grad and (rows_, C_) == (self.rows, self.C)
+                and ws_.numel() == ws_floats and ws_.dtype == torch.float32 and ws_.data_ptr() == self.ops.ln_deferred.arena.data_ptr())
+
+    def parked_row(self, ws):
+        return (ws.data_ptr(), self.nblk, self.C, self.gamma.grad.data_ptr(), self.beta.grad.data_ptr())
+
+
+def test_ln_handoff_without_sinks_reduces_at_once_and_returns_the_gradients(monkeypatch):
+    from lavt_hip import ops
+    with ops.use_context(ops.StepContext()):
+        c = _LnCase(monkeypatch, ops, sink=False)
+        g_g, g_b = ops._ln_bwd(*c.args())
+        assert not c.partial and len(c.now) == 1
+        dy, x, gather, gamma, beta, mean, rstd, dx, xn, dg, db, dres, rows, C = c.now[0]
+        assert dy is c.dy and x is c.x and gather is None and beta is None and xn is None and mean is c.mean and rstd is c.rstd and dx is c.dx and dres is c.dres
+        assert gamma.data_ptr() == c.gamma.data_ptr() and (rows, C) == (c.rows, c.C)
+        assert g_g.shape == g_b.shape == (c.C,) and g_g.data_ptr() == dg.data_ptr() and g_b.data_ptr() == db.data_ptr() and dg.data_ptr() != db.data_ptr()
+        assert not ops.ln_deferred.items and not ops.wgrads.pending
+
+
+def test_ln_handoff_into_sinks_parks_the_partial_sums(monkeypatch):
+    """sinks + the step harness: the partial-sum launcher gets an arena slice of nblk * 2 * C floats, ONE row lands in ln_deferred.items, both parameters
+    are pending (reported at the flush), backward returns None for both"""
+    from lavt_hip import ops
+    with ops.use_context(ops.StepContext()):
+        c = _LnCase(monkeypatch, ops)
+        assert ops._ln_bwd(*c.args()) == (None, None)
+        assert not c.now and len(c.partial) == 1
+        a, kw = c.partial[0]
+        assert c.is_rider(a, c.nblk * 2 * c.C) and kw == dict(gather=None, beta=None, xn=None, carry=True)
+        assert ops.ln_deferred.items == [c.parked_row(a[6])]
+        assert ops.wgrads.pending == {id(c.gamma), id(c.beta)} and not c.ready
+        assert ops.sinks.used == {id(c.gamma), id(c.beta)}
+
+
+@pytest.mark.parametrize("why", ["arena-too-small", "queue-off"])
+def test_ln_handoff_into_sinks_that_cannot_park_reports_each_parameter_once(monkeypatch, why):
+    from lavt_hip import ops
+    with ops.use_context(ops.StepContext()):
+        probe = _LnCase(monkeypatch, ops, sink=False)
+        c = _LnCase(monkeypatch, ops, enabled=why != "queue-off", arena=probe.nblk * 2 * probe.C - (1 if why == "arena-too-small" else 0))
+        assert ops._ln_bwd(*c.args()) == (None, None)
+        assert not c.partial and len(c.now) == 1
+        assert c.now[0][9].data_ptr() == c.gamma.grad.data_ptr() and c.now[0][10].data_ptr() == c.beta.grad.data_ptr()       # added straight into the sinks
+        assert len(c.ready) == 2 and c.ready[0] is c.gamma and c.ready[1] is c.beta
+        assert not ops.ln_deferred.items and not ops.wgrads.pending
+
+
+@pytest.mark.parametrize("sink", [False, True], ids=["immediate", "parked"])
+def test_ln_handoff_xn_form_passes_beta_and_xn_through(monkeypatch, sink):
+    from lavt_hip import ops
+    with ops.use_context(ops.StepContext()):
+        c = _LnCase(monkeypatch, ops, sink=sink)
+        gather = torch.zeros(c.rows, 4, dtype=torch.int32)
+        ops._ln_bwd(*c.args(), gather=gather, xn=c.xn)
+        if sink:
+            (a, kw), = c.partial
+            assert kw["xn"] is c.xn and kw["beta"].data_ptr() == c.beta.data_ptr() and not kw["beta"].requires_grad and kw["gather"] is gather and kw["carry"] is True
+        else:
+            (a,) = c.now
+            assert a[8] is c.xn and a[4].data_ptr() == c.beta.data_ptr() and not a[4].requires_grad and a[2] is gather
+
+
+def test_ln_handoff_rider_form(monkeypatch):
+    """_WmsaFused.backward's use: the decision hands out the rider, the node queues its weight gradients, the completion launches nothing when told the
+    rider rode -- and the partial-sum launch without a carried job when it did not.  Either way the arena slice is registered once."""
+    from lavt_hip import ops
+    for rode in (True, False):
+        with ops.use_context(ops.StepContext()):
+            c = _LnCase(monkeypatch, ops)
+            ln = ops._LnBwd(*c.args())
+            assert isinstance(ln.rider, tuple) and len(ln.rider) == 10 and c.is_rider(ln.rider, c.nblk * 2 * c.C)
+            assert not c.partial and not c.now and not ops.ln_deferred.items          # nothing launched or registered by the decision
+            assert ln.close(rode=rode, carry=False) == (None, None)
+            assert not c.now and ops.ln_deferred.items == [c.parked_row(ln.rider[6])] and ops.wgrads.pending == {id(c.gamma), id(c.beta)}
+            if rode:
+                assert not c.partial
+            else:
+                (a, kw), = c.partial
+                assert a == ln.rider and kw == dict(gather=None, beta=None, xn=None, carry=False)
+    with ops.use_context(ops.StepContext()):
+        c = _LnCase(monkeypatch, ops, sink=False)
+        ln = ops._LnBwd(*c.args())
+        assert ln.rider is None
+        g_g, g_b = ln.close(rode=False, carry=False)
+        assert len(c.now) == 1 and not c.partial and g_g.shape == (c.C,) and g_b.shape == (c.C,)
+
+
+class _ConvCase:
+    """ops._conv_contract driven on the CPU: a 3x3 convolution over 6 rows, ops.gemm_nt and the two reduction entry points replaced by recording fakes.
+    The expected keyword arguments are those of the launches _ConvTaps.forward / .backward and conv3x3_bn_relu_folded spelled out before the helper."""
+    M, N, taps = 6, 16, 9
+
+    def __init__(self, monkeypatch, ops):
+        self.ops, self.nt, self.reduce = ops, [], []
+        monkeypatch.setattr(ops, "gemm_nt", lambda *a, **kw: self.nt.append((a, kw)) or "stats")
+        monkeypatch.setattr(ops.K, "ptr", lambda t: None if t is None else t.data_ptr())
+        monkeypatch.setattr(ops.K, "stream", lambda: 0)
+        for name in ("lavt_splitk_reduce", "lavt_splitk_reduce_epi"):
+            monkeypatch.setattr(ops.K.lib, name, lambda *a, _n=name: self.reduce.append((_n, a)) or 0, raising=False)
+        self.out = torch.empty(self.M, self.N, dtype=torch.bfloat16)
+        self.geom = (2, 3, 128, 0, 1, 1, 3, 3)
+
+    def unset(self, kw, *names):
+        defaults = dict(batch=1, strideB=0, strideC=0, c_f32=False, conv_tap_split=0, conv_kc_split=0, b_off=0, b_tap_stride=0, A2=None, bias=None,
+                        act=self.ops.K.ACT_NONE, want_colstats=False, Cpre=None, b_kmajor=False)
+        return all(n not in kw or (not torch.is_tensor(kw[n]) and kw[n] == defaults[n]) for n in names)          # absent, or gemm_nt's default
+
+
+@pytest.mark.parametrize("split", [(0, False), (3, False), (2, True)], ids=["whole", "tap-groups", "channel-pieces"])
+@pytest.mark.parametrize("epilogue", [False, True], ids=["plain", "bias-relu"])
+def test_conv_contract_weight_major(monkeypatch, split, epilogue):
+    """forward / folded forward: A2 / lda2 / a_split reach every launch; the epilogue (and Cpre, the statistics request) only the unsplit one; the pieces
+    are summed by lavt_splitk_reduce, or by lavt_splitk_reduce_epi with the bias and the activation"""
+    from lavt_hip import ops
+    c = _ConvCase(monkeypatch, ops)
+    M, N, taps, Kc, C1, C2 = c.M, c.N, c.taps, 128, 64, 64
+    x1, x2, Wp = torch.empty(M, C1, dtype=torch.bfloat16), torch.empty(M, C2, dtype=torch.bfloat16), torch.empty(N, taps * Kc, dtype=torch.bfloat16)
+    bias, act = (torch.zeros(N), ops.K.ACT_RELU) if epilogue else (None, ops.K.ACT_NONE)
+    pre = torch.empty_like(c.out)
+    got = ops._conv_contract(torch.bfloat16, split, M, N, Kc, taps, x1, C1, Wp, taps * Kc, c.out, c.geom, bias=bias, act=act, A2=x2, lda2=C2, a_split=C1,
+                             Cpre=pre, ldcpre=N, want_colstats=True)
+    (a, kw), = c.nt
+    sp, over_ch = split
+    assert a[:2] == (torch.bfloat16, M) and a[2] == N and a[4] is x1 and a[5] == C1 and a[6] is Wp and a[7] == taps * Kc and a[9] == N
+    assert kw["A2"] is x2 and kw["lda2"] == C2 and kw["a_split"] == C1 and kw["conv"] == c.geom and c.unset(kw, "b_kmajor", "b_off", "b_tap_stride")
+    if not sp:
+        assert got == "stats" and a[3] == taps * Kc and a[8] is c.out and not c.reduce
+        assert kw["bias"] is bias and kw["act"] == act and kw["Cpre"] is pre and kw["ldcpre"] == N and kw["want_colstats"] is True
+        assert c.unset(kw, "batch", "strideB", "strideC", "c_f32", "conv_tap_split", "conv_kc_split")
+        return
+    parts = a[8]
+    assert got is None and parts.shape == (sp, M, N) and parts.dtype == torch.float32
+    assert kw["batch"] == sp and kw["strideC"] == M * N and kw["c_f32"] is True and c.unset(kw, "bias", "act", "want_colstats", "Cpre")
+    if over_ch:
+        assert a[3] == taps * (Kc // sp) == 576 and kw["conv_kc_split"] == Kc // sp == 64 and c.unset(kw, "conv_tap_split", "strideB")
+    else:
+        assert a[3] == (taps // sp) * Kc == 384 and kw["conv_tap_split"] == taps // sp == 3 and kw["strideB"] == (taps // sp) * Kc == 384 and c.unset(kw, "conv_kc_split")
+    (name, r), = c.reduce
+    head, tail = (ops.K.dt(torch.bfloat16), parts.data_ptr(), sp, M, N), (c.out.data_ptr(), N, 0)
+    if epilogue:
+        assert name == "lavt_splitk_reduce_epi" and r == head + (bias.data_ptr(), ops.K.ACT_RELU) + tail
+    else:
+        assert name == "lavt_splitk_reduce" and r == head + tail
+
+
+@pytest.mark.parametrize("split", [(0, False), (3, False), (2, True)], ids=["whole", "tap-groups", "channel-pieces"])
+def test_conv_contract_k_major_column_block(monkeypatch, split):
+    """the data gradient onto one column block of the packed weight [Cout][taps][Cin]: b_kmajor with the tap stride Cin and the block's offset in every
+    launch; tap groups need NO strideB in this layout; always the plain reduction"""
+    from lavt_hip import ops
+    c = _ConvCase(monkeypatch, ops)
+    M, N, taps, Cout, Cin, boff = c.M, c.N, c.taps, 128, 80, 64
+    dy, Wp = torch.empty(M, Cout, dtype=torch.bfloat16), torch.empty(Cout, taps * Cin, dtype=torch.bfloat16)
+    geom = (2, 3, Cout, 1, 1, 1, 3, 3)
+    got = ops._conv_contract(torch.bfloat16, split, M, N, Cout, taps, dy, Cout, Wp, taps * Cin, c.out, geom, b_kmajor=True, b_tap_stride=Cin, b_off=boff)
+    (a, kw), = c.nt
+    sp, over_ch = split
+    assert a[:3] == (torch.bfloat16, M, N) and a[4] is dy and a[5] == Cout and a[6] is Wp and a[7] == taps * Cin and a[9] == N
+    assert kw["b_kmajor"] is True and kw["b_tap_stride"] == Cin and kw["b_off"] == boff and kw["conv"] == geom
+    assert c.unset(kw, "A2", "bias", "act", "want_colstats", "Cpre", "strideB")
+    if not sp:
+        assert got == "stats" and a[3] == taps * Cout and a[8] is c.out and not c.reduce
+        assert c.unset(kw, "batch", "strideC", "c_f32", "conv_tap_split", "conv_kc_split")
+        return
+    parts = a[8]
+    assert got is None and parts.shape == (sp, M, N) and parts.dtype == torch.float32
+    assert kw["batch"] == sp and kw["strideC"] == M * N and kw["c_f32"] is True
+    if over_ch:
+        assert a[3] == taps * (Cout // sp) == 576 and kw["conv_kc_split"] == 64 and c.unset(kw, "conv_tap_split")
+    else:
+        assert a[3] == (taps // sp) * Cout == 384 and kw["conv_tap_split"] == 3 and c.unset(kw, "conv_kc_split")
+    assert c.reduce == [("lavt_splitk_reduce", (ops.K.dt(torch.bfloat16), parts.data_ptr(), sp, M, N, c.out.data_ptr(), N, 0))]
+
+
+@pytest.mark.parametrize("crit", ["ce", "dice", "dice_boundary"])
+@pytest.mark.parametrize("which", ["fwd", "bwd"])
+def test_criterion_entry_rule(monkeypatch, crit, which):
+    """every fused criterion pass has a plain and a _sel_ entry point, the second with (selection pointer, int32 length) directly after x; ops._criterion_entry
+    names exactly that entry point and inserts exactly those two arguments"""
+    import ctypes as C
+    from lavt_hip import _capi as K
+    from lavt_hip import ops
+    plain, sel = f"lavt_upsample_{crit}_{which}", f"lavt_upsample_{crit}_sel_{which}"
+    assert plain in K._PROTOTYPES and sel in K._PROTOTYPES
+    want = list(K._PROTOTYPES[plain])
+    want[2:2] = [C.c_void_p, C.c_int32]
+    assert K._PROTOTYPES[sel] == want
+
+    class _Names:
+        def __getattr__(self, name):
+            return name
+    monkeypatch.setattr(ops.K, "lib", _Names())
+    assert ops._criterion_entry(crit, which, None) == (plain, ())
+    frames = SimpleNamespace(is_cuda=True, data_ptr=lambda: 4096, numel=lambda: 3)
+    assert ops._criterion_entry(crit, which, frames) == (sel, (4096, 3))
+
+
 def test_syncbn_rank_statistics_combination():
     """SyncBN forward: the ranks' (sum, centred M2) pairs, gathered with ONE collective, combine to the statistics of the whole batch --
     also when the channel means are large compared with the spread (no E[x^2] - E[x]^2 cancellation)"""
