@@ -656,7 +656,11 @@ int lavt_adamw_step_chunks(const int64_t* desc, const float* hyper, const int32_
  * Control block `ctl`: device fp32[8], zero-initialised by the caller except ctl[1] = 1.
  *   [0] global L2 norm of the gradients        [1] clip coefficient the update multiplies every gradient by
  *   [2] skip: 1 = this update must not happen  [3] running count of skipped updates (incremented by the guarded update's tick)
- *   [4] hold: written by the HOST only; non-zero = the update does nothing and nothing is counted      [5..7] reserved, zero
+ *   [4] hold: written by the HOST only; non-zero = the update does nothing and nothing is counted
+ *   [5] accumulating: written by lavt_grad_accumulate; 1 = this micro-step does not end its accumulation cycle -- lavt_grad_norm and the guarded
+ *       updates then behave as under hold (no store, ctl[0..3] and the step counter untouched)
+ *   [6] micro index m of the accumulation cycle, 0 <= m < k: read by lavt_grad_accumulate, advanced by the guarded update's tick
+ *   [7] reserved, zero.   Without lavt_grad_accumulate [5] and [6] stay 0 and every entry point below computes what it computed before they existed.
  *
  * lavt_grad_norm: global L2 norm over the gradients listed by the desc / chunks tables of the chunked update above (so it covers exactly the
  * tensors the update touches), in two launches without atomics: one workgroup per chunk writes an fp32 sum of squares to ws[chunk], one
@@ -666,7 +670,7 @@ int lavt_adamw_step_chunks(const int64_t* desc, const float* hyper, const int32_
  * A chunk's fp32 sum of squares that overflows for finite gradients (|g| ~ 1e19 and beyond) makes the norm Inf: that counts as non-finite.
  * ws: device scratch of lavt_grad_norm_ws floats; the formula is part of the interface:  ws floats = nchunks  (one partial per chunk).
  *
- * lavt_adamw_step_chunks_guarded: the chunked update with every gradient multiplied by ctl[1]; if ctl[2] != 0 or ctl[4] != 0 every workgroup
+ * lavt_adamw_step_chunks_guarded: the chunked update with every gradient multiplied by ctl[1]; if ctl[2] != 0 or ctl[4] != 0 (or ctl[5] != 0) every workgroup
  * returns before its first store (parameters, both moments and the bf16 `copy` column stay untouched) and the step counter does not advance;
  * ctl[3] += ctl[2] unless on hold (hence the non-const pointer).  With ctl[1] = 1, ctl[2] = ctl[4] = 0 the result equals the unguarded
  * update's bit for bit (one shared update body). */
@@ -684,6 +688,18 @@ int lavt_adamw_step_chunks_guarded(const int64_t* desc, const float* hyper, cons
  * on skip or hold nothing is stored (x included), the step counter does not advance, and ctl[3] += ctl[2] unless on hold (hence non-const). */
 int lavt_adamw_step_chunks_amsgrad(const int64_t* desc, const int64_t* vmax, const float* hyper, const int32_t* chunks, int nchunks, float* step, float total_steps,
                                    float power, float* ctl /* NULL: unguarded */, void* stream);
+/* Gradient accumulation over k micro-batches (a new symbol under ABI v7): fold the flat fp32 gradient g [n] of one micro-batch into the accumulation
+ * buffer acc [n] (no overlap with g) and keep the phase of the cycle in the control block above, all on the device.  With s = 1/k (fp32) and
+ * m = ctl[6]:
+ *   ctl[4] != 0 (hold): nothing is read or written -- acc, ctl[5] and ctl[6] keep their bits;
+ *   otherwise  acc[i] = (m == 0) ? s * g[i] : fmaf(s, g[i], acc[i])  -- the first micro-step of a cycle SELECTS: acc is not read, so it needs no
+ *   zero fill and a NaN / Inf left by an earlier cycle cannot survive -- and then ctl[5] = (m != k - 1).
+ * One streaming launch, no atomics, bitwise reproducible; float4 accesses when both bases are 16-byte aligned, element by element otherwise and for
+ * the n % 4 tail.  m itself is advanced -- m = (m + 1) % k, not under hold -- by the tick of the guarded update that follows in the same step
+ * (lavt_adamw_step_chunks_guarded, lavt_adamw_step_chunks_amsgrad with ctl), after every kernel of that step has read the phase: the sequence of
+ * one micro-step is  lavt_grad_accumulate -> [lavt_grad_norm over acc] -> guarded update over acc.  On the k-th micro-step of a cycle ctl[5] = 0 and
+ * norm, clip, non-finite skip and update act on acc = the mean of the k gradients; on the others they do nothing.  1 <= k <= 2^20. */
+int lavt_grad_accumulate(const float* g, float* acc, int64_t n, int k, float* ctl, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Inference path (csrc/infer.hip; reference test.py:60-110 and test_ytvos.py:230-260: batch-1 forward under model.eval() / torch.no_grad(), argmax,

@@ -11,7 +11,7 @@ constexpr int ADAMW_CE = 8192;            // elements per chunk: 256 threads x 2
 // non-zero `copy` is the parameter's bf16 compute copy in the same layout (Linear / 1x1 weights), written from the registers that hold the
 // updated value -- the separate re-cast pass (a second read of every parameter) disappears.
 // GUARD: ctl is the fp32[8] control block of lavt_grad_norm (wave-uniform, read once per workgroup): the workgroup returns before its first
-// store when ctl[2] (skip) or ctl[4] (hold) is set, and gradients are scaled by ctl[1] (the clip coefficient; x * 1.0f is exact, so a
+// store when ctl[2] (skip), ctl[4] (hold) or ctl[5] (accumulating: lavt_grad_accumulate, this micro-step does not end its cycle) is set, and gradients are scaled by ctl[1] (the clip coefficient; x * 1.0f is exact, so a
 // coefficient of 1 gives the unguarded bits).
 // AMSGRAD: a fifth fp32 stream x = max_exp_avg_sq, addressed by vmax: int64 [count], one pointer per desc row (desc keeps its six columns: the norm
 // kernel and the plain entry points read that layout).  torch.optim.AdamW(amsgrad=True), single-tensor form: x = max(x, v) with the UNcorrected v
@@ -22,7 +22,7 @@ __device__ __forceinline__ void adamw_chunk_update(const int64_t* __restrict__ d
                                                    const float* __restrict__ ctl) {
     float coef = 1.f;
     if constexpr (GUARD) {
-        if (ctl[2] != 0.f || ctl[4] != 0.f) return;
+        if (ctl[2] != 0.f || ctl[4] != 0.f || ctl[5] != 0.f) return;
         coef = ctl[1];
     }
     const int2 ch = chunks[blockIdx.x];

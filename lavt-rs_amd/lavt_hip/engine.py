@@ -3,8 +3,16 @@
     zero grads -> out = model(image, l, l_mask) -> F.cross_entropy(out, target, weight=[0.9, 1.1]) -> backward
     -> gradient all-reduce (world > 1)
 
-Gradient accumulation over micro-batches is not supported by this harness (every parameter receives exactly one weight gradient per
-step into a buffer zeroed at the start of the step; lavt_hip.ops.sinks refuses a second one).
+Gradient accumulation over micro-batches: TrainStep(accumulate=k) with an owned optimizer.  Every call of step() is one MICRO-step on whatever the
+static buffers hold: its body is the one above, unchanged (every parameter still receives exactly one weight gradient per micro-step into a buffer
+zeroed at its start; lavt_hip.ops.sinks still refuses a second one), then lavt_grad_accumulate folds the flat gradient, times 1/k, into a second
+flat buffer (`acc`) and the optimizer's guarded kernels read `acc`.  The phase of the cycle lives on the device (FusedAdamW.guard[5:7]): ONE captured
+graph serves all k micro-steps -- replays 1 .. k-1 leave parameters, moments, compute copies and the step counter bit for bit alone, replay k applies
+one AdamW update from the mean of the k gradients (clip and non-finite skip act on that mean) and ticks the schedule once.  Per micro-step, as in
+PyTorch under accumulation: BatchNorm normalises with (and its running statistics follow) each micro-batch's own statistics, DropPath draws new
+masks, the fp8 |max| history advances; step() returns, and `stats` holds, that micro-batch's loss.  world > 1: the buckets are all-reduced in
+every micro-step (correct by linearity -- the fold runs after GradBuckets.finish()); leaving out the all-reduce of the first k-1 micro-steps is not
+done.  Checkpoints are taken at cycle boundaries (micro_step() == 0): `acc` is part of no state dict; after loading one, reset_accumulation().
 
 The whole step is ~1,000 kernel launches for Swin-B; issued from Python it is launch-bound, so on one GPU the
 step is captured once into a hipGraph (torch.cuda.CUDAGraph on the stream our C-ABI launches go to) and
@@ -26,6 +34,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from . import _capi as K
 from .ddp import GradBuckets
 from .runtime import compute_dtype, fp8_enabled
 
@@ -89,7 +98,7 @@ class _ValidIndices:
 
 class TrainStep(_ValidIndices):
     def __init__(self, model, image, l_feats, l_mask, target, world=1, use_graph=True, bucket_mib=32.0, fused_loss=True, refresh_weights_in_step=False, context=None,
-                 *, loss="ce", valid_indices=None, dice_rate=1.0, boundary_rate=0.05, deterministic=None):
+                 *, loss="ce", valid_indices=None, dice_rate=1.0, boundary_rate=0.05, deterministic=None, accumulate=1):
         """context: the ops.StepContext this harness keeps its state in (gradient sinks, deferred-launch queues, weight copies, scratch).  None = the
         process-wide default context -- what the drop-in path and a single harness use.  Give every further model in the process its own
         `ops.StepContext()` (and its optimizer the same one: FusedAdamW(..., context=)): their steps can then alternate freely.
@@ -102,7 +111,18 @@ class TrainStep(_ValidIndices):
         deterministic: True / False sets the mode of the step's context, None keeps it (a context starts with LAVT_DETERMINISTIC).  In deterministic mode
         two steps from identical state (parameters, optimizer state, BatchNorm buffers, DropPath generator) on identical inputs give identical bits --
         loss, gradients, updated parameters, moments, running statistics -- eagerly and under graph replay, on ONE GPU (LAVT_FP8=1 included: its |max| history
-        is part of the state): world > 1 and collectives forced in a 1-rank group raise NotImplementedError (DESIGN.md "Deterministic mode")."""
+        is part of the state): world > 1 and collectives forced in a 1-rank group raise NotImplementedError (DESIGN.md "Deterministic mode").
+        accumulate: k >= 1 micro-batches per optimizer update (module docstring; DESIGN.md "Gradient accumulation").  1 = no accumulation: no second
+        buffer, no further launch.  k > 1 needs an owned optimizer (make_optimizer / attach_optimizer) by warmup_and_capture(); the fold is element-wise,
+        so the deterministic mode keeps its promise across cycles."""
+        import operator
+        try:
+            k = operator.index(accumulate)
+        except TypeError:
+            k = 0
+        if k < 1:
+            raise ValueError(f"TrainStep: accumulate must be an integer >= 1 (micro-batches per optimizer update), got {accumulate!r}")
+        self.accumulate = k
         if loss not in ("ce", "mc_dice", "dice_boundary"):
             raise ValueError(f"TrainStep: loss must be 'ce', 'mc_dice' or 'dice_boundary', got {loss!r}")
         if valid_indices is not None:
@@ -145,6 +165,8 @@ class TrainStep(_ValidIndices):
         self._seen = None
         self._one = None
         self.opt = None                          # the owned optimizer (make_optimizer / attach_optimizer): its step ends _body
+        # accumulate > 1: the mean of the cycle's flat gradients so far, in the layout of buckets.flat.  Never zero-filled: the first fold of a cycle overwrites it
+        self.acc = torch.zeros_like(self.buckets.flat) if self.accumulate > 1 else None
 
     def set_deterministic(self, deterministic, world=None):
         """Set the mode of the step's context (None: keep it).  Before warmup_and_capture() only: the captured launch sequence is frozen.  Raises
@@ -192,11 +214,33 @@ class TrainStep(_ValidIndices):
         if self.opt is not None:
             raise RuntimeError("TrainStep: an optimizer is already attached")
 
+    # ---- gradient accumulation: the phase lives in the optimizer's control block ----
+    def micro_step(self) -> int:
+        """the micro index m of the running cycle, 0 <= m < accumulate: the next step() is micro-step m (synchronises).  0 = a cycle boundary."""
+        if self.acc is None or self.opt is None or self.opt.guard is None:
+            return 0
+        return int(self.opt.guard[6].item())
+
+    def reset_accumulation(self):
+        """Restart the cycle: the next step() is its first micro-step (which overwrites `acc`).  For use after loading a checkpoint -- checkpoints are
+        taken at cycle boundaries, `acc` and the phase are part of no state dict.  A host write of guard[5:7], like FusedAdamW.hold(): call it outside
+        any capture; it waits for the device on both sides."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("TrainStep.reset_accumulation() is a host write: call it outside the graph capture")
+        if self.acc is None or self.opt is None:
+            return
+        g = self.opt._make_guard()
+        torch.cuda.synchronize(g.device)
+        g[5:7].zero_()
+        torch.cuda.synchronize(g.device)
+
     def _param_stamp(self):
         return sum(p._version for p in self._params), sum(p.data_ptr() for p in self._params)
 
     @_in_context
     def _body(self):
+        if self.acc is not None and (self.opt is None or self.opt._grad_source is None):
+            raise RuntimeError("TrainStep(accumulate > 1): call make_optimizer() and warmup_and_capture() before step() (the owned optimizer reads `acc`)")
         if self.refresh_in_step:
             ops.weights.refresh_all()            # re-cast weights inside the step (for optimizers that do not maintain the compute copies)
         arena = ops.zero_arena.begin_step(self.x.device, defer=True)          # one fill for every small zero-initialised buffer of the step ...
@@ -233,6 +277,10 @@ class TrainStep(_ValidIndices):
         self.buckets.finish()                    # stragglers (never-used parameters) + join of the communication stream
         ops.zero_arena.end_step()
         ops.fp8.end_step()
+        if self.acc is not None:
+            # after buckets.finish() (world > 1: all-reduced already): acc = flat / k on the first micro-step of a cycle, acc += flat / k on the others;
+            # sets guard[5] unless this micro-step ends the cycle -- the optimizer's kernels below then return before their first store
+            K.check(K.lib.lavt_grad_accumulate(K.ptr(self.buckets.flat), K.ptr(self.acc), self.acc.numel(), self.accumulate, K.ptr(self.opt.guard), K.stream()))
         if self.opt is not None:
             # after buckets.finish(): with world > 1 the gradients are all-reduced already, the update needs no collective of its own.  Eager: the host-side
             # scan (re)builds the descriptor tables; inside the capture they are final (step(check_tables=False) raises if they are not).
@@ -247,7 +295,14 @@ class TrainStep(_ValidIndices):
         Side effects beyond `eager_iters` steps: one more eager step when the bucket layout is still to settle (eager_iters = 1), and the zero-fill-skip validation below replays the captured step up to three more times on
         NaN-poisoned gradient buffers.  Each of those replays is a real training step of the forward pass -- BatchNorm running statistics and
         `num_batches_tracked`, the fp8 |max| history and the DropPath generator advance, and with world > 1 the poisoned buckets are all-reduced
-        (NaN on every rank alike) -- the gradients of such a replay are discarded by the next step's fill.  LAVT_ZERO_SKIP=0 captures once."""
+        (NaN on every rank alike) -- the gradients of such a replay are discarded by the next step's fill.  LAVT_ZERO_SKIP=0 captures once.
+        Accumulation (accumulate > 1): hold also stops the fold, so `acc` and the micro index leave the warm-up as they entered it -- the first step()
+        afterwards starts a cycle."""
+        if self.accumulate > 1:
+            if self.opt is None:
+                raise RuntimeError("TrainStep(accumulate > 1) needs an owned optimizer: the update that ends a cycle is part of the step.  Call "
+                                   "make_optimizer() (or attach_optimizer()) before warmup_and_capture()")
+            self.opt.set_grad_source(self.buckets.flat, self.acc)          # (creates the control block; outside any capture)
         self._warmed = True
         if self.opt is None:
             return self._warmup_and_capture(eager_iters)
@@ -267,7 +322,7 @@ class TrainStep(_ValidIndices):
                 if it == 0:                      # every compute copy exists now: one descriptor table for the one-launch refresh
                     ops.weights.build_multicast(compute_dtype())
                     ops.weights.refresh_all()
-            if self.use_graph and self.buckets._relayout:
+            if (self.use_graph or self.acc is not None) and self.buckets._relayout:          # (accumulation: `acc` follows the layout, which must not move inside a cycle)
                 # GradBuckets lays the flat buffer out again in the zero() after its first step (parameters nothing reported join the late bucket): that
                 # moves p.grad and must happen in an eager step -- inside the capture window zero() would raise and the harness would silently run eagerly
                 self.loss = self._body()

@@ -455,8 +455,9 @@ class _GradSinks:
             # GradBuckets.zero() in between, would silently lose a contribution.  Refuse instead.
             if id(p) in self.used:
                 raise RuntimeError("fused gradient accumulation: a second weight gradient for the same parameter within one step (parameter shared "
-                                   "between two ops, or gradient accumulation over micro-batches) is not supported by the step harness; "
-                                   "call ops.sinks.clear() to use ordinary autograd accumulation")
+                                   "between two ops, or a second backward without GradBuckets.zero() in between) is not supported by the step harness; "
+                                   "for gradient accumulation over micro-batches use engine.TrainStep(accumulate=k), which folds the flat buffer "
+                                   "between micro-steps; call ops.sinks.clear() to use ordinary autograd accumulation")
             self.used.add(id(p))
             return ent[1].view(shape), True
         return torch.zeros(shape, dtype=torch.float32, device=p.device), False

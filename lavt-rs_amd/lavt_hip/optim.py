@@ -14,9 +14,15 @@ of the uncorrected second moment, which replaces it in the denominator (lavt_ada
 every group carries the constructor's value, and a checkpoint written with the other value is refused rather than half-loaded.
 
 The guard (opt-in: max_grad_norm > 0, skip_nonfinite=True, or hold()): a device fp32[8] control block `opt.guard` = [global gradient norm, clip
-coefficient, skip flag, skipped-step count, hold flag, 0, 0, 0].  lavt_grad_norm fills the first three from the gradients the update is about to
-read, the guarded update multiplies every gradient by the coefficient and does nothing at all (no store, no tick of the step counter) when skip
-or hold is set -- no device-to-host synchronisation and no data-dependent launch, so it survives graph capture.
+coefficient, skip flag, skipped-step count, hold flag, accumulating flag, micro index, 0].  lavt_grad_norm fills the first three from the gradients the
+update is about to read, the guarded update multiplies every gradient by the coefficient and does nothing at all (no store, no tick of the step
+counter) when skip or hold is set -- no device-to-host synchronisation and no data-dependent launch, so it survives graph capture.
+
+Gradient accumulation (set_grad_source; engine.TrainStep(accumulate=k)): the update reads its gradients from a second flat buffer into which
+lavt_grad_accumulate folds each micro-batch's flat gradient.  guard[5] (accumulating: this micro-step does not end its cycle) is written by that
+fold and obeyed by the norm, the update and the tick exactly like hold -- guard[0..3] and the step counter keep the values of the last applied
+cycle; guard[6] is the micro index m, moved by the guarded tick ((m + 1) % k; not under hold).  Clip and the non-finite skip therefore act once per
+cycle, on the accumulated gradient.  The accumulation buffer and the phase are not part of state_dict(): checkpoints are taken at cycle boundaries.
 """
 import os
 from typing import Iterable
@@ -81,6 +87,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self.max_grad_norm, self.skip_nonfinite = float(max_grad_norm), bool(skip_nonfinite)
         self.guard = None          # the device control block (see the module docstring); None = the unguarded path
         self._norm_ws = None       # lavt_grad_norm's per-chunk partial sums
+        self._grad_source = None   # set_grad_source: (flat, acc) -- read gradients from `acc` at the offsets p.grad has in `flat`
         if self._wants_norm():
             self._make_guard()
 
@@ -117,6 +124,31 @@ class FusedAdamW(torch.optim.Optimizer):
         torch.cuda.synchronize(g.device)
         g[4:5].fill_(1.0 if flag else 0.0)
         torch.cuda.synchronize(g.device)
+
+    def set_grad_source(self, flat=None, acc=None):
+        """Read every gradient from `acc` at the offset its p.grad has inside `flat` (two flat fp32 buffers of one layout: GradBuckets.flat and the
+        buffer lavt_grad_accumulate folds it into) instead of from p.grad itself; None, None: back to p.grad.  The descriptor tables are still keyed
+        and probed by p.grad, so a re-layout of the flat buffer rebuilds them as before.  Creates the control block (as hold() does: outside a
+        capture) and thereby selects the guarded launches: the fold's accumulating flag lives in guard[5]."""
+        if (flat is None) != (acc is None):
+            raise ValueError("FusedAdamW.set_grad_source: give both buffers, or neither")
+        if flat is not None:
+            if not (flat.is_cuda and acc.is_cuda and flat.dtype == acc.dtype == torch.float32 and flat.dim() == acc.dim() == 1 and flat.numel() == acc.numel()
+                    and flat.is_contiguous() and acc.is_contiguous() and flat.data_ptr() != acc.data_ptr()):
+                raise ValueError("FusedAdamW.set_grad_source: flat and acc must be two distinct contiguous 1-d float32 GPU buffers of one size")
+            self._make_guard()
+        self._grad_source = (flat, acc) if flat is not None else None
+        self._tables = None
+
+    def _grad_address(self, p):
+        """the address the update reads p's gradient at"""
+        if self._grad_source is None:
+            return p.grad.data_ptr()
+        flat, acc = self._grad_source
+        off = p.grad.data_ptr() - flat.data_ptr()
+        if off < 0 or off % 4 or off + 4 * p.numel() > 4 * flat.numel():
+            raise RuntimeError("FusedAdamW: set_grad_source() is in effect, but a parameter's .grad is not a view into that flat buffer")
+        return acc.data_ptr() + off
 
     def last_grad_norm(self):
         """global gradient norm of the last guarded step (synchronises); None when no norm is computed"""
@@ -169,12 +201,12 @@ class FusedAdamW(torch.optim.Optimizer):
                 fused[ck] = copy
             for c in range(-(-p.numel() // ce)):
                 chunks.append([len(desc), c])
-            desc.append([p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(), copy])
+            desc.append([p.data_ptr(), self._grad_address(p), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(), copy])
             hyper.append([g["lr"], g["weight_decay"], g["betas"][0], g["betas"][1], g["eps"]])
             if self.amsgrad:
                 vmax.append(st["max_exp_avg_sq"].data_ptr())
         # (the copies' addresses are baked into the table: ops.weights.generation moves whenever one of them gets a new buffer)
-        key = tuple(d[1] for d in desc) + tuple(tuple(h) for h in hyper) + (ops_generation(),)
+        key = self._current_key()          # tracks p.grad (also under set_grad_source: desc[.][1] is then an address inside the accumulation buffer)
         # (every described parameter with the gradient address the table holds: step(check_tables=False) compares them all -- integer work on the host,
         # no device synchronisation; three probed addresses missed a single re-created .grad)
         self._probe = [(p, p.grad.data_ptr()) for _, p in ps if p.grad is not None]

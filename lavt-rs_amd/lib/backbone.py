@@ -61,9 +61,13 @@ class _LangCtx:
         return (ops.linear(self.lt, f_key.weight, f_key.bias, **kw), ops.linear(self.lt, f_value.weight, f_value.bias, **kw), None)
 
     @classmethod
-    def get(cls, l, l_mask, dtype):
-        key = (id(l), id(l_mask), l._version, l_mask._version, dtype)
-        if cls._cache is None or cls._cache[0] != key or cls._cache[2] is not l or cls._cache[3] is not l_mask:
+    def get(cls, l, l_mask, dtype, entry=False):
+        """entry: the call that opens a backbone's forward.  While a graph is being captured it builds the context anew whatever the cache holds: a
+        context cached by an earlier eager forward would leave ITS tensors in the graph as constants -- the transposed features and the mask rows would
+        not be recomputed on replay, and what the caller copies into static l / l_mask buffers between replays (the next batch) would never be seen."""
+        capturing = l.is_cuda and torch.cuda.is_current_stream_capturing()
+        key = (id(l), id(l_mask), l._version, l_mask._version, dtype, capturing)          # (nor does an eager forward reuse tensors of a graph's memory pool)
+        if (entry and capturing) or cls._cache is None or cls._cache[0] != key or cls._cache[2] is not l or cls._cache[3] is not l_mask:
             cls._cache = (key, cls(l, l_mask, dtype), l, l_mask)
         return cls._cache[1]
 
@@ -453,7 +457,7 @@ class MultiModalSwinTransformer(nn.Module):
         if l.shape[0] != B * S:
             raise ValueError(f"language batch {l.shape[0]} != image batch {B} x expand {S}")
         self._draw_drop_path(B, x.device)
-        lang = _LangCtx.get(l, l_mask, dtype)
+        lang = _LangCtx.get(l, l_mask, dtype, entry=True)
         lang.set_plan([(layer.fusion.image_lang_att.f_key[0], layer.fusion.image_lang_att.f_value[0]) for layer in self.layers])
         t, Wh, Ww = self.patch_embed.tokens(x, dtype)
         t = t.view(B, Wh * Ww, self.embed_dim)

@@ -381,7 +381,7 @@ class MultiModalSwinTransformer3D(nn.Module):
         dtype = compute_dtype()
         B = x.shape[0]
         self._draw_drop_path(B, x.device)
-        lang = _LangCtx.get(l, l_mask, dtype)
+        lang = _LangCtx.get(l, l_mask, dtype, entry=True)
         fusions = [layer.fusion if layer.sep_t_pwam else layer.fusion.image_lang_att for layer in self.layers]
         lang.set_plan([(f.f_key[0], f.f_value[0]) for f in fusions])
         t, T, Wh, Ww = self.patch_embed.tokens(x, dtype)
