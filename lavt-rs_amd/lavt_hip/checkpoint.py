@@ -12,7 +12,12 @@ Reference behaviour mirrored here:
   first 9 characters removed, SUM the patch-embed weight over its temporal axis (keepdim).
 * lib/_utils.py:133-238 (2-D LAVT weights into the video model): patch-embed `unsqueeze(2)`, tables as in inflate_weights, optionally
   dropping the '.fusion' tensors.
+
+Training state (DESIGN.md "Checkpoint and resume"): save_train_state / load_train_state write and read the whole state of an engine.TrainStep -- the
+reference's `{'model', 'optimizer', 'epoch', 'lr_scheduler', ...}` file (train.py:749-763) plus one more key, 'lavt_train_state' -- and the pure
+parts of TrainStep.state_dict() / load_state_dict() live here: the configuration fingerprint's comparison, the names of the fp8 sites, the writer.
 """
+import os
 from collections import OrderedDict
 
 import torch
@@ -129,3 +134,118 @@ def convert_lavt2d_to_video_state_dict(checkpoint, video_model, drop_fusion=Fals
 
 def load_lavt2d_into_video(video_model, filename, drop_fusion=False, map_location="cpu"):
     return _load_tolerant(video_model, convert_lavt2d_to_video_state_dict(torch.load(filename, map_location=map_location, weights_only=False), video_model, drop_fusion))
+
+
+# ------------------------------------------------------------------------------------------------ training state (engine.TrainStep)
+TRAIN_STATE_FORMAT = 1
+TRAIN_STATE_KEYS = ("model", "optimizer", "lavt_train_state")
+# the fields of the fingerprint, in the order they are compared
+CONFIG_FIELDS = ("criterion", "dice_rate", "boundary_rate", "accumulate", "amsgrad", "max_grad_norm", "skip_nonfinite", "deterministic", "compute_dtype",
+                 "fp8", "world", "param_groups")
+
+
+def _plain(v):
+    """tuples -> lists, recursively: what a fingerprint looks like after a trip through a file is what it is compared as"""
+    if isinstance(v, (list, tuple)):
+        return [_plain(x) for x in v]
+    return v
+
+
+def compare_fingerprints(saved, current, who="TrainStep.load_state_dict"):
+    """ValueError naming the FIRST field of CONFIG_FIELDS in which the checkpoint's fingerprint differs from this step's; for the parameter list, the first
+    group and entry (a missing, extra, renamed or reshaped parameter)."""
+    for f in CONFIG_FIELDS:
+        if f not in saved:
+            raise ValueError(f"{who}: the checkpoint's config has no field '{f}'")
+        a, b = _plain(saved[f]), _plain(current[f])
+        if a == b:
+            continue
+        if f != "param_groups":
+            raise ValueError(f"{who}: config field '{f}' differs: the checkpoint was written with {f}={saved[f]!r}, this step runs with {f}={current[f]!r}")
+        if len(a) != len(b):
+            raise ValueError(f"{who}: config field 'param_groups' differs: the checkpoint has {len(a)} parameter groups, this step's optimizer {len(b)}")
+        for gi, (ga, gb) in enumerate(zip(a, b)):
+            for pi, (ea, eb) in enumerate(zip(ga, gb)):
+                if ea != eb:
+                    what = "was reshaped" if ea[0] == eb[0] else "is another parameter"
+                    raise ValueError(f"{who}: config field 'param_groups' differs: group {gi}, entry {pi} {what}: the checkpoint has {ea[0]} {tuple(ea[1])}, "
+                                     f"this step {eb[0]} {tuple(eb[1])}")
+            if len(ga) != len(gb):
+                extra, side = (ga[len(gb)], "the checkpoint") if len(ga) > len(gb) else (gb[len(ga)], "this step")
+                raise ValueError(f"{who}: config field 'param_groups' differs: group {gi} has {len(ga)} parameters in the checkpoint and {len(gb)} in this "
+                                 f"step: {extra[0]} {tuple(extra[1])} is in {side} only")
+        raise ValueError(f"{who}: config field 'param_groups' differs")
+
+
+def fp8_site_name(key, names):
+    """The name a delayed-scaling site is saved under.  `key`: the site's key in _Fp8State.slots -- id(weight) for the activations the contraction with
+    `weight` reads, (id(weight), 'dy') for the output gradient its backward quantises; names: {id(parameter): qualified name}.  Slot numbers follow the
+    order of first use and mean nothing in another process; the consuming parameter's name does."""
+    pid, kind = (key[0], str(key[1])) if isinstance(key, tuple) else (key, "act")
+    if pid not in names:
+        raise ValueError(f"fp8 site {key!r}: its consuming weight is not a parameter of the step's model")
+    return f"{names[pid]}|{kind}"
+
+
+def fp8_site_slots(slots, names):
+    """{site name: slot number} of an _Fp8State.slots dict"""
+    out = {}
+    for key, i in slots.items():
+        n = fp8_site_name(key, names)
+        if n in out:
+            raise ValueError(f"fp8 sites: two sites are named {n}")
+        out[n] = int(i)
+    return out
+
+
+def match_fp8_sites(saved_names, own_names, who="TrainStep.load_state_dict"):
+    """ValueError unless the checkpoint's sites are exactly this step's"""
+    own = set(own_names)
+    for n in saved_names:
+        if n not in own:
+            raise ValueError(f"{who}: fp8 site '{n}' of the checkpoint does not exist in this step (its model quantises "
+                             f"{len(own)} sites: {', '.join(sorted(own)[:4])}{' ...' if len(own) > 4 else ''})")
+    missing = sorted(own - set(saved_names))
+    if missing:
+        raise ValueError(f"{who}: fp8 site '{missing[0]}' of this step is not in the checkpoint")
+
+
+def to_host(v):
+    """tensors -> detached CPU copies, through dicts, lists and tuples (what torch.load(..., weights_only=True) reads back)"""
+    if torch.is_tensor(v):
+        return v.detach().to("cpu", copy=True)
+    if isinstance(v, dict):
+        return {k: to_host(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return type(v)(to_host(x) for x in v)
+    return v
+
+
+def write_atomic(path, obj, _save=torch.save):
+    """torch.save to `path + '.tmp'`, then os.replace: a reader (and a run killed mid-write) sees the old file or the new one, never a torn one"""
+    path = os.fspath(path)
+    tmp = path + ".tmp"
+    try:
+        _save(obj, tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def save_train_state(path, step, **extra):
+    """Write step.state_dict() -- 'model', 'optimizer', 'lavt_train_state' -- with `extra` (the reference's 'epoch', 'lr_scheduler', any metadata
+    torch.load(weights_only=True) can read) merged at the top level, atomically."""
+    for k in extra:
+        if k in TRAIN_STATE_KEYS:
+            raise ValueError(f"save_train_state: '{k}' is written by the step itself")
+    state = step.state_dict()
+    state.update(extra)
+    write_atomic(path, state)
+
+
+def load_train_state(path, step):
+    """Read a file of save_train_state into `step` (TrainStep.load_state_dict: after warmup_and_capture(), in place) -> the extra keys"""
+    state = torch.load(os.fspath(path), map_location="cpu", weights_only=True)
+    step.load_state_dict(state)
+    return {k: v for k, v in state.items() if k not in TRAIN_STATE_KEYS}

@@ -12,7 +12,13 @@ one AdamW update from the mean of the k gradients (clip and non-finite skip act 
 PyTorch under accumulation: BatchNorm normalises with (and its running statistics follow) each micro-batch's own statistics, DropPath draws new
 masks, the fp8 |max| history advances; step() returns, and `stats` holds, that micro-batch's loss.  world > 1: the buckets are all-reduced in
 every micro-step (correct by linearity -- the fold runs after GradBuckets.finish()); leaving out the all-reduce of the first k-1 micro-steps is not
-done.  Checkpoints are taken at cycle boundaries (micro_step() == 0): `acc` is part of no state dict; after loading one, reset_accumulation().
+done.
+
+Checkpoint and resume: state_dict() / load_state_dict() (lavt_hip.checkpoint.save_train_state / load_train_state for files) hold the WHOLE state of a
+captured run -- model, optimizer, the control block with the accumulation phase, `acc` when the checkpoint lies inside a cycle, the DropPath
+generator, the fp8 |max| history, torch's CUDA generator -- and load it, after warmup_and_capture(), into the storage the captured graph reads.  In
+deterministic mode on one GPU a run that is saved, torn down, rebuilt and resumed gives the bits of one that never stopped (DESIGN.md "Checkpoint
+and resume").  A checkpoint may be taken at any micro-step; one from a cycle boundary (micro_step() == 0) carries no `acc`.
 
 The whole step is ~1,000 kernel launches for Swin-B; issued from Python it is launch-bound, so on one GPU the
 step is captured once into a hipGraph (torch.cuda.CUDAGraph on the stream our C-ABI launches go to) and
@@ -131,6 +137,7 @@ class TrainStep(_ValidIndices):
         self.dice_rate, self.boundary_rate = float(dice_rate), float(boundary_rate)
         self.context = context if context is not None else ops.default_context()
         self._warmed = False
+        self._dtype = None                       # (compute dtype, fp8) the launch sequence was warmed up and captured with
         self.set_deterministic(deterministic, world=world)
         with ops.use_context(self.context):
             self._init(model, image, l_feats, l_mask, target, world, use_graph, bucket_mib, fused_loss, refresh_weights_in_step)
@@ -206,6 +213,8 @@ class TrainStep(_ValidIndices):
                              "replay would read bf16 / packed weight copies that are never refreshed (training on frozen weights, silently).  "
                              "Construct it with FusedAdamW(..., context=step.context), or use step.make_optimizer()")
         self.opt = opt
+        import weakref
+        opt._owner = weakref.ref(self)           # (FusedAdamW.load_state_dict refuses once this step is captured: state_dict / load_state_dict below)
         return opt
 
     def _check_attach_window(self):
@@ -222,9 +231,10 @@ class TrainStep(_ValidIndices):
         return int(self.opt.guard[6].item())
 
     def reset_accumulation(self):
-        """Restart the cycle: the next step() is its first micro-step (which overwrites `acc`).  For use after loading a checkpoint -- checkpoints are
-        taken at cycle boundaries, `acc` and the phase are part of no state dict.  A host write of guard[5:7], like FusedAdamW.hold(): call it outside
-        any capture; it waits for the device on both sides."""
+        """Restart the cycle: the next step() is its first micro-step (which overwrites `acc`) -- to drop the micro-batches of an open cycle, or after
+        loading model and optimizer state dicts by hand.  load_state_dict() needs no such call: state_dict() saves `acc` and the phase inside a cycle,
+        and a checkpoint from a cycle boundary sets the phase to 0 itself.  A host write of guard[5:7], like FusedAdamW.hold(): call it outside any
+        capture; it waits for the device on both sides."""
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("TrainStep.reset_accumulation() is a host write: call it outside the graph capture")
         if self.acc is None or self.opt is None:
@@ -233,6 +243,142 @@ class TrainStep(_ValidIndices):
         torch.cuda.synchronize(g.device)
         g[5:7].zero_()
         torch.cuda.synchronize(g.device)
+
+    # ---- checkpoint and resume (DESIGN.md "Checkpoint and resume") ----
+    def _config(self):
+        """the fingerprint a checkpoint is compared by (checkpoint.CONFIG_FIELDS): what decides the captured launch sequence and the layout of the state"""
+        names = {id(p): n for n, p in self.model.named_parameters()}
+        dtype, fp8 = self._dtype if self._dtype is not None else (compute_dtype(), fp8_enabled())
+        groups = [[[names.get(id(p), f"<group {gi} entry {pi}: not a parameter of the model>"), [int(s) for s in p.shape]] for pi, p in enumerate(g["params"])]
+                  for gi, g in enumerate(self.opt.param_groups)]
+        return {"criterion": self.criterion, "dice_rate": self.dice_rate, "boundary_rate": self.boundary_rate, "accumulate": self.accumulate,
+                "amsgrad": bool(self.opt.amsgrad), "max_grad_norm": float(self.opt.max_grad_norm), "skip_nonfinite": bool(self.opt.skip_nonfinite),
+                "deterministic": bool(self.context.deterministic), "compute_dtype": str(dtype), "fp8": bool(fp8), "world": int(self.world),
+                "param_groups": groups}
+
+    def _acc_layout(self):
+        """[name, offset] of every parameter's gradient in the flat buffer `acc` mirrors, in offset order"""
+        names = {id(p): n for n, p in self.model.named_parameters()}
+        return sorted(([names.get(id(p), "?"), int(self.buckets.offset_of[id(p)])] for p in self.buckets.params), key=lambda e: e[1])
+
+    def _fp8_sites(self):
+        """{site name: slot} of the step's delayed-scaling sites; {} when fp8 is off"""
+        from .checkpoint import fp8_site_slots
+        f8 = self.context.fp8
+        if not self._config()["fp8"] or f8.prev is None:
+            return {}
+        return fp8_site_slots(f8.slots, {id(p): n for n, p in self.model.named_parameters()})
+
+    def _needs_owned_optimizer(self, who):
+        if self.opt is None:
+            raise RuntimeError(f"{who}: the step owns no optimizer (make_optimizer / attach_optimizer): only with one is a step() a whole training iteration "
+                               "whose state is the step's to save")
+
+    @staticmethod
+    def _not_capturing(who):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{who} synchronises and copies between host and device: call it outside the graph capture")
+
+    @_in_context
+    def state_dict(self):
+        """The whole state of the run, as CPU tensors and plain Python values (torch.load(..., weights_only=True) reads it back); synchronises.
+          'model'             model.state_dict() -- the reference's key (train.py:610)
+          'optimizer'         FusedAdamW.state_dict() -- torch.optim.AdamW's layout (train.py:724)
+          'lavt_train_state'  format, config (the fingerprint load_state_dict compares), guard (the optimizer's control block; hold saved as 0), acc (+
+                              its layout; only inside a cycle, micro_step() != 0 -- at a boundary it is dead), droppath (ops.droppath_state_dict() of the
+                              step's context), fp8 ({'<consuming parameter>|act' or '|dy': [prev, cur]}; {} without fp8), torch_cuda_rng.
+        Not state: gradients, the static input buffers, compute copies (re-made from the parameters), scratch.  checkpoint.save_train_state writes it."""
+        from .checkpoint import TRAIN_STATE_FORMAT, to_host
+        self._needs_owned_optimizer("TrainStep.state_dict")
+        self._not_capturing("TrainStep.state_dict")
+        dev = self._params[0].device
+        torch.cuda.synchronize(dev)
+        guard = None
+        if self.opt.guard is not None:
+            guard = self.opt.guard.detach().to("cpu", copy=True)
+            guard[4] = 0.0
+        train = {"format": TRAIN_STATE_FORMAT, "config": self._config(), "guard": guard, "droppath": ops.droppath_state_dict(), "fp8": {},
+                 "torch_cuda_rng": torch.cuda.get_rng_state(dev)}
+        if self.acc is not None and guard is not None and int(guard[6]) != 0:
+            train["acc"] = self.acc.detach().to("cpu", copy=True)
+            train["acc_layout"] = self._acc_layout()
+        sites = self._fp8_sites()
+        if sites:
+            prev, cur = self.context.fp8.prev.cpu(), self.context.fp8.cur.cpu()
+            train["fp8"] = {n: torch.stack([prev[i], cur[i]]) for n, i in sites.items()}
+        return {"model": to_host(self.model.state_dict()), "optimizer": to_host(self.opt.state_dict()), "lavt_train_state": train}
+
+    @_in_context
+    def load_state_dict(self, state):
+        """Continue the run `state` (a state_dict(), possibly through a file) was taken from: after warmup_and_capture() only, and IN PLACE -- parameters,
+        buffers, both moments, max_exp_avg_sq, the step counter, the control block, acc, the DropPath generator, the fp8 |max| arrays and torch's CUDA
+        generator are written into the storage they have, which is the storage the captured graph reads; then the compute copies are re-made and the
+        next step() replays.  Before any write the checkpoint's fingerprint is compared with this step's (ValueError naming the first field that
+        differs), and the model's, the optimizer's and the fp8 sites' entries are checked to fit: a load that raises has changed nothing.
+        A checkpoint from a cycle boundary holds no acc: the phase is set to 0, as reset_accumulation() does.  world > 1: every rank loads its own file."""
+        from .checkpoint import TRAIN_STATE_FORMAT, TRAIN_STATE_KEYS, compare_fingerprints, match_fp8_sites
+        who = "TrainStep.load_state_dict"
+        if not self._warmed or self._seen is None:
+            raise RuntimeError(f"{who}: call warmup_and_capture() first.  Its eager iterations and validation replays advance forward-side state -- BatchNorm "
+                               "running statistics and num_batches_tracked, the fp8 |max| history, the DropPath and torch generators -- so a state loaded "
+                               "before it is not the state the first step() starts from; and the load writes into the storage the captured graph reads")
+        self._needs_owned_optimizer(who)
+        # ---- 1. everything that can be refused, before the first write
+        missing = [k for k in TRAIN_STATE_KEYS if not isinstance(state, dict) or k not in state]
+        if missing:
+            raise ValueError(f"{who}: not a TrainStep.state_dict(): no '{missing[0]}'")
+        train = state["lavt_train_state"]
+        if train.get("format") != TRAIN_STATE_FORMAT:
+            raise ValueError(f"{who}: format {train.get('format')!r} of 'lavt_train_state' is not {TRAIN_STATE_FORMAT}")
+        compare_fingerprints(train["config"], self._config(), who)
+        own = self.model.state_dict()
+        for k, v in state["model"].items():
+            if k not in own:
+                raise ValueError(f"{who}: 'model' has an entry {k} that this model does not have")
+            if tuple(v.shape) != tuple(own[k].shape):
+                raise ValueError(f"{who}: 'model' entry {k} is {tuple(v.shape)} in the checkpoint, {tuple(own[k].shape)} in this model")
+        for k in own:
+            if k not in state["model"]:
+                raise ValueError(f"{who}: 'model' has no entry {k}")
+        plan = self.opt.check_state_dict_in_place(state["optimizer"])
+        guard, acc = train.get("guard"), train.get("acc")
+        if (guard is None) != (self.opt.guard is None) or (guard is not None and tuple(guard.shape) != (8,)):
+            raise ValueError(f"{who}: the checkpoint has {'no' if guard is None else 'a'} control block ('guard'), this step's optimizer has {'none' if self.opt.guard is None else 'one'}")
+        if acc is not None:
+            if self.acc is None or tuple(acc.shape) != tuple(self.acc.shape) or train.get("acc_layout") != self._acc_layout():
+                raise ValueError(f"{who}: 'acc' of the checkpoint does not have the layout of this step's gradient buffer")
+        sites = self._fp8_sites()
+        match_fp8_sites(train["fp8"], sites, who)
+        rng = train["torch_cuda_rng"]
+        if not torch.is_tensor(rng) or rng.dtype != torch.uint8:
+            raise ValueError(f"{who}: 'torch_cuda_rng' is not a generator state (a uint8 tensor)")
+        # ---- 2. the writes: host copies on the current stream, between two synchronisations
+        self._not_capturing(who)
+        dev = self._params[0].device
+        torch.cuda.synchronize(dev)
+        with torch.no_grad():
+            self.model.load_state_dict(state["model"], strict=True)          # copies into the parameters and buffers
+            self.opt.load_state_dict_in_place(state["optimizer"], plan)
+            if guard is not None:
+                g = guard.detach().to(torch.float32).clone()
+                g[4] = 0.0
+                if acc is None:
+                    g[5:7] = 0.0
+                self.opt.guard.copy_(g)
+            if acc is not None:
+                self.acc.copy_(acc)
+            ops.droppath_load_state_dict(train["droppath"])
+            if sites:
+                f8 = self.context.fp8
+                order = sorted(sites, key=sites.get)
+                idx = torch.tensor([sites[n] for n in order], dtype=torch.int64).to(dev)
+                vals = torch.stack([train["fp8"][n].to(torch.float32) for n in order]).to(dev)
+                f8.prev.index_copy_(0, idx, vals[:, 0].contiguous())
+                f8.cur.index_copy_(0, idx, vals[:, 1].contiguous())
+            torch.cuda.set_rng_state(rng, dev)
+            ops.weights.refresh_all()                 # the compute copies the next replay reads, from the loaded parameters, into the storage they have
+        torch.cuda.synchronize(dev)
+        self._seen = self._param_stamp()
 
     def _param_stamp(self):
         return sum(p._version for p in self._params), sum(p.data_ptr() for p in self._params)
@@ -314,6 +460,7 @@ class TrainStep(_ValidIndices):
 
     @_in_context
     def _warmup_and_capture(self, eager_iters):
+        self._dtype = (compute_dtype(), fp8_enabled())
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):

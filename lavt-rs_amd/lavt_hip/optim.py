@@ -22,7 +22,10 @@ Gradient accumulation (set_grad_source; engine.TrainStep(accumulate=k)): the upd
 lavt_grad_accumulate folds each micro-batch's flat gradient.  guard[5] (accumulating: this micro-step does not end its cycle) is written by that
 fold and obeyed by the norm, the update and the tick exactly like hold -- guard[0..3] and the step counter keep the values of the last applied
 cycle; guard[6] is the micro index m, moved by the guarded tick ((m + 1) % k; not under hold).  Clip and the non-finite skip therefore act once per
-cycle, on the accumulated gradient.  The accumulation buffer and the phase are not part of state_dict(): checkpoints are taken at cycle boundaries.
+cycle, on the accumulated gradient.  The accumulation buffer and the phase are not part of THIS state_dict(): engine.TrainStep.state_dict() saves them
+(and everything else a captured run needs to continue bit for bit), and TrainStep.load_state_dict() restores the optimizer through
+load_state_dict_in_place() -- into the tensors it has, because a captured graph keeps their addresses.  load_state_dict(), which installs new tensors,
+refuses an optimizer whose step has been captured.
 """
 import os
 from typing import Iterable
@@ -88,6 +91,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self.guard = None          # the device control block (see the module docstring); None = the unguarded path
         self._norm_ws = None       # lavt_grad_norm's per-chunk partial sums
         self._grad_source = None   # set_grad_source: (flat, acc) -- read gradients from `acc` at the offsets p.grad has in `flat`
+        self._owner = None         # weak reference to the engine.TrainStep this optimizer is attached to (attach_optimizer)
         if self._wants_norm():
             self._make_guard()
 
@@ -281,7 +285,87 @@ class FusedAdamW(torch.optim.Optimizer):
             sd["lavt_schedule"]["skipped_steps"] = self.skipped_steps()
         return sd
 
+    # ---- in-place load: for a captured step, whose graph holds the addresses of the moments and the counters ----
+    _HYPER = ("lr", "weight_decay", "betas", "eps")
+
+    def check_state_dict_in_place(self, state_dict):
+        """Everything load_state_dict_in_place() will do, decided and checked without a write: -> the plan it takes.  ValueError for a state dict that does
+        not fit -- amsgrad, the number of groups or of their parameters, a moment of another shape -- or that asks for what a captured launch sequence
+        cannot follow: total_steps / power are kernel arguments and the groups' hyper-parameters a device table built with the descriptor tables, so they
+        must be the ones this optimizer was constructed with."""
+        who = "FusedAdamW.load_state_dict_in_place"
+        theirs = {bool(g.get("amsgrad", False)) for g in state_dict["param_groups"]}
+        if theirs != {self.amsgrad}:
+            raise ValueError(f"{who}: the checkpoint's param_groups have amsgrad={sorted(theirs)} but this optimizer was built with amsgrad={self.amsgrad}")
+        groups = state_dict["param_groups"]
+        if len(groups) != len(self.param_groups):
+            raise ValueError(f"{who}: the checkpoint has {len(groups)} parameter groups, this optimizer {len(self.param_groups)}")
+        sched = state_dict.get("lavt_schedule")
+        if sched is not None and (float(sched["total_steps"]), float(sched["power"])) != (self.total_steps, self.power):
+            raise ValueError(f"{who}: the checkpoint's schedule (total_steps={sched['total_steps']}, power={sched['power']}) is not this optimizer's "
+                             f"(total_steps={self.total_steps}, power={self.power}), which the captured launches carry as arguments")
+        pairs = []
+        for gi, (sg, g) in enumerate(zip(groups, self.param_groups)):
+            if len(sg["params"]) != len(g["params"]):
+                raise ValueError(f"{who}: group {gi} has {len(sg['params'])} parameters in the checkpoint, {len(g['params'])} here")
+            if sched is not None:          # (a torch.optim.AdamW checkpoint under a LambdaLR holds the scheduled lr: the group keeps its own, as load_state_dict's 'initial_lr' rule does)
+                for h in self._HYPER:
+                    a, b = sg.get(h, g[h]), g[h]
+                    if (tuple(float(v) for v in a) != tuple(float(v) for v in b)) if h == "betas" else float(a) != float(b):
+                        raise ValueError(f"{who}: group {gi} was saved with {h}={a}, this optimizer has {h}={b}: the device table of the captured step keeps "
+                                         "the constructor's hyper-parameters")
+            pairs += list(zip(sg["params"], g["params"]))
+        keys = ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if self.amsgrad else ())
+        saved, plan, steps = state_dict["state"], [], None
+        for sid, p in pairs:
+            if not p.requires_grad:
+                continue
+            st = self.state.get(p)
+            if st is None or any(k not in st for k in keys) or self._step is None:
+                raise RuntimeError(f"{who}: this optimizer has no state yet to load into (it is created by the first step(): load in place after the warm-up)")
+            src = saved.get(sid)
+            for k in keys:
+                if src is None:
+                    plan.append((st[k], None))          # (no entry: the parameter had seen no gradient; its moments start at zero)
+                    continue
+                if k not in src:
+                    raise ValueError(f"{who}: the checkpoint's state of parameter {sid} has no '{k}'")
+                if tuple(src[k].shape) != tuple(st[k].shape):
+                    raise ValueError(f"{who}: '{k}' of parameter {sid} is {tuple(src[k].shape)} in the checkpoint, {tuple(st[k].shape)} here")
+                plan.append((st[k], src[k]))
+            if src is not None and steps is None and "step" in src:
+                steps = float(src["step"].item()) if torch.is_tensor(src["step"]) else float(src["step"])
+        if sched is not None:
+            steps = float(sched["steps_taken"])
+        skipped = float(sched["skipped_steps"]) if sched is not None and "skipped_steps" in sched else None
+        if skipped and self.guard is None:
+            raise ValueError(f"{who}: the checkpoint counts {int(skipped)} skipped steps, this optimizer has no control block to keep the count in")
+        return plan, float(steps or 0.0), skipped
+
+    @torch.no_grad()
+    def load_state_dict_in_place(self, state_dict, plan=None):
+        """load_state_dict for an optimizer whose tensors a captured graph reads: both moments, max_exp_avg_sq, the step counter and the skipped-step count
+        are WRITTEN INTO the storage they have (host writes: outside any capture); no tensor is replaced, the descriptor tables stay.  The groups keep
+        their hyper-parameters, which must equal the checkpoint's (check_state_dict_in_place: everything is checked before the first write).
+        engine.TrainStep.load_state_dict() is the caller that also restores what the optimizer does not own."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdamW.load_state_dict_in_place() writes from the host: call it outside the graph capture")
+        moments, steps, skipped = plan if plan is not None else self.check_state_dict_in_place(state_dict)
+        for dst, src in moments:
+            if src is None:
+                dst.zero_()
+            else:
+                dst.copy_(src)
+        self._step.fill_(steps)
+        if skipped is not None and self.guard is not None:
+            self.guard[3:4].fill_(skipped)
+
     def load_state_dict(self, state_dict):
+        owner = self._owner() if self._owner is not None else None
+        if owner is not None and owner.graph is not None:
+            raise RuntimeError("FusedAdamW.load_state_dict: this optimizer is part of a TrainStep whose step has been captured: the graph keeps the addresses "
+                               "of the moments and the step counter this call would replace, and would go on training from the old ones.  Use "
+                               "TrainStep.load_state_dict(), which loads in place")
         sched = state_dict.get("lavt_schedule")
         theirs = {bool(g.get("amsgrad", False)) for g in state_dict["param_groups"]}
         if theirs != {self.amsgrad}:
