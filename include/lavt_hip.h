@@ -700,6 +700,17 @@ int lavt_adamw_step_chunks_amsgrad(const int64_t* desc, const int64_t* vmax, con
  * one micro-step is  lavt_grad_accumulate -> [lavt_grad_norm over acc] -> guarded update over acc.  On the k-th micro-step of a cycle ctl[5] = 0 and
  * norm, clip, non-finite skip and update act on acc = the mean of the k gradients; on the others they do nothing.  1 <= k <= 2^20. */
 int lavt_grad_accumulate(const float* g, float* acc, int64_t n, int k, float* ctl, void* stream);
+/* Weight EMA (two new symbols under ABI v7): the chunked update with one more fp32 stream e = the exponential moving average of the parameter.
+ * torch.optim.swa_utils.AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(decay)), applied after the parameter update from the registers that hold
+ * the new p:   step[0] == 0 (the first applied update): e = p;   otherwise  e += (1 - decay) * (p - e).
+ * desc, hyper, chunks, step, the schedule and ctl are those of lavt_adamw_step_chunks_amsgrad; ema: device int64 [count] = the fp32 device pointer of e
+ * for every desc row; vmax: the AMSGrad table, or NULL for the plain rule; 0 < decay < 1.  ctl == NULL: the unguarded update and tick.  ctl != NULL: on
+ * skip, hold or an accumulating micro-step nothing is stored, e included -- the average moves exactly when the parameters move.
+ * lavt_ema_swap: p <-> e in place for every tensor of the same tables (one launch; every element is read and written by one thread); where
+ * desc[.][5] names a bf16 compute copy it is written from the new p.  Two calls restore every bit. */
+int lavt_adamw_step_chunks_ema(const int64_t* desc, const int64_t* vmax /* NULL: no AMSGrad */, const int64_t* ema, const float* hyper, const int32_t* chunks, int nchunks,
+                               float* step, float total_steps, float power, float decay, float* ctl /* NULL: unguarded */, void* stream);
+int lavt_ema_swap(const int64_t* desc, const int64_t* ema, const int32_t* chunks, int nchunks, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Inference path (csrc/infer.hip; reference test.py:60-110 and test_ytvos.py:230-260: batch-1 forward under model.eval() / torch.no_grad(), argmax,

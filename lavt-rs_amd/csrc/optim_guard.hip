@@ -76,6 +76,51 @@ __global__ __launch_bounds__(256) void adamw_chunks_amsgrad_kernel(const int64_t
 }
 __global__ void adamw_tick_kernel(float* step) { step[0] += 1.f; }          // the unguarded tick, as behind lavt_adamw_step_chunks
 
+// Weight EMA (adamw_body.h: EMA): the same body with the average's stream behind `ema`; vmax is read only with AMSGRAD, ctl only with GUARD
+template <bool GUARD, bool AMSGRAD>
+__global__ __launch_bounds__(256) void adamw_chunks_ema_kernel(const int64_t* __restrict__ desc, const int64_t* __restrict__ vmax, const int64_t* __restrict__ ema,
+                                                               const float* __restrict__ hyper, const int2* __restrict__ chunks, const float* __restrict__ step,
+                                                               float total_steps, float power, float decay, const float* __restrict__ ctl) {
+    adamw_chunk_update<GUARD, AMSGRAD, true>(desc, vmax, hyper, chunks, step, total_steps, power, ctl, ema, decay);
+}
+
+// In-place exchange of p and e over the update's chunk table: workgroup c swaps elements [chunk * CE, (chunk + 1) * CE) of tensor chunks[c].x, every
+// element is read and written by exactly one thread.  A bf16 compute copy (desc[.][5]) is written from the registers that hold the new p, as the
+// update writes it.  Whole aligned chunks: two rounds of 4 float4 loads per stream and thread, a round's loads all issued before its first store.
+__global__ __launch_bounds__(256) void ema_swap_kernel(const int64_t* __restrict__ desc, const int64_t* __restrict__ ema, const int2* __restrict__ chunks) {
+    const int2 ch = chunks[blockIdx.x];
+    const int t = ch.x;
+    float* p = reinterpret_cast<float*>(desc[6 * t]);
+    float* e = reinterpret_cast<float*>(ema[t]);
+    const int64_t n = desc[6 * t + 4];
+    bf16* cp = reinterpret_cast<bf16*>(desc[6 * t + 5]);
+    const int64_t e0 = (int64_t)ch.y * ADAMW_CE, e1 = min(n, e0 + ADAMW_CE);
+    const bool vec = ((desc[6 * t] | ema[t]) & 15) == 0 && (desc[6 * t + 5] & 7) == 0;
+    if (vec && e1 - e0 == ADAMW_CE) {
+#pragma unroll
+        for (int round = 0; round < 2; ++round) {
+            float4 pp[4], ee[4];
+            const int64_t base = e0 + (int64_t)round * 4096 + threadIdx.x * 4;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                pp[u] = *reinterpret_cast<const float4*>(p + base + u * 1024); ee[u] = *reinterpret_cast<const float4*>(e + base + u * 1024);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int64_t i = base + u * 1024;
+                *reinterpret_cast<float4*>(p + i) = ee[u]; *reinterpret_cast<float4*>(e + i) = pp[u];
+                if (cp) *reinterpret_cast<uint2*>(cp + i) = make_uint2(pack_bf16x2(ee[u].x, ee[u].y), pack_bf16x2(ee[u].z, ee[u].w));
+            }
+        }
+    } else {                                   // a tensor's last chunk / unaligned tensors
+        for (int64_t i = e0 + threadIdx.x; i < e1; i += 256) {
+            const float pv = p[i], ev = e[i];
+            p[i] = ev; e[i] = pv;
+            if (cp) cp[i] = from_f<bf16>(ev);
+        }
+    }
+}
+
 // the step counter advances only when the update ran; a skipped step is counted unless the optimizer is on hold.  Gradient accumulation: the tick is
 // the last reader of the phase in a step, so it is also the one that moves the micro index -- an accumulating micro-step (ctl[5], set by
 // lavt_grad_accumulate from m != k - 1) counts m up and nothing else (ctl[2] is the LAST cycle's skip flag then), the step that ends a cycle puts
@@ -183,6 +228,32 @@ extern "C" int lavt_adamw_step_chunks_amsgrad(const int64_t* desc, const int64_t
         hipLaunchKernelGGL(adamw_tick_kernel, dim3(1), dim3(1), 0, ST, step);
     }
     LAVT_CHECK_LAUNCH("lavt_adamw_step_chunks_amsgrad");
+    return LAVT_OK;
+}
+
+extern "C" int lavt_adamw_step_chunks_ema(const int64_t* desc, const int64_t* vmax, const int64_t* ema, const float* hyper, const int32_t* chunks, int nchunks, float* step,
+                                          float total_steps, float power, float decay, float* ctl, void* stream) {
+    LAVT_CHECK_ARG(desc && ema && hyper && chunks && step && nchunks > 0, "lavt_adamw_step_chunks_ema: bad arguments");
+    LAVT_CHECK_ARG(decay > 0.f && decay < 1.f, "lavt_adamw_step_chunks_ema: the decay must lie in (0, 1)");
+    const int2* ch = reinterpret_cast<const int2*>(chunks);
+    const dim3 grid(nchunks), block(256);
+    if (ctl) {
+        if (vmax) hipLaunchKernelGGL((adamw_chunks_ema_kernel<true, true>), grid, block, 0, ST, desc, vmax, ema, hyper, ch, step, total_steps, power, decay, ctl);
+        else hipLaunchKernelGGL((adamw_chunks_ema_kernel<true, false>), grid, block, 0, ST, desc, nullptr, ema, hyper, ch, step, total_steps, power, decay, ctl);
+        hipLaunchKernelGGL(adamw_tick_guarded_kernel, dim3(1), dim3(1), 0, ST, step, ctl);
+    } else {
+        if (vmax) hipLaunchKernelGGL((adamw_chunks_ema_kernel<false, true>), grid, block, 0, ST, desc, vmax, ema, hyper, ch, step, total_steps, power, decay, nullptr);
+        else hipLaunchKernelGGL((adamw_chunks_ema_kernel<false, false>), grid, block, 0, ST, desc, nullptr, ema, hyper, ch, step, total_steps, power, decay, nullptr);
+        hipLaunchKernelGGL(adamw_tick_kernel, dim3(1), dim3(1), 0, ST, step);
+    }
+    LAVT_CHECK_LAUNCH("lavt_adamw_step_chunks_ema");
+    return LAVT_OK;
+}
+
+extern "C" int lavt_ema_swap(const int64_t* desc, const int64_t* ema, const int32_t* chunks, int nchunks, void* stream) {
+    LAVT_CHECK_ARG(desc && ema && chunks && nchunks > 0, "lavt_ema_swap: bad arguments");
+    hipLaunchKernelGGL(ema_swap_kernel, dim3(nchunks), dim3(256), 0, ST, desc, ema, reinterpret_cast<const int2*>(chunks));
+    LAVT_CHECK_LAUNCH("lavt_ema_swap");
     return LAVT_OK;
 }
 

@@ -235,6 +235,8 @@ _PROTOTYPES = {
     "lavt_adamw_step_chunks_guarded": [vp, vp, vp, i32, vp, f32, f32, vp, vp],
     "lavt_adamw_step_chunks_amsgrad": [vp, vp, vp, vp, i32, vp, f32, f32, vp, vp],
     "lavt_grad_accumulate": [vp, vp, i64, i32, vp, vp],
+    "lavt_adamw_step_chunks_ema": [vp, vp, vp, vp, vp, i32, vp, f32, f32, f32, vp, vp],
+    "lavt_ema_swap": [vp, vp, vp, i32, vp],
     "lavt_ln_fold_multi": [vp, i32, vp],
     "lavt_upsample_ce_fwd": [i32, vp, vp, f32, f32, vp, i64, vp, i32, i32, i32, i32, i32, vp],
     "lavt_upsample_ce_bwd": [i32, vp, vp, f32, f32, vp, vp, vp, i32, i32, i32, i32, i32, vp],

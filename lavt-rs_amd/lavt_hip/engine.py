@@ -311,7 +311,7 @@ class TrainStep(_ValidIndices):
     @_in_context
     def load_state_dict(self, state):
         """Continue the run `state` (a state_dict(), possibly through a file) was taken from: after warmup_and_capture() only, and IN PLACE -- parameters,
-        buffers, both moments, max_exp_avg_sq, the step counter, the control block, acc, the DropPath generator, the fp8 |max| arrays and torch's CUDA
+        buffers, both moments, max_exp_avg_sq, the weight average (FusedAdamW(ema_decay=...)), the step counter, the control block, acc, the DropPath generator, the fp8 |max| arrays and torch's CUDA
         generator are written into the storage they have, which is the storage the captured graph reads; then the compute copies are re-made and the
         next step() replays.  Before any write the checkpoint's fingerprint is compared with this step's (ValueError naming the first field that
         differs), and the model's, the optimizer's and the fp8 sites' entries are checked to fit: a load that raises has changed nothing.
@@ -450,6 +450,7 @@ class TrainStep(_ValidIndices):
                                    "make_optimizer() (or attach_optimizer()) before warmup_and_capture()")
             self.opt.set_grad_source(self.buckets.flat, self.acc)          # (creates the control block; outside any capture)
         self._warmed = True
+        ops.note_raw_write()                     # (the forward passes below move the BatchNorm running statistics, as every step() does)
         if self.opt is None:
             return self._warmup_and_capture(eager_iters)
         self.opt.hold(True)
@@ -541,6 +542,11 @@ class TrainStep(_ValidIndices):
 
     @_in_context
     def step(self):
+        if self.opt is not None and self.opt.ema_swapped:
+            raise RuntimeError("TrainStep.step: the model's parameters hold the weight average (FusedAdamW.swap_ema() / inside ema_weights()): a step now "
+                               "would train on the average -- swap back first")
+        # eager or replay, with an optimizer or without: the train-mode BatchNorm kernels write running statistics through raw pointers on every forward
+        ops.note_raw_write()
         if not self.refresh_in_step:
             stamp = self._param_stamp()
             if stamp != self._seen:                 # weights changed behind the compute copies' back (see __init__): refresh before the step
@@ -614,7 +620,9 @@ class Predictor(_ValidIndices):
         self._seen = None
 
     def _stamp(self):
-        return sum(t._version for t in self._state), sum(t.data_ptr() for t in self._state)
+        # (ops.raw_writes: the fused optimizer, the train-mode BatchNorm kernels, an in-place checkpoint load and the weight-average swap write through
+        # raw pointers -- no version moves.  A predictor built on the model that is being trained re-folds at its first step() after any of them)
+        return sum(t._version for t in self._state), sum(t.data_ptr() for t in self._state), ops.raw_writes()
 
     @_in_context
     def _body(self):

@@ -33,6 +33,20 @@ KV_LD = 32          # padded word axis of PWAM keys/values (N_l <= 32)
 # optimizer inside `with use_context(ctx):`, so two models -- or a train + eval pair -- in one process cannot share sinks, queues or scratch.
 _ctx = None
 
+# Raw-pointer writes into parameters and buffers move no `_version` counter: the fused AdamW update, the BatchNorm kernels' running statistics, an
+# in-place checkpoint load, the weight-average swap.  Every HOST call that launches such writes advances this process-wide monotone counter (one count per
+# call -- a graph replay is one call), and whoever caches something derived from the weights across such calls (engine.Predictor: casts and BatchNorm
+# folds read by its captured graph) puts it into its stamp.
+_raw_writes = [0]
+
+
+def raw_writes() -> int:
+    return _raw_writes[0]
+
+
+def note_raw_write() -> None:
+    _raw_writes[0] += 1
+
 
 class _Proxy:
     """module-level stand-in for one member of the current StepContext: attribute reads / writes go to `getattr(_ctx, name)`"""

@@ -26,6 +26,13 @@ cycle, on the accumulated gradient.  The accumulation buffer and the phase are n
 (and everything else a captured run needs to continue bit for bit), and TrainStep.load_state_dict() restores the optimizer through
 load_state_dict_in_place() -- into the tensors it has, because a captured graph keeps their addresses.  load_state_dict(), which installs new tensors,
 refuses an optimizer whose step has been captured.
+
+Weight EMA (ema_decay=d, off by default; DESIGN.md "Weight EMA"): a further flat fp32 buffer holds state[p]["ema"], torch's
+AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(d)) of the parameter, maintained by the update kernel itself (lavt_adamw_step_chunks_ema) -- a graph
+replay runs no Python, and a stream of the update obeys the control block with the moments: a skipped, held or accumulating step leaves it alone.  It
+travels through state_dict() (`ema` per parameter, `ema_decay` in every group; a checkpoint with another decay, or with the average on one side only,
+is refused before anything is written).  swap_ema() / ema_weights() exchange parameters and average in place for an evaluation, ema_state_dict(model)
+exports the average; while swapped, step(), state_dict() and the loads raise.
 """
 import os
 from typing import Iterable
@@ -70,18 +77,41 @@ def ops_generation():
     return (ops.weights.generation, ddp.layout_generation[0])
 
 
+def _check_ema_decay(d):
+    """None, or the decay as a float strictly between 0 and 1 (0 would be the iterate itself, 1 a constant): ValueError for anything else"""
+    if d is None:
+        return None
+    if isinstance(d, bool) or not isinstance(d, (int, float)) or not 0.0 < float(d) < 1.0:
+        raise ValueError(f"FusedAdamW: ema_decay must be None or a number strictly between 0 and 1, got {d!r}")
+    return float(d)
+
+
+def _ema_of_groups(groups):
+    """the set of ema_decay values a state dict's param_groups carry (None: no average)"""
+    return {None if g.get("ema_decay") is None else float(g["ema_decay"]) for g in groups}
+
+
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params: Iterable, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, total_steps=0, power=0.9, context=None,
-                 max_grad_norm=0.0, skip_nonfinite=False):
+                 max_grad_norm=0.0, skip_nonfinite=False, ema_decay=None):
         """max_grad_norm > 0: clip by the global L2 norm (torch.nn.utils.clip_grad_norm_'s coefficient); skip_nonfinite: leave parameters, moments, compute
         copies and the step counter untouched when that norm is NaN / Inf (counted in skipped_steps()).  With both off and hold() never called, step()
         is the unguarded launch sequence: no control block, no extra launch.
         context: the ops.StepContext whose compute-dtype weight copies this optimizer maintains (None = the process-wide default; pass the one given to
-        engine.TrainStep when the model runs in a private context)"""
+        engine.TrainStep when the model runs in a private context)
+        ema_decay: None = no average (no buffer, no table, the launches of an optimizer built without the argument).  A number d in (0, 1): the update kernel
+        also maintains state[p]["ema"], torch.optim.swa_utils.AveragedModel's exponential moving average with get_ema_multi_avg_fn(d) -- the first applied
+        update copies the parameter, every later one is ema += (1 - d) * (p - ema); skip, hold and accumulating micro-steps leave it alone, as they
+        leave the moments.  swap_ema() / ema_weights() put it in the parameters' place for an evaluation, ema_state_dict(model) exports it."""
         from . import ops
         self.context = context if context is not None else ops.default_context()
         self.amsgrad = bool(amsgrad)          # optimizer-wide (one kernel for the whole chunk table): add_param_group reads it during super().__init__
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=self.amsgrad))
+        self.ema_decay = _check_ema_decay(ema_decay)          # optimizer-wide as well (a kernel argument)
+        self.ema_swapped = False              # swap_ema(): the parameters hold the average, state[p]["ema"] the iterate
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=self.amsgrad)
+        if self.ema_decay is not None:
+            defaults["ema_decay"] = self.ema_decay
+        super().__init__(params, defaults)
         self.total_steps, self.power = float(total_steps), float(power)
         self.fuse_copies = os.environ.get("LAVT_ADAMW_FUSE_COPIES", "1") != "0"
         self._tables = None
@@ -99,6 +129,9 @@ class FusedAdamW(torch.optim.Optimizer):
         if isinstance(param_group, dict) and "amsgrad" in param_group and bool(param_group["amsgrad"]) != self.amsgrad:
             raise ValueError(f"FusedAdamW: amsgrad is optimizer-wide: a group with amsgrad={param_group['amsgrad']} cannot join an optimizer built with "
                              f"amsgrad={self.amsgrad}")
+        if isinstance(param_group, dict) and "ema_decay" in param_group and _ema_of_groups([param_group]) != {self.ema_decay}:
+            raise ValueError(f"FusedAdamW: ema_decay is optimizer-wide: a group with ema_decay={param_group['ema_decay']} cannot join an optimizer built with "
+                             f"ema_decay={self.ema_decay}")
         super().add_param_group(param_group)
 
     # ---- the guard ----
@@ -174,6 +207,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if not all("exp_avg" in self.state[p] for _, p in ps):
             flat_m, flat_v = torch.zeros(total, dtype=torch.float32, device=dev), torch.zeros(total, dtype=torch.float32, device=dev)
             flat_x = torch.zeros(total, dtype=torch.float32, device=dev) if self.amsgrad else None
+            flat_e = torch.empty(total, dtype=torch.float32, device=dev) if self.ema_decay is not None else None
             off = 0
             for _, p in ps:
                 n = p.numel()
@@ -182,12 +216,18 @@ class FusedAdamW(torch.optim.Optimizer):
                 st["exp_avg"], st["exp_avg_sq"] = flat_m[off:off + n].view_as(p), flat_v[off:off + n].view_as(p)
                 if self.amsgrad:
                     st["max_exp_avg_sq"] = flat_x[off:off + n].view_as(p)
+                if self.ema_decay is not None:
+                    st["ema"] = flat_e[off:off + n].view_as(p)
+                    st["ema"].copy_(p.detach())          # (the first applied update overwrites it: until then the average of no iterates is the parameter)
                 off += n
         if self.amsgrad and not all("max_exp_avg_sq" in self.state[p] for _, p in ps):
             raise ValueError("FusedAdamW(amsgrad=True): a parameter's state has exp_avg but no max_exp_avg_sq (it was written without amsgrad); the running "
                              "maximum is not started at zero silently")
+        if self.ema_decay is not None and not all("ema" in self.state[p] for _, p in ps):
+            raise ValueError("FusedAdamW(ema_decay=...): a parameter's state has exp_avg but no ema (it was written without the average); averaging is not "
+                             "started silently in the middle of a run -- load a matching checkpoint, or call reset_ema() to start it from the current parameters")
         from . import ops
-        desc, hyper, missing, chunks, fused, vmax = [], [], [], [], {}, []
+        desc, hyper, missing, chunks, fused, vmax, ema = [], [], [], [], {}, [], []
         ce = int(K.lib.lavt_adamw_chunk_elems())
         for g, p in ps:
             if p.grad is None:
@@ -209,6 +249,9 @@ class FusedAdamW(torch.optim.Optimizer):
             hyper.append([g["lr"], g["weight_decay"], g["betas"][0], g["betas"][1], g["eps"]])
             if self.amsgrad:
                 vmax.append(st["max_exp_avg_sq"].data_ptr())
+            if self.ema_decay is not None:
+                assert st["ema"].dtype == torch.float32 and st["ema"].is_contiguous() and st["ema"].numel() == p.numel()
+                ema.append(st["ema"].data_ptr())
         # (the copies' addresses are baked into the table: ops.weights.generation moves whenever one of them gets a new buffer)
         key = self._current_key()          # tracks p.grad (also under set_grad_source: desc[.][1] is then an address inside the accumulation buffer)
         # (every described parameter with the gradient address the table holds: step(check_tables=False) compares them all -- integer work on the host,
@@ -217,6 +260,8 @@ class FusedAdamW(torch.optim.Optimizer):
         self._tables = (key, torch.tensor(desc, dtype=torch.int64).to(dev), torch.tensor(hyper, dtype=torch.float32).to(dev), len(desc),
                         torch.tensor(chunks, dtype=torch.int32).to(dev), len(chunks), dict(fused),
                         torch.tensor(vmax, dtype=torch.int64).to(dev) if self.amsgrad else None)          # [7]: one max_exp_avg_sq address per desc row
+        if self.ema_decay is not None:
+            self._tables += (torch.tensor(ema, dtype=torch.int64).to(dev),)          # [8], only with the average on: one ema address per desc row
         if self._wants_norm():
             need = int(K.lib.lavt_grad_norm_ws(len(chunks)))
             if self._norm_ws is None or self._norm_ws.numel() < need:
@@ -235,8 +280,95 @@ class FusedAdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None, check_tables=True):
         from . import ops
+        self._refuse_swapped("step")
+        ops.note_raw_write()          # parameters (and compute copies) are written through raw pointers: engine.Predictor watches this counter
         with ops.use_context(self.context):
             return self._step_in_context(closure, check_tables)
+
+    # ---- the weight average ----
+    def _refuse_swapped(self, what):
+        if self.ema_swapped:
+            raise RuntimeError(f"FusedAdamW.{what}: the parameters hold the weight average (swap_ema() / inside ema_weights()): training on the average, or "
+                               "saving it as the iterate, is never silent -- swap back first")
+
+    def _needs_ema(self, what):
+        if self.ema_decay is None:
+            raise RuntimeError(f"FusedAdamW.{what}: this optimizer keeps no weight average (ema_decay=None)")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"FusedAdamW.{what} is a host call: it is refused inside a graph capture")
+
+    def _ema_pairs(self, what):
+        ps = [p for g in self.param_groups for p in g["params"] if p.requires_grad]
+        if not all("ema" in self.state.get(p, ()) for p in ps):          # (.get: looking must not create empty state entries)
+            raise RuntimeError(f"FusedAdamW.{what}: the optimizer's state does not exist yet (the first step() creates it)")
+        return [(p, self.state[p]["ema"]) for p in ps]
+
+    @torch.no_grad()
+    def reset_ema(self):
+        """ema <- p for every parameter: the explicit way to (re)start the average from the current iterate -- also on a state that has moments but no
+        average yet (installed by hand from a run without one; the tables are then rebuilt by the next step()).  A host call outside any capture; it
+        waits for the device on both sides, like hold()."""
+        from . import ops
+        self._needs_ema("reset_ema")
+        self._refuse_swapped("reset_ema")
+        ps = [p for g in self.param_groups for p in g["params"] if p.requires_grad]
+        if not all("exp_avg" in self.state.get(p, ()) for p in ps):
+            raise RuntimeError("FusedAdamW.reset_ema: the optimizer's state does not exist yet (the first step() creates it, with the average at the parameters)")
+        dev = ps[0].device
+        torch.cuda.synchronize(dev)
+        for p in ps:
+            st = self.state[p]
+            if "ema" in st:
+                st["ema"].copy_(p.detach())          # in place: a captured update keeps the address
+            else:
+                st["ema"] = p.detach().clone()
+                self._tables = None
+        ops.note_raw_write()
+        torch.cuda.synchronize(dev)
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange every parameter with its average, in place (lavt_ema_swap: one launch over the update's own tables; the bf16 copies the update
+        maintains are written from the new parameter), then refresh every other compute copy of the optimizer's context.  Toggles `ema_swapped`; while
+        it is set, step(), state_dict() and the load_state_dict family raise.  Refused inside a capture.  Two calls restore every bit."""
+        from . import ops
+        self._needs_ema("swap_ema")
+        with ops.use_context(self.context):
+            if self._tables is None:
+                raise RuntimeError("FusedAdamW.swap_ema: the optimizer's state and tables do not exist yet (the first step() creates them)")
+            if self._tables[0] != self._current_key():
+                owner = self._owner() if self._owner is not None else None
+                if owner is not None and owner.graph is not None:
+                    raise RuntimeError("FusedAdamW.swap_ema: a compute copy was re-allocated, a gradient moved or a hyper-parameter was edited after the step "
+                                       "was captured: the tables the captured update reads no longer describe the optimizer")
+                self._build()
+            _, desc, _, _, chunks, nchunks, fused, _, ema = self._tables
+            K.check(K.lib.lavt_ema_swap(K.ptr(desc), K.ptr(ema), K.ptr(chunks), nchunks, K.stream()))
+            self.ema_swapped = not self.ema_swapped
+            ops.note_raw_write()
+            ops.weights.refresh_all(done=fused)          # (as after step(): packed conv weights, e4m3 copies, LayerNorm and BatchNorm folds follow)
+
+    def ema_weights(self):
+        """`with opt.ema_weights(): evaluate` -- swap_ema() on entry and on exit (also when the body raises)"""
+        import contextlib
+
+        @contextlib.contextmanager
+        def swapped():
+            self.swap_ema()
+            try:
+                yield self
+            finally:
+                self.swap_ema()
+        return swapped()
+
+    @torch.no_grad()
+    def ema_state_dict(self, model):
+        """model.state_dict() with every averaged parameter replaced by a CPU copy of its average; parameters this optimizer does not update and all
+        buffers as they are (torch's AveragedModel(use_buffers=False)): what to write as 'model_ema' next to 'model'.  Correct in either swap state."""
+        if self.ema_decay is None:
+            raise RuntimeError("FusedAdamW.ema_state_dict: this optimizer keeps no weight average (ema_decay=None)")
+        avg = {id(p): (p if self.ema_swapped else e) for p, e in self._ema_pairs("ema_state_dict")}
+        return {k: avg.get(id(v), v).detach().to("cpu", copy=True) for k, v in model.state_dict(keep_vars=True).items()}
 
     def _step_in_context(self, closure=None, check_tables=True):
         """check_tables=False skips the (host-side) scan for re-allocated gradients / edited hyper-parameters: use it when the gradients
@@ -244,7 +376,8 @@ class FusedAdamW(torch.optim.Optimizer):
         loss = closure() if closure is not None else None
         if self._tables is None or (check_tables and self._tables[0] != self._current_key()):
             self._build()
-        _, desc, hyper, n, chunks, nchunks, fused, vmax = self._tables
+        _, desc, hyper, n, chunks, nchunks, fused, vmax = self._tables[:8]
+        ema = self._tables[8] if self.ema_decay is not None else None
         if not check_tables and (self._tables[0][-1] != ops_generation()
                                  or any(p.grad is None or p.grad.data_ptr() != a for p, a in self._probe)):
             # (captured steps skip the host-side scan, but a copy that moved since the table was built would be written at its OLD address, and a
@@ -254,7 +387,10 @@ class FusedAdamW(torch.optim.Optimizer):
                                "after the descriptor table was built; call step() once with check_tables=True (outside a capture) first")
         if self.guard is not None and self._wants_norm():
             K.check(K.lib.lavt_grad_norm(K.ptr(desc), K.ptr(chunks), nchunks, K.ptr(self._norm_ws), K.ptr(self.guard), self.max_grad_norm, int(self.skip_nonfinite), K.stream()))
-        if self.amsgrad:
+        if ema is not None:
+            K.check(K.lib.lavt_adamw_step_chunks_ema(K.ptr(desc), K.ptr(vmax), K.ptr(ema), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(self._step), self.total_steps,
+                                                     self.power, self.ema_decay, K.ptr(self.guard), K.stream()))
+        elif self.amsgrad:
             K.check(K.lib.lavt_adamw_step_chunks_amsgrad(K.ptr(desc), K.ptr(vmax), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(self._step), self.total_steps, self.power,
                                                          K.ptr(self.guard), K.stream()))
         elif self.guard is None:
@@ -279,11 +415,24 @@ class FusedAdamW(torch.optim.Optimizer):
         return max(1.0 - k / self.total_steps, 0.0) ** self.power if self.total_steps > 0 else 1.0
 
     def state_dict(self):
+        self._refuse_swapped("state_dict")
         sd = super().state_dict()
         sd["lavt_schedule"] = {"total_steps": self.total_steps, "power": self.power, "steps_taken": self.steps_taken()}
         if self.guard is not None:
             sd["lavt_schedule"]["skipped_steps"] = self.skipped_steps()
         return sd
+
+    def _check_ema_of(self, state_dict, who):
+        """refuse, before any write, a checkpoint whose weight average is not this optimizer's: present on one side only (averaging would start, or end,
+        silently in the middle of a run) or kept with another decay"""
+        theirs = _ema_of_groups(state_dict["param_groups"])
+        if theirs != {self.ema_decay}:
+            raise ValueError(f"{who}: the checkpoint's param_groups have ema_decay={sorted(theirs, key=lambda d: -1.0 if d is None else d)} but this optimizer "
+                             f"was built with ema_decay={self.ema_decay}: the weight average (ema) is not started, dropped or re-weighted silently")
+        has = {"ema" in st for st in state_dict["state"].values() if "exp_avg" in st}
+        if has and has != {self.ema_decay is not None}:
+            raise ValueError(f"{who}: the checkpoint's per-parameter state {'lacks' if self.ema_decay is not None else 'carries'} the weight average "
+                             f"('ema'), this optimizer was built with ema_decay={self.ema_decay}")
 
     # ---- in-place load: for a captured step, whose graph holds the addresses of the moments and the counters ----
     _HYPER = ("lr", "weight_decay", "betas", "eps")
@@ -294,9 +443,11 @@ class FusedAdamW(torch.optim.Optimizer):
         cannot follow: total_steps / power are kernel arguments and the groups' hyper-parameters a device table built with the descriptor tables, so they
         must be the ones this optimizer was constructed with."""
         who = "FusedAdamW.load_state_dict_in_place"
+        self._refuse_swapped("load_state_dict_in_place")
         theirs = {bool(g.get("amsgrad", False)) for g in state_dict["param_groups"]}
         if theirs != {self.amsgrad}:
             raise ValueError(f"{who}: the checkpoint's param_groups have amsgrad={sorted(theirs)} but this optimizer was built with amsgrad={self.amsgrad}")
+        self._check_ema_of(state_dict, who)
         groups = state_dict["param_groups"]
         if len(groups) != len(self.param_groups):
             raise ValueError(f"{who}: the checkpoint has {len(groups)} parameter groups, this optimizer {len(self.param_groups)}")
@@ -315,7 +466,7 @@ class FusedAdamW(torch.optim.Optimizer):
                         raise ValueError(f"{who}: group {gi} was saved with {h}={a}, this optimizer has {h}={b}: the device table of the captured step keeps "
                                          "the constructor's hyper-parameters")
             pairs += list(zip(sg["params"], g["params"]))
-        keys = ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if self.amsgrad else ())
+        keys = ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if self.amsgrad else ()) + (("ema",) if self.ema_decay is not None else ())
         saved, plan, steps = state_dict["state"], [], None
         for sid, p in pairs:
             if not p.requires_grad:
@@ -326,7 +477,7 @@ class FusedAdamW(torch.optim.Optimizer):
             src = saved.get(sid)
             for k in keys:
                 if src is None:
-                    plan.append((st[k], None))          # (no entry: the parameter had seen no gradient; its moments start at zero)
+                    plan.append((st[k], None if k != "ema" else p))          # (no entry: the parameter had seen no gradient; its moments start at zero, its average at the parameter)
                     continue
                 if k not in src:
                     raise ValueError(f"{who}: the checkpoint's state of parameter {sid} has no '{k}'")
@@ -348,9 +499,12 @@ class FusedAdamW(torch.optim.Optimizer):
         are WRITTEN INTO the storage they have (host writes: outside any capture); no tensor is replaced, the descriptor tables stay.  The groups keep
         their hyper-parameters, which must equal the checkpoint's (check_state_dict_in_place: everything is checked before the first write).
         engine.TrainStep.load_state_dict() is the caller that also restores what the optimizer does not own."""
+        self._refuse_swapped("load_state_dict_in_place")
+        moments, steps, skipped = plan if plan is not None else self.check_state_dict_in_place(state_dict)          # (pure host checks: before touching the device)
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("FusedAdamW.load_state_dict_in_place() writes from the host: call it outside the graph capture")
-        moments, steps, skipped = plan if plan is not None else self.check_state_dict_in_place(state_dict)
+        from . import ops
+        ops.note_raw_write()          # (TrainStep.load_state_dict writes parameters and buffers around this call)
         for dst, src in moments:
             if src is None:
                 dst.zero_()
@@ -366,7 +520,9 @@ class FusedAdamW(torch.optim.Optimizer):
             raise RuntimeError("FusedAdamW.load_state_dict: this optimizer is part of a TrainStep whose step has been captured: the graph keeps the addresses "
                                "of the moments and the step counter this call would replace, and would go on training from the old ones.  Use "
                                "TrainStep.load_state_dict(), which loads in place")
+        self._refuse_swapped("load_state_dict")
         sched = state_dict.get("lavt_schedule")
+        self._check_ema_of(state_dict, "FusedAdamW.load_state_dict")
         theirs = {bool(g.get("amsgrad", False)) for g in state_dict["param_groups"]}
         if theirs != {self.amsgrad}:
             # (a plain checkpoint would start max_exp_avg_sq at zero, an AMSGrad one would lose it: neither silently)

@@ -6,13 +6,14 @@
     (c) owned_guarded  the same with max_grad_norm=1.0, skip_nonfinite=True (lavt_grad_norm + the guarded update in the graph)
     (d) grad_norm      lavt_grad_norm alone over route (c)'s descriptor tables
     (e) torch_norm     torch.linalg.vector_norm over the same flat gradient buffer: the outside yardstick for (d)
+    (f) owned_guarded_ema   route (c) with ema_decay=D -- only with --ema-decay D (a fourth model)
 
 One process, three models in private contexts; the routes are timed ALTERNATELY (a, b, c, d, e, a, b, ...) so that whatever else the host is doing
 hits all of them alike.  Every repetition is a window of `--steps` iterations between two device events, ended by a synchronise; reported per route:
 median / min / max over the repetitions (the spread is the unit any difference between routes has to be read against).  lr = 0 as in bench.py's
 separate optimizer timing: same memory traffic, weights left alone.  Prints one JSON line per route and appends them to profiles/train_iter_time.jsonl.
 
-    python tools/train_iter_time.py [--steps 20] [--reps 7] [--warmup 5]
+    python tools/train_iter_time.py [--steps 20] [--reps 7] [--warmup 5] [--ema-decay D]
 """
 import argparse
 import json
@@ -32,6 +33,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20, help="iterations per timed window")
     ap.add_argument("--reps", type=int, default=7, help="timed windows per route")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--ema-decay", type=float, default=None, help="add route (f): the guarded owned optimizer with this weight-EMA decay")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_iter_time.jsonl"))
     a = ap.parse_args()
 
@@ -81,6 +83,13 @@ def main():
     routes = [("parent_route", it_a, a.steps), ("owned", sb.step, a.steps), ("owned_guarded", sc.step, a.steps),
               ("grad_norm", lambda: K.check(K.lib.lavt_grad_norm(K.ptr(desc), K.ptr(chunks), nchunks, K.ptr(ws), K.ptr(ctl), 1.0, 1, K.stream())), 25 * a.steps),
               ("torch_norm", lambda: torch.linalg.vector_norm(flat), 25 * a.steps)]
+    if a.ema_decay is not None:
+        sf, of = harness(True, max_grad_norm=1.0, skip_nonfinite=True, ema_decay=a.ema_decay)
+        routes.append(("owned_guarded_ema", sf.step, a.steps))
+    # route (a)'s descriptor tables were built before the later harnesses laid out their flat gradient buffers (ddp.layout_generation is process-wide):
+    # one step with the host-side check rebuilds them, outside the timed windows
+    sa.step()
+    oa.step()
     for _, fn, _n in routes:
         for _ in range(a.warmup):
             fn()
@@ -100,6 +109,8 @@ def main():
              "owned_guarded": {"optimizer_steps": oc.steps_taken(), "skipped_steps": oc.skipped_steps(), "grad_norm": oc.last_grad_norm()},
              "grad_norm": {"elements": norm_elems, "bytes": 4 * norm_elems, "norm": float(ctl[0])},
              "torch_norm": {"elements": flat.numel(), "bytes": 4 * flat.numel(), "norm": float(torch.linalg.vector_norm(flat))}}
+    if a.ema_decay is not None:
+        extra["owned_guarded_ema"] = {"optimizer_steps": of.steps_taken(), "skipped_steps": of.skipped_steps(), "ema_decay": a.ema_decay}
     lines = []
     for name, _, n in routes:
         ts = times[name]
