@@ -756,6 +756,38 @@ int lavt_resize_norm_u8(const uint8_t* src, int64_t frame_stride, int N, int Hs,
 int lavt_resize_nearest_u8(const uint8_t* src, int64_t frame_stride, int N, int Hs, int Ws, const int32_t* idx_y, const int32_t* idx_x, int64_t* out, int Ho,
                            int Wo, void* stream);
 
+/* Batched form for sources of MIXED sizes (a training batch of RefCOCO / COCO images; lavt_hip/preprocess.py: pack_batch, BatchPreprocessor): one
+ * launch for all output frames.  New symbols only, added under ABI v7.
+ *
+ * lavt_pp_item_t: one descriptor per OUTPUT frame, 64 bytes.  An image descriptor names its source (src_off: byte offset of an Hs x Ws x 3 HWC
+ *   image in the pixel buffer; any alignment) and its four tables as ELEMENT offsets into one int32 table buffer: coef_x [Wo][ksize_x],
+ *   bounds_x [Wo][2], coef_y [Ho][ksize_y], bounds_y [Ho][2] (the tables of lavt_resize_norm_u8).  A target descriptor names its mask (mask_off:
+ *   byte offset of an Hs x Ws mask in the mask buffer) and its nearest-index tables idx_y [Ho], idx_x [Wo].  Fields a launch does not use are
+ *   ignored by it.  Several descriptors may name the same source and the same tables; their order is free (output frame i = descriptor i).
+ * lavt_resize_norm_u8_batch: n image descriptors -> out fp32 [n][3][Ho][Wo], the arithmetic of lavt_resize_norm_u8.  items / tables / pixels are
+ *   device memory; items_host / tables_host are the same descriptors and tables in HOST memory (they are packed there).  From the host copy the
+ *   entry checks, before launching: 1 <= n <= 65535; every source lies inside pixel_bytes; every table lies inside table_elems; ksize > 0; every
+ *   bounds row is a tap range inside its source (0 <= first, 0 <= taps <= ksize, first + taps <= size); bounds_y is non-decreasing in first and in
+ *   first + taps.  It picks ONE tile height for the launch, the largest of 16, 8, 4, 2, 1 whose worst source-row span over all items keeps the LDS
+ *   request (192 bytes per source row) within 64 KB.  LAVT_ERR_INVALID with a message, and no launch, when any check fails or a single output row of
+ *   some item does not fit.  The kernel repeats the range checks on what it reads from device memory: a descriptor or table that does not belong
+ *   causes no read outside the buffers and no write.
+ * lavt_resize_nearest_u8_batch: n target descriptors -> out int64 [n][Ho][Wo] = mask[idx_y[y]][idx_x[x]].  Checked from the host copy: n >= 1,
+ *   every mask inside mask_bytes, every table inside table_elems, every index inside its mask. */
+typedef struct lavt_pp_item {
+    int64_t src_off, mask_off;
+    int32_t Hs, Ws;
+    int32_t coef_x, bounds_x, ksize_x;
+    int32_t coef_y, bounds_y, ksize_y;
+    int32_t idx_y, idx_x;
+    int32_t reserved0, reserved1;
+} lavt_pp_item_t;
+int lavt_resize_norm_u8_batch(const lavt_pp_item_t* items, const lavt_pp_item_t* items_host, int n, const int32_t* tables, const int32_t* tables_host,
+                              int64_t table_elems, const uint8_t* pixels, int64_t pixel_bytes, float* out, int Ho, int Wo, float mean0, float mean1,
+                              float mean2, float std0, float std1, float std2, void* stream);
+int lavt_resize_nearest_u8_batch(const lavt_pp_item_t* items, const lavt_pp_item_t* items_host, int n, const int32_t* tables, const int32_t* tables_host,
+                                 int64_t table_elems, const uint8_t* masks, int64_t mask_bytes, int64_t* out, int Ho, int Wo, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Text side (lavt_one / lavt_video carry BERT inside the model: lib/_utils.py:38-52; train.py:595-602; the encoder is HF transformers
  * 3.0.2 `BertModel`, absent from the reference tree).  Its Linear / LayerNorm / GELU / attention GEMMs use the entry points above.

@@ -21,18 +21,16 @@ __device__ __forceinline__ uint32_t pp_round_clip(uint32_t acc) {
 // One work-group = TH x 64 output pixels of one frame, 256 threads = 4 waves.  Lane = x within the tile in both passes.
 //   pass 1: source rows y0 .. y1 (what the tile's output rows read) resampled along x into LDS as uint8 [row][c][x]
 //   pass 2: output (row, channel) pairs, one per wave at a time, resampled along y out of LDS, normalised, stored along x
-__global__ __launch_bounds__(256) void resize_norm_u8_kernel(const uint8_t* __restrict__ src, int64_t frame_stride, int Hs, int Ws,
-                                                             const int32_t* __restrict__ coef_x, const int32_t* __restrict__ bounds_x, int ksize_x,
-                                                             const int32_t* __restrict__ coef_y, const int32_t* __restrict__ bounds_y, int ksize_y,
-                                                             float* __restrict__ out, int Ho, int Wo, int TH, int lds_rows, Norm3 nm) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t rows[];
+// `frame` = the work-group's source, `plane` = its output frame: everything here is block-uniform, and so are the exits in front of the barrier.
+__device__ __forceinline__ void pp_tile(const uint8_t* __restrict__ frame, int Hs, int Ws, const int32_t* __restrict__ coef_x, const int32_t* __restrict__ bounds_x, int ksize_x,
+                                        const int32_t* __restrict__ coef_y, const int32_t* __restrict__ bounds_y, int ksize_y, float* __restrict__ plane, int Ho, int Wo,
+                                        int TH, int lds_rows, const Norm3& nm, uint8_t* rows) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x = blockIdx.x * PP_TW + lane;
     const int r0 = blockIdx.y * TH, r1 = min(r0 + TH, Ho) - 1;          // first / last output row of the tile
     const int y0 = bounds_y[2 * r0], y1 = bounds_y[2 * r1] + bounds_y[2 * r1 + 1];          // xmin and xmin + n are non-decreasing in the output index
     const int span = y1 - y0;
     if (span > lds_rows || y0 < 0 || y1 > Hs) return;          // tables that do not belong to this launch: nothing is written (block-uniform)
-    const uint8_t* frame = src + (int64_t)blockIdx.z * frame_stride;
 
     if (x < Wo) {
         const int xmin = bounds_x[2 * x], nx = bounds_x[2 * x + 1];
@@ -56,7 +54,6 @@ __global__ __launch_bounds__(256) void resize_norm_u8_kernel(const uint8_t* __re
     __syncthreads();
     if (x >= Wo) return;
     const int nrows = r1 - r0 + 1;
-    float* plane = out + (int64_t)blockIdx.z * 3 * Ho * Wo;
     for (int j = wave; j < nrows * 3; j += 4) {
         const int ty = j / 3, c = j - ty * 3, y = r0 + ty;
         const int ymin = bounds_y[2 * y], ny = bounds_y[2 * y + 1];
@@ -71,6 +68,15 @@ __global__ __launch_bounds__(256) void resize_norm_u8_kernel(const uint8_t* __re
     }
 }
 
+__global__ __launch_bounds__(256) void resize_norm_u8_kernel(const uint8_t* __restrict__ src, int64_t frame_stride, int Hs, int Ws,
+                                                             const int32_t* __restrict__ coef_x, const int32_t* __restrict__ bounds_x, int ksize_x,
+                                                             const int32_t* __restrict__ coef_y, const int32_t* __restrict__ bounds_y, int ksize_y,
+                                                             float* __restrict__ out, int Ho, int Wo, int TH, int lds_rows, Norm3 nm) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t rows[];
+    pp_tile(src + (int64_t)blockIdx.z * frame_stride, Hs, Ws, coef_x, bounds_x, ksize_x, coef_y, bounds_y, ksize_y, out + (int64_t)blockIdx.z * 3 * Ho * Wo, Ho, Wo, TH, lds_rows,
+            nm, rows);
+}
+
 __global__ __launch_bounds__(256) void resize_nearest_u8_kernel(const uint8_t* __restrict__ src, int64_t frame_stride, int Hs, int Ws, const int32_t* __restrict__ idx_y,
                                                                 const int32_t* __restrict__ idx_x, int64_t* __restrict__ out, int Ho, int Wo, int64_t total) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -81,7 +87,124 @@ __global__ __launch_bounds__(256) void resize_nearest_u8_kernel(const uint8_t* _
     }
 }
 
+// ---- batched form: sources of mixed sizes, one descriptor per output frame (lavt_pp_item_t), every table an element offset into one int32 buffer ----
+static_assert(sizeof(lavt_pp_item_t) == 64 && alignof(lavt_pp_item_t) == 8, "lavt_pp_item_t is 64 bytes (lavt_hip/_capi.py: PPItem, lavt_hip/preprocess.py: ITEM_DTYPE)");
+
+// [off, off + len) lies inside a buffer of `total` elements
+__host__ __device__ __forceinline__ bool pp_inside(int64_t off, int64_t len, int64_t total) { return off >= 0 && len >= 0 && off <= total - len; }
+
+__host__ __device__ __forceinline__ bool pp_image_item_inside(const lavt_pp_item_t& it, int Ho, int Wo, int64_t table_elems, int64_t pixel_bytes) {
+    return it.Hs > 0 && it.Ws > 0 && it.ksize_x > 0 && it.ksize_y > 0 && pp_inside(it.src_off, (int64_t)it.Hs * it.Ws * 3, pixel_bytes) &&
+           pp_inside(it.coef_x, (int64_t)Wo * it.ksize_x, table_elems) && pp_inside(it.bounds_x, 2 * (int64_t)Wo, table_elems) &&
+           pp_inside(it.coef_y, (int64_t)Ho * it.ksize_y, table_elems) && pp_inside(it.bounds_y, 2 * (int64_t)Ho, table_elems);
+}
+
+__host__ __device__ __forceinline__ bool pp_target_item_inside(const lavt_pp_item_t& it, int Ho, int Wo, int64_t table_elems, int64_t mask_bytes) {
+    return it.Hs > 0 && it.Ws > 0 && pp_inside(it.mask_off, (int64_t)it.Hs * it.Ws, mask_bytes) && pp_inside(it.idx_y, Ho, table_elems) &&
+           pp_inside(it.idx_x, Wo, table_elems);
+}
+
+// pp_tile with blockIdx.z = the descriptor: Hs, Ws, both ksize and the source-row span differ between the work-groups of one launch; TH and lds_rows
+// are the launch's (the entry sized them for the worst item).  Everything read from the descriptor is block-uniform, so are the exits.
+__global__ __launch_bounds__(256) void resize_norm_u8_batch_kernel(const lavt_pp_item_t* __restrict__ items, const int32_t* __restrict__ tables, int64_t table_elems,
+                                                                   const uint8_t* __restrict__ pixels, int64_t pixel_bytes, float* __restrict__ out, int Ho, int Wo,
+                                                                   int TH, int lds_rows, Norm3 nm) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t rows[];
+    const lavt_pp_item_t it = items[blockIdx.z];
+    if (!pp_image_item_inside(it, Ho, Wo, table_elems, pixel_bytes)) return;          // a descriptor that does not belong to these buffers: nothing is read, nothing written
+    pp_tile(pixels + it.src_off, it.Hs, it.Ws, tables + it.coef_x, tables + it.bounds_x, it.ksize_x, tables + it.coef_y, tables + it.bounds_y, it.ksize_y,
+            out + (int64_t)blockIdx.z * 3 * Ho * Wo, Ho, Wo, TH, lds_rows, nm, rows);
+}
+
+__global__ __launch_bounds__(256) void resize_nearest_u8_batch_kernel(const lavt_pp_item_t* __restrict__ items, const int32_t* __restrict__ tables, int64_t table_elems,
+                                                                      const uint8_t* __restrict__ masks, int64_t mask_bytes, int64_t* __restrict__ out, int Ho, int Wo,
+                                                                      int64_t total) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int xo = (int)(i % Wo), yo = (int)((i / Wo) % Ho);
+        const lavt_pp_item_t it = items[i / ((int64_t)Wo * Ho)];
+        if (!pp_target_item_inside(it, Ho, Wo, table_elems, mask_bytes)) continue;          // a descriptor that does not belong to these buffers: its frame is not written
+        const int ys = min(max(tables[it.idx_y + yo], 0), it.Hs - 1), xs = min(max(tables[it.idx_x + xo], 0), it.Ws - 1);          // never read outside the mask
+        out[i] = masks[it.mask_off + (int64_t)ys * it.Ws + xs];
+    }
+}
+
 }  // namespace
+
+extern "C" int lavt_resize_norm_u8_batch(const lavt_pp_item_t* items, const lavt_pp_item_t* items_host, int n, const int32_t* tables, const int32_t* tables_host,
+                                         int64_t table_elems, const uint8_t* pixels, int64_t pixel_bytes, float* out, int Ho, int Wo, float mean0, float mean1,
+                                         float mean2, float std0, float std1, float std2, void* stream) {
+    LAVT_CHECK_ARG(items && items_host && tables && tables_host && pixels && out, "lavt_resize_norm_u8_batch: null pointer");
+    LAVT_CHECK_ARG(n > 0 && n <= 65535 && Ho > 0 && Wo > 0 && table_elems > 0 && pixel_bytes > 0, "lavt_resize_norm_u8_batch: bad sizes (1 <= n <= 65535)");
+    LAVT_CHECK_ARG(std0 != 0.f && std1 != 0.f && std2 != 0.f, "lavt_resize_norm_u8_batch: std must be nonzero");
+    for (int i = 0; i < n; ++i) {
+        const lavt_pp_item_t& it = items_host[i];
+        LAVT_CHECK_ARG(it.Hs > 0 && it.Ws > 0 && it.ksize_x > 0 && it.ksize_y > 0, "lavt_resize_norm_u8_batch: item %d: source %d x %d with %d / %d taps: all must be positive", i,
+                       it.Hs, it.Ws, it.ksize_x, it.ksize_y);
+        LAVT_CHECK_ARG(pp_inside(it.src_off, (int64_t)it.Hs * it.Ws * 3, pixel_bytes), "lavt_resize_norm_u8_batch: item %d: a %d x %d x 3 source at byte offset %lld lies outside the %lld bytes of pixels",
+                       i, it.Hs, it.Ws, (long long)it.src_off, (long long)pixel_bytes);
+        LAVT_CHECK_ARG(pp_image_item_inside(it, Ho, Wo, table_elems, pixel_bytes),
+                       "lavt_resize_norm_u8_batch: item %d: a table (coef_x %d, bounds_x %d, coef_y %d, bounds_y %d; %d / %d taps) lies outside the %lld table elements", i, it.coef_x,
+                       it.bounds_x, it.coef_y, it.bounds_y, it.ksize_x, it.ksize_y, (long long)table_elems);
+        const int32_t *bx = tables_host + it.bounds_x, *by = tables_host + it.bounds_y;
+        for (int x = 0; x < Wo; ++x)
+            LAVT_CHECK_ARG(bx[2 * x] >= 0 && bx[2 * x + 1] >= 0 && bx[2 * x + 1] <= it.ksize_x && bx[2 * x] + bx[2 * x + 1] <= it.Ws,
+                           "lavt_resize_norm_u8_batch: item %d: bounds_x[%d] = (%d, %d) is not a column range of a %d-column source with %d taps", i, x, bx[2 * x], bx[2 * x + 1], it.Ws,
+                           it.ksize_x);
+        for (int y = 0; y < Ho; ++y) {
+            const int ymin = by[2 * y], t = by[2 * y + 1];
+            LAVT_CHECK_ARG(ymin >= 0 && t >= 0 && t <= it.ksize_y && ymin + t <= it.Hs && (y == 0 || (ymin >= by[2 * y - 2] && ymin + t >= by[2 * y - 2] + by[2 * y - 1])),
+                           "lavt_resize_norm_u8_batch: item %d: bounds_y[%d] = (%d, %d) is not a row range of a %d-row source with %d taps", i, y, ymin, t, it.Hs, it.ksize_y);
+        }
+    }
+    // one tile height for the launch: the largest whose source-row span fits the LDS request for EVERY item
+    int TH = 0, lds_rows = 0, worst_item = 0;
+    for (int th = 16; th >= 1 && !TH; th >>= 1) {
+        int worst = 0;
+        for (int i = 0; i < n; ++i) {
+            const int32_t* by = tables_host + items_host[i].bounds_y;
+            for (int r0 = 0; r0 < Ho; r0 += th) {
+                const int r1 = (r0 + th < Ho ? r0 + th : Ho) - 1;
+                const int span = by[2 * r1] + by[2 * r1 + 1] - by[2 * r0];
+                if (span > worst) { worst = span; worst_item = i; }
+            }
+        }
+        if ((int64_t)worst * PP_ROW <= PP_LDS_MAX) { TH = th; lds_rows = worst; }
+    }
+    LAVT_CHECK_ARG(TH > 0, "lavt_resize_norm_u8_batch: item %d: %d -> %d rows: one output row reads more source rows than fit %d bytes of LDS (%d bytes each)", worst_item,
+                   items_host[worst_item].Hs, Ho, PP_LDS_MAX, PP_ROW);
+    const int gy = cdiv(Ho, TH);
+    LAVT_CHECK_ARG(gy <= 65535, "lavt_resize_norm_u8_batch: too many output rows for one launch");
+    Norm3 nm;
+    nm.mean[0] = mean0; nm.mean[1] = mean1; nm.mean[2] = mean2; nm.std[0] = std0; nm.std[1] = std1; nm.std[2] = std2;
+    const size_t lds = (size_t)(lds_rows > 0 ? lds_rows : 1) * PP_ROW;
+    hipLaunchKernelGGL(resize_norm_u8_batch_kernel, dim3(cdiv(Wo, PP_TW), gy, n), dim3(256), lds, ST, items, tables, table_elems, pixels, pixel_bytes, out, Ho, Wo, TH, lds_rows, nm);
+    LAVT_CHECK_LAUNCH("lavt_resize_norm_u8_batch");
+    return LAVT_OK;
+}
+
+extern "C" int lavt_resize_nearest_u8_batch(const lavt_pp_item_t* items, const lavt_pp_item_t* items_host, int n, const int32_t* tables, const int32_t* tables_host,
+                                            int64_t table_elems, const uint8_t* masks, int64_t mask_bytes, int64_t* out, int Ho, int Wo, void* stream) {
+    LAVT_CHECK_ARG(items && items_host && tables && tables_host && masks && out, "lavt_resize_nearest_u8_batch: null pointer");
+    LAVT_CHECK_ARG(n > 0 && n <= 65535 && Ho > 0 && Wo > 0 && table_elems > 0 && mask_bytes > 0, "lavt_resize_nearest_u8_batch: bad sizes (1 <= n <= 65535)");
+    for (int i = 0; i < n; ++i) {
+        const lavt_pp_item_t& it = items_host[i];
+        LAVT_CHECK_ARG(it.Hs > 0 && it.Ws > 0 && pp_inside(it.mask_off, (int64_t)it.Hs * it.Ws, mask_bytes),
+                       "lavt_resize_nearest_u8_batch: item %d: a %d x %d mask at byte offset %lld lies outside the %lld bytes of masks", i, it.Hs, it.Ws, (long long)it.mask_off,
+                       (long long)mask_bytes);
+        LAVT_CHECK_ARG(pp_target_item_inside(it, Ho, Wo, table_elems, mask_bytes), "lavt_resize_nearest_u8_batch: item %d: an index table (idx_y %d, idx_x %d) lies outside the %lld table elements",
+                       i, it.idx_y, it.idx_x, (long long)table_elems);
+        const int32_t *iy = tables_host + it.idx_y, *ix = tables_host + it.idx_x;
+        for (int y = 0; y < Ho; ++y)
+            LAVT_CHECK_ARG(iy[y] >= 0 && iy[y] < it.Hs, "lavt_resize_nearest_u8_batch: item %d: idx_y[%d] = %d is not a row of a %d-row mask", i, y, iy[y], it.Hs);
+        for (int x = 0; x < Wo; ++x)
+            LAVT_CHECK_ARG(ix[x] >= 0 && ix[x] < it.Ws, "lavt_resize_nearest_u8_batch: item %d: idx_x[%d] = %d is not a column of a %d-column mask", i, x, ix[x], it.Ws);
+    }
+    const int64_t total = (int64_t)n * Ho * Wo, blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(resize_nearest_u8_batch_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, ST, items, tables, table_elems, masks, mask_bytes, out, Ho, Wo,
+                       total);
+    LAVT_CHECK_LAUNCH("lavt_resize_nearest_u8_batch");
+    return LAVT_OK;
+}
 
 extern "C" int lavt_resize_norm_u8(const uint8_t* src, int64_t frame_stride, int N, int Hs, int Ws, const int32_t* coef_x, const int32_t* bounds_x, int ksize_x,
                                    const int32_t* coef_y, const int32_t* bounds_y, int ksize_y, const int32_t* bounds_y_host, float* out, int Ho, int Wo,

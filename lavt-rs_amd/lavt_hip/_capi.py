@@ -140,6 +140,12 @@ class GemmTN(C.Structure):
     ]
 
 
+class PPItem(C.Structure):
+    """lavt_pp_item_t: one output frame of the batched input stage (64 bytes; lavt_hip.preprocess.ITEM_DTYPE is the numpy form the blob is packed with)"""
+    _fields_ = [("src_off", i64), ("mask_off", i64), ("Hs", i32), ("Ws", i32), ("coef_x", i32), ("bounds_x", i32), ("ksize_x", i32),
+                ("coef_y", i32), ("bounds_y", i32), ("ksize_y", i32), ("idx_y", i32), ("idx_x", i32), ("reserved0", i32), ("reserved1", i32)]
+
+
 # every symbol include/lavt_hip.h declares, with its argument types (tests check this list against the header)
 _PROTOTYPES = {
     "lavt_abi_version": [],
@@ -273,6 +279,8 @@ _PROTOTYPES = {
     "lavt_upsample_mask": [i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "lavt_resize_norm_u8": [vp, i64, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, vp],
     "lavt_resize_nearest_u8": [vp, i64, i32, i32, i32, vp, vp, vp, i32, i32, vp],
+    "lavt_resize_norm_u8_batch": [vp, vp, i32, vp, vp, i64, vp, i64, vp, i32, i32, f32, f32, f32, f32, f32, f32, vp],
+    "lavt_resize_nearest_u8_batch": [vp, vp, i32, vp, vp, i64, vp, i64, vp, i32, i32, vp],
     # deterministic forms (no float atomics): the host calls them instead of their siblings in deterministic mode
     "lavt_gemm_tn_v2_eligible": [C.POINTER(GemmTN)],
     "lavt_reduce_partials_det_stage": [i32],

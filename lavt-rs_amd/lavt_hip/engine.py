@@ -102,7 +102,68 @@ class _ValidIndices:
         self.valid_indices.copy_(flat, non_blocking=True)
 
 
-class TrainStep(_ValidIndices):
+class _BatchInput:
+    """load_batch / stage_batch / commit_batch of TrainStep and Predictor: the static `image` (and `target`) buffers filled from a raw host batch whose
+    images all have their own size (RefCOCO / COCO) -- the reference's Resize -> ToTensor -> Normalize (transforms.py:20-31, 83-87, 106-113) on the
+    device with PIL's pixels, one upload and one launch per kind (lavt_hip.preprocess.BatchPreprocessor).  Everything runs eagerly on the current
+    stream in front of step(), as Predictor.load_frames does: nothing joins the captured graph; the host waits only for work two batches old (slot
+    reuse), so it runs up to one iteration ahead of the device."""
+    batch_preprocessor = None          # the BatchPreprocessor(network input size), made on first use (assign one for another mean / std)
+
+    def _batch_preprocessor(self):
+        from .preprocess import BatchPreprocessor
+        if self.batch_preprocessor is None:
+            self.batch_preprocessor = BatchPreprocessor((int(self.x.shape[-2]), int(self.x.shape[-1])), device=self.x.device)
+        return self.batch_preprocessor
+
+    def stage_batch(self, images, targets=None, repeat=None, *, frame_map=None, target_map=None):
+        """Pack the batch and start its upload; writes neither `image` nor `target`, so it may be called while the previous replay is still running.
+        images: host list of PIL images / uint8 (Hs, Ws, 3) arrays, one per frame of the image buffer (B, or B*T for a clip buffer (B, T, 3, H, W),
+        which is written as B*T frames); repeat=T: B still images, each repeated into a T-frame clip (`--pseudo_video_aug vanilla`, args.py:132-134).
+        targets: host list of masks for a `target` buffer of network-input size, as many as it holds -- with `valid_indices` that is nsel, one mask per
+        selected frame; under `repeat`, as many masks as the buffer holds are taken one to one, B masks for a buffer of B*T are repeated like the
+        images.  frame_map / target_map: the source of every output frame / mask, for any other arrangement.
+        ValueError for wrong counts or a target buffer of another size, TypeError for CUDA input, RuntimeError inside a graph capture: in every case
+        before anything is written."""
+        from .preprocess import _BatchPlan
+        who = f"{type(self).__name__}.stage_batch"
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{who}: the input stage runs eagerly in front of step() (a host-side pack and an upload): call it outside the graph capture")
+        H, W = int(self.x.shape[-2]), int(self.x.shape[-1])
+        if targets is not None:
+            if self.t is None:
+                raise ValueError(f"{who}: targets given, but there is no target buffer")
+            if tuple(self.t.shape[-2:]) != (H, W):
+                raise ValueError(f"{who}: the target buffer is {tuple(self.t.shape[-2:])}, not the network input size {(H, W)} (the via_size / out_size flow keeps "
+                                 "targets at the original frame size): copy those into `target` yourself")
+            if repeat is not None and target_map is None and isinstance(targets, (list, tuple)) and len(targets) == self.t.shape[0]:
+                target_map = range(len(targets))          # one mask per target sample already (valid_indices: the annotated frame of every clip)
+        plan = _BatchPlan(images, targets, (H, W), frame_map, target_map, repeat)
+        L = plan.layout
+        if L.n_frames != self._n_frames():
+            raise ValueError(f"{who}: {L.n_frames} frames for an image buffer of {self._n_frames()} ({tuple(self.x.shape)})")
+        if L.n_targets and L.n_targets != self.t.shape[0]:
+            raise ValueError(f"{who}: {L.n_targets} target masks for a target buffer of {self.t.shape[0]}")
+        self._batch_preprocessor()._stage(plan)
+
+    def commit_batch(self):
+        """Launch the kernels of the staged batch into `image` (and `target`, when targets were staged) on the current stream -- the stream step()
+        replays on, so they run after the previous replay and before the next."""
+        who = f"{type(self).__name__}.commit_batch"
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{who}: the input stage runs eagerly in front of step(): call it outside the graph capture")
+        pp = self.batch_preprocessor
+        if pp is None or pp._staged is None:
+            raise RuntimeError(f"{who}: no staged batch (call stage_batch() first; a batch is committed once)")
+        pp.commit(self.x, self.t if pp._staged[1].n_targets else None)
+
+    def load_batch(self, images, targets=None, repeat=None, *, frame_map=None, target_map=None):
+        """stage_batch + commit_batch"""
+        self.stage_batch(images, targets, repeat, frame_map=frame_map, target_map=target_map)
+        self.commit_batch()
+
+
+class TrainStep(_ValidIndices, _BatchInput):
     def __init__(self, model, image, l_feats, l_mask, target, world=1, use_graph=True, bucket_mib=32.0, fused_loss=True, refresh_weights_in_step=False, context=None,
                  *, loss="ce", valid_indices=None, dice_rate=1.0, boundary_rate=0.05, deterministic=None, accumulate=1):
         """context: the ops.StepContext this harness keeps its state in (gradient sinks, deferred-launch queues, weight copies, scratch).  None = the
@@ -560,7 +621,7 @@ class TrainStep(_ValidIndices):
         return self.loss
 
 
-class Predictor(_ValidIndices):
+class Predictor(_ValidIndices, _BatchInput):
     """The inference sibling of TrainStep: the reference's evaluation loop body (test.py:60-83, test_ytvos.py:230-260)
 
         model.eval(); with torch.no_grad(): out = model(image, l, l_mask); mask = out.argmax(1); I, U = computeIoU(mask, target)

@@ -16,6 +16,7 @@ import weakref
 from dataclasses import dataclass
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _capi as K
@@ -3251,4 +3252,38 @@ def resize_nearest_u8(src, out):
     iy, ix = P.device_nearest_table(Hs, Ho, src.device), P.device_nearest_table(Ws, Wo, src.device)
     _note(f"resize-nearest {N}x{Hs}x{Ws}->{Ho}x{Wo}", nbytes=N * (Hs * Ws + 8 * Ho * Wo))
     K.check(K.lib.lavt_resize_nearest_u8(K.ptr(src), stride, N, Hs, Ws, K.ptr(iy), K.ptr(ix), K.ptr(out), Ho, Wo, K.stream()))
+    return out
+
+
+def _packed_batch(who, blob, blob_host, layout, out, n, shape, dtype):
+    if not isinstance(blob, torch.Tensor) or not blob.is_cuda or not out.is_cuda:
+        raise RuntimeError(f"liblavt_hip operates on GPU memory only (got a CPU tensor for `{who}`); there is no CPU fallback")
+    if blob.dtype != torch.uint8 or not blob.is_contiguous() or blob.numel() < layout.nbytes or blob_host.dtype != np.uint8 or blob_host.size < layout.nbytes or not blob_host.flags.c_contiguous:
+        raise ValueError(f"{who}: the blob and its host copy must be contiguous uint8 of at least {layout.nbytes} bytes, got {tuple(blob.shape)} on the device and {blob_host.shape} on the host")
+    if out.dtype != dtype or not out.is_contiguous() or tuple(out.shape) != (n,) + shape:
+        raise ValueError(f"{who}: out must be contiguous {dtype} {(n,) + shape} for the {n} descriptors of the layout, got {out.dtype} {tuple(out.shape)}")
+    return blob.data_ptr(), blob_host.ctypes.data
+
+
+def resize_normalize_u8_batch(blob, blob_host, layout, out, mean, std):
+    """resize_normalize_u8 for sources of mixed sizes, one launch: `blob` is a packed batch (lavt_hip.preprocess.pack_batch: descriptors, int32 tables,
+    pixels) on the device, `blob_host` the same bytes on the host (a uint8 numpy array: the C entry validates descriptors and tables from it before it
+    launches), `layout` the record pack_batch returned -> out fp32 (n_frames, 3, Ho, Wo), written in place."""
+    Ho, Wo = layout.out_size
+    d, h = _packed_batch("resize_normalize_u8_batch", blob, blob_host, layout, out, layout.n_frames, (3, Ho, Wo), torch.float32)
+    _note(f"resize-norm-batch {layout.n_frames}->{Ho}x{Wo}", nbytes=layout.pixel_bytes + layout.n_frames * 12 * Ho * Wo)
+    K.check(K.lib.lavt_resize_norm_u8_batch(d + layout.items_off, h + layout.items_off, layout.n_frames, d + layout.tables_off, h + layout.tables_off, layout.table_elems,
+                                            d + layout.pixels_off, layout.pixel_bytes, K.ptr(out), Ho, Wo, *(float(v) for v in mean), *(float(v) for v in std), K.stream()))
+    return out
+
+
+def resize_nearest_u8_batch(blob, blob_host, layout, out):
+    """resize_nearest_u8 for masks of mixed sizes, one launch, from the same packed batch -> out int64 (n_targets, Ho, Wo), written in place"""
+    Ho, Wo = layout.out_size
+    if layout.n_targets < 1:
+        raise ValueError("resize_nearest_u8_batch: the batch was packed without targets")
+    d, h = _packed_batch("resize_nearest_u8_batch", blob, blob_host, layout, out, layout.n_targets, (Ho, Wo), torch.int64)
+    _note(f"resize-nearest-batch {layout.n_targets}->{Ho}x{Wo}", nbytes=layout.mask_bytes + layout.n_targets * 8 * Ho * Wo)
+    K.check(K.lib.lavt_resize_nearest_u8_batch(d + layout.titems_off, h + layout.titems_off, layout.n_targets, d + layout.tables_off, h + layout.tables_off, layout.table_elems,
+                                               d + layout.masks_off, layout.mask_bytes, K.ptr(out), Ho, Wo, K.stream()))
     return out

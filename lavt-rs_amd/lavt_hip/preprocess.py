@@ -10,9 +10,14 @@ The passes run width first, then height, as the recipe says.  That is what PIL r
 times taller than wide that is downscaled along its height, Pillow 12.2 was seen to return the height-first result instead (off by one on some
 pixels).  Such strips are outside what this module reproduces.
 
+Sources of mixed sizes -- a training batch of RefCOCO / COCO images -- go through the batched stage at the end of this module: `pack_batch` lays images,
+masks, the tables they need and one descriptor per output frame out as ONE blob, `BatchPreprocessor` uploads it in one copy and runs one launch per
+kind (`lavt_resize_norm_u8_batch`, `lavt_resize_nearest_u8_batch`); `apply_packed_numpy` reads a blob as the kernels do, for tests.
+
 This module is host logic: it imports without the shared library and without a GPU.  Everything that touches pixels runs in HIP; there is no CPU
 fallback (transforms.get_transform is the CPU pipeline, unchanged)."""
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -202,6 +207,368 @@ class FramePreprocessor:
             out = torch.empty(N, Ho, Wo, dtype=torch.int64, device=src.device)
         ops.resize_nearest_u8(src, _as_frames(out, (N, Ho, Wo), torch.int64, "targets"))
         return out
+
+
+# ================================================================================================ batched input stage: sources of mixed sizes
+# One training batch (RefCOCO / COCO: every image has its own size) is packed on the host into ONE blob -- descriptors, int32 tables, pixels, masks --
+# uploaded in one copy and resized by one launch per kind (lavt_resize_norm_u8_batch, lavt_resize_nearest_u8_batch; DESIGN.md "Batched input stage").
+ITEM_DTYPE = np.dtype([("src_off", "<i8"), ("mask_off", "<i8"), ("Hs", "<i4"), ("Ws", "<i4"), ("coef_x", "<i4"), ("bounds_x", "<i4"), ("ksize_x", "<i4"),
+                       ("coef_y", "<i4"), ("bounds_y", "<i4"), ("ksize_y", "<i4"), ("idx_y", "<i4"), ("idx_x", "<i4"), ("reserved0", "<i4"), ("reserved1", "<i4")])
+assert ITEM_DTYPE.itemsize == 64          # lavt_pp_item_t (include/lavt_hip.h)
+SECTION_ALIGN = 16
+
+
+class BatchLayout(NamedTuple):
+    """Where the sections of a packed batch lie.  Offsets are bytes from the start of the blob, every section starts 16-byte aligned; the offsets
+    INSIDE descriptors are relative to their section (bytes into pixels / masks, int32 elements into tables)."""
+    nbytes: int             # the blob: descriptors | tables | pixels | masks
+    out_size: tuple         # (Ho, Wo)
+    n_frames: int           # image descriptors = output frames
+    n_targets: int          # target descriptors = output masks (0: packed without targets)
+    items_off: int          # image descriptors, ITEM_DTYPE [n_frames]
+    titems_off: int         # target descriptors, ITEM_DTYPE [n_targets]
+    tables_off: int
+    table_elems: int
+    pixels_off: int         # the images, HWC, back to back (odd offsets are normal)
+    pixel_bytes: int
+    masks_off: int
+    mask_bytes: int
+    tables: tuple           # (("resample" | "nearest", in, out), element offset) of every stored table: one per distinct size pair
+
+
+def _align(n):
+    return -(-n // SECTION_ALIGN) * SECTION_ALIGN
+
+
+def _host_u8(x, channels, what):
+    """one host image (H, W, 3) / mask (H, W) as a uint8 array; device data is refused with the route that takes it"""
+    if isinstance(x, torch.Tensor):
+        if x.is_cuda:
+            raise TypeError(f"{what}: got a CUDA tensor; the batched input stage packs HOST data (PIL images, uint8 arrays) into one upload -- "
+                            "FramePreprocessor.images / .targets is the route for data that is already on the device")
+        x = x.numpy()
+    a = np.asarray(x)
+    if a.dtype != np.uint8:
+        raise TypeError(f"{what}: must be uint8, got {a.dtype}")
+    if (a.ndim != 3 or a.shape[2] != 3) if channels else a.ndim != 2:
+        raise ValueError(f"{what}: expected {'(H, W, 3) RGB' if channels else '(H, W)'}, got shape {a.shape}")
+    if min(a.shape[:2]) < 1:
+        raise ValueError(f"{what}: empty input {a.shape}")
+    return a
+
+
+def _host_list(xs, channels, what):
+    if isinstance(xs, torch.Tensor) and xs.is_cuda:
+        _host_u8(xs, channels, what)
+    if isinstance(xs, np.ndarray) and xs.ndim == (3 if channels else 2):
+        xs = [xs]          # a single image / mask
+    return [_host_u8(x, channels, f"{what}[{i}]") for i, x in enumerate(xs)]
+
+
+def _source_map(m, n_src, what):
+    m = [int(v) for v in m]
+    bad = [v for v in m if not 0 <= v < n_src]
+    if bad or not m:
+        raise ValueError(f"pack_batch: {what} must name sources 0..{n_src - 1} for at least one output frame, got {m}")
+    return m
+
+
+class _BatchPlan:
+    """a batch laid out but not yet written: `layout`, and `write(buf)` that fills the first layout.nbytes bytes of a uint8 array"""
+
+    def __init__(self, images, targets, out_size, frame_map, target_map, repeat):
+        Ho, Wo = (int(out_size), int(out_size)) if isinstance(out_size, int) else (int(out_size[0]), int(out_size[1]))
+        if min(Ho, Wo) < 1:
+            raise ValueError(f"pack_batch: out_size must be positive, got {(Ho, Wo)}")
+        self.images = _host_list(images, True, "pack_batch: images")
+        self.masks = _host_list(targets, False, "pack_batch: targets") if targets is not None else []
+        if not self.images:
+            raise ValueError("pack_batch: no images")
+        if targets is not None and not self.masks:
+            raise ValueError("pack_batch: an empty list of targets (pass None for none)")
+        if repeat is not None:
+            T = int(repeat)
+            if T < 1 or frame_map is not None:
+                raise ValueError("pack_batch: repeat must be >= 1 and stands in place of frame_map")
+            frame_map = [i for i in range(len(self.images)) for _ in range(T)]
+            if target_map is None and self.masks:
+                target_map = [i for i in range(len(self.masks)) for _ in range(T)]
+        frame_map = _source_map(range(len(self.images)) if frame_map is None else frame_map, len(self.images), "frame_map")
+        if self.masks:
+            target_map = _source_map(range(len(self.masks)) if target_map is None else target_map, len(self.masks), "target_map")
+        elif target_map is not None:
+            raise ValueError("pack_batch: target_map without targets")
+        else:
+            target_map = []
+        if max(len(frame_map), len(target_map)) > 65535:
+            raise ValueError("pack_batch: at most 65535 output frames per batch")
+
+        self.tables, where, elems = [], {}, 0          # [(element offset, int32 array)]; one entry per distinct (kind, in, out)
+
+        def table(kind, n_in, n_out):
+            nonlocal elems
+            key = (kind, n_in, n_out)
+            if key not in where:
+                arrays = resample_tables(n_in, n_out) if kind == "resample" else (nearest_table(n_in, n_out),)
+                offs = []
+                for a in arrays:
+                    offs.append(elems)
+                    self.tables.append((elems, a))
+                    elems += a.size
+                where[key] = tuple(offs) + ((arrays[0].shape[1],) if kind == "resample" else ())
+            return where[key]
+
+        src_off, off = [], 0
+        for a in self.images:
+            src_off.append(off)
+            off += a.size
+        pixel_bytes = off
+        mask_off, off = [], 0
+        for a in self.masks:
+            mask_off.append(off)
+            off += a.size
+        mask_bytes = off
+
+        self.items = np.zeros(len(frame_map), dtype=ITEM_DTYPE)
+        for it, s in zip(self.items, frame_map):
+            Hs, Ws = self.images[s].shape[:2]
+            it["src_off"], it["Hs"], it["Ws"] = src_off[s], Hs, Ws
+            it["coef_x"], it["bounds_x"], it["ksize_x"] = table("resample", Ws, Wo)
+            it["coef_y"], it["bounds_y"], it["ksize_y"] = table("resample", Hs, Ho)
+        self.titems = np.zeros(len(target_map), dtype=ITEM_DTYPE)
+        for it, s in zip(self.titems, target_map):
+            Hs, Ws = self.masks[s].shape
+            it["mask_off"], it["Hs"], it["Ws"] = mask_off[s], Hs, Ws
+            it["idx_y"], it["idx_x"] = table("nearest", Hs, Ho)[0], table("nearest", Ws, Wo)[0]
+        if elems >= 2 ** 31:
+            raise ValueError("pack_batch: the tables of this batch exceed 2^31 elements")
+
+        items_off = 0
+        titems_off = _align(items_off + self.items.nbytes)
+        tables_off = _align(titems_off + self.titems.nbytes)
+        pixels_off = _align(tables_off + 4 * elems)
+        masks_off = _align(pixels_off + pixel_bytes)
+        self.layout = BatchLayout(nbytes=_align(masks_off + mask_bytes), out_size=(Ho, Wo), n_frames=len(frame_map), n_targets=len(target_map), items_off=items_off,
+                                  titems_off=titems_off, tables_off=tables_off, table_elems=elems, pixels_off=pixels_off, pixel_bytes=pixel_bytes, masks_off=masks_off,
+                                  mask_bytes=mask_bytes, tables=tuple((k, v[0]) for k, v in where.items()))
+        self._src_off, self._mask_off = src_off, mask_off
+
+    def write(self, buf):
+        L = self.layout
+        if buf.dtype != np.uint8 or buf.ndim != 1 or buf.size < L.nbytes:
+            raise ValueError(f"pack_batch: the destination must be a flat uint8 array of at least {L.nbytes} bytes")
+        buf[L.items_off:L.items_off + self.items.nbytes] = self.items.view(np.uint8)
+        buf[L.titems_off:L.titems_off + self.titems.nbytes] = self.titems.view(np.uint8)
+        for off, a in self.tables:
+            buf[L.tables_off + 4 * off:L.tables_off + 4 * (off + a.size)] = a.reshape(-1).view(np.uint8)
+        for off, a in zip(self._src_off, self.images):
+            buf[L.pixels_off + off:L.pixels_off + off + a.size] = a.reshape(-1)
+        for off, a in zip(self._mask_off, self.masks):
+            buf[L.masks_off + off:L.masks_off + off + a.size] = a.reshape(-1)
+
+
+def pack_batch(images, targets=None, *, out_size, frame_map=None, target_map=None, repeat=None):
+    """Pack host images (PIL or uint8 (H, W, 3) arrays, every one its own size) and optionally masks (PIL 'L' / 'P' or uint8 (H, W)) for the batched
+    kernels -> (blob, layout): one contiguous uint8 array and the BatchLayout that says where its sections and descriptors lie.
+    Sections, each 16-byte aligned: image descriptors, target descriptors, int32 tables, pixels, masks.  The tables are the cached resample_tables /
+    nearest_table, stored once per distinct (in, out) size pair of the batch.
+    frame_map[i] / target_map[i] = the source of output frame / mask i (default: identity; a source may be named more than once, in any order);
+    repeat=T is shorthand for every source T times in a row: a still image as a T-frame clip (`--pseudo_video_aug vanilla`, args.py:132-134)."""
+    plan = _BatchPlan(images, targets, out_size, frame_map, target_map, repeat)
+    blob = np.zeros(plan.layout.nbytes, dtype=np.uint8)
+    plan.write(blob)
+    return blob, plan.layout
+
+
+def _resample_rows(src, coef, bounds):
+    """the integer stage along axis 1 of src (A, B, C) by one table pair -> uint8 (A, out, C)"""
+    out = np.empty((src.shape[0], coef.shape[0], src.shape[2]), dtype=np.uint8)
+    s = src.astype(np.int64)
+    for xx in range(coef.shape[0]):
+        x0, n = int(bounds[xx, 0]), int(bounds[xx, 1])
+        acc = (1 << (PRECISION_BITS - 1)) + np.einsum("hkc,k->hc", s[:, x0:x0 + n], coef[xx, :n].astype(np.int64))
+        out[:, xx] = np.clip(acc >> PRECISION_BITS, 0, 255)
+    return out
+
+
+def apply_packed_numpy(blob, layout, mean=MEAN, std=STD, integer_stage=False):
+    """A packed batch read exactly as the kernels read it -- the descriptors and tables OF THE BLOB, the same offsets, the same integer stage, the same
+    three fp32 operations in numpy float32 -- for tests only: packing is checked without a GPU.
+    -> (images fp32 (n_frames, 3, Ho, Wo), targets int64 (n_targets, Ho, Wo) or None); integer_stage=True: images as uint8 (n_frames, Ho, Wo, 3)."""
+    L = layout
+    Ho, Wo = L.out_size
+    blob = np.asarray(blob)
+    tables = blob[L.tables_off:L.tables_off + 4 * L.table_elems].view(np.int32)
+    pixels, masks = blob[L.pixels_off:L.pixels_off + L.pixel_bytes], blob[L.masks_off:L.masks_off + L.mask_bytes]
+
+    def tab(off, rows, cols):
+        assert 0 <= off and off + rows * cols <= L.table_elems, "a table outside the table section"
+        return tables[off:off + rows * cols].reshape(rows, cols)
+
+    u8 = np.empty((L.n_frames, Ho, Wo, 3), dtype=np.uint8)
+    for i, it in enumerate(blob[L.items_off:L.items_off + 64 * L.n_frames].view(ITEM_DTYPE)):
+        Hs, Ws, o = int(it["Hs"]), int(it["Ws"]), int(it["src_off"])
+        assert 0 <= o and o + Hs * Ws * 3 <= L.pixel_bytes, "a source outside the pixel section"
+        src = pixels[o:o + Hs * Ws * 3].reshape(Hs, Ws, 3)
+        h = _resample_rows(src, tab(int(it["coef_x"]), Wo, int(it["ksize_x"])), tab(int(it["bounds_x"]), Wo, 2))
+        u8[i] = _resample_rows(h.transpose(1, 0, 2), tab(int(it["coef_y"]), Ho, int(it["ksize_y"])), tab(int(it["bounds_y"]), Ho, 2)).transpose(1, 0, 2)
+    tg = None
+    if L.n_targets:
+        tg = np.empty((L.n_targets, Ho, Wo), dtype=np.int64)
+        for i, it in enumerate(blob[L.titems_off:L.titems_off + 64 * L.n_targets].view(ITEM_DTYPE)):
+            Hs, Ws, o = int(it["Hs"]), int(it["Ws"]), int(it["mask_off"])
+            assert 0 <= o and o + Hs * Ws <= L.mask_bytes, "a mask outside the mask section"
+            m = masks[o:o + Hs * Ws].reshape(Hs, Ws)
+            tg[i] = m[tab(int(it["idx_y"]), Ho, 1)[:, 0]][:, tab(int(it["idx_x"]), Wo, 1)[:, 0]]
+    if integer_stage:
+        return u8, tg
+    v = u8.transpose(0, 3, 1, 2).astype(np.float32) / np.float32(255)
+    m32, s32 = np.asarray(mean, dtype=np.float32).reshape(1, 3, 1, 1), np.asarray(std, dtype=np.float32).reshape(1, 3, 1, 1)
+    return np.ascontiguousarray((v - m32) / s32), tg
+
+
+def collate_raw(samples):
+    """`collate_fn` of a DataLoader whose dataset returns (image, mask, ...) UNtransformed: images and masks stay lists of uint8 arrays (every one its
+    own size: what TrainStep.stage_batch / load_batch take), everything after them is collated as usual -> (images, masks, *rest)"""
+    from torch.utils.data import default_collate
+    samples = list(samples)
+    images = [_host_u8(s[0], True, f"collate_raw: image of sample {i}") for i, s in enumerate(samples)]
+    masks = [_host_u8(s[1], False, f"collate_raw: mask of sample {i}") for i, s in enumerate(samples)]
+    rest = default_collate([tuple(s[2:]) for s in samples]) if len(samples[0]) > 2 else []
+    return (images, masks, *rest)
+
+
+class BatchPreprocessor:
+    """The batched input stage: host images of mixed sizes (and masks) -> fp32 (n, 3, Ho, Wo) (and int64 (n', Ho, Wo)) on the device with one upload
+    and one launch per kind.
+
+    stage(images, targets=None, frame_map=None, target_map=None, repeat=None) packs into one of two pinned host slots and starts ONE asynchronous
+    upload on the preprocessor's own copy stream into the matching one of two device slots; it touches no output, so it may run while the consumer of
+    the previous batch's output is still busy.  commit(out_images, out_targets=None) makes the current stream wait for that upload and launches the
+    kernels into `out`.  batch(...) does both and returns the outputs.
+    Slot reuse is ordered by events: before a pinned slot is rewritten the host waits for the previous upload out of it; before a device slot is
+    overwritten the host waits for the kernels that last read it -- those of the commit before the last one, so in a steady loop the host runs at
+    most one iteration ahead of the device and never waits for the batch in flight.  Slots grow geometrically (outside any capture: stage and
+    commit refuse to run inside one)."""
+
+    def __init__(self, out_size, mean=MEAN, std=STD, device=None):
+        self.out_size = (int(out_size), int(out_size)) if isinstance(out_size, int) else (int(out_size[0]), int(out_size[1]))
+        if min(self.out_size) < 1:
+            raise ValueError(f"BatchPreprocessor: out_size must be positive, got {self.out_size}")
+        self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+        if len(self.mean) != 3 or len(self.std) != 3 or any(s == 0.0 for s in self.std):
+            raise ValueError("BatchPreprocessor: mean and std are three values each, std nonzero")
+        self.device = device
+        self._host, self._dev = [None, None], [None, None]          # pinned uint8 / device uint8, per slot
+        self._uploaded = [None, None]          # event on the copy stream: the last upload out of pinned slot i (into device slot i) has ended
+        self._consumed = [None, None]          # event on the committing stream: the kernels that last read device slot i have ended
+        self._next, self._staged, self._copy_stream = 0, None, None
+
+    def _device(self):
+        if not torch.cuda.is_available():
+            raise RuntimeError(_NO_CPU.format("no GPU is available"))
+        return torch.device(self.device if self.device is not None else f"cuda:{torch.cuda.current_device()}")
+
+    @staticmethod
+    def _not_capturing(who):
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"BatchPreprocessor.{who}: the input stage runs eagerly in front of the captured step (pinned slots, an upload on a copy stream): "
+                               "call it outside the graph capture")
+
+    def _reserve(self, slot, nbytes, dev):
+        have = 0 if self._host[slot] is None else self._host[slot].numel()
+        if have >= nbytes:
+            return
+        for ev in (self._uploaded[slot], self._consumed[slot]):          # nothing in flight may still use the buffers that are let go
+            if ev is not None:
+                ev.synchronize()
+        size = max(nbytes, 2 * have, 1 << 16)
+        self._host[slot] = torch.empty(size, dtype=torch.uint8).pin_memory()
+        self._dev[slot] = torch.empty(size, dtype=torch.uint8, device=dev)
+        self._uploaded[slot], self._consumed[slot] = None, None
+        self._copy_stream.wait_stream(torch.cuda.current_stream(dev))          # (the allocator may hand out memory the current stream still works on)
+
+    def stage(self, images, targets=None, *, frame_map=None, target_map=None, repeat=None):
+        """-> the BatchLayout of the staged batch.  A batch staged before and never committed is dropped."""
+        self._not_capturing("stage")
+        return self._stage(_BatchPlan(images, targets, self.out_size, frame_map, target_map, repeat))          # (every refusal of the input comes first)
+
+    def _stage(self, plan):
+        dev = self._device()
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(dev)
+        slot, self._next = self._next, self._next ^ 1
+        nbytes = plan.layout.nbytes
+        self._reserve(slot, nbytes, dev)
+        if self._uploaded[slot] is not None:
+            self._uploaded[slot].synchronize()          # the previous upload out of this pinned slot (long finished in a steady loop)
+        plan.write(self._host[slot].numpy())
+        cs = self._copy_stream
+        if self._consumed[slot] is not None:
+            # The kernels that last read this device slot: those of the commit before the last one.  The HOST waits for them, not the copy stream: a
+            # stream that waits for an event of the stream a captured step replays on was measured to cost every replay ~0.3 ms (DESIGN.md "Batched
+            # input stage"), a host wait nothing -- it keeps the host at most one iteration ahead of the device, with a whole replay still queued
+            self._consumed[slot].synchronize()
+        with torch.cuda.stream(cs):
+            self._dev[slot][:nbytes].copy_(self._host[slot][:nbytes], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(cs)
+        self._uploaded[slot] = ev
+        self._staged = (slot, plan.layout)
+        return plan.layout
+
+    def commit(self, out_images, out_targets=None):
+        """launch the kernels of the staged batch into `out_images` (contiguous fp32 holding (n_frames, 3, Ho, Wo); leading dimensions may be split,
+        e.g. (B, T, 3, H, W)) and `out_targets` (int64 (n_targets, Ho, Wo)) on the current stream -> (out_images, out_targets)"""
+        from . import ops
+        self._not_capturing("commit")
+        if self._staged is None:
+            raise RuntimeError("BatchPreprocessor.commit: no staged batch (call stage() first; a batch is committed once)")
+        slot, L = self._staged
+        Ho, Wo = L.out_size
+        img = _batch_out(out_images, (L.n_frames, 3, Ho, Wo), torch.float32, "out_images")
+        if (out_targets is None) != (L.n_targets == 0):
+            raise ValueError(f"BatchPreprocessor.commit: the staged batch has {L.n_targets} targets, out_targets is {'missing' if out_targets is None else 'given'}")
+        tgt = _batch_out(out_targets, (L.n_targets, Ho, Wo), torch.int64, "out_targets") if out_targets is not None else None
+        self._staged = None
+        cur = torch.cuda.current_stream(self._dev[slot].device)
+        cur.wait_event(self._uploaded[slot])
+        host = self._host[slot].numpy()
+        try:
+            ops.resize_normalize_u8_batch(self._dev[slot], host, L, img, self.mean, self.std)
+            if tgt is not None:
+                ops.resize_nearest_u8_batch(self._dev[slot], host, L, tgt)
+        finally:
+            ev = torch.cuda.Event()
+            ev.record(cur)
+            self._consumed[slot] = ev
+        return out_images, out_targets
+
+    def batch(self, images, targets=None, *, out_images=None, out_targets=None, frame_map=None, target_map=None, repeat=None):
+        """stage + commit -> (images fp32 (n_frames, 3, Ho, Wo), targets int64 (n_targets, Ho, Wo) or None), into `out_*` when given"""
+        self._not_capturing("batch")
+        plan = _BatchPlan(images, targets, self.out_size, frame_map, target_map, repeat)
+        L, dev = plan.layout, self._device()
+        Ho, Wo = L.out_size
+        if out_images is None:
+            out_images = torch.empty(L.n_frames, 3, Ho, Wo, dtype=torch.float32, device=dev)
+        if out_targets is None and L.n_targets:
+            out_targets = torch.empty(L.n_targets, Ho, Wo, dtype=torch.int64, device=dev)
+        self._stage(plan)
+        return self.commit(out_images, out_targets)
+
+
+def _batch_out(out, shape, dtype, what):
+    """_as_frames for BatchPreprocessor.commit"""
+    if not isinstance(out, torch.Tensor) or not out.is_cuda:
+        raise RuntimeError(_NO_CPU.format(f"got a CPU tensor for `{what}`"))
+    n = 1
+    for s in shape:
+        n *= s
+    if out.dtype != dtype or not out.is_contiguous() or out.numel() != n or tuple(out.shape[-2:]) != tuple(shape[-2:]):
+        raise ValueError(f"BatchPreprocessor.commit: `{what}` must be a contiguous {dtype} tensor holding {tuple(shape)} (the frames of the staged batch), "
+                         f"got {out.dtype} {tuple(out.shape)}")
+    return out.view(shape)
 
 
 def _as_frames(out, shape, dtype, what):
