@@ -713,6 +713,52 @@ int lavt_adamw_step_chunks_ema(const int64_t* desc, const int64_t* vmax /* NULL:
 int lavt_ema_swap(const int64_t* desc, const int64_t* ema, const int32_t* chunks, int nchunks, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Training meters (csrc/meters.hip; the reference's per-iteration log, train.py:231-235 and 463-500: loss.item(), IoU(output, masks),
+ * precision@X, cumulative I / U, metric_logger.update(loss=, lr=, iou=)) kept on the device: they follow graph replays and are copied out when the
+ * host wants to look.  Three new symbols under ABI v7: no existing prototype or struct changed.
+ *
+ * The meter block: lavt_meter_bytes(capacity) = 8 * LAVT_METER_HEADER_DOUBLES + capacity * LAVT_METER_RECORD_BYTES bytes of device memory, 8-byte
+ * aligned, zero-filled by the caller except header[0].  Header: fp64[LAVT_METER_HEADER_DOUBLES] (counts are whole numbers held in fp64):
+ *   [0] capacity (host; informational)      [1] hold: written by the HOST only, non-zero = an append does nothing
+ *   [2] n: records appended since the block was made = the `it` of the next record          [3] n at the last epoch reset (host)
+ *   the epoch accumulators, zeroed by the host's epoch reset:
+ *   [4] iterations          [5] sum of the finite losses    [6] their count          [7] non-finite losses (left out of [5])
+ *   [8] sum of iou          [9] cumulative I                [10] cumulative U        [11..15] seg_correct: iterations with iou >= .5, .6, .7, .8, .9
+ *   [16] applied updates    [17] skipped updates            [18] accumulating micro-steps
+ *   [19] sum of lr          [20] sum of the finite gradient norms of the records that ended a cycle    [21] their count    [22..31] reserved, zero
+ * Ring: capacity records of LAVT_METER_RECORD_BYTES bytes behind the header, record `it` in slot it % capacity:
+ *   offset 0 fp32 loss | 4 fp32 I | 8 fp32 U | 12 fp32 lr | 16 fp32 grad_norm | 20 uint32 flags | 24 fp64 iou | 32 int64 it
+ *
+ * lavt_meter_append: ONE single-writer launch at the end of an iteration, after the optimizer's tick.  stats: the fp32[4] {loss, sum of weights, I, U} of
+ * the fused criteria.  ctl: the control block of lavt_grad_norm, or NULL.  step: the optimizer's counter, or NULL.  hyper: the hyper row whose base lr is
+ * logged (fp32[5], [0] = base lr), or NULL.  Nothing at all is stored when header[1] != 0 or ctl[4] != 0.  Otherwise the record is
+ *   iou  = (I == 0 || U == 0) ? 0 : (double)I / (double)U  (train.py:64-76), seg_correct compares it in fp64 against the double literals;
+ *   lr   = hyper[0] * (total_steps > 0 ? powf(fmaxf(1 - step[0] / total_steps, 0), power) : 1) with the counter as the update's tick left it -- the lr
+ *          of the NEXT update, what optimizer.param_groups[0]["lr"] holds after lr_scheduler.step(); 0 without step or hyper;
+ *   grad_norm = ctl[0], 0 without ctl;     flags: the bits below;     it = header[2];
+ * and the accumulators move as listed.  A non-finite loss is counted in [7] and left OUT of [5] (the reference's running sum would stay NaN for the
+ * rest of the epoch); the ring keeps the raw value.  Plain stores from one lane, no atomics: launches are ordered on the stream.
+ * Flags: ACCUMULATING = ctl[5] != 0 (the micro-step did not end its cycle); SKIPPED = not accumulating and ctl[2] != 0; APPLIED = a step counter was
+ * given and neither of the two; LOSS_NONFINITE = the loss is NaN / Inf.  `capacity` must be the block's.
+ *
+ * lavt_grad_norm_tensors: per-tensor sums of squares from the per-chunk partials lavt_grad_norm's first pass left in ws [nchunks] -- the chunk table
+ * lists every tensor's chunks contiguously in ascending order, so tensor t owns ws[first[t] .. first[t + 1]) (first: device int32 [count + 1]).  One
+ * launch, one wave per tensor in turn: lane l adds partials l, l + 64, ... in sequence in fp64, a fixed xor tree joins the lanes -- bit-reproducible.
+ *   out[t] = the sum (fp64; sqrt gives the norm);   bad: device int32[4] = {first non-finite tensor of this call or -1, how many were non-finite,
+ *   first non-finite tensor of the most recent call that had one (sticky: initialise to -1), reserved}.
+ * ctl[4] != 0 (hold) or ctl[5] != 0 (accumulating): returns before any store, exactly like lavt_grad_norm (out and bad keep the last cycle's). */
+#define LAVT_METER_HEADER_DOUBLES 32
+#define LAVT_METER_RECORD_BYTES 40
+#define LAVT_METER_APPLIED 1u
+#define LAVT_METER_SKIPPED 2u
+#define LAVT_METER_ACCUMULATING 4u
+#define LAVT_METER_LOSS_NONFINITE 8u
+int64_t lavt_meter_bytes(int capacity);
+int lavt_meter_append(const float* stats, const float* ctl /* NULL */, const float* step /* NULL */, const float* hyper /* NULL */, float total_steps, float power,
+                      void* block, int capacity, void* stream);
+int lavt_grad_norm_tensors(const float* ws, int nchunks, const int32_t* first, int count, const float* ctl, double* out, int32_t* bad, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Inference path (csrc/infer.hip; reference test.py:60-110 and test_ytvos.py:230-260: batch-1 forward under model.eval() / torch.no_grad(), argmax,
  * I / U).  New symbols only, added under ABI v7: no existing prototype or struct changed.
  *

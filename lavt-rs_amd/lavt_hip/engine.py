@@ -32,6 +32,10 @@ step is bound by the ~23 ms of host-side launch work.
 
 The optimizer is the caller's by default (opt.step() after TrainStep.step()).  TrainStep.make_optimizer() / attach_optimizer() make the step OWN a
 FusedAdamW on the step's context: its update then ends the step's body, inside the same capture, and one replay is one whole training iteration.
+
+Training meters (TrainStep(meters=) / make_meters(); lavt_hip.meters): one more launch behind the optimizer's tick logs loss, lr, I, U, IoU, the gradient norm
+and the update's verdict of every step() into a ring on the device and moves the epoch accumulators of the reference's log (train.py:463-500); the host reads
+them with TrainMeters.poll(), which never waits.  Off by default: a step built without meters launches what it launched before.
 """
 import os
 import sys
@@ -165,7 +169,7 @@ class _BatchInput:
 
 class TrainStep(_ValidIndices, _BatchInput):
     def __init__(self, model, image, l_feats, l_mask, target, world=1, use_graph=True, bucket_mib=32.0, fused_loss=True, refresh_weights_in_step=False, context=None,
-                 *, loss="ce", valid_indices=None, dice_rate=1.0, boundary_rate=0.05, deterministic=None, accumulate=1):
+                 *, loss="ce", valid_indices=None, dice_rate=1.0, boundary_rate=0.05, deterministic=None, accumulate=1, meters=None):
         """context: the ops.StepContext this harness keeps its state in (gradient sinks, deferred-launch queues, weight copies, scratch).  None = the
         process-wide default context -- what the drop-in path and a single harness use.  Give every further model in the process its own
         `ops.StepContext()` (and its optimizer the same one: FusedAdamW(..., context=)): their steps can then alternate freely.
@@ -181,7 +185,10 @@ class TrainStep(_ValidIndices, _BatchInput):
         is part of the state): world > 1 and collectives forced in a 1-rank group raise NotImplementedError (DESIGN.md "Deterministic mode").
         accumulate: k >= 1 micro-batches per optimizer update (module docstring; DESIGN.md "Gradient accumulation").  1 = no accumulation: no second
         buffer, no further launch.  k > 1 needs an owned optimizer (make_optimizer / attach_optimizer) by warmup_and_capture(); the fold is element-wise,
-        so the deterministic mode keeps its promise across cycles."""
+        so the deterministic mode keeps its promise across cycles.
+        meters: a lavt_hip.meters.TrainMeters (or make_meters() later, before warmup_and_capture()): the step's body then ends with ONE more launch,
+        lavt_meter_append, which logs loss, lr, IoU, gradient norm and the update's verdict of every step() on the device (DESIGN.md "Training meters").
+        None: the launches of a step built without the argument.  Needs a fused criterion (`stats`)."""
         import operator
         try:
             k = operator.index(accumulate)
@@ -202,6 +209,9 @@ class TrainStep(_ValidIndices, _BatchInput):
         self.set_deterministic(deterministic, world=world)
         with ops.use_context(self.context):
             self._init(model, image, l_feats, l_mask, target, world, use_graph, bucket_mib, fused_loss, refresh_weights_in_step)
+        self.meters = None
+        if meters is not None:
+            self.attach_meters(meters)
 
     def _init(self, model, image, l_feats, l_mask, target, world, use_graph, bucket_mib, fused_loss, refresh_weights_in_step):
         self.model = model
@@ -277,6 +287,27 @@ class TrainStep(_ValidIndices, _BatchInput):
         import weakref
         opt._owner = weakref.ref(self)           # (FusedAdamW.load_state_dict refuses once this step is captured: state_dict / load_state_dict below)
         return opt
+
+    # ---- training meters ----
+    def make_meters(self, **kw):
+        """Build a lavt_hip.meters.TrainMeters(**kw) on the step's device, attach it and return it.  Before warmup_and_capture() only."""
+        from .meters import TrainMeters
+        kw.setdefault("device", self.x.device)
+        return self.attach_meters(TrainMeters(**kw))
+
+    def attach_meters(self, meters):
+        """Make an existing TrainMeters part of the step: every step() appends one record.  Before warmup_and_capture() only."""
+        if self._warmed:
+            raise RuntimeError("TrainStep: meters must be attached before warmup_and_capture() (the captured launch sequence is frozen)")
+        if self.meters is not None:
+            raise RuntimeError("TrainStep: meters are already attached")
+        if not self.fused_loss:
+            raise ValueError("TrainStep: meters log the `stats` of a fused criterion (loss, I, U on the device); this step does not run one (fused_loss=False, "
+                             "or a model without forward_lowres)")
+        if meters.block.device != self.x.device:
+            raise ValueError(f"TrainStep: the meters live on {meters.block.device}, the step on {self.x.device}")
+        self.meters = meters
+        return meters
 
     def _check_attach_window(self):
         if self._warmed:
@@ -492,6 +523,13 @@ class TrainStep(_ValidIndices, _BatchInput):
             # after buckets.finish(): with world > 1 the gradients are all-reduced already, the update needs no collective of its own.  Eager: the host-side
             # scan (re)builds the descriptor tables; inside the capture they are final (step(check_tables=False) raises if they are not).
             self.opt.step(check_tables=not torch.cuda.is_current_stream_capturing())
+        if self.meters is not None:
+            # the last launch of the iteration, behind the optimizer's tick: the record's lr is the one the NEXT update will use, as the reference logs it
+            if self.opt is not None:
+                ctl, cnt, hyper, total, power = self.opt.meter_args()
+                self.meters.append(self.stats, ctl, cnt, hyper, total, power)
+            else:
+                self.meters.append(self.stats)
         return loss.detach()
 
     def warmup_and_capture(self, eager_iters=3):
@@ -512,13 +550,19 @@ class TrainStep(_ValidIndices, _BatchInput):
             self.opt.set_grad_source(self.buckets.flat, self.acc)          # (creates the control block; outside any capture)
         self._warmed = True
         ops.note_raw_write()                     # (the forward passes below move the BatchNorm running statistics, as every step() does)
-        if self.opt is None:
-            return self._warmup_and_capture(eager_iters)
-        self.opt.hold(True)
+        if self.meters is not None:
+            self.meters.pause()                  # the eager iterations and validation replays leave no record, with or without an owned optimizer
         try:
-            return self._warmup_and_capture(eager_iters)
+            if self.opt is None:
+                return self._warmup_and_capture(eager_iters)
+            self.opt.hold(True)
+            try:
+                return self._warmup_and_capture(eager_iters)
+            finally:
+                self.opt.hold(False)
         finally:
-            self.opt.hold(False)
+            if self.meters is not None:
+                self.meters.resume()
 
     @_in_context
     def _warmup_and_capture(self, eager_iters):

@@ -33,6 +33,10 @@ replay runs no Python, and a stream of the update obeys the control block with t
 travels through state_dict() (`ema` per parameter, `ema_decay` in every group; a checkpoint with another decay, or with the average on one side only,
 is refused before anything is written).  swap_ema() / ema_weights() exchange parameters and average in place for an evaluation, ema_state_dict(model)
 exports the average; while swapped, step(), state_dict() and the loads raise.
+
+Per-tensor gradient norms (tensor_norms=True, off by default; DESIGN.md "Training meters"): lavt_grad_norm's first pass already leaves one sum of squares per
+chunk, and the chunk table lists every tensor's chunks contiguously -- lavt_grad_norm_tensors, one launch behind it, adds them per tensor in fp64 and notes
+the first tensor that is not finite.  grad_norms() / last_nonfinite() read them (and synchronise); nothing of it enters state_dict() or a fingerprint.
 """
 import os
 from typing import Iterable
@@ -93,7 +97,7 @@ def _ema_of_groups(groups):
 
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params: Iterable, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, total_steps=0, power=0.9, context=None,
-                 max_grad_norm=0.0, skip_nonfinite=False, ema_decay=None):
+                 max_grad_norm=0.0, skip_nonfinite=False, ema_decay=None, *, tensor_norms=False):
         """max_grad_norm > 0: clip by the global L2 norm (torch.nn.utils.clip_grad_norm_'s coefficient); skip_nonfinite: leave parameters, moments, compute
         copies and the step counter untouched when that norm is NaN / Inf (counted in skipped_steps()).  With both off and hold() never called, step()
         is the unguarded launch sequence: no control block, no extra launch.
@@ -102,7 +106,11 @@ class FusedAdamW(torch.optim.Optimizer):
         ema_decay: None = no average (no buffer, no table, the launches of an optimizer built without the argument).  A number d in (0, 1): the update kernel
         also maintains state[p]["ema"], torch.optim.swa_utils.AveragedModel's exponential moving average with get_ema_multi_avg_fn(d) -- the first applied
         update copies the parameter, every later one is ema += (1 - d) * (p - ema); skip, hold and accumulating micro-steps leave it alone, as they
-        leave the moments.  swap_ema() / ema_weights() put it in the parameters' place for an evaluation, ema_state_dict(model) exports it."""
+        leave the moments.  swap_ema() / ema_weights() put it in the parameters' place for an evaluation, ema_state_dict(model) exports it.
+        tensor_norms: True selects the guarded path (as hold() does: the global norm is computed, with max_grad_norm = 0 and skip_nonfinite off it changes
+        no bit of the update) and adds ONE launch behind lavt_grad_norm, lavt_grad_norm_tensors, which adds every tensor's per-chunk partial sums: grad_norms()
+        reads the per-tensor norms of the last applied or skipped cycle, last_nonfinite() names the first tensor whose gradient was NaN / Inf the last time
+        any was.  Not part of state_dict(), not part of a checkpoint's fingerprint."""
         from . import ops
         self.context = context if context is not None else ops.default_context()
         self.amsgrad = bool(amsgrad)          # optimizer-wide (one kernel for the whole chunk table): add_param_group reads it during super().__init__
@@ -121,6 +129,10 @@ class FusedAdamW(torch.optim.Optimizer):
         self.guard = None          # the device control block (see the module docstring); None = the unguarded path
         self._norm_ws = None       # lavt_grad_norm's per-chunk partial sums
         self._grad_source = None   # set_grad_source: (flat, acc) -- read gradients from `acc` at the offsets p.grad has in `flat`
+        self.tensor_norms = bool(tensor_norms)
+        self._tn = None            # tensor_norms: (first-chunk table int32[count + 1], out fp64[count], parameters in desc order); _tn_bad: int32[4], kept across rebuilds
+        self._tn_bad = None
+        self._lr_row = 0           # the desc / hyper row of the first described parameter of group 0: the lr TrainMeters logs
         self._owner = None         # weak reference to the engine.TrainStep this optimizer is attached to (attach_optimizer)
         if self._wants_norm():
             self._make_guard()
@@ -136,7 +148,7 @@ class FusedAdamW(torch.optim.Optimizer):
 
     # ---- the guard ----
     def _wants_norm(self):
-        return self.max_grad_norm > 0.0 or self.skip_nonfinite
+        return self.max_grad_norm > 0.0 or self.skip_nonfinite or self.tensor_norms
 
     def _device(self):
         return next(p for g in self.param_groups for p in g["params"]).device
@@ -194,6 +206,39 @@ class FusedAdamW(torch.optim.Optimizer):
     def skipped_steps(self) -> int:
         return int(self.guard[3].item()) if self.guard is not None else 0
 
+    def _tensor_names(self):
+        """what grad_norms() / last_nonfinite() call every described tensor: its name in the owning step's model, else its index in the tables"""
+        if self._tn is None:
+            raise RuntimeError("FusedAdamW: per-tensor norms exist with tensor_norms=True, after the first step()")
+        owner = self._owner() if self._owner is not None else None
+        names = {id(p): k for k, p in owner.model.named_parameters()} if owner is not None else {}
+        return [names.get(id(p), i) for i, p in enumerate(self._tn[2])]
+
+    def grad_norms(self):
+        """{parameter name (with an owning TrainStep) or table index: L2 norm of its gradient} as of the last cycle that computed a norm (synchronises);
+        under accumulation that is the accumulated gradient's"""
+        if not self.tensor_norms:
+            raise RuntimeError("FusedAdamW.grad_norms: build the optimizer with tensor_norms=True")
+        names = self._tensor_names()
+        return dict(zip(names, self._tn[1].sqrt().tolist()))
+
+    def last_nonfinite(self):
+        """the first tensor (name or index, as grad_norms() keys it) whose gradient norm was NaN / Inf in the most recent cycle that had one; None when
+        none ever was (synchronises).  Sticky: clean cycles afterwards do not clear it."""
+        if not self.tensor_norms:
+            raise RuntimeError("FusedAdamW.last_nonfinite: build the optimizer with tensor_norms=True")
+        if self._tn_bad is None:
+            return None
+        t = int(self._tn_bad[2].item())
+        return self._tensor_names()[t] if t >= 0 else None
+
+    def meter_args(self):
+        """(control block or None, step counter, address of the hyper row whose lr is logged, total_steps, power): what TrainMeters.append reads of an
+        optimizer -- valid once the tables exist (after the first step())"""
+        if self._tables is None or self._step is None:
+            raise RuntimeError("FusedAdamW.meter_args: the optimizer's tables do not exist yet (the first step() creates them)")
+        return self.guard, self._step, self._tables[2].data_ptr() + 20 * self._lr_row, self.total_steps, self.power
+
     # ---- flat optimizer state + device descriptor tables (built lazily: gradients must exist / be re-pointed first) ----
     def _build(self):
         ps = [(g, p) for g in self.param_groups for p in g["params"] if p.requires_grad]
@@ -228,6 +273,7 @@ class FusedAdamW(torch.optim.Optimizer):
                              "started silently in the middle of a run -- load a matching checkpoint, or call reset_ema() to start it from the current parameters")
         from . import ops
         desc, hyper, missing, chunks, fused, vmax, ema = [], [], [], [], {}, [], []
+        first, described, lr_row = [], [], None          # tensor_norms: the first chunk of every desc row; the parameter behind it
         ce = int(K.lib.lavt_adamw_chunk_elems())
         for g, p in ps:
             if p.grad is None:
@@ -243,6 +289,10 @@ class FusedAdamW(torch.optim.Optimizer):
             if ent is not None and ent[2]() is p and ent[1].numel() == p.numel() and ent[1].is_contiguous():
                 copy = ent[1].data_ptr()
                 fused[ck] = copy
+            first.append(len(chunks))
+            described.append(p)
+            if lr_row is None and g is self.param_groups[0]:
+                lr_row = len(desc)
             for c in range(-(-p.numel() // ce)):
                 chunks.append([len(desc), c])
             desc.append([p.data_ptr(), self._grad_address(p), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(), copy])
@@ -262,10 +312,16 @@ class FusedAdamW(torch.optim.Optimizer):
                         torch.tensor(vmax, dtype=torch.int64).to(dev) if self.amsgrad else None)          # [7]: one max_exp_avg_sq address per desc row
         if self.ema_decay is not None:
             self._tables += (torch.tensor(ema, dtype=torch.int64).to(dev),)          # [8], only with the average on: one ema address per desc row
+        self._lr_row = lr_row or 0
         if self._wants_norm():
             need = int(K.lib.lavt_grad_norm_ws(len(chunks)))
             if self._norm_ws is None or self._norm_ws.numel() < need:
                 self._norm_ws = torch.empty(need, dtype=torch.float32, device=dev)
+        if self.tensor_norms:
+            # (the chunk table lists every tensor's chunks contiguously, in ascending order: tensor t owns partials first[t] .. first[t + 1])
+            self._tn = (torch.tensor(first + [len(chunks)], dtype=torch.int32).to(dev), torch.zeros(len(desc), dtype=torch.float64, device=dev), described)
+            if self._tn_bad is None:
+                self._tn_bad = torch.tensor([-1, 0, -1, 0], dtype=torch.int32).to(dev)
 
     def _current_key(self):
         out = []
@@ -387,6 +443,8 @@ class FusedAdamW(torch.optim.Optimizer):
                                "after the descriptor table was built; call step() once with check_tables=True (outside a capture) first")
         if self.guard is not None and self._wants_norm():
             K.check(K.lib.lavt_grad_norm(K.ptr(desc), K.ptr(chunks), nchunks, K.ptr(self._norm_ws), K.ptr(self.guard), self.max_grad_norm, int(self.skip_nonfinite), K.stream()))
+            if self.tensor_norms:
+                K.check(K.lib.lavt_grad_norm_tensors(K.ptr(self._norm_ws), nchunks, K.ptr(self._tn[0]), n, K.ptr(self.guard), K.ptr(self._tn[1]), K.ptr(self._tn_bad), K.stream()))
         if ema is not None:
             K.check(K.lib.lavt_adamw_step_chunks_ema(K.ptr(desc), K.ptr(vmax), K.ptr(ema), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(self._step), self.total_steps,
                                                      self.power, self.ema_decay, K.ptr(self.guard), K.stream()))
