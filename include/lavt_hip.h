@@ -648,9 +648,22 @@ int lavt_adamw_step(const int64_t* desc, const float* hyper, int count, float* s
  * parameter's bf16 compute copy in the same layout, written by the same kernel (the mixed-precision trainer's re-cast of the weights the next
  * forward reads, without a second pass over the parameters); chunks int32 [nchunks][2] = {tensor index, chunk index}: workgroup c updates elements
  * [chunk * lavt_adamw_chunk_elems(), ...) of its tensor, so every workgroup has work.  hyper, step, schedule as above. */
+#define LAVT_ADAMW_DESC_COLS 6 /* int64 columns of a desc row, in this order: */
+#define LAVT_ADAMW_DESC_PARAM 0
+#define LAVT_ADAMW_DESC_GRAD 1
+#define LAVT_ADAMW_DESC_EXP_AVG 2
+#define LAVT_ADAMW_DESC_EXP_AVG_SQ 3
+#define LAVT_ADAMW_DESC_NUMEL 4
+#define LAVT_ADAMW_DESC_COPY 5
+#define LAVT_ADAMW_HYPER_COLS 5 /* fp32 columns of a hyper row, in this order: */
+#define LAVT_ADAMW_HYPER_LR 0
+#define LAVT_ADAMW_HYPER_WEIGHT_DECAY 1
+#define LAVT_ADAMW_HYPER_BETA1 2
+#define LAVT_ADAMW_HYPER_BETA2 3
+#define LAVT_ADAMW_HYPER_EPS 4
 int lavt_adamw_chunk_elems(void);
 int lavt_adamw_step_chunks(const int64_t* desc, const float* hyper, const int32_t* chunks, int nchunks, float* step, float total_steps, float power, void* stream);
-/* The guard around the optimizer step (csrc/optim_guard.hip): every decision is taken on the device, so the sequence can be captured into a
+/* The guard around the optimizer step (csrc/optim.hip): every decision is taken on the device, so the sequence can be captured into a
  * hipGraph.  All three entry points were added under ABI v7 (new symbols only: no existing prototype or struct changed).
  *
  * Control block `ctl`: device fp32[8], zero-initialised by the caller except ctl[1] = 1.
@@ -674,6 +687,14 @@ int lavt_adamw_step_chunks(const int64_t* desc, const float* hyper, const int32_
  * returns before its first store (parameters, both moments and the bf16 `copy` column stay untouched) and the step counter does not advance;
  * ctl[3] += ctl[2] unless on hold (hence the non-const pointer).  With ctl[1] = 1, ctl[2] = ctl[4] = 0 the result equals the unguarded
  * update's bit for bit (one shared update body). */
+#define LAVT_CTL_NORM 0 /* the slots of the control block, as numbered above */
+#define LAVT_CTL_CLIP 1
+#define LAVT_CTL_SKIP 2
+#define LAVT_CTL_SKIPPED 3
+#define LAVT_CTL_HOLD 4
+#define LAVT_CTL_ACCUMULATING 5
+#define LAVT_CTL_MICRO 6
+#define LAVT_CTL_FLOATS 8
 int64_t lavt_grad_norm_ws(int nchunks);
 int lavt_grad_norm(const int64_t* desc, const int32_t* chunks, int nchunks, float* ws, float* ctl, float max_norm, int skip_nonfinite, void* stream);
 int lavt_adamw_step_chunks_guarded(const int64_t* desc, const float* hyper, const int32_t* chunks, int nchunks, float* step, float total_steps, float power,
@@ -741,7 +762,7 @@ int lavt_ema_swap(const int64_t* desc, const int64_t* ema, const int32_t* chunks
  * Flags: ACCUMULATING = ctl[5] != 0 (the micro-step did not end its cycle); SKIPPED = not accumulating and ctl[2] != 0; APPLIED = a step counter was
  * given and neither of the two; LOSS_NONFINITE = the loss is NaN / Inf.  `capacity` must be the block's.
  *
- * lavt_grad_norm_tensors: per-tensor sums of squares from the per-chunk partials lavt_grad_norm's first pass left in ws [nchunks] -- the chunk table
+ * lavt_grad_norm_tensors (csrc/optim.hip, with the norm it reads): per-tensor sums of squares from the per-chunk partials lavt_grad_norm's first pass left in ws [nchunks] -- the chunk table
  * lists every tensor's chunks contiguously in ascending order, so tensor t owns ws[first[t] .. first[t + 1]) (first: device int32 [count + 1]).  One
  * launch, one wave per tensor in turn: lane l adds partials l, l + 64, ... in sequence in fp64, a fixed xor tree joins the lanes -- bit-reproducible.
  *   out[t] = the sum (fp64; sqrt gives the norm);   bad: device int32[4] = {first non-finite tensor of this call or -1, how many were non-finite,

@@ -6,8 +6,9 @@
 Gradient accumulation over micro-batches: TrainStep(accumulate=k) with an owned optimizer.  Every call of step() is one MICRO-step on whatever the
 static buffers hold: its body is the one above, unchanged (every parameter still receives exactly one weight gradient per micro-step into a buffer
 zeroed at its start; lavt_hip.ops.sinks still refuses a second one), then lavt_grad_accumulate folds the flat gradient, times 1/k, into a second
-flat buffer (`acc`) and the optimizer's guarded kernels read `acc`.  The phase of the cycle lives on the device (FusedAdamW.guard[5:7]): ONE captured
-graph serves all k micro-steps -- replays 1 .. k-1 leave parameters, moments, compute copies and the step counter bit for bit alone, replay k applies
+flat buffer (`acc`) and the optimizer's guarded kernels read `acc`.  The phase of the cycle lives on the device (the accumulating flag and the micro index of
+FusedAdamW's control block; this module asks the optimizer for them -- micro_index(), reset_phase(), control_state() / load_control_state() -- and
+never indexes the block): ONE captured graph serves all k micro-steps -- replays 1 .. k-1 leave parameters, moments, compute copies and the step counter bit for bit alone, replay k applies
 one AdamW update from the mean of the k gradients (clip and non-finite skip act on that mean) and ticks the schedule once.  Per micro-step, as in
 PyTorch under accumulation: BatchNorm normalises with (and its running statistics follow) each micro-batch's own statistics, DropPath draws new
 masks, the fp8 |max| history advances; step() returns, and `stats` holds, that micro-batch's loss.  world > 1: the buckets are all-reduced in
@@ -318,23 +319,20 @@ class TrainStep(_ValidIndices, _BatchInput):
     # ---- gradient accumulation: the phase lives in the optimizer's control block ----
     def micro_step(self) -> int:
         """the micro index m of the running cycle, 0 <= m < accumulate: the next step() is micro-step m (synchronises).  0 = a cycle boundary."""
-        if self.acc is None or self.opt is None or self.opt.guard is None:
+        if self.acc is None or self.opt is None:
             return 0
-        return int(self.opt.guard[6].item())
+        return self.opt.micro_index()
 
     def reset_accumulation(self):
         """Restart the cycle: the next step() is its first micro-step (which overwrites `acc`) -- to drop the micro-batches of an open cycle, or after
         loading model and optimizer state dicts by hand.  load_state_dict() needs no such call: state_dict() saves `acc` and the phase inside a cycle,
-        and a checkpoint from a cycle boundary sets the phase to 0 itself.  A host write of guard[5:7], like FusedAdamW.hold(): call it outside any
-        capture; it waits for the device on both sides."""
+        and a checkpoint from a cycle boundary sets the phase to 0 itself.  A host write (FusedAdamW.reset_phase()), like FusedAdamW.hold(): call it
+        outside any capture; it waits for the device on both sides."""
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("TrainStep.reset_accumulation() is a host write: call it outside the graph capture")
         if self.acc is None or self.opt is None:
             return
-        g = self.opt._make_guard()
-        torch.cuda.synchronize(g.device)
-        g[5:7].zero_()
-        torch.cuda.synchronize(g.device)
+        self.opt.reset_phase()
 
     # ---- checkpoint and resume (DESIGN.md "Checkpoint and resume") ----
     def _config(self):
@@ -385,13 +383,10 @@ class TrainStep(_ValidIndices, _BatchInput):
         self._not_capturing("TrainStep.state_dict")
         dev = self._params[0].device
         torch.cuda.synchronize(dev)
-        guard = None
-        if self.opt.guard is not None:
-            guard = self.opt.guard.detach().to("cpu", copy=True)
-            guard[4] = 0.0
+        guard = self.opt.control_state()
         train = {"format": TRAIN_STATE_FORMAT, "config": self._config(), "guard": guard, "droppath": ops.droppath_state_dict(), "fp8": {},
                  "torch_cuda_rng": torch.cuda.get_rng_state(dev)}
-        if self.acc is not None and guard is not None and int(guard[6]) != 0:
+        if self.micro_step() != 0:
             train["acc"] = self.acc.detach().to("cpu", copy=True)
             train["acc_layout"] = self._acc_layout()
         sites = self._fp8_sites()
@@ -434,8 +429,7 @@ class TrainStep(_ValidIndices, _BatchInput):
                 raise ValueError(f"{who}: 'model' has no entry {k}")
         plan = self.opt.check_state_dict_in_place(state["optimizer"])
         guard, acc = train.get("guard"), train.get("acc")
-        if (guard is None) != (self.opt.guard is None) or (guard is not None and tuple(guard.shape) != (8,)):
-            raise ValueError(f"{who}: the checkpoint has {'no' if guard is None else 'a'} control block ('guard'), this step's optimizer has {'none' if self.opt.guard is None else 'one'}")
+        self.opt.check_control_state(guard, who)
         if acc is not None:
             if self.acc is None or tuple(acc.shape) != tuple(self.acc.shape) or train.get("acc_layout") != self._acc_layout():
                 raise ValueError(f"{who}: 'acc' of the checkpoint does not have the layout of this step's gradient buffer")
@@ -451,12 +445,7 @@ class TrainStep(_ValidIndices, _BatchInput):
         with torch.no_grad():
             self.model.load_state_dict(state["model"], strict=True)          # copies into the parameters and buffers
             self.opt.load_state_dict_in_place(state["optimizer"], plan)
-            if guard is not None:
-                g = guard.detach().to(torch.float32).clone()
-                g[4] = 0.0
-                if acc is None:
-                    g[5:7] = 0.0
-                self.opt.guard.copy_(g)
+            self.opt.load_control_state(guard, keep_phase=acc is not None)
             if acc is not None:
                 self.acc.copy_(acc)
             ops.droppath_load_state_dict(train["droppath"])
@@ -517,7 +506,7 @@ class TrainStep(_ValidIndices, _BatchInput):
         ops.fp8.end_step()
         if self.acc is not None:
             # after buckets.finish() (world > 1: all-reduced already): acc = flat / k on the first micro-step of a cycle, acc += flat / k on the others;
-            # sets guard[5] unless this micro-step ends the cycle -- the optimizer's kernels below then return before their first store
+            # sets the accumulating flag unless this micro-step ends the cycle -- the optimizer's kernels below then return before their first store
             K.check(K.lib.lavt_grad_accumulate(K.ptr(self.buckets.flat), K.ptr(self.acc), self.acc.numel(), self.accumulate, K.ptr(self.opt.guard), K.stream()))
         if self.opt is not None:
             # after buckets.finish(): with world > 1 the gradients are all-reduced already, the update needs no collective of its own.  Eager: the host-side

@@ -14,7 +14,9 @@ of the uncorrected second moment, which replaces it in the denominator (lavt_ada
 every group carries the constructor's value, and a checkpoint written with the other value is refused rather than half-loaded.
 
 The guard (opt-in: max_grad_norm > 0, skip_nonfinite=True, or hold()): a device fp32[8] control block `opt.guard` = [global gradient norm, clip
-coefficient, skip flag, skipped-step count, hold flag, accumulating flag, micro index, 0].  lavt_grad_norm fills the first three from the gradients the
+coefficient, skip flag, skipped-step count, hold flag, accumulating flag, micro index, 0] -- the slots are named once, CTL_* below (LAVT_CTL_* of
+include/lavt_hip.h), and the block is read and written from the host by this class alone: hold(), micro_index(), reset_phase(), control_state() /
+load_control_state() for engine.TrainStep's checkpoints.  lavt_grad_norm fills the first three from the gradients the
 update is about to read, the guarded update multiplies every gradient by the coefficient and does nothing at all (no store, no tick of the step
 counter) when skip or hold is set -- no device-to-host synchronisation and no data-dependent launch, so it survives graph capture.
 
@@ -39,11 +41,39 @@ chunk, and the chunk table lists every tensor's chunks contiguously -- lavt_grad
 the first tensor that is not finite.  grad_norms() / last_nonfinite() read them (and synchronise); nothing of it enters state_dict() or a fingerprint.
 """
 import os
-from typing import Iterable
+from typing import Iterable, NamedTuple, Optional
 
 import torch
 
 from . import _capi as K
+
+
+# The device protocol of the optimizer's kernels (include/lavt_hip.h: LAVT_CTL_*, LAVT_ADAMW_*; tests/test_optim_protocol_host.py compares the two): the
+# slots of the control block, and how many columns a row of the descriptor / hyper-parameter table has.  Nothing else in Python knows the layout.
+CTL_NORM, CTL_CLIP, CTL_SKIP, CTL_SKIPPED, CTL_HOLD, CTL_ACCUMULATING, CTL_MICRO = range(7)
+CTL_FLOATS = 8
+DESC_COLS = 6          # param, grad, exp_avg, exp_avg_sq, numel, copy
+HYPER_COLS = 5         # lr, weight_decay, beta1, beta2, eps
+
+
+def initial_control_block():
+    """the control block as the kernels expect to find it before the first launch (a CPU tensor): zeros, and a clip coefficient of 1"""
+    g = torch.zeros(CTL_FLOATS, dtype=torch.float32)
+    g[CTL_CLIP] = 1.0
+    return g
+
+
+class _Tables(NamedTuple):
+    """what one _build() leaves for step(): the key it was built for, the device tables and their sizes"""
+    key: tuple
+    desc: torch.Tensor            # int64 [count][DESC_COLS]
+    hyper: torch.Tensor           # fp32 [count][HYPER_COLS]
+    count: int
+    chunks: torch.Tensor          # int32 [nchunks][2] = {desc row, chunk of that tensor}
+    nchunks: int
+    fused: dict                   # {compute-copy key: address} of the bf16 copies the update writes itself
+    vmax: Optional[torch.Tensor]  # int64 [count]: one max_exp_avg_sq address per desc row; None without amsgrad
+    ema: Optional[torch.Tensor]   # int64 [count]: one ema address per desc row; None without the average
 
 
 LANG_ENC_PARAMS = ("encoder-10", "encoder-all", "embeddings+encoder-10", "embeddings+encoder-all")
@@ -160,19 +190,55 @@ class FusedAdamW(torch.optim.Optimizer):
                 raise RuntimeError("FusedAdamW runs on GPU memory only (no CPU fallback)")
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("FusedAdamW: the control block cannot be created inside a graph capture (construct with the guard options, or call hold() first)")
-            self.guard = torch.tensor([0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float32).to(dev)
+            self.guard = initial_control_block().to(dev)
         return self.guard
+
+    def _host_write(self, who, write):
+        """write(control block) from the host between two waits for the device (ordered against work on every stream); refused inside a capture"""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{who} is a host write: call it outside the graph capture")
+        g = self._make_guard()
+        torch.cuda.synchronize(g.device)
+        write(g)
+        torch.cuda.synchronize(g.device)
 
     def hold(self, flag=True):
         """While held, step() changes nothing -- parameters, moments, compute copies, step counter, skipped-step count -- whatever the gradients hold
-        (TrainStep uses it for its warm-up iterations and validation replays).  A host write of guard[4]: call it outside any capture; it waits for the
-        device on both sides, so it is ordered against work on every stream."""
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("FusedAdamW.hold() is a host write: call it outside the graph capture")
-        g = self._make_guard()
-        torch.cuda.synchronize(g.device)
-        g[4:5].fill_(1.0 if flag else 0.0)
-        torch.cuda.synchronize(g.device)
+        (TrainStep uses it for its warm-up iterations and validation replays).  A host write of the hold slot: call it outside any capture; it waits for
+        the device on both sides, so it is ordered against work on every stream."""
+        self._host_write("FusedAdamW.hold()", lambda g: g[CTL_HOLD:CTL_HOLD + 1].fill_(1.0 if flag else 0.0))
+
+    # ---- the phase of an accumulation cycle and the block as a whole: what engine.TrainStep asks of the control block ----
+    def micro_index(self) -> int:
+        """the micro index m of the running accumulation cycle (synchronises); 0 without a control block"""
+        return int(self.guard[CTL_MICRO].item()) if self.guard is not None else 0
+
+    def reset_phase(self):
+        """accumulating flag and micro index back to 0: the next step is the first micro-step of a cycle.  A host write, like hold()."""
+        self._host_write("FusedAdamW.reset_phase()", lambda g: g[CTL_ACCUMULATING:CTL_MICRO + 1].zero_())
+
+    def control_state(self):
+        """a CPU copy of the control block with hold saved as 0 (a checkpoint never holds), or None without one; the caller has synchronised"""
+        if self.guard is None:
+            return None
+        g = self.guard.detach().to("cpu", copy=True)
+        g[CTL_HOLD] = 0.0
+        return g
+
+    def check_control_state(self, saved, who):
+        """ValueError unless `saved` (a control_state(), or None) fits this optimizer: a block on both sides or on neither, of CTL_FLOATS words.  No write."""
+        if (saved is None) != (self.guard is None) or (saved is not None and tuple(saved.shape) != (CTL_FLOATS,)):
+            raise ValueError(f"{who}: the checkpoint has {'no' if saved is None else 'a'} control block ('guard'), this step's optimizer has {'none' if self.guard is None else 'one'}")
+
+    def load_control_state(self, saved, keep_phase):
+        """a checked control_state() into the block this optimizer has (a host copy: the caller synchronises around it); hold comes back as 0, and so
+        does the phase unless keep_phase (without it the checkpoint was taken at a cycle boundary)"""
+        if saved is not None:
+            g = saved.detach().to(torch.float32).clone()
+            g[CTL_HOLD] = 0.0
+            if not keep_phase:
+                g[CTL_ACCUMULATING:CTL_MICRO + 1] = 0.0
+            self.guard.copy_(g)
 
     def set_grad_source(self, flat=None, acc=None):
         """Read every gradient from `acc` at the offset its p.grad has inside `flat` (two flat fp32 buffers of one layout: GradBuckets.flat and the
@@ -201,16 +267,23 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def last_grad_norm(self):
         """global gradient norm of the last guarded step (synchronises); None when no norm is computed"""
-        return float(self.guard[0].item()) if self.guard is not None and self._wants_norm() else None
+        return float(self.guard[CTL_NORM].item()) if self.guard is not None and self._wants_norm() else None
 
     def skipped_steps(self) -> int:
-        return int(self.guard[3].item()) if self.guard is not None else 0
+        return int(self.guard[CTL_SKIPPED].item()) if self.guard is not None else 0
+
+    def _owner_step(self):
+        """the engine.TrainStep this optimizer is attached to, or None (never attached, or the step is gone)"""
+        return self._owner() if self._owner is not None else None
+
+    def _trainable(self):
+        return [p for g in self.param_groups for p in g["params"] if p.requires_grad]
 
     def _tensor_names(self):
         """what grad_norms() / last_nonfinite() call every described tensor: its name in the owning step's model, else its index in the tables"""
         if self._tn is None:
             raise RuntimeError("FusedAdamW: per-tensor norms exist with tensor_norms=True, after the first step()")
-        owner = self._owner() if self._owner is not None else None
+        owner = self._owner_step()
         names = {id(p): k for k, p in owner.model.named_parameters()} if owner is not None else {}
         return [names.get(id(p), i) for i, p in enumerate(self._tn[2])]
 
@@ -237,7 +310,7 @@ class FusedAdamW(torch.optim.Optimizer):
         optimizer -- valid once the tables exist (after the first step())"""
         if self._tables is None or self._step is None:
             raise RuntimeError("FusedAdamW.meter_args: the optimizer's tables do not exist yet (the first step() creates them)")
-        return self.guard, self._step, self._tables[2].data_ptr() + 20 * self._lr_row, self.total_steps, self.power
+        return self.guard, self._step, self._tables.hyper.data_ptr() + 4 * HYPER_COLS * self._lr_row, self.total_steps, self.power
 
     # ---- flat optimizer state + device descriptor tables (built lazily: gradients must exist / be re-pointed first) ----
     def _build(self):
@@ -307,11 +380,11 @@ class FusedAdamW(torch.optim.Optimizer):
         # (every described parameter with the gradient address the table holds: step(check_tables=False) compares them all -- integer work on the host,
         # no device synchronisation; three probed addresses missed a single re-created .grad)
         self._probe = [(p, p.grad.data_ptr()) for _, p in ps if p.grad is not None]
-        self._tables = (key, torch.tensor(desc, dtype=torch.int64).to(dev), torch.tensor(hyper, dtype=torch.float32).to(dev), len(desc),
-                        torch.tensor(chunks, dtype=torch.int32).to(dev), len(chunks), dict(fused),
-                        torch.tensor(vmax, dtype=torch.int64).to(dev) if self.amsgrad else None)          # [7]: one max_exp_avg_sq address per desc row
-        if self.ema_decay is not None:
-            self._tables += (torch.tensor(ema, dtype=torch.int64).to(dev),)          # [8], only with the average on: one ema address per desc row
+        assert all(len(row) == DESC_COLS for row in desc) and all(len(row) == HYPER_COLS for row in hyper)
+        self._tables = _Tables(key, torch.tensor(desc, dtype=torch.int64).to(dev), torch.tensor(hyper, dtype=torch.float32).to(dev), len(desc),
+                               torch.tensor(chunks, dtype=torch.int32).to(dev), len(chunks), dict(fused),
+                               torch.tensor(vmax, dtype=torch.int64).to(dev) if self.amsgrad else None,
+                               torch.tensor(ema, dtype=torch.int64).to(dev) if self.ema_decay is not None else None)
         self._lr_row = lr_row or 0
         if self._wants_norm():
             need = int(K.lib.lavt_grad_norm_ws(len(chunks)))
@@ -354,7 +427,7 @@ class FusedAdamW(torch.optim.Optimizer):
             raise RuntimeError(f"FusedAdamW.{what} is a host call: it is refused inside a graph capture")
 
     def _ema_pairs(self, what):
-        ps = [p for g in self.param_groups for p in g["params"] if p.requires_grad]
+        ps = self._trainable()
         if not all("ema" in self.state.get(p, ()) for p in ps):          # (.get: looking must not create empty state entries)
             raise RuntimeError(f"FusedAdamW.{what}: the optimizer's state does not exist yet (the first step() creates it)")
         return [(p, self.state[p]["ema"]) for p in ps]
@@ -367,7 +440,7 @@ class FusedAdamW(torch.optim.Optimizer):
         from . import ops
         self._needs_ema("reset_ema")
         self._refuse_swapped("reset_ema")
-        ps = [p for g in self.param_groups for p in g["params"] if p.requires_grad]
+        ps = self._trainable()
         if not all("exp_avg" in self.state.get(p, ()) for p in ps):
             raise RuntimeError("FusedAdamW.reset_ema: the optimizer's state does not exist yet (the first step() creates it, with the average at the parameters)")
         dev = ps[0].device
@@ -392,17 +465,17 @@ class FusedAdamW(torch.optim.Optimizer):
         with ops.use_context(self.context):
             if self._tables is None:
                 raise RuntimeError("FusedAdamW.swap_ema: the optimizer's state and tables do not exist yet (the first step() creates them)")
-            if self._tables[0] != self._current_key():
-                owner = self._owner() if self._owner is not None else None
+            if self._tables.key != self._current_key():
+                owner = self._owner_step()
                 if owner is not None and owner.graph is not None:
                     raise RuntimeError("FusedAdamW.swap_ema: a compute copy was re-allocated, a gradient moved or a hyper-parameter was edited after the step "
                                        "was captured: the tables the captured update reads no longer describe the optimizer")
                 self._build()
-            _, desc, _, _, chunks, nchunks, fused, _, ema = self._tables
-            K.check(K.lib.lavt_ema_swap(K.ptr(desc), K.ptr(ema), K.ptr(chunks), nchunks, K.stream()))
+            T = self._tables
+            K.check(K.lib.lavt_ema_swap(K.ptr(T.desc), K.ptr(T.ema), K.ptr(T.chunks), T.nchunks, K.stream()))
             self.ema_swapped = not self.ema_swapped
             ops.note_raw_write()
-            ops.weights.refresh_all(done=fused)          # (as after step(): packed conv weights, e4m3 copies, LayerNorm and BatchNorm folds follow)
+            ops.weights.refresh_all(done=T.fused)          # (as after step(): packed conv weights, e4m3 copies, LayerNorm and BatchNorm folds follow)
 
     def ema_weights(self):
         """`with opt.ema_weights(): evaluate` -- swap_ema() on entry and on exit (also when the body raises)"""
@@ -430,39 +503,36 @@ class FusedAdamW(torch.optim.Optimizer):
         """check_tables=False skips the (host-side) scan for re-allocated gradients / edited hyper-parameters: use it when the gradients
         live in a fixed flat buffer (lavt_hip.ddp.GradBuckets) and the call is being captured into a hipGraph."""
         loss = closure() if closure is not None else None
-        if self._tables is None or (check_tables and self._tables[0] != self._current_key()):
+        if self._tables is None or (check_tables and self._tables.key != self._current_key()):
             self._build()
-        _, desc, hyper, n, chunks, nchunks, fused, vmax = self._tables[:8]
-        ema = self._tables[8] if self.ema_decay is not None else None
-        if not check_tables and (self._tables[0][-1] != ops_generation()
-                                 or any(p.grad is None or p.grad.data_ptr() != a for p, a in self._probe)):
+        T = self._tables
+        if not check_tables and (T.key[-1] != ops_generation() or any(p.grad is None or p.grad.data_ptr() != a for p, a in self._probe)):
             # (captured steps skip the host-side scan, but a copy that moved since the table was built would be written at its OLD address, and a
             # gradient buffer that was laid out again -- GradBuckets moves unreported parameters to the late bucket in its second zero() -- would be
             # read at its OLD offsets)
             raise RuntimeError("FusedAdamW.step(check_tables=False): a compute copy was re-allocated or the flat gradient buffer was laid out again "
                                "after the descriptor table was built; call step() once with check_tables=True (outside a capture) first")
+        desc, hyper, chunks, step, guard = K.ptr(T.desc), K.ptr(T.hyper), K.ptr(T.chunks), K.ptr(self._step), K.ptr(self.guard)
         if self.guard is not None and self._wants_norm():
-            K.check(K.lib.lavt_grad_norm(K.ptr(desc), K.ptr(chunks), nchunks, K.ptr(self._norm_ws), K.ptr(self.guard), self.max_grad_norm, int(self.skip_nonfinite), K.stream()))
+            K.check(K.lib.lavt_grad_norm(desc, chunks, T.nchunks, K.ptr(self._norm_ws), guard, self.max_grad_norm, int(self.skip_nonfinite), K.stream()))
             if self.tensor_norms:
-                K.check(K.lib.lavt_grad_norm_tensors(K.ptr(self._norm_ws), nchunks, K.ptr(self._tn[0]), n, K.ptr(self.guard), K.ptr(self._tn[1]), K.ptr(self._tn_bad), K.stream()))
-        if ema is not None:
-            K.check(K.lib.lavt_adamw_step_chunks_ema(K.ptr(desc), K.ptr(vmax), K.ptr(ema), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(self._step), self.total_steps,
-                                                     self.power, self.ema_decay, K.ptr(self.guard), K.stream()))
+                K.check(K.lib.lavt_grad_norm_tensors(K.ptr(self._norm_ws), T.nchunks, K.ptr(self._tn[0]), T.count, guard, K.ptr(self._tn[1]), K.ptr(self._tn_bad), K.stream()))
+        if T.ema is not None:
+            K.check(K.lib.lavt_adamw_step_chunks_ema(desc, K.ptr(T.vmax), K.ptr(T.ema), hyper, chunks, T.nchunks, step, self.total_steps, self.power, self.ema_decay,
+                                                     guard, K.stream()))
         elif self.amsgrad:
-            K.check(K.lib.lavt_adamw_step_chunks_amsgrad(K.ptr(desc), K.ptr(vmax), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(self._step), self.total_steps, self.power,
-                                                         K.ptr(self.guard), K.stream()))
+            K.check(K.lib.lavt_adamw_step_chunks_amsgrad(desc, K.ptr(T.vmax), hyper, chunks, T.nchunks, step, self.total_steps, self.power, guard, K.stream()))
         elif self.guard is None:
-            K.check(K.lib.lavt_adamw_step_chunks(K.ptr(desc), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(self._step), self.total_steps, self.power, K.stream()))
+            K.check(K.lib.lavt_adamw_step_chunks(desc, hyper, chunks, T.nchunks, step, self.total_steps, self.power, K.stream()))
         else:
-            K.check(K.lib.lavt_adamw_step_chunks_guarded(K.ptr(desc), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(self._step), self.total_steps, self.power,
-                                                         K.ptr(self.guard), K.stream()))
+            K.check(K.lib.lavt_adamw_step_chunks_guarded(desc, hyper, chunks, T.nchunks, step, self.total_steps, self.power, guard, K.stream()))
         # The kernel writes the parameters through raw pointers: p._version does not move, so the cached compute copies (bf16 Linear weights,
         # packed conv weights) are stale now.  They are part of the optimizer's output (fp32 master weights + the compute-dtype copies the next
         # forward reads, as in any mixed-precision trainer): re-cast them here, on the same stream, so that the forward/backward step itself
         # carries no cast kernels (the step harness refreshes them only when asked to: TrainStep(refresh_weights_in_step=True)).
         # (after a skipped or held step the same casts run on unchanged weights: harmless, and the launch sequence stays fixed for a capture)
         from . import ops
-        ops.weights.refresh_all(done=fused)          # the copies in `fused` were written by the update kernel: only their stamps move
+        ops.weights.refresh_all(done=T.fused)          # the copies in `fused` were written by the update kernel: only their stamps move
         return loss
 
     def steps_taken(self) -> int:
@@ -479,6 +549,12 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.guard is not None:
             sd["lavt_schedule"]["skipped_steps"] = self.skipped_steps()
         return sd
+
+    def _check_amsgrad_of(self, state_dict, who):
+        """refuse a checkpoint written with the other amsgrad setting (a plain one would start max_exp_avg_sq at zero, an AMSGrad one would lose it)"""
+        theirs = {bool(g.get("amsgrad", False)) for g in state_dict["param_groups"]}
+        if theirs != {self.amsgrad}:
+            raise ValueError(f"{who}: the checkpoint's param_groups have amsgrad={sorted(theirs)} but this optimizer was built with amsgrad={self.amsgrad}")
 
     def _check_ema_of(self, state_dict, who):
         """refuse, before any write, a checkpoint whose weight average is not this optimizer's: present on one side only (averaging would start, or end,
@@ -502,9 +578,7 @@ class FusedAdamW(torch.optim.Optimizer):
         must be the ones this optimizer was constructed with."""
         who = "FusedAdamW.load_state_dict_in_place"
         self._refuse_swapped("load_state_dict_in_place")
-        theirs = {bool(g.get("amsgrad", False)) for g in state_dict["param_groups"]}
-        if theirs != {self.amsgrad}:
-            raise ValueError(f"{who}: the checkpoint's param_groups have amsgrad={sorted(theirs)} but this optimizer was built with amsgrad={self.amsgrad}")
+        self._check_amsgrad_of(state_dict, who)
         self._check_ema_of(state_dict, who)
         groups = state_dict["param_groups"]
         if len(groups) != len(self.param_groups):
@@ -570,10 +644,10 @@ class FusedAdamW(torch.optim.Optimizer):
                 dst.copy_(src)
         self._step.fill_(steps)
         if skipped is not None and self.guard is not None:
-            self.guard[3:4].fill_(skipped)
+            self.guard[CTL_SKIPPED:CTL_SKIPPED + 1].fill_(skipped)
 
     def load_state_dict(self, state_dict):
-        owner = self._owner() if self._owner is not None else None
+        owner = self._owner_step()
         if owner is not None and owner.graph is not None:
             raise RuntimeError("FusedAdamW.load_state_dict: this optimizer is part of a TrainStep whose step has been captured: the graph keeps the addresses "
                                "of the moments and the step counter this call would replace, and would go on training from the old ones.  Use "
@@ -581,11 +655,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self._refuse_swapped("load_state_dict")
         sched = state_dict.get("lavt_schedule")
         self._check_ema_of(state_dict, "FusedAdamW.load_state_dict")
-        theirs = {bool(g.get("amsgrad", False)) for g in state_dict["param_groups"]}
-        if theirs != {self.amsgrad}:
-            # (a plain checkpoint would start max_exp_avg_sq at zero, an AMSGrad one would lose it: neither silently)
-            raise ValueError(f"FusedAdamW.load_state_dict: the checkpoint's param_groups have amsgrad={sorted(theirs)} but this optimizer was built with "
-                             f"amsgrad={self.amsgrad}")
+        self._check_amsgrad_of(state_dict, "FusedAdamW.load_state_dict")
         super().load_state_dict({k: v for k, v in state_dict.items() if k != "lavt_schedule"})
         steps = None
         if sched is not None:
@@ -604,5 +674,5 @@ class FusedAdamW(torch.optim.Optimizer):
         for st in self.state.values():
             st["step"] = self._step
         if sched is not None and "skipped_steps" in sched and (self.guard is not None or sched["skipped_steps"]):
-            self._make_guard()[3:4].fill_(float(sched["skipped_steps"]))
+            self._make_guard()[CTL_SKIPPED:CTL_SKIPPED + 1].fill_(float(sched["skipped_steps"]))
         self._tables = None

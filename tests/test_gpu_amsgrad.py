@@ -349,7 +349,7 @@ def test_plain_path_carries_no_maximum():
     assert isinstance(key, tuple) and n == len(ps) and nchunks == want_chunks == 16 and fused == {}
     assert desc.shape == (len(ps), 6) and desc.dtype == torch.int64 and hyper.shape == (len(ps), 5) and hyper.dtype == torch.float32
     assert chunks.shape == (want_chunks, 2) and chunks.dtype == torch.int32
-    assert opt._tables[7:] == (None,)
+    assert opt._tables[7:] == (None, None)
     qs, ams = _ours(R["params"], copies=False)
     _set_grads(qs, R["grads"][0])
     ams.step()

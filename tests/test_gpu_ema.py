@@ -225,7 +225,7 @@ def test_without_ema_decay_nothing_is_added(amsgrad):
     old = "lavt_adamw_step_chunks_amsgrad" if amsgrad else "lavt_adamw_step_chunks"
     assert names.count(old) == 3 and "lavt_adamw_step_chunks_ema" not in names and "lavt_ema_swap" not in names
     assert all("ema" not in opt.state[p] for p in ps) and all("ema" not in st for st in opt.state_dict()["state"].values())
-    assert len(opt._tables) == 8 and opt.ema_decay is None
+    assert opt._tables.ema is None and opt.ema_decay is None
     assert len(_state(avg, qs)) == len(_state(opt, ps)) + len(SHAPES)
     worst = 0.0
     for p, q in zip(ps, qs):

@@ -63,21 +63,21 @@ def main():
 
     s_off, o_off = harness()
     s_ema, o_ema = harness(ema_decay=0.999)
-    assert len(o_off._tables) == 8 and len(o_ema._tables) == 9
+    assert o_off._tables.ema is None and o_ema._tables.ema is not None
 
     def update_off():
-        _, desc, hyper, _, chunks, nchunks = o_off._tables[:6]
-        K.check(K.lib.lavt_adamw_step_chunks_guarded(K.ptr(desc), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(o_off._step), o_off.total_steps, o_off.power,
+        T = o_off._tables
+        K.check(K.lib.lavt_adamw_step_chunks_guarded(K.ptr(T.desc), K.ptr(T.hyper), K.ptr(T.chunks), T.nchunks, K.ptr(o_off._step), o_off.total_steps, o_off.power,
                                                      K.ptr(o_off.guard), K.stream()))
 
     def update_ema():
-        _, desc, hyper, _, chunks, nchunks = o_ema._tables[:6]
-        K.check(K.lib.lavt_adamw_step_chunks_ema(K.ptr(desc), None, K.ptr(o_ema._tables[8]), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(o_ema._step),
+        T = o_ema._tables
+        K.check(K.lib.lavt_adamw_step_chunks_ema(K.ptr(T.desc), None, K.ptr(T.ema), K.ptr(T.hyper), K.ptr(T.chunks), T.nchunks, K.ptr(o_ema._step),
                                                  o_ema.total_steps, o_ema.power, o_ema.ema_decay, K.ptr(o_ema.guard), K.stream()))
 
     def swap():
-        _, desc, _, _, chunks, nchunks = o_ema._tables[:6]
-        K.check(K.lib.lavt_ema_swap(K.ptr(desc), K.ptr(o_ema._tables[8]), K.ptr(chunks), nchunks, K.stream()))
+        T = o_ema._tables
+        K.check(K.lib.lavt_ema_swap(K.ptr(T.desc), K.ptr(T.ema), K.ptr(T.chunks), T.nchunks, K.stream()))
 
     k = 10 * a.steps
     routes = [("replay_off", s_off.step, a.steps), ("replay_ema", s_ema.step, a.steps), ("update_off", update_off, k), ("update_ema", update_ema, k),
@@ -98,7 +98,7 @@ def main():
             torch.cuda.synchronize()
             times[name].append(e0.elapsed_time(e1) / n)
     elems = sum(p.numel() for g in o_ema.param_groups for p in g["params"] if p.requires_grad)
-    copies = sum(s_ema.context.weights.store[key][1].numel() for key in o_ema._tables[6])          # the bf16 copies the update writes itself
+    copies = sum(s_ema.context.weights.store[key][1].numel() for key in o_ema._tables.fused)          # the bf16 copies the update writes itself
     nbytes = {"update_off": 28 * elems + 2 * copies, "update_ema": 36 * elems + 2 * copies, "swap": 16 * elems + 2 * copies}
     lines = []
     for name, _, n in routes:

@@ -28,14 +28,15 @@ def timeit(fn, n=10):
     for _ in range(n): fn()
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / n
-_, desc, hyper, n, chunks, nchunks, fused = opt._tables[:7]
+T = opt._tables
+desc, hyper, n, chunks, nchunks, fused = T.desc, T.hyper, T.count, T.chunks, T.nchunks, T.fused
 nparam = sum(p.numel() for g in opt.param_groups for p in g["params"])
 print("tensors", n, "parameters %.1f M" % (nparam / 1e6))
 t_all = timeit(lambda: opt.step(check_tables=False))
 if EMA is None:
     t_adam = timeit(lambda: K.check(K.lib.lavt_adamw_step_chunks(K.ptr(desc), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(opt._step), opt.total_steps, opt.power, K.stream())))
 else:
-    t_adam = timeit(lambda: K.check(K.lib.lavt_adamw_step_chunks_ema(K.ptr(desc), None, K.ptr(opt._tables[8]), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(opt._step),
+    t_adam = timeit(lambda: K.check(K.lib.lavt_adamw_step_chunks_ema(K.ptr(desc), None, K.ptr(T.ema), K.ptr(hyper), K.ptr(chunks), nchunks, K.ptr(opt._step),
                                                                      opt.total_steps, opt.power, EMA, None, K.stream())))
 t_ref = None
 t_ref = timeit(lambda: ops.weights.refresh_all(done=fused))

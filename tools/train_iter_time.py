@@ -42,7 +42,7 @@ def main():
     from lavt_hip import ops, _capi as K
     from lavt_hip.detweights import det_inputs, fill_state_dict_
     from lavt_hip.engine import TrainStep
-    from lavt_hip.optim import FusedAdamW, lavt_param_groups
+    from lavt_hip.optim import FusedAdamW, initial_control_block, lavt_param_groups
     from lib import segmentation
     if not torch.cuda.is_available():
         sys.exit("train_iter_time.py measures on the GPU only")
@@ -71,8 +71,8 @@ def main():
     sa, oa = harness(False)
     sb, ob = harness(True)
     sc, oc = harness(True, max_grad_norm=1.0, skip_nonfinite=True)
-    _, desc, _, _, chunks, nchunks, _ = oc._tables[:7]
-    ctl = torch.tensor([0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0]).to(dev)
+    desc, chunks, nchunks = oc._tables.desc, oc._tables.chunks, oc._tables.nchunks
+    ctl = initial_control_block().to(dev)
     ws = torch.empty(int(K.lib.lavt_grad_norm_ws(nchunks)), dtype=torch.float32, device=dev)
     flat = sc.buckets.flat
     norm_elems = sum(p.numel() for g in oc.param_groups for p in g["params"] if p.requires_grad)
