@@ -780,6 +780,32 @@ int lavt_meter_append(const float* stats, const float* ctl /* NULL */, const flo
 int lavt_grad_norm_tensors(const float* ws, int nchunks, const int32_t* first, int count, const float* ctl, double* out, int32_t* bad, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Evaluation meter (csrc/meters.hip; the reference's evaluation log, test.py:84-108: per-sample IoU, cumulative I / U, precision@X) kept on the
+ * device like the training meters: it follows graph replays and is copied out when the host wants to look.  Two new symbols under ABI v7.
+ *
+ * The block: lavt_eval_meter_bytes(capacity) = 8 * LAVT_EVAL_METER_HEADER_DOUBLES + capacity * LAVT_EVAL_METER_RECORD_BYTES bytes of device memory,
+ * 8-byte aligned, zero-filled by the caller except header[0].  Header: fp64[LAVT_EVAL_METER_HEADER_DOUBLES]; counts are whole numbers held in fp64,
+ * exact up to 2^53:
+ *   [0] capacity (host; informational)      [1] hold: written by the HOST only, non-zero = an append does nothing
+ *   [2] n: samples appended since the block was made = the running sample number of the next record
+ *   the accumulators, zeroed by the host's reset:
+ *   [3] count      [4] sum of iou      [5] cumulative I      [6] cumulative U      [7..11] correct: samples with iou >= .5, .6, .7, .8, .9
+ *   [12..15] reserved, zero
+ * Ring: capacity records of LAVT_EVAL_METER_RECORD_BYTES bytes behind the header, sample `s` in slot s % capacity:
+ *   offset 0 int32 I | 4 int32 U | 8 int64 running sample number
+ *
+ * lavt_eval_meter_append: ONE single-writer launch behind the mask kernel.  iu: int32 [n][2], the (I, U) rows of lavt_upsample_mask(_pairs).
+ * image_of: the pair list's DEVICE int32 [n] with n_images (the image_of contract below), or NULL = every slot is live.  For every live slot in
+ * slot order, what EvalMeter.update does for one (I, U) (test.py:84-95):
+ *   iou = U == 0 ? 0 : (double)I / (double)U (an fp64 division); count += 1; sum of iou += iou (fp64, in order); cumulative I += I, U += U;
+ *   correct[k] += iou >= th_k, compared in fp64 against the double literals .5 .. .9; the record {I, U, header[2]} is stored and header[2] += 1.
+ * An empty slot's row of iu is not read.  Nothing at all is stored when header[1] != 0.  `capacity` must be the block's. */
+#define LAVT_EVAL_METER_HEADER_DOUBLES 16
+#define LAVT_EVAL_METER_RECORD_BYTES 16
+int64_t lavt_eval_meter_bytes(int capacity);
+int lavt_eval_meter_append(const int32_t* iu, const int32_t* image_of /* NULL: every slot live */, int n_images, int n, void* block, int capacity, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Inference path (csrc/infer.hip; reference test.py:60-110 and test_ytvos.py:230-260: batch-1 forward under model.eval() / torch.no_grad(), argmax,
  * I / U).  New symbols only, added under ABI v7: no existing prototype or struct changed.
  *
@@ -802,6 +828,17 @@ int lavt_conv_bn_fold(const float* w, const float* gamma, const float* beta, con
 int lavt_splitk_reduce_epi(int dtype, const float* parts, int splits, int64_t M, int N, const float* bias, int act, void* out, int64_t ldc, void* stream);
 int lavt_upsample_mask(int dtype, const void* x, int B, int Hi, int Wi, int Hm, int Wm, int Ho, int Wo, uint8_t* mask, const int64_t* target, int32_t* iu,
                        void* stream);
+/* Pair-list prediction batches.  A batch is a list of n pairs (image, expression): the network holds n_images images and n expressions, and a DEVICE
+ * int32 [n] buffer image_of names the image of every slot (lavt_gather_samples repeats stage 0's rows by it; everything behind runs on n samples).
+ * Contract for image_of, next to the contract for sel above: n may be smaller than, equal to or larger than n_images; entries may repeat; an entry
+ * outside [0, n_images) -- canonically -1 -- marks an EMPTY slot, so the last batch of a dataset replays the graph of a full one.  The kernels read
+ * image_of on the device, so a replayed graph follows a changed buffer, and therefore they cannot raise: an empty slot is gathered as zeros, the
+ * network runs on those and on whatever language the slot holds, and its logits (possibly NaN) are never read for a decision.  Range is checked on
+ * the host where the entries arrive from the host (lavt_hip.engine: Predictor.set_image_of).
+ * lavt_upsample_mask_pairs: lavt_upsample_mask with B = n slots and that buffer.  A live slot's mask bytes and iu row are those lavt_upsample_mask
+ * stores for the same logit rows; an empty slot's mask is all zero and it adds nothing to iu, so its row stays what the caller's fill left: (0, 0). */
+int lavt_upsample_mask_pairs(int dtype, const void* x, int B, int Hi, int Wi, int Hm, int Wm, int Ho, int Wo, uint8_t* mask, const int64_t* target, int32_t* iu,
+                             const int32_t* image_of, int n_images, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Frame preprocessing (csrc/preprocess.hip; replaces the host-side transforms.py:20-31 (Resize), 83-87 (ToTensor), 106-113 (Normalize) and the

@@ -109,9 +109,12 @@ template <typename T> __device__ __forceinline__ bool up_mask_pixel(const T* bas
 
 // One thread = 4 consecutive pixels of the flat [B*Ho*Wo] mask (a group may run over a row or sample end), stored as one 32-bit word.  Counts: one
 // ballot per pixel slot, popcounts added per wave, two integer atomics per wave when the whole wave lies in one sample (all but <= B - 1 waves).
-template <typename T>
+// PAIRS (include/lavt_hip.h: the image_of contract): sample b is slot b of a pair list, live when image_of[b] lies in [0, n_images).  The liveness test
+// is per pixel's sample, because a group of 4 and a wave run over sample ends: a pixel of an empty slot loads no logits (they may be NaN), stores a
+// zero byte and is false in both ballots -- an empty slot's wave counts 0 and issues no atomic.  PAIRS = false is the plain kernel, the two arguments unused.
+template <typename T, bool PAIRS>
 __global__ __launch_bounds__(256) void upsample_mask_kernel(const T* __restrict__ x, UpMaskDims d, uint8_t* __restrict__ mask, const int64_t* __restrict__ target,
-                                                            int* __restrict__ iu) {
+                                                            int* __restrict__ iu, const int32_t* __restrict__ image_of, int n_images) {
     const int64_t HW = (int64_t)d.Ho * d.Wo, total = d.B * HW;
     const int64_t g0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) * 4;
     uint32_t word = 0;
@@ -121,6 +124,10 @@ __global__ __launch_bounds__(256) void upsample_mask_kernel(const T* __restrict_
         const int64_t g = g0 + j;
         if (g < total) {
             const int b = (int)(g / HW);
+            if constexpr (PAIRS) {
+                const int img = image_of[b];
+                if (img < 0 || img >= n_images) continue;
+            }
             const int64_t r = g - b * HW;
             const int yo = (int)(r / d.Wo), xo = (int)(r - (int64_t)yo * d.Wo);
             const bool p = up_mask_pixel<T>(x + (int64_t)b * d.Hi * d.Wi * 2, d, yo, xo);
@@ -190,21 +197,38 @@ extern "C" int lavt_splitk_reduce_epi(int dtype, const float* parts, int splits,
     return LAVT_OK;
 }
 
-extern "C" int lavt_upsample_mask(int dtype, const void* x, int B, int Hi, int Wi, int Hm, int Wm, int Ho, int Wo, uint8_t* mask, const int64_t* target, int32_t* iu,
-                                  void* stream) {
-    LAVT_CHECK_ARG(x && mask && B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "lavt_upsample_mask: bad arguments");
-    LAVT_CHECK_ARG((Hm == 0 && Wm == 0) || (Hm > 0 && Wm > 0), "lavt_upsample_mask: Hm, Wm are both 0 (one interpolation) or both positive");
-    LAVT_CHECK_ARG(!target || iu, "lavt_upsample_mask: a target needs the iu output");
-    LAVT_CHECK_ARG(((uintptr_t)mask % 4) == 0 && ((uintptr_t)x % 8) == 0, "lavt_upsample_mask: mask must be 4-byte, x 8-byte aligned");
+static int upsample_mask_launch(const char* who, int dtype, const void* x, int B, int Hi, int Wi, int Hm, int Wm, int Ho, int Wo, uint8_t* mask, const int64_t* target,
+                                int32_t* iu, const int32_t* image_of, int n_images, void* stream) {
+    if (!(x && mask && B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0)) { lavt_set_error("%s: bad arguments", who); return LAVT_ERR_INVALID; }
+    if (!((Hm == 0 && Wm == 0) || (Hm > 0 && Wm > 0))) { lavt_set_error("%s: Hm, Wm are both 0 (one interpolation) or both positive", who); return LAVT_ERR_INVALID; }
+    if (target && !iu) { lavt_set_error("%s: a target needs the iu output", who); return LAVT_ERR_INVALID; }
+    if (((uintptr_t)mask % 4) != 0 || ((uintptr_t)x % 8) != 0) { lavt_set_error("%s: mask must be 4-byte, x 8-byte aligned", who); return LAVT_ERR_INVALID; }
     UpMaskDims d;
     d.B = B; d.Hi = Hi; d.Wi = Wi; d.Hm = Hm; d.Wm = Wm; d.Ho = Ho; d.Wo = Wo;
     if (Hm > 0) { d.sh = bl_scale(Hm, Ho); d.sw = bl_scale(Wm, Wo); d.mh = bl_scale(Hi, Hm); d.mw = bl_scale(Wi, Wm); }
     else { d.sh = bl_scale(Hi, Ho); d.sw = bl_scale(Wi, Wo); d.mh = d.mw = 0.f; }
     const int64_t groups = ((int64_t)B * Ho * Wo + 3) / 4, blocks = (groups + 255) / 256;
-    LAVT_CHECK_ARG(blocks <= 0x7fffffff, "lavt_upsample_mask: too many pixels for one launch");
-    if (dtype == LAVT_F32) hipLaunchKernelGGL(upsample_mask_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, ST, (const float*)x, d, mask, target, iu);
-    else if (dtype == LAVT_BF16) hipLaunchKernelGGL(upsample_mask_kernel<bf16>, dim3((unsigned)blocks), dim3(256), 0, ST, (const bf16*)x, d, mask, target, iu);
-    else { lavt_set_error("lavt_upsample_mask: bad dtype %d", dtype); return LAVT_ERR_INVALID; }
-    LAVT_CHECK_LAUNCH("lavt_upsample_mask");
+    if (blocks > 0x7fffffff) { lavt_set_error("%s: too many pixels for one launch", who); return LAVT_ERR_INVALID; }
+    const dim3 grid((unsigned)blocks), block(256);
+    if (dtype != LAVT_F32 && dtype != LAVT_BF16) { lavt_set_error("%s: bad dtype %d", who, dtype); return LAVT_ERR_INVALID; }
+    if (image_of) {
+        if (dtype == LAVT_F32) hipLaunchKernelGGL((upsample_mask_kernel<float, true>), grid, block, 0, ST, (const float*)x, d, mask, target, iu, image_of, n_images);
+        else hipLaunchKernelGGL((upsample_mask_kernel<bf16, true>), grid, block, 0, ST, (const bf16*)x, d, mask, target, iu, image_of, n_images);
+    } else {
+        if (dtype == LAVT_F32) hipLaunchKernelGGL((upsample_mask_kernel<float, false>), grid, block, 0, ST, (const float*)x, d, mask, target, iu, nullptr, 0);
+        else hipLaunchKernelGGL((upsample_mask_kernel<bf16, false>), grid, block, 0, ST, (const bf16*)x, d, mask, target, iu, nullptr, 0);
+    }
+    LAVT_CHECK_LAUNCH(who);
     return LAVT_OK;
+}
+
+extern "C" int lavt_upsample_mask(int dtype, const void* x, int B, int Hi, int Wi, int Hm, int Wm, int Ho, int Wo, uint8_t* mask, const int64_t* target, int32_t* iu,
+                                  void* stream) {
+    return upsample_mask_launch("lavt_upsample_mask", dtype, x, B, Hi, Wi, Hm, Wm, Ho, Wo, mask, target, iu, nullptr, 0, stream);
+}
+
+extern "C" int lavt_upsample_mask_pairs(int dtype, const void* x, int B, int Hi, int Wi, int Hm, int Wm, int Ho, int Wo, uint8_t* mask, const int64_t* target, int32_t* iu,
+                                        const int32_t* image_of, int n_images, void* stream) {
+    LAVT_CHECK_ARG(image_of && n_images > 0 && ((uintptr_t)image_of % 4) == 0, "lavt_upsample_mask_pairs: image_of (4-byte aligned) and n_images > 0 are required");
+    return upsample_mask_launch("lavt_upsample_mask_pairs", dtype, x, B, Hi, Wi, Hm, Wm, Ho, Wo, mask, target, iu, image_of, n_images, stream);
 }

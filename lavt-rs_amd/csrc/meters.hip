@@ -3,6 +3,8 @@
 // iteration (train.py:231-235, 463-477) stays on the device and follows graph replays; the host copies the block out when it wants to look.
 // A latency-bound single-round launch: every load is issued before the first use.  What it reads of the optimizer -- the control block's slots, the
 // hyper row, the schedule -- it reads through optim_protocol.h and the LAVT_CTL_* / LAVT_ADAMW_HYPER_* names of the public header.
+// The evaluation meter (include/lavt_hip.h "Evaluation meter") is its sibling behind a Predictor's mask kernel: the (I, U) rows of a prediction batch
+// go into the accumulators of the reference's evaluation loop (test.py:84-108) and a ring of per-sample records.
 #include "common.h"
 #include "optim_protocol.h"
 
@@ -79,6 +81,69 @@ __global__ __launch_bounds__(64) void meter_append_kernel(const float* __restric
     }
 }
 
+// ---------------------------------------------------------------------------------------------- evaluation meter (include/lavt_hip.h "Evaluation meter")
+// What EvalMeter.update does for the (I, U) rows of one prediction batch (test.py:84-95), on the device.  One wave: every lane loads one slot's counts and
+// liveness (all loads of a chunk of 64 slots in flight at once), lane 0 then walks the live slots in slot order -- the fp64 sum is sequential.
+enum { E_CAPACITY = 0, E_HOLD, E_N, E_COUNT, E_IOU_SUM, E_CUM_I, E_CUM_U, E_CORRECT0 };
+
+struct eval_record {
+    int32_t I, U;
+    int64_t sample;
+};
+static_assert(sizeof(eval_record) == LAVT_EVAL_METER_RECORD_BYTES, "the record layout is the contract of include/lavt_hip.h");
+static_assert(E_CORRECT0 + 5 <= LAVT_EVAL_METER_HEADER_DOUBLES, "the header holds the five precision counters");
+
+__global__ __launch_bounds__(64) void eval_meter_append_kernel(const int32_t* __restrict__ iu, const int32_t* __restrict__ image_of, int n_images, int n,
+                                                               double* __restrict__ block, int capacity) {
+    __shared__ int32_t sI[64], sU[64];
+    const int lane = threadIdx.x;
+    double h[E_CORRECT0 + 5];
+#pragma unroll
+    for (int i = 0; i < E_CORRECT0 + 5; ++i) h[i] = block[i];
+    // hold (host-written), or a block that was never initialised: nothing is stored (uniform over the wave, so the barriers below are safe)
+    if (h[E_HOLD] != 0.0 || !(h[E_N] >= 0.0 && h[E_N] < 9.0e15) || capacity <= 0) return;
+    eval_record* ring = reinterpret_cast<eval_record*>(block + LAVT_EVAL_METER_HEADER_DOUBLES);
+    const double thr[5] = {0.5, 0.6, 0.7, 0.8, 0.9};
+    for (int base = 0; base < n; base += 64) {
+        const int s = base + lane;
+        bool live = s < n;
+        if (live && image_of) {
+            const int img = image_of[s];
+            live = img >= 0 && img < n_images;
+        }
+        int32_t I = 0, U = 0;
+        if (live) { I = iu[2 * s]; U = iu[2 * s + 1]; }
+        sI[lane] = I;
+        sU[lane] = U;
+        const unsigned long long mask = __ballot(live);
+        __syncthreads();
+        if (lane == 0) {
+            for (int j = 0; j < 64; ++j) {
+                if (!((mask >> j) & 1ull)) continue;
+                const int32_t cI = sI[j], cU = sU[j];
+                const double iou = cU == 0 ? 0.0 : (double)cI / (double)cU;          // test.py:86-89: a true fp64 division
+                const int64_t sample = (int64_t)h[E_N];
+                eval_record r;
+                r.I = cI; r.U = cU; r.sample = sample;
+                ring[sample % capacity] = r;
+                h[E_N] += 1.0;
+                h[E_COUNT] += 1.0;
+                h[E_IOU_SUM] += iou;
+                h[E_CUM_I] += (double)cI;
+                h[E_CUM_U] += (double)cU;
+#pragma unroll
+                for (int k = 0; k < 5; ++k)
+                    if (iou >= thr[k]) h[E_CORRECT0 + k] += 1.0;
+            }
+        }
+        __syncthreads();
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = E_N; i < E_CORRECT0 + 5; ++i) block[i] = h[i];
+    }
+}
+
 }  // namespace
 
 #define ST reinterpret_cast<hipStream_t>(stream)
@@ -93,5 +158,18 @@ extern "C" int lavt_meter_append(const float* stats, const float* ctl, const flo
     LAVT_CHECK_ARG((reinterpret_cast<uintptr_t>(block) & 7) == 0, "lavt_meter_append: the block must be 8-byte aligned");
     hipLaunchKernelGGL(meter_append_kernel, dim3(1), dim3(64), 0, ST, stats, ctl, step, hyper, total_steps, power, reinterpret_cast<double*>(block), capacity);
     LAVT_CHECK_LAUNCH("lavt_meter_append");
+    return LAVT_OK;
+}
+
+extern "C" int64_t lavt_eval_meter_bytes(int capacity) {
+    return capacity > 0 ? (int64_t)LAVT_EVAL_METER_HEADER_DOUBLES * 8 + (int64_t)capacity * LAVT_EVAL_METER_RECORD_BYTES : 0;
+}
+
+extern "C" int lavt_eval_meter_append(const int32_t* iu, const int32_t* image_of, int n_images, int n, void* block, int capacity, void* stream) {
+    LAVT_CHECK_ARG(iu && block && n > 0 && capacity > 0, "lavt_eval_meter_append: bad arguments (iu, block, n > 0, capacity > 0)");
+    LAVT_CHECK_ARG(!image_of || n_images > 0, "lavt_eval_meter_append: image_of needs n_images > 0");
+    LAVT_CHECK_ARG((reinterpret_cast<uintptr_t>(block) & 7) == 0, "lavt_eval_meter_append: the block must be 8-byte aligned");
+    hipLaunchKernelGGL(eval_meter_append_kernel, dim3(1), dim3(64), 0, ST, iu, image_of, n_images, n, reinterpret_cast<double*>(block), capacity);
+    LAVT_CHECK_LAUNCH("lavt_eval_meter_append");
     return LAVT_OK;
 }

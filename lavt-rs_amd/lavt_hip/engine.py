@@ -673,10 +673,20 @@ class Predictor(_ValidIndices, _BatchInput):
       valid_indices   optional device int32 [nsel], a static buffer: the flat numbers of the annotated frames of the clips (A2D-Sentences / JHMDB,
                   test.py:182-205).  The backbone runs on all frames, the decoder and the mask kernel on the nsel selected ones: mask (nsel, Ho, Wo),
                   target (if given) (nsel, Ho, Wo), iu (nsel, 2).  set_valid_indices(per_clip, frames_per_clip) fills it, also between replays.
-    step() never synchronises: it returns the static mask tensor, the caller decides when to read it (EvalMeter.update(pred.iu) reads `.iu`)."""
+      image_of    optional device int32 [N], a static buffer, N = lang.shape[0]: a PAIR-LIST batch (include/lavt_hip.h: the image_of contract).  `image`
+                  holds B images, lang / l_mask N expressions, slot j pairs expression j with image image_of[j]; N may be smaller or larger than B
+                  (RefCOCO: a ragged number of sentences per referent, several referents per image), an entry outside [0, B) -- canonically -1 --
+                  is an EMPTY slot: zero mask, iu row (0, 0), so the last batch of a dataset needs no second graph.  mask (N, Ho, Wo), target (if
+                  given) (N, Ho, Wo), iu (N, 2).  set_image_of(seq) fills it, also between replays.  load_batch / stage_batch(target_map=) bring B
+                  images and N target masks.
+      meter       optional lavt_hip.metrics.DeviceEvalMeter (or make_meter() / attach_meter() later, before warmup_and_capture()): the body ends with
+                  one more launch that does EvalMeter.update(pred.iu) on the device, for the live slots only.  Needs a target.
+    step() never synchronises: it returns the static mask tensor, the caller decides when to read it (EvalMeter.update(pred.iu) reads `.iu` with one
+    copy per call; a DeviceEvalMeter reads nothing until poll() / read()).  Built with neither image_of nor meter, the launches are those of a
+    predictor without the two arguments."""
 
     def __init__(self, model, image, lang, l_mask, *, target=None, out_size=None, via_size=None, expressions_per_image=1, use_graph=True, context=None,
-                 valid_indices=None):
+                 valid_indices=None, image_of=None, meter=None):
         if model.training:
             raise RuntimeError("Predictor: the model is in training mode -- call model.eval() first (BatchNorm is folded from the running statistics, DropPath is off)")
         for name, t in (("image", image), ("lang", lang), ("l_mask", l_mask), ("target", target)):
@@ -692,9 +702,23 @@ class Predictor(_ValidIndices, _BatchInput):
                 raise ValueError("Predictor: valid_indices selects frames of clips; it cannot be combined with expressions_per_image > 1")
             _check_index_buffer("Predictor", valid_indices, target, image.numel() // (3 * int(image.shape[-2]) * int(image.shape[-1])))
         self.valid_indices = valid_indices
+        if image_of is not None:
+            if S != 1:
+                raise ValueError("Predictor: image_of names the image of every expression; it cannot be combined with expressions_per_image != 1")
+            if valid_indices is not None:
+                raise ValueError("Predictor: image_of (pair-list batches) cannot be combined with valid_indices (annotated frames of clips)")
+            if not getattr(model.backbone, "shares_stage0", False):
+                raise NotImplementedError(f"Predictor: image_of needs a backbone that shares stage 0 between expressions; {type(model.backbone).__name__} does not")
+            if not isinstance(image_of, torch.Tensor) or not image_of.is_cuda:
+                raise RuntimeError("liblavt_hip operates on GPU memory only (got a CPU tensor for `image_of`); there is no CPU fallback")
+            if image_of.dtype != torch.int32 or image_of.dim() != 1 or not image_of.is_contiguous() or image_of.numel() != lang.shape[0]:
+                raise ValueError(f"Predictor: image_of must be a contiguous int32 vector with one entry per expression ({lang.shape[0]}), got {image_of.dtype} {tuple(image_of.shape)}")
+            if target is not None and target.shape[0] != image_of.numel():
+                raise ValueError(f"Predictor: {image_of.numel()} pairs need a target of as many samples, got {tuple(target.shape)}")
+        self.image_of = image_of
         if S > 1 and not getattr(model.backbone, "shares_stage0", False):
             raise NotImplementedError(f"Predictor: expressions_per_image > 1 needs a backbone that shares stage 0 between expressions; {type(model.backbone).__name__} does not")
-        if lang.shape[0] != image.shape[0] * S:
+        if image_of is None and lang.shape[0] != image.shape[0] * S:
             raise ValueError(f"Predictor: {lang.shape[0]} expressions for {image.shape[0]} images x {S} expressions per image")
         self.context = context if context is not None else ops.default_context()
         self.model, self.x, self.l, self.m, self.t = model, image, lang, l_mask, target
@@ -712,6 +736,47 @@ class Predictor(_ValidIndices, _BatchInput):
         # buffers (the running statistics are folded into weights) and re-casts / re-folds eagerly, into the same storage, when anything moved
         self._state = [t for t in list(model.parameters()) + list(model.buffers())]
         self._seen = None
+        self._warmed = False
+        self.meter = None
+        if meter is not None:
+            self.attach_meter(meter)
+
+    # ---- pair-list batches ----
+    def set_image_of(self, image_of):
+        """image_of[j] = the image of slot j (host integers; -1 = an empty slot): writes the static index buffer after checking the length and that
+        every entry is -1 or in [0, B) (ValueError).  An asynchronous copy through pinned memory on the current stream, nothing synchronises;
+        usable between replays -- the captured kernels read the buffer on the device."""
+        if self.image_of is None:
+            raise ValueError("Predictor.set_image_of: built without an image_of buffer")
+        pairs = [int(v) for v in image_of]
+        B = int(self.x.shape[0])
+        if len(pairs) != self.image_of.numel():
+            raise ValueError(f"Predictor.set_image_of: {len(pairs)} entries for an index buffer of {self.image_of.numel()}")
+        bad = [(j, v) for j, v in enumerate(pairs) if not -1 <= v < B]
+        if bad:
+            raise ValueError(f"Predictor.set_image_of: (slot, image) {bad} -- an entry is -1 (an empty slot) or one of the {B} images of the batch")
+        self.image_of.copy_(torch.tensor(pairs, dtype=torch.int32).pin_memory(), non_blocking=True)
+
+    # ---- the evaluation log on the device ----
+    def make_meter(self, **kw):
+        """Build a lavt_hip.metrics.DeviceEvalMeter(**kw) on the predictor's device, attach it and return it.  Before warmup_and_capture() only."""
+        from .metrics import DeviceEvalMeter
+        kw.setdefault("device", self.x.device)
+        return self.attach_meter(DeviceEvalMeter(**kw))
+
+    def attach_meter(self, meter):
+        """Make an existing DeviceEvalMeter part of the prediction step: the body then ends with ONE more launch, lavt_eval_meter_append on `iu`, which
+        counts every live sample of every step().  Before warmup_and_capture() only; needs a `target`."""
+        if self._warmed:
+            raise RuntimeError("Predictor: a meter must be attached before warmup_and_capture() (the captured launch sequence is frozen)")
+        if self.meter is not None:
+            raise RuntimeError("Predictor: a meter is already attached")
+        if self.t is None:
+            raise ValueError("Predictor: a meter logs the I / U counts of `iu`; this predictor was built without a target")
+        if meter.block.device != self.x.device:
+            raise ValueError(f"Predictor: the meter lives on {meter.block.device}, the predictor on {self.x.device}")
+        self.meter = meter
+        return meter
 
     def _stamp(self):
         # (ops.raw_writes: the fused optimizer, the train-mode BatchNorm kernels, an in-place checkpoint load and the weight-average swap write through
@@ -721,19 +786,36 @@ class Predictor(_ValidIndices, _BatchInput):
     @_in_context
     def _body(self):
         with torch.no_grad():
-            if self.valid_indices is None:
+            if self.image_of is not None:
+                y = self.model.forward_lowres(self.x, self.l, self.m, folded=True, image_of=self.image_of)
+            elif self.valid_indices is None:
                 y = self.model.forward_lowres(self.x, self.l, self.m, folded=True, expand=self.S)
             else:
                 y = self.model.forward_lowres(self.x, self.l, self.m, folded=True, frames=self.valid_indices)
             n, _, h, w = y.shape
             from lib.mask_predictor import nchw_rows
-            self.mask, self.iu = ops.upsample_mask(nchw_rows(y, y.dtype), n, h, w, self.out_size, via_size=self.via_size, target=self.t)
+            n_images = int(self.x.shape[0]) if self.image_of is not None else None
+            self.mask, self.iu = ops.upsample_mask(nchw_rows(y, y.dtype), n, h, w, self.out_size, via_size=self.via_size, target=self.t, image_of=self.image_of,
+                                                   n_images=n_images)
+            if self.meter is not None:          # the last launch of the step
+                self.meter.append(self.iu, self.image_of, n_images or 0)
         return self.mask
 
-    @_in_context
     def warmup_and_capture(self, eager_iters=2):
         """eager_iters eager runs on a side stream (every compute copy and row map exists afterwards), then -- use_graph -- the body is captured into one
-        torch.cuda.CUDAGraph on that stream: a straight-line sequence, no forked branches.  A failed capture is reported and the eager path kept."""
+        torch.cuda.CUDAGraph on that stream: a straight-line sequence, no forked branches.  A failed capture is reported and the eager path kept.
+        An attached meter is on hold (DeviceEvalMeter.pause) for the eager runs and the capture and released at the end: its count is what it was."""
+        self._warmed = True
+        if self.meter is None:
+            return self._warmup_and_capture(eager_iters)
+        self.meter.pause()
+        try:
+            return self._warmup_and_capture(eager_iters)
+        finally:
+            self.meter.resume()
+
+    @_in_context
+    def _warmup_and_capture(self, eager_iters):
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):

@@ -191,7 +191,87 @@ def reference_log(losses, Is, Us, capacity, window_size, lrs=None, grad_norms=No
     return Snapshot(raw, capacity, window_size)
 
 
-class TrainMeters:
+class DeviceBlock:
+    """A block of fp64 words on the device -- word 0 the capacity, word 1 the hold word, as both meter layouts of include/lavt_hip.h have them -- with
+    two pinned host buffers: the looking (poll / read) and the host writes (pause / resume, between two synchronisations) of TrainMeters and of
+    lavt_hip.metrics.DeviceEvalMeter.  A subclass sets `nbytes`, `capacity`, `header_doubles` before _host_init() and decodes a copy in _decode()."""
+    header_doubles = HEADER_DOUBLES
+
+    def _host_init(self, device):
+        who = type(self).__name__
+        self._not_capturing(f"{who}()")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError(f"{who} lives in GPU memory only (no CPU fallback)")
+        words = torch.zeros(self.nbytes // 8, dtype=torch.float64)
+        words[H_CAPACITY] = float(self.capacity)
+        self.block = words.to(dev)                               # fp64 words: 8-byte aligned; the ring is addressed in bytes behind the header
+        self.header = self.block[:self.header_doubles]
+        self._host = [torch.empty(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self._events = [torch.cuda.Event(), torch.cuda.Event()]
+        self._inflight = None                                    # index of the buffer a copy is on its way to
+        self._next = 0
+        self._latest = None
+
+    @staticmethod
+    def _not_capturing(who):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{who} is a host call: it is refused inside a graph capture")
+
+    def _decode(self, raw):
+        raise NotImplementedError
+
+    # ---- looking
+    def _collect(self):
+        i = self._inflight
+        if i is not None and self._events[i].query():
+            self._latest = self._decode(self._host[i].numpy())
+            self._inflight = None
+
+    def _enqueue(self):
+        i = self._next
+        with torch.no_grad():
+            self._host[i].copy_(self.block.view(torch.uint8), non_blocking=True)
+        self._events[i].record()
+        self._inflight, self._next = i, 1 - i
+
+    def poll(self):
+        """Enqueue a device-to-host copy of the block on the CURRENT stream and record an event; never waits.  -> the newest Snapshot whose copy has
+        completed (None before the first): it may be one poll old.  While an earlier copy is still on its way no further one is enqueued."""
+        self._not_capturing(f"{type(self).__name__}.poll")
+        self._collect()
+        if self._inflight is None:
+            self._enqueue()
+        return self._latest
+
+    def read(self):
+        """poll(), then wait for that one copy -> its Snapshot: the block as of everything enqueued on the current stream so far"""
+        self._not_capturing(f"{type(self).__name__}.read")
+        if self._inflight is not None:
+            self._events[self._inflight].synchronize()
+            self._collect()
+        self._enqueue()
+        self._events[self._inflight].synchronize()
+        self._collect()
+        return self._latest
+
+    # ---- host writes, between two synchronisations like FusedAdamW.hold()
+    def _host_write(self, who, fn):
+        self._not_capturing(who)
+        torch.cuda.synchronize(self.block.device)
+        with torch.no_grad():
+            fn()
+        torch.cuda.synchronize(self.block.device)
+
+    def pause(self):
+        """appends do nothing until resume() (warmup_and_capture pauses its eager iterations, the capture and the validation replays)"""
+        self._host_write(f"{type(self).__name__}.pause", lambda: self.header[H_HOLD:H_HOLD + 1].fill_(1.0))
+
+    def resume(self):
+        self._host_write(f"{type(self).__name__}.resume", lambda: self.header[H_HOLD:H_HOLD + 1].fill_(0.0))
+
+
+class TrainMeters(DeviceBlock):
     """The device block and two pinned host buffers.  capacity: records the ring holds (>= window_size); window_size: the reference's
     SmoothedValue(window_size=20).  device: where the block lives (default: the current CUDA device).  Attach to a step with
     TrainStep(..., meters=) or step.make_meters()."""
@@ -206,25 +286,8 @@ class TrainMeters:
             raise RuntimeError("TrainMeters: the library's block size is not the documented formula")
         self._host_init(device)
 
-    def _host_init(self, device):
-        self._not_capturing("TrainMeters()")
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("TrainMeters lives in GPU memory only (no CPU fallback)")
-        words = torch.zeros(self.nbytes // 8, dtype=torch.float64)
-        words[H_CAPACITY] = float(self.capacity)
-        self.block = words.to(dev)                               # fp64 words: 8-byte aligned; the ring is addressed in bytes behind the header
-        self.header = self.block[:HEADER_DOUBLES]
-        self._host = [torch.empty(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self._events = [torch.cuda.Event(), torch.cuda.Event()]
-        self._inflight = None                                    # index of the buffer a copy is on its way to
-        self._next = 0
-        self._latest = None
-
-    @staticmethod
-    def _not_capturing(who):
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"{who} is a host call: it is refused inside a graph capture")
+    def _decode(self, raw):
+        return Snapshot(raw, self.capacity, self.window_size)
 
     # ---- the launch (TrainStep._body ends with it)
     def append(self, stats, ctl=None, step=None, hyper=None, total_steps=0.0, power=0.0):
@@ -233,52 +296,10 @@ class TrainMeters:
         K.check(K.lib.lavt_meter_append(K.ptr(stats), K.ptr(ctl), K.ptr(step), hyper if isinstance(hyper, int) else K.ptr(hyper), float(total_steps), float(power),
                                         K.ptr(self.block), self.capacity, K.stream()))
 
-    # ---- looking
-    def _collect(self):
-        i = self._inflight
-        if i is not None and self._events[i].query():
-            self._latest = Snapshot(self._host[i].numpy(), self.capacity, self.window_size)
-            self._inflight = None
-
-    def _enqueue(self):
-        i = self._next
-        with torch.no_grad():
-            self._host[i].copy_(self.block.view(torch.uint8), non_blocking=True)
-        self._events[i].record()
-        self._inflight, self._next = i, 1 - i
-
-    def poll(self):
-        """Enqueue a device-to-host copy of the block on the CURRENT stream and record an event; never waits.  -> the newest Snapshot whose copy has
-        completed (None before the first): it may be one poll old.  While an earlier copy is still on its way no further one is enqueued."""
-        self._not_capturing("TrainMeters.poll")
-        self._collect()
-        if self._inflight is None:
-            self._enqueue()
-        return self._latest
-
-    def read(self):
-        """poll(), then wait for that one copy -> its Snapshot: the block as of everything enqueued on the current stream so far"""
-        self._not_capturing("TrainMeters.read")
-        if self._inflight is not None:
-            self._events[self._inflight].synchronize()
-            self._collect()
-        self._enqueue()
-        self._events[self._inflight].synchronize()
-        self._collect()
-        return self._latest
-
     def epoch_summary(self):
         """train.py:487-500 (synchronises once): mean IoU, precision@.5 .. .9 and overall IoU in percent, mean loss over the finite losses, and the
         iterations, applied / skipped updates and non-finite losses of the epoch"""
         return self.read().summary()
-
-    # ---- host writes, between two synchronisations like FusedAdamW.hold()
-    def _host_write(self, who, fn):
-        self._not_capturing(who)
-        torch.cuda.synchronize(self.block.device)
-        with torch.no_grad():
-            fn()
-        torch.cuda.synchronize(self.block.device)
 
     def reset_epoch(self):
         """zero the epoch accumulators and start the window here; `it` keeps counting"""
@@ -286,13 +307,6 @@ class TrainMeters:
             self.header[H_EPOCH_START:H_EPOCH_START + 1].copy_(self.header[H_N:H_N + 1])
             self.header[EPOCH_WORDS].zero_()
         self._host_write("TrainMeters.reset_epoch", write)
-
-    def pause(self):
-        """appends do nothing until resume() (TrainStep.warmup_and_capture pauses its eager iterations and validation replays)"""
-        self._host_write("TrainMeters.pause", lambda: self.header[H_HOLD:H_HOLD + 1].fill_(1.0))
-
-    def resume(self):
-        self._host_write("TrainMeters.resume", lambda: self.header[H_HOLD:H_HOLD + 1].fill_(0.0))
 
     # ---- checkpoint: an extra key of checkpoint.save_train_state(path, step, meters=meters.state_dict())
     def state_dict(self):

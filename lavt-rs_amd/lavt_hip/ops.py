@@ -3160,14 +3160,16 @@ def upsample_dice_boundary_loss(x, target, B, Hi, Wi, Ho, Wo, sel=None, dice_rat
     return _UpsampleDiceBoundary.apply(x, target, B, Hi, Wi, Ho, Wo, float(dice_rate), float(boundary_rate), _frame_sel(sel, B, "upsample_dice_boundary_loss"))
 
 
-def gather_samples(x, sel):
+def gather_samples(x, sel, pairs=False):
     """`torch.index_select(x, 0, sel)` for whole samples with sel on the device (int32 [nsel], see _frame_sel), no layout change: x is a dense tensor in
     ANY dimension order (an NCHW-shaped view of NHWC memory, as the backbone returns its feature maps, included) whose samples are contiguous blocks;
-    the result has x's strides with nsel samples.  Not differentiable (the inference path: lib._utils forward_lowres(frames=))."""
+    the result has x's strides with nsel samples.  Not differentiable (the inference path: lib._utils forward_lowres(frames=)).
+    pairs=True: sel is the `image_of` buffer of a pair-list batch (include/lavt_hip.h) -- 1..65535 entries, more than B allowed, entries may repeat, an
+    entry outside [0, B) gives a zero sample."""
     if not x.is_cuda:
         raise RuntimeError("liblavt_hip operates on GPU memory only (got a CPU tensor for `gather_samples`); there is no CPU fallback")
     B = int(x.shape[0])
-    sel = _frame_sel(sel, B, "gather_samples")
+    sel = _frame_sel(sel, 65535 if pairs else B, "gather_samples")
     per = x[0].numel()
     inner, expect = sorted((st, sz) for st, sz in zip(x.stride()[1:], x.shape[1:]) if sz > 1), 1
     for st, sz in inner:                         # a sample is a dense block when its strides, sorted, are the running products of its sizes
@@ -3183,16 +3185,24 @@ def gather_samples(x, sel):
 
 
 # ------------------------------------------------------------------------------------------ fused upsample + argmax (+ I/U counts): inference
-def upsample_mask(rows, B, Hi, Wi, out_size, via_size=None, target=None):
+def upsample_mask(rows, B, Hi, Wi, out_size, via_size=None, target=None, image_of=None, n_images=None):
     """`F.interpolate(y, out_size, bilinear, align_corners=True).argmax(1)` (lib/_utils.py:21 + test.py:81-83) on the decoder's 2-class logit rows
     [B*Hi*Wi, 2] without writing the upsampled logits: -> (mask uint8 [B, Ho, Wo], iu).  via_size = (Hm, Wm): the composition of two interpolations
     (Hi, Wi) -> via_size -> out_size of test_ytvos.py:249-253.  target (int64 [B, Ho, Wo], nonzero = foreground): iu int32 [B, 2] = per-sample
-    (sum(pred & gt), sum(pred | gt)) of test.py:242-246, zeroed here in front of every launch (a fill node of a captured sequence); else iu is None."""
+    (sum(pred & gt), sum(pred | gt)) of test.py:242-246, zeroed here in front of every launch (a fill node of a captured sequence); else iu is None.
+    image_of (device int32 [B]) with n_images: the B samples are the slots of a pair list (include/lavt_hip.h: the image_of contract):
+    a slot whose entry lies outside [0, n_images) gets an all-zero mask and the iu row (0, 0), its logits are never read."""
     rows = rows.contiguous()
     Ho, Wo = int(out_size[0]), int(out_size[1])
     Hm, Wm = (int(via_size[0]), int(via_size[1])) if via_size is not None else (0, 0)
     if rows.shape != (B * Hi * Wi, 2):
         raise ValueError(f"upsample_mask: expected [{B * Hi * Wi}, 2] logit rows, got {tuple(rows.shape)}")
+    if image_of is not None:
+        buf = image_of
+        if not isinstance(buf, torch.Tensor) or not buf.is_cuda:
+            raise RuntimeError("liblavt_hip operates on GPU memory only (got a CPU tensor for `image_of`); there is no CPU fallback")
+        if buf.dtype != torch.int32 or buf.dim() != 1 or not buf.is_contiguous() or buf.numel() != B or n_images is None or int(n_images) < 1:
+            raise ValueError(f"upsample_mask: image_of must be a contiguous int32 vector of {B} entries, with n_images >= 1; got {buf.dtype} {tuple(buf.shape)}, {n_images}")
     mask = torch.empty(B, Ho, Wo, dtype=torch.uint8, device=rows.device)
     iu = None
     if target is not None:
@@ -3201,7 +3211,11 @@ def upsample_mask(rows, B, Hi, Wi, out_size, via_size=None, target=None):
         target = target.contiguous()
         iu = torch.zeros(B, 2, dtype=torch.int32, device=rows.device)
     _note(f"upsample-mask {B}x{Hi}x{Wi}->{Ho}x{Wo}", nbytes=rows.numel() * rows.element_size() + mask.numel() + (8 * mask.numel() if target is not None else 0))
-    K.check(K.lib.lavt_upsample_mask(K.dt(rows.dtype), K.ptr(rows), B, Hi, Wi, Hm, Wm, Ho, Wo, K.ptr(mask), K.ptr(target), K.ptr(iu), K.stream()))
+    if image_of is None:
+        K.check(K.lib.lavt_upsample_mask(K.dt(rows.dtype), K.ptr(rows), B, Hi, Wi, Hm, Wm, Ho, Wo, K.ptr(mask), K.ptr(target), K.ptr(iu), K.stream()))
+    else:
+        K.check(K.lib.lavt_upsample_mask_pairs(K.dt(rows.dtype), K.ptr(rows), B, Hi, Wi, Hm, Wm, Ho, Wo, K.ptr(mask), K.ptr(target), K.ptr(iu), K.ptr(buf), int(n_images),
+                                               K.stream()))
     return mask, iu
 
 

@@ -57,6 +57,22 @@ def _check_frames(module, folded, frames):
                          "loss: fused_loss(y, target, valid_indices=frames)")
 
 
+def _check_image_of(expand, frames, image_of):
+    """image_of= (a pair-list batch, lib/backbone.py: forward; inference only, the backbone refuses it in training mode): one batch arrangement at a time"""
+    if image_of is None:
+        return
+    if expand != 1:
+        raise ValueError("forward_lowres: image_of= names the image of every expression; it cannot be combined with expand != 1")
+    if frames is not None:
+        raise ValueError("forward_lowres: image_of= cannot be combined with frames= (the annotated-frame selection of clip batches)")
+
+
+def _backbone(backbone, x, l_feats, l_mask, expand, image_of):
+    if image_of is not None:
+        return backbone(x, l_feats, l_mask, image_of=image_of)
+    return backbone(x, l_feats, l_mask, expand=expand) if expand != 1 else backbone(x, l_feats, l_mask)
+
+
 def _decode(classifier, folded, x_c4, x_c3, x_c2, x_c1, frames=None):
     """frames (device int32 [nsel]): decode only those samples -- test.py:182-205 of the reference selects the annotated frame of every clip behind
     the decoder; the BatchNorm-folded decoder is per-sample independent, so the backbone outputs are gathered in front of it instead
@@ -75,12 +91,15 @@ class _LAVTSimpleDecode(nn.Module):
         self.backbone = backbone
         self.classifier = classifier
 
-    def forward_lowres(self, x, l_feats, l_mask, folded=False, expand=1, frames=None):
+    def forward_lowres(self, x, l_feats, l_mask, folded=False, expand=1, frames=None, image_of=None):
         """decoder output before the final upsample, (B, 2, H/4, W/4)-shaped: feed it to `fused_loss`.
         Inference (lavt_hip.engine.Predictor): folded = the BatchNorm-folded decoder (eval mode); expand = S > 1 = S expressions per image (l_feats /
-        l_mask hold B * S of them), stage 0 of the backbone shared between the expressions of an image; frames: see _decode."""
+        l_mask hold B * S of them), stage 0 of the backbone shared between the expressions of an image; frames: see _decode.
+        image_of (device int32 [N]): a pair-list batch, l_feats / l_mask hold N expressions and the result N samples (lib/backbone.py: forward);
+        mutually exclusive with expand != 1 and with frames."""
         _check_frames(self, folded, frames)          # (raises in front of the backbone)
-        x_c1, x_c2, x_c3, x_c4 = self.backbone(x, l_feats, l_mask, expand=expand) if expand != 1 else self.backbone(x, l_feats, l_mask)
+        _check_image_of(expand, frames, image_of)
+        x_c1, x_c2, x_c3, x_c4 = _backbone(self.backbone, x, l_feats, l_mask, expand, image_of)
         return _decode(self.classifier, folded, x_c4, x_c3, x_c2, x_c1, frames)
 
     def forward(self, x, l_feats, l_mask):
@@ -119,13 +138,14 @@ class _LAVTOneSimpleDecode(nn.Module):
         self.text_encoder = _build_text_encoder(args)
         self.lazy_pred = bool(getattr(args, "lazy_pred", False))
 
-    def forward_lowres(self, x, text, l_mask, folded=False, expand=1, frames=None):
+    def forward_lowres(self, x, text, l_mask, folded=False, expand=1, frames=None, image_of=None):
         """token ids (B, N_l) + attention mask (B, N_l) -> decoder logits at 1/4 resolution (what the fused upsample + CE kernel consumes).
-        folded / expand / frames: see LAVT.forward_lowres (with expand = S the ids and the mask hold B * S expressions)."""
+        folded / expand / frames / image_of: see LAVT.forward_lowres (with expand = S the ids and the mask hold B * S expressions, with image_of N)."""
         _check_frames(self, folded, frames)
+        _check_image_of(expand, frames, image_of)
         l_feats = self.text_encoder(text, attention_mask=l_mask)[0].permute(0, 2, 1)      # (B, 768, N_l)
         l_mask = l_mask.unsqueeze(dim=-1)
-        features = self.backbone(x, l_feats, l_mask, expand=expand) if expand != 1 else self.backbone(x, l_feats, l_mask)
+        features = _backbone(self.backbone, x, l_feats, l_mask, expand, image_of)
         if self.lazy_pred:
             x_c1, (x_c2, x_c3, x_c4) = None, features
         else:
@@ -169,11 +189,13 @@ class _LAVTVideoSimpleDecode(nn.Module):
         l_feats = self.text_encoder(text, attention_mask=l_mask)[0].permute(0, 2, 1)      # (B, 768, N_l)
         return self.forward_backbone(x, l_feats, l_mask.unsqueeze(dim=-1))
 
-    def forward_lowres(self, x, text, l_mask, folded=False, expand=1, frames=None):
+    def forward_lowres(self, x, text, l_mask, folded=False, expand=1, frames=None, image_of=None):
         """clip (B, T, 3, H, W) + token ids + attention mask -> decoder logits (B*T, 2, H/4, W/4)-shaped, before the final upsample.
-        folded: the BatchNorm-folded decoder (eval mode).  The video backbone has no shared stage 0: expand > 1 raises NotImplementedError.
+        folded: the BatchNorm-folded decoder (eval mode).  The video backbone has no shared stage 0: expand > 1 and image_of raise NotImplementedError.
         frames (device int32 [nsel], flat numbers i * T + ind): only the annotated frames are decoded, -> (nsel, 2, H/4, W/4)-shaped; see _decode."""
         _check_frames(self, folded, frames)
+        if image_of is not None:
+            raise NotImplementedError("LAVTVideo.forward_lowres: image_of= (pair-list batches) needs a backbone that shares stage 0 between expressions; the video backbone does not")
         l_feats = self.text_encoder(text, attention_mask=l_mask)[0].permute(0, 2, 1)
         features = self.backbone(x.permute(0, 2, 1, 3, 4), l_feats, l_mask.unsqueeze(dim=-1), expand=expand)
         if self.lazy_pred:

@@ -443,18 +443,28 @@ class MultiModalSwinTransformer(nn.Module):
         for i, d in enumerate(live):
             d._batched = [f[2 * i], f[2 * i + 1]]
 
-    def forward(self, x, l, l_mask, expand=1):
+    def forward(self, x, l, l_mask, expand=1, image_of=None):
         """expand = S > 1 (inference: test.py:73-79 runs the whole network once per sentence of an image): x holds B images, l / l_mask B * S
         expressions, expression j of image i at index i * S + j.  Patch embedding and the Swin blocks of stage 0 do not depend on the sentence: they
-        run once per image, their rows are repeated S times in front of stage 0's PWAM, and everything after runs on B * S samples."""
+        run once per image, their rows are repeated S times in front of stage 0's PWAM, and everything after runs on B * S samples.
+        image_of (device int32 [N], inference): a pair-list batch -- x holds B images, l / l_mask N expressions, slot j pairs expression j with image
+        image_of[j]; N may be smaller or larger than B, an entry outside [0, B) is an empty slot (zero rows).  Stage 0's rows are gathered by the
+        buffer on the device (ops.gather_samples), so a captured replay follows a changed buffer; everything after runs on N samples."""
         dtype = compute_dtype()
         B = x.shape[0]
         S = int(expand)
         if S < 1:
             raise ValueError("expand must be >= 1")
+        if image_of is not None:
+            if S != 1:
+                raise ValueError("image_of names the image of every expression; it cannot be combined with expand != 1")
+            if self.training:
+                raise RuntimeError("image_of shares stage 0 across expressions: inference only (model.eval())")
+            if l.shape[0] != image_of.numel():
+                raise ValueError(f"language batch {l.shape[0]} != the {image_of.numel()} entries of image_of")
         if S > 1 and self.training:
             raise RuntimeError("expand > 1 shares stage 0 across expressions: inference only (model.eval())")
-        if l.shape[0] != B * S:
+        if image_of is None and l.shape[0] != B * S:
             raise ValueError(f"language batch {l.shape[0]} != image batch {B} x expand {S}")
         self._draw_drop_path(B, x.device)
         lang = _LangCtx.get(l, l_mask, dtype, entry=True)
@@ -463,7 +473,11 @@ class MultiModalSwinTransformer(nn.Module):
         t = t.view(B, Wh * Ww, self.embed_dim)
         outs = []
         for i, layer in enumerate(self.layers):
-            if i == 0 and S > 1:
+            if i == 0 and image_of is not None:
+                t = ops.gather_samples(layer.run_blocks(t, Wh, Ww), image_of, pairs=True)
+                B = t.shape[0]
+                f, H, W, t, Wh, Ww = layer.fuse_language(t, Wh, Ww, l, l_mask)
+            elif i == 0 and S > 1:
                 # each image's rows S times in a row (what repeat_interleave(S, 0) gives, written as expand + copy: no host synchronisation, so it can be
                 # captured); 14 400 x C elements per image at 480^2: not worth a kernel
                 t = layer.run_blocks(t, Wh, Ww)

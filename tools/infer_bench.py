@@ -20,7 +20,13 @@ and the decoder's launch count per call (profiler records in the "decoder" scope
     --video-select IND   (opt-in, runs ONLY this) annotated-frame selection on the geometry of `bench.py --workload video_swin_b_t8_384` (Video-Swin-B, one clip
                          of T = 8 frames at 384^2, batch 1; A2D-Sentences / JHMDB annotate one frame per clip), two captured predictors in one process:
   video_all_frames_then_index   the all-frame Predictor replay followed by mask[sel] / iu[sel] (what a caller does without selection)
-  video_valid_indices           Predictor(valid_indices=[IND]): the decoder and the mask kernel run on the one annotated frame"""
+  video_valid_indices           Predictor(valid_indices=[IND]): the decoder and the mask kernel run on the one annotated frame
+
+    --pairs N   (opt-in, runs ONLY this) N (image, expression) pairs over ceil(N / 3) images, on the Swin-B w12 480^2 bf16 workload above.  Both figures
+                are milliseconds PER PAIR, the median over --calls repetitions of the whole loop (host wall clock, a synchronise on both sides):
+  pairs_batch1_eval_meter       N batch-1 replays, each followed by EvalMeter.update(pred.iu) -- the evaluation loop as it stands: one device-to-host
+                                read per prediction
+  pairs_image_of_device_meter   ONE replay of Predictor(image_of=) with the DeviceEvalMeter appended to its body, and a single meter.read() at the end"""
 import argparse
 import json
 import os
@@ -105,6 +111,63 @@ def video_select(a, report):
            mask_pixels_differing_from_all_frames=differ, speedup=round(med_a / med_s, 3), **common)
 
 
+def pairs(a, report):
+    import lavt_hip
+    from lavt_hip import ops
+    from lavt_hip.detweights import det_inputs, fill_state_dict_
+    from lavt_hip.engine import Predictor
+    from lavt_hip.metrics import EvalMeter
+    from lib import segmentation
+    dev, N = "cuda:0", int(a.pairs)
+    if N < 1:
+        raise SystemExit("--pairs: at least one pair")
+    B = (N + 2) // 3
+    image_of = [j // 3 for j in range(N)]
+    lavt_hip.set_compute_dtype(torch.bfloat16 if a.dtype == "bf16" else torch.float32)
+    model = segmentation.lavt("", SimpleNamespace(swin_type=a.variant, window12=a.variant == "base", drop_path_rate=0.3))
+    fill_state_dict_(model)
+    model.to(dev).eval()
+    x = det_inputs(B, a.size, 20, seed=1234)[0].to(dev)
+    _, l, m, tgt = (t.to(dev) for t in det_inputs(N, a.size, 20, seed=77))
+    single = Predictor(model, x[:1].clone(), l[:1].clone(), m[:1].clone(), target=tgt[:1].clone(), context=ops.StepContext())
+    single.warmup_and_capture()
+    host = EvalMeter()
+
+    def batch1():
+        host.reset()
+        for j in range(N):
+            single.x.copy_(x[image_of[j]:image_of[j] + 1])
+            single.l.copy_(l[j:j + 1])
+            single.m.copy_(m[j:j + 1])
+            single.t.copy_(tgt[j:j + 1])
+            single.step()
+            host.update(single.iu)
+        return host.summary()
+    med_a, lo_a, hi_a = timed(batch1, a.calls, a.warmup)
+    want = batch1()
+    paired = Predictor(model, x.clone(), l.clone(), m.clone(), target=tgt.clone(), image_of=torch.tensor(image_of, dtype=torch.int32, device=dev),
+                       context=ops.StepContext())
+    meter = paired.make_meter(capacity=N)
+    paired.warmup_and_capture()
+
+    def one_replay():          # (both loops fill their static buffers from the same device tensors: the input stage is not what is compared)
+        meter.reset()
+        paired.x.copy_(x)
+        paired.l.copy_(l)
+        paired.m.copy_(m)
+        paired.t.copy_(tgt)
+        paired.set_image_of(image_of)
+        paired.step()
+        return meter.read().summary()
+    med_b, lo_b, hi_b = timed(one_replay, a.calls, a.warmup)
+    got = one_replay()
+    common = dict(pairs=N, images=B, batch=1)
+    report(path="pairs_batch1_eval_meter", captured=single.captured, ms_per_pair_median=round(med_a / N, 4), ms_per_pair_min=round(lo_a / N, 4),
+           ms_per_pair_max=round(hi_a / N, 4), overall_iou=round(want["overall_iou"], 4), **common)
+    report(path="pairs_image_of_device_meter", captured=paired.captured, ms_per_pair_median=round(med_b / N, 4), ms_per_pair_min=round(lo_b / N, 4),
+           ms_per_pair_max=round(hi_b / N, 4), overall_iou=round(got["overall_iou"], 4), speedup=round(med_a / med_b, 3), **common)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=30)
@@ -115,9 +178,22 @@ def main():
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("--frames-u8", default=None, metavar="HxW", help="also time the input stage for a uint8 frame of this size: CPU pipeline vs Predictor.load_frames")
     ap.add_argument("--video-select", default=None, metavar="IND", help="run ONLY the annotated-frame comparison on Video-Swin-B, T=8, 384^2: all frames + index vs valid_indices=[IND]")
+    ap.add_argument("--pairs", type=int, default=None, metavar="N", help="run ONLY the pair-list comparison: N batch-1 replays + EvalMeter.update vs one image_of replay + device meter")
     a = ap.parse_args()
     if a.calls < 20:
         ap.error("--calls must be at least 20")
+    if a.pairs is not None:
+        lines = []
+
+        def report_pairs(**kw):
+            kw.update(variant=a.variant, size=a.size, dtype=a.dtype, calls=a.calls)
+            lines.append(json.dumps(kw))
+            print(lines[-1], flush=True)
+        pairs(a, report_pairs)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if a.video_select is not None:
         lines = []
 
