@@ -66,9 +66,12 @@ int lavt_tuning_reload(void); /* ABI v5: re-read the LAVT_* tuning switches from
  *   (fused torch.cat of [top-down, skip], lib/mask_predictor.py:60,70,81).
  * B_op: b_kmajor = 0: B[N][K] (nn.Linear weight layout);  1: B[K][N] (used for x @ W, i.e. data gradients).
  *   With conv and b_kmajor = 1, k = tap*conv_kc + c addresses B + c*ldb + tap*b_tap_stride + n.
- * Epilogue, in order: *alpha, +bias[n], *row_scale[m], (Cpre = value), act, *mul[out_row][n], +R[out_row][n], store.
- *   Output row = c_rowmap[m] (or m); -1 drops the row.  Columns >= c_split go to C2 (fused split of the
- *   gradient of a concatenation).  c_f32 stores fp32 whatever dtype is.
+ * Epilogue, in order: *alpha, +bias[n], *row_scale[m / row_scale_div], (Cpre[out_row][n] = value), act, *mul[out_row][n],
+ *   +R[out_row][n], store.  Output row = c_rowmap[m] (or m); -1 drops the row: nothing of it is stored, in C, C2 or Cpre.
+ *   row_scale is indexed by the GEMM row m; every side buffer that has the output's shape -- Cpre, mul, R, dact_pre -- by the
+ *   output row.  Columns >= c_split go to C2 (fused split of the gradient of a concatenation).  c_f32 stores C and C2 as
+ *   fp32 whatever dtype is.  With batch > 1, bias / row_scale / C (and C2) advance by their strides per entry; Cpre, mul, R
+ *   and dact_pre have no stride.  The kernel writes nothing else: columns between N (or c_split) and ldc keep their bytes.
  * Requirements: K % (16/sizeof(dtype)) == 0; if b_kmajor, N % (16/sizeof(dtype)) == 0; lda/ldb/ldc multiples of
  *   the same; all pointers 16-byte aligned.
  * ------------------------------------------------------------------------------------------- */
@@ -112,10 +115,12 @@ typedef struct lavt_gemm_nt {
      * (batch, conv_d, conv_h, conv_w) grid and the taps run over conv_kd x conv_kh x conv_kw (each 1 or 3, 'same' zero padding), kw fastest.
      * All zero = the 2-D default (conv_d = 1, taps 1 x 3 x 3). */
     int32_t conv_d, conv_kd, conv_kh, conv_kw;
-    /* Fused activation gradient (ABI v2): when dact_pre != NULL the stored value is C * act'(dact_pre[row][n]) with act = dact (LAVT_ACT_*):
+    /* Fused activation gradient (ABI v2): when dact_pre != NULL the stored value is C * act'(dact_pre[out_row][n]) (+ R[out_row][n], if given)
+     * with act = dact (LAVT_ACT_*), C = (alpha acc + bias) row_scale and out_row the OUTPUT row (c_rowmap[m], as for R and mul):
      * the data gradient of the layer AFTER an activation leaves as the gradient w.r.t. the pre-activation (fc2's dgrad of a Swin Mlp applies
      * GELU' of fc1's saved pre-activation, reference lib/backbone.py:24-30 under autograd), so no separate element-wise pass exists.
-     * bf16, b_kmajor, no conv taps, K % 64 == 0, lddact % 8 == 0 only (LAVT_ERR_INVALID otherwise: the caller keeps the two-kernel form). */
+     * bf16, b_kmajor, no conv taps, K % 64 == 0, lddact % 8 == 0, no act / mul / Cpre / C2 / c_f32 only (LAVT_ERR_INVALID otherwise: the caller
+     * keeps the two-kernel form). */
     const void* dact_pre;
     int64_t lddact;
     int32_t dact;

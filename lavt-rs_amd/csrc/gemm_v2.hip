@@ -468,8 +468,9 @@ int launch_nt_v2_fp8(const lavt_gemm_nt_t& p, hipStream_t st) {
 // Fused activation-gradient epilogue (dact_pre): data gradients only (k-major B, plain K walk); the flag is a template parameter so that no
 // other instantiation pays its registers (as a run-time branch in every kernel it cost 12 VGPRs and 0.25 ms per step in round 1).
 int launch_nt_v2_dact(const lavt_gemm_nt_t& p, hipStream_t st) {
-    if (!p.b_kmajor || p.conv_kc > 0 || p.A2 || p.K % 64 || p.lddact % 8 || p.c_f32 || p.C2 || p.Cpre || (p.R && !p.res_first) || p.act || p.mul) {
-        lavt_set_error("lavt_gemm_nt: dact_pre needs a plain k-major data-gradient problem (no taps / concat / residual / activation, K %% 64 == 0)");
+    // (a residual is taken in both orders the header states: C * act'(pre) + R, and with res_first (C + R) * act'(pre))
+    if (!p.b_kmajor || p.conv_kc > 0 || p.A2 || p.K % 64 || p.lddact % 8 || p.c_f32 || p.C2 || p.Cpre || p.act || p.mul) {
+        lavt_set_error("lavt_gemm_nt: dact_pre needs a plain k-major data-gradient problem (no taps / concat / activation / second output, K %% 64 == 0)");
         return LAVT_ERR_INVALID;
     }
     const long tiles128 = (long)cdiv(p.M, 128) * cdiv(p.N, 128) * p.batch, tiles64 = (long)cdiv(p.M, 64) * cdiv(p.N, 64) * p.batch;
