@@ -190,7 +190,16 @@ int lavt_splitk_reduce(int dtype, const float* parts, int splits, int64_t M, int
  * for that tap (channels >= b_split from B2).  c_conv_permute stores column (tap,c) at c*9+tap so that C is
  * directly the PyTorch [Cout][Cin][3][3] gradient.  The reduction over k is split across workgroups
  * (split_k, 0 = auto) and accumulated with fp32 atomics: C must hold zeros or a running sum.
- * colsum (optional, fp32 [I]) additionally receives sum_k A[k][i] (the bias gradient).
+ * colsum (optional, fp32 [I]) additionally receives the bias gradient under the same factors as C:
+ *     colsum[i] += alpha * sum_k s_k * A[a_rowmap[k]][i],      s_k = a_rowscale[k / a_rowscale_div]
+ * (s_k = 1 without a row scale; with a_rowscale_binary: 1 where the entry is non-zero -- the caller folded the
+ * one non-zero value into alpha, so alpha carries it into C and colsum alike: the fc2 bias gradient of a block
+ * under DropPath needs its 1 / keep).  Every kernel of the family computes this.
+ * batch > 1: entry b reads A + b * strideA and B + b * strideB and writes C + b * strideC and
+ * colsum + b * strideColsum (one vector of I sums per entry); a_rowmap, b_rowmap and a_rowscale are indexed by
+ * k alone and shared by the entries, as is B2.
+ * accumulate covers colsum as it covers C: 0 promises that both hold zeros (an unsplit launch may store them
+ * plainly, a split one adds), 1 adds to their contents; colsum_atomic adds to colsum in either case.
  * Requirements: I, J (and conv_kc) % (16/sizeof(dtype)) == 0; lda/ldb likewise.
  * ------------------------------------------------------------------------------------------- */
 typedef struct lavt_gemm_tn {

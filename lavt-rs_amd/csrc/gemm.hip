@@ -365,7 +365,9 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const lavt_gemm_tn_t p, in
             }
         }
     }
-    if (do_colsum && i0 + tid < p.I) atomicAdd(p.colsum + (int64_t)bz * p.strideColsum + i0 + tid, csum);
+    // alpha belongs to the column sum as it does to C (the header's contract; tn_tile_range of gemm_tn_v2.hip): with a binary row scale the caller folded the
+    // mask's one non-zero value -- DropPath's 1 / keep -- into alpha, and the bias gradient needs it
+    if (do_colsum && i0 + tid < p.I) atomicAdd(p.colsum + (int64_t)bz * p.strideColsum + i0 + tid, csum * p.alpha);
 }
 
 template <typename T, int BI, int BJ> int launch_tn(const lavt_gemm_tn_t& p, hipStream_t st) {

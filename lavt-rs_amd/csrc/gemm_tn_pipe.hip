@@ -417,7 +417,8 @@ __global__ __launch_bounds__(256) void tnp_reduce_pieces(const TnpGroup g) {
     const int64_t W = (int64_t)m.I * m.J, total = W + (m.colsum ? m.I : 0);
     const int64_t e0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (e0 >= total) return;
-    const bool v4 = (m.flags & TNP_PART_VEC4) && (m.flags & TNP_VEC4) && (m.J % 4 == 0);
+    const bool no_b = (m.flags & TNP_NO_B) != 0;          // a column-sum-only member stored no C pieces (tnp_tile: has_b): its C stays as it is
+    const bool v4 = !no_b && (m.flags & TNP_PART_VEC4) && (m.flags & TNP_VEC4) && (m.J % 4 == 0);
     if (v4 && e0 + 3 < W) {
         const float* q = m.part + e0;
         // eight pieces in flight per thread (stage 0 cuts its members into ~20 pieces: four in flight were five serial round trips)
@@ -451,6 +452,7 @@ __global__ __launch_bounds__(256) void tnp_reduce_pieces(const TnpGroup g) {
     for (int k = 0; k < 4; ++k) {
         const int64_t e = e0 + k;
         if (e >= total) break;
+        if (no_b && e < W) continue;
         const float* q = e < W ? m.part + e : m.part + (int64_t)ns * W + (e - W);
         const int64_t st = e < W ? W : m.I;
         float t = 0.f;
@@ -472,8 +474,9 @@ __global__ __launch_bounds__(256) void tnp_reduce_pieces_deep(const TnpGroup g) 
     if ((int64_t)blockIdx.x * 64 >= total) return;
     const int col = threadIdx.x & 63, sl = threadIdx.x >> 6;
     const int64_t e = (int64_t)blockIdx.x * 64 + col;
+    const bool live = e < total && !((m.flags & TNP_NO_B) && e < W);          // a column-sum-only member stored no C pieces: its C stays as it is
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    if (e < total) {
+    if (live) {
         const float* q = e < W ? m.part + e : m.part + (int64_t)ns * W + (e - W);
         const int64_t st = e < W ? W : m.I;
         int s = sl;
@@ -482,7 +485,7 @@ __global__ __launch_bounds__(256) void tnp_reduce_pieces_deep(const TnpGroup g) 
     }
     red[sl][col] = (a0 + a1) + (a2 + a3);
     __syncthreads();
-    if (sl == 0 && e < total) {
+    if (sl == 0 && live) {
         const float t = (red[0][col] + red[1][col]) + (red[2][col] + red[3][col]);
         if (e < W) { const int64_t i = e / m.J; m.C[i * m.ldc + (e - i * m.J)] += t; }
         else if (m.flags & TNP_COLSUM_ATOMIC) atomicAdd(m.colsum + (e - W), t);
