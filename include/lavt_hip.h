@@ -613,6 +613,18 @@ int lavt_upsample_dice_boundary_sel_bwd(int dtype, const void* x, const int32_t*
  * decoder; in eval mode the decoder is per-sample independent).  16-byte copies when the sample size and both bases are multiples of 16 bytes,
  * element copies otherwise.  sel as above. */
 int lavt_gather_samples(int dtype, const void* src, const int32_t* sel, int nsel, int B, int64_t sample_elems, void* dst, void* stream);
+/* The backward of that gather for a pair-list TRAIN batch (the reference trains one image per sentence, train.py:197-243, on datasets that carry
+ * several sentences per image, data/dataset_refer_bert.py; here stage 0 runs once per image and its rows are gathered per slot):
+ *   dx[b] = sum over {j : sel[j] == b} of dy[j]        dy holds nsel samples, dx B, sel is the DEVICE int32 [nsel] of the forward.
+ * Gather form, no atomics: a workgroup owns a slice of one image's sample, walks j = 0 .. nsel-1, adds the slots that name its image and stores
+ * once.  THE SUMMATION ORDER IS FIXED: ascending j, fp32 adds starting from +0.0, and for bf16 one round-to-nearest-even at the end -- the same bits
+ * on every launch, so the default and the deterministic mode share the kernel.  Every element of dx is written: an image no slot names gets zeros
+ * (dx may arrive uninitialised).  An entry of sel outside [0, B) is never read through and contributes nothing: memory-safe for any buffer
+ * contents.  A slot that names another image costs a workgroup one scalar load and no vector traffic, so the launch reads nsel samples and writes
+ * B.  16-byte accesses when the sample size and both bases are multiples of 16 bytes, element accesses otherwise, as in the forward.
+ * 1 <= nsel <= 65535, 1 <= B <= 65535 (a grid dimension), sample_elems > 0, dtype LAVT_F32 / LAVT_BF16; else LAVT_ERR_INVALID, nothing launched.
+ * Correct for any nsel in range, but every workgroup scans all of sel: linear in nsel per workgroup.  Training uses tens of slots. */
+int lavt_gather_samples_bwd(int dtype, const void* dy, const int32_t* sel, int nsel, int B, int64_t sample_elems, void* dx, void* stream);
 /* ---- fp8 (OCP e4m3) operand preparation for lavt_gemm_nt(dtype = LAVT_FP8) ----
  * lavt_fp8_quantize: activations, delayed scaling: dst[i] = e4m3(clamp(src[i] * s, +-448)), s = *amax_prev > 0 ? 448 / *amax_prev : 1 (the |max| seen
  *   in the PREVIOUS step; the GEMM reads the same float through deq_a); max |src| of THIS call is folded into *amax_cur (atomic max).

@@ -1174,3 +1174,71 @@ extern "C" int lavt_gather_samples(int dtype, const void* src, const int32_t* se
     LAVT_CHECK_LAUNCH("lavt_gather_samples");
     return LAVT_OK;
 }
+
+// ---- dx[b] = sum over {j : sel[j] == b} of dy[j] for whole samples: the backward of the pair gather in front of stage 0's PWAM when a train batch is a
+// pair list (train.py:197-243 of the reference runs one image per sentence; data/dataset_refer_bert.py draws several sentences per image).  Gather form:
+// workgroup (x, b) owns tiles of image b's sample, walks the slots in ascending j, adds those that name b in fp32 and stores once -- no atomics, one
+// summation order, an image nobody names gets zeros.  sel[j] is uniform over the grid row (a scalar load and a scalar branch in front of any vector load:
+// a slot of another image costs no memory traffic, every dy element is read once per launch); an entry outside [0, B) equals no blockIdx.y and is
+// never read through.  Per slot each thread has GSB_U independent loads in flight (indices clamped to the sample instead of predicated, so no load
+// sits behind a lane mask), of V = uint4 when the sample size and both bases are multiples of 16 bytes, else of the element type.
+#define GSB_U 4
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void gather_samples_bwd_kernel(const void* __restrict__ dy_, const int32_t* __restrict__ sel, int nsel, int64_t per, void* __restrict__ dx_) {
+    using V = typename std::conditional<VEC, uint4, T>::type;
+    constexpr int N = VEC ? Chunk<T>::N : 1;
+    const int b = blockIdx.y;
+    const V* __restrict__ dy = (const V*)dy_;
+    V* __restrict__ dx = (V*)dx_ + (int64_t)b * per;
+    for (int64_t t0 = (int64_t)blockIdx.x * (256 * GSB_U); t0 < per; t0 += (int64_t)gridDim.x * (256 * GSB_U)) {
+        int64_t idx[GSB_U];
+        float acc[GSB_U][N];
+#pragma unroll
+        for (int u = 0; u < GSB_U; ++u) {
+            const int64_t i = t0 + u * 256 + threadIdx.x;
+            idx[u] = i < per ? i : per - 1;
+#pragma unroll
+            for (int k = 0; k < N; ++k) acc[u][k] = 0.f;
+        }
+        for (int j = 0; j < nsel; ++j) {
+            if (sel[j] != b) continue;
+            const V* __restrict__ s = dy + (int64_t)j * per;
+            V v[GSB_U];
+#pragma unroll
+            for (int u = 0; u < GSB_U; ++u) v[u] = s[idx[u]];
+#pragma unroll
+            for (int u = 0; u < GSB_U; ++u) {
+                float f[N];
+                if constexpr (VEC) chunk_to_f<T>(v[u], f);
+                else f[0] = to_f<T>(v[u]);
+#pragma unroll
+                for (int k = 0; k < N; ++k) acc[u][k] += f[k];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < GSB_U; ++u) {
+            const int64_t i = t0 + u * 256 + threadIdx.x;
+            if (i < per) {
+                if constexpr (VEC) dx[i] = f_to_chunk<T>(acc[u]);
+                else dx[i] = from_f<T>(acc[u][0]);
+            }
+        }
+    }
+}
+template <typename T>
+static void gather_samples_bwd_launch(const void* dy, const int32_t* sel, int nsel, int B, int64_t sample_elems, void* dx, void* stream) {
+    const int64_t bytes = sample_elems * (int64_t)sizeof(T);
+    const bool vec = bytes % 16 == 0 && ((uintptr_t)dy | (uintptr_t)dx) % 16 == 0;
+    const int64_t per = vec ? bytes / 16 : sample_elems, tiles = (per + 256 * GSB_U - 1) / (256 * GSB_U), cap = 2048 / B > 0 ? 2048 / B : 1;          // ~8 workgroups per CU over the B grid rows, the rest by grid stride
+    const dim3 grid((unsigned)(tiles < cap ? tiles : cap), (unsigned)B);
+    if (vec) hipLaunchKernelGGL((gather_samples_bwd_kernel<T, true>), grid, dim3(256), 0, ST, dy, sel, nsel, per, dx);
+    else hipLaunchKernelGGL((gather_samples_bwd_kernel<T, false>), grid, dim3(256), 0, ST, dy, sel, nsel, per, dx);
+}
+extern "C" int lavt_gather_samples_bwd(int dtype, const void* dy, const int32_t* sel, int nsel, int B, int64_t sample_elems, void* dx, void* stream) {
+    LAVT_CHECK_ARG(dy && sel && dx && nsel > 0 && nsel <= 65535 && B > 0 && B <= 65535 && sample_elems > 0 && (dtype | 1) == 1,
+                   "lavt_gather_samples_bwd: bad arguments (1 <= nsel <= 65535, 1 <= B <= 65535, sample_elems > 0, dtype fp32 or bf16)");
+    if (dtype == LAVT_F32) gather_samples_bwd_launch<float>(dy, sel, nsel, B, sample_elems, dx, stream);
+    else gather_samples_bwd_launch<bf16>(dy, sel, nsel, B, sample_elems, dx, stream);
+    LAVT_CHECK_LAUNCH("lavt_gather_samples_bwd");
+    return LAVT_OK;
+}

@@ -258,6 +258,7 @@ _PROTOTYPES = {
     "lavt_upsample_dice_sel_fwd": [i32, vp, vp, i32, vp, vp, i64, vp, i32, i32, i32, i32, i32, vp],
     "lavt_upsample_dice_sel_bwd": [i32, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "lavt_gather_samples": [i32, vp, vp, i32, i32, i64, vp, vp],
+    "lavt_gather_samples_bwd": [i32, vp, vp, i32, i32, i64, vp, vp],
     "lavt_upsample_dice_boundary_ws": [i32, i32, i32],
     "lavt_upsample_dice_boundary_fwd": [i32, vp, vp, f32, f32, vp, i64, vp, i32, i32, i32, i32, i32, vp],
     "lavt_upsample_dice_boundary_bwd": [i32, vp, vp, f32, f32, vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, vp],

@@ -153,7 +153,13 @@ def _plain(v):
 
 def compare_fingerprints(saved, current, who="TrainStep.load_state_dict"):
     """ValueError naming the FIRST field of CONFIG_FIELDS in which the checkpoint's fingerprint differs from this step's; for the parameter list, the first
-    group and entry (a missing, extra, renamed or reshaped parameter)."""
+    group and entry (a missing, extra, renamed or reshaped parameter).  'pair_slots' (N of a TrainStep(image_of=), engine._config) is an OPTIONAL field,
+    present only in the fingerprint of a pair-list step -- a plain step's fingerprint is what it was -- and compared first: a plain run's checkpoint is
+    refused by a pair run and the other way round."""
+    if saved.get("pair_slots") != current.get("pair_slots"):
+        def _say(v):
+            return "without image_of (a plain batch)" if v is None else f"with image_of of {v} slots"
+        raise ValueError(f"{who}: config field 'pair_slots' differs: the checkpoint was written {_say(saved.get('pair_slots'))}, this step runs {_say(current.get('pair_slots'))}")
     for f in CONFIG_FIELDS:
         if f not in saved:
             raise ValueError(f"{who}: the checkpoint's config has no field '{f}'")

@@ -89,6 +89,43 @@ def _check_index_buffer(who, valid_indices, target, n_frames):
         raise ValueError(f"{who}: {valid_indices.numel()} valid indices need a target of as many samples, got {tuple(target.shape)}")
 
 
+def _check_pair_buffer(who, image_of, n_expressions, target):
+    """the static `image_of` buffer of a pair-list batch (TrainStep, Predictor): checked before anything touches the GPU"""
+    if not isinstance(image_of, torch.Tensor):
+        raise RuntimeError(f"liblavt_hip operates on GPU memory only (got {type(image_of).__name__} for `image_of`); there is no CPU fallback")
+    if image_of.dtype != torch.int32 or image_of.dim() != 1 or not image_of.is_contiguous() or image_of.numel() != n_expressions:
+        raise ValueError(f"{who}: image_of must be a contiguous int32 vector with one entry per expression ({n_expressions}), got {image_of.dtype} {tuple(image_of.shape)}")
+    if target is not None and target.shape[0] != image_of.numel():
+        raise ValueError(f"{who}: {image_of.numel()} pairs need a target of as many samples, got {tuple(target.shape)}")
+    if not image_of.is_cuda:          # (after the shape checks: a buffer of the wrong kind is named as such wherever it lives)
+        raise RuntimeError("liblavt_hip operates on GPU memory only (got a CPU tensor for `image_of`); there is no CPU fallback")
+
+
+class _ImageOf:
+    """set_image_of of TrainStep and Predictor: `image_of` is a static device buffer like image and target"""
+    image_of = None               # the static device int32 [N] buffer; None = not a pair-list batch
+    _empty_slots = False          # may an entry be -1 (an empty slot)?  Predictor: yes.  TrainStep: no -- a zero-row slot would enter the criterion as a sample
+
+    def set_image_of(self, image_of):
+        """image_of[j] = the image of slot j (host integers): writes the static index buffer after checking the length and that every entry is one of
+        the B images of the batch -- or, for a Predictor, -1 = an empty slot (ValueError).  An asynchronous copy through pinned memory on the current
+        stream, nothing synchronises; usable between replays -- the captured kernels read the buffer on the device.  A TrainStep reads it in the
+        forward AND the backward of a step: written here, between steps and on the stream the step runs on, it never changes inside one."""
+        who = f"{type(self).__name__}.set_image_of"
+        if self.image_of is None:
+            raise ValueError(f"{who}: built without an image_of buffer")
+        pairs = [int(v) for v in image_of]
+        B = int(self.x.shape[0])
+        if len(pairs) != self.image_of.numel():
+            raise ValueError(f"{who}: {len(pairs)} entries for an index buffer of {self.image_of.numel()}")
+        bad = [(j, v) for j, v in enumerate(pairs) if not (-1 if self._empty_slots else 0) <= v < B]
+        if bad:
+            raise ValueError(f"{who}: (slot, image) {bad} -- an entry is " + ("-1 (an empty slot) or " if self._empty_slots else "") + f"one of the {B} images of the batch"
+                             + ("" if self._empty_slots else " (a train batch has no empty slots: sample full batches, drop the ragged last one)"))
+        flat = torch.tensor(pairs, dtype=torch.int32)
+        self.image_of.copy_(flat.pin_memory() if self.image_of.is_cuda else flat, non_blocking=True)
+
+
 class _ValidIndices:
     """set_valid_indices of TrainStep and Predictor: `valid_indices` is a static device buffer like image and target"""
 
@@ -127,7 +164,9 @@ class _BatchInput:
         which is written as B*T frames); repeat=T: B still images, each repeated into a T-frame clip (`--pseudo_video_aug vanilla`, args.py:132-134).
         targets: host list of masks for a `target` buffer of network-input size, as many as it holds -- with `valid_indices` that is nsel, one mask per
         selected frame; under `repeat`, as many masks as the buffer holds are taken one to one, B masks for a buffer of B*T are repeated like the
-        images.  frame_map / target_map: the source of every output frame / mask, for any other arrangement.
+        images.  frame_map / target_map: the source of every output frame / mask, for any other arrangement.  Frames are counted against the image
+        buffer and masks against the target buffer separately, so a pair-list batch (image_of=) brings its B images and its N masks, mask j for slot
+        j, as they are: every image is decoded, resized and uploaded once, however many slots name it.
         ValueError for wrong counts or a target buffer of another size, TypeError for CUDA input, RuntimeError inside a graph capture: in every case
         before anything is written."""
         from .preprocess import _BatchPlan
@@ -168,9 +207,9 @@ class _BatchInput:
         self.commit_batch()
 
 
-class TrainStep(_ValidIndices, _BatchInput):
+class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
     def __init__(self, model, image, l_feats, l_mask, target, world=1, use_graph=True, bucket_mib=32.0, fused_loss=True, refresh_weights_in_step=False, context=None,
-                 *, loss="ce", valid_indices=None, dice_rate=1.0, boundary_rate=0.05, deterministic=None, accumulate=1, meters=None):
+                 *, loss="ce", valid_indices=None, dice_rate=1.0, boundary_rate=0.05, deterministic=None, accumulate=1, meters=None, image_of=None):
         """context: the ops.StepContext this harness keeps its state in (gradient sinks, deferred-launch queues, weight copies, scratch).  None = the
         process-wide default context -- what the drop-in path and a single harness use.  Give every further model in the process its own
         `ops.StepContext()` (and its optimizer the same one: FusedAdamW(..., context=)): their steps can then alternate freely.
@@ -189,7 +228,14 @@ class TrainStep(_ValidIndices, _BatchInput):
         so the deterministic mode keeps its promise across cycles.
         meters: a lavt_hip.meters.TrainMeters (or make_meters() later, before warmup_and_capture()): the step's body then ends with ONE more launch,
         lavt_meter_append, which logs loss, lr, IoU, gradient norm and the update's verdict of every step() on the device (DESIGN.md "Training meters").
-        None: the launches of a step built without the argument.  Needs a fused criterion (`stats`)."""
+        None: the launches of a step built without the argument.  Needs a fused criterion (`stats`).
+        image_of: device int32 [N], a static buffer like image and target -- a PAIR-LIST train batch (include/lavt_hip.h: the image_of contract; DESIGN.md
+        "Pair-list training").  `image` holds B images, l_feats / l_mask N expressions, target is (N, H, W); slot j trains expression j on image
+        image_of[j].  Patch embedding and stage 0's Swin blocks run forward and backward once per IMAGE, ops.gather_pairs repeats their rows per slot
+        and sums the slots' gradients per image (ascending slot order, fp32, no atomics: the same kernel in deterministic mode); everything behind runs
+        on N samples, and loss, `stats` and the meters cover the N slots.  Fill it with set_image_of(pairs), before capture or between replays: every
+        entry names one of the B images (no empty slots in training).  Needs a fused criterion and a backbone that shares stage 0; cannot be combined
+        with valid_indices.  None (the default): the launches of a step built without the argument."""
         import operator
         try:
             k = operator.index(accumulate)
@@ -200,9 +246,17 @@ class TrainStep(_ValidIndices, _BatchInput):
         self.accumulate = k
         if loss not in ("ce", "mc_dice", "dice_boundary"):
             raise ValueError(f"TrainStep: loss must be 'ce', 'mc_dice' or 'dice_boundary', got {loss!r}")
+        if image_of is not None:
+            if valid_indices is not None:
+                raise ValueError("TrainStep: image_of (pair-list batches) cannot be combined with valid_indices (annotated frames of clips)")
+            _check_pair_buffer("TrainStep", image_of, l_feats.shape[0], target)
+            if not fused_loss or not hasattr(model, "forward_lowres"):
+                raise ValueError("TrainStep: image_of needs a fused criterion (fused_loss=True and a model with forward_lowres)")
+            if not getattr(model.backbone, "shares_stage0", False):
+                raise NotImplementedError(f"TrainStep: image_of needs a backbone that shares stage 0 between expressions; {type(model.backbone).__name__} does not")
         if valid_indices is not None:
             _check_index_buffer("TrainStep", valid_indices, target, image.numel() // (3 * int(image.shape[-2]) * int(image.shape[-1])))
-        self.criterion, self.valid_indices = loss, valid_indices
+        self.criterion, self.valid_indices, self.image_of = loss, valid_indices, image_of
         self.dice_rate, self.boundary_rate = float(dice_rate), float(boundary_rate)
         self.context = context if context is not None else ops.default_context()
         self._warmed = False
@@ -344,7 +398,7 @@ class TrainStep(_ValidIndices, _BatchInput):
         return {"criterion": self.criterion, "dice_rate": self.dice_rate, "boundary_rate": self.boundary_rate, "accumulate": self.accumulate,
                 "amsgrad": bool(self.opt.amsgrad), "max_grad_norm": float(self.opt.max_grad_norm), "skip_nonfinite": bool(self.opt.skip_nonfinite),
                 "deterministic": bool(self.context.deterministic), "compute_dtype": str(dtype), "fp8": bool(fp8), "world": int(self.world),
-                "param_groups": groups}
+                "param_groups": groups, **({} if self.image_of is None else {"pair_slots": int(self.image_of.numel())})}
 
     def _acc_layout(self):
         """[name, offset] of every parameter's gradient in the flat buffer `acc` mirrors, in offset order"""
@@ -477,7 +531,7 @@ class TrainStep(_ValidIndices, _BatchInput):
             ops.fp8.advance()                    # delayed scaling: last step's |max| values become this step's quantisation scales
         if self.fused_loss:                       # upsample + criterion (+ I/U) fused: the (B,2,H,W) logits are never written
             from lib._utils import fused_dice_boundary_loss, fused_dice_loss, fused_loss
-            y = self.model.forward_lowres(self.x, self.l, self.m)
+            y = self.model.forward_lowres(self.x, self.l, self.m) if self.image_of is None else self.model.forward_lowres(self.x, self.l, self.m, image_of=self.image_of)
             if self.criterion == "ce":
                 loss, self.stats = fused_loss(y, self.t, (0.9, 1.1), valid_indices=self.valid_indices)
             elif self.criterion == "mc_dice":
@@ -654,7 +708,7 @@ class TrainStep(_ValidIndices, _BatchInput):
         return self.loss
 
 
-class Predictor(_ValidIndices, _BatchInput):
+class Predictor(_ValidIndices, _ImageOf, _BatchInput):
     """The inference sibling of TrainStep: the reference's evaluation loop body (test.py:60-83, test_ytvos.py:230-260)
 
         model.eval(); with torch.no_grad(): out = model(image, l, l_mask); mask = out.argmax(1); I, U = computeIoU(mask, target)
@@ -709,12 +763,7 @@ class Predictor(_ValidIndices, _BatchInput):
                 raise ValueError("Predictor: image_of (pair-list batches) cannot be combined with valid_indices (annotated frames of clips)")
             if not getattr(model.backbone, "shares_stage0", False):
                 raise NotImplementedError(f"Predictor: image_of needs a backbone that shares stage 0 between expressions; {type(model.backbone).__name__} does not")
-            if not isinstance(image_of, torch.Tensor) or not image_of.is_cuda:
-                raise RuntimeError("liblavt_hip operates on GPU memory only (got a CPU tensor for `image_of`); there is no CPU fallback")
-            if image_of.dtype != torch.int32 or image_of.dim() != 1 or not image_of.is_contiguous() or image_of.numel() != lang.shape[0]:
-                raise ValueError(f"Predictor: image_of must be a contiguous int32 vector with one entry per expression ({lang.shape[0]}), got {image_of.dtype} {tuple(image_of.shape)}")
-            if target is not None and target.shape[0] != image_of.numel():
-                raise ValueError(f"Predictor: {image_of.numel()} pairs need a target of as many samples, got {tuple(target.shape)}")
+            _check_pair_buffer("Predictor", image_of, lang.shape[0], target)
         self.image_of = image_of
         if S > 1 and not getattr(model.backbone, "shares_stage0", False):
             raise NotImplementedError(f"Predictor: expressions_per_image > 1 needs a backbone that shares stage 0 between expressions; {type(model.backbone).__name__} does not")
@@ -741,21 +790,7 @@ class Predictor(_ValidIndices, _BatchInput):
         if meter is not None:
             self.attach_meter(meter)
 
-    # ---- pair-list batches ----
-    def set_image_of(self, image_of):
-        """image_of[j] = the image of slot j (host integers; -1 = an empty slot): writes the static index buffer after checking the length and that
-        every entry is -1 or in [0, B) (ValueError).  An asynchronous copy through pinned memory on the current stream, nothing synchronises;
-        usable between replays -- the captured kernels read the buffer on the device."""
-        if self.image_of is None:
-            raise ValueError("Predictor.set_image_of: built without an image_of buffer")
-        pairs = [int(v) for v in image_of]
-        B = int(self.x.shape[0])
-        if len(pairs) != self.image_of.numel():
-            raise ValueError(f"Predictor.set_image_of: {len(pairs)} entries for an index buffer of {self.image_of.numel()}")
-        bad = [(j, v) for j, v in enumerate(pairs) if not -1 <= v < B]
-        if bad:
-            raise ValueError(f"Predictor.set_image_of: (slot, image) {bad} -- an entry is -1 (an empty slot) or one of the {B} images of the batch")
-        self.image_of.copy_(torch.tensor(pairs, dtype=torch.int32).pin_memory(), non_blocking=True)
+    _empty_slots = True          # pair-list batches (_ImageOf.set_image_of): -1 marks an empty slot
 
     # ---- the evaluation log on the device ----
     def make_meter(self, **kw):

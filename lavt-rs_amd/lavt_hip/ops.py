@@ -3166,11 +3166,17 @@ def gather_samples(x, sel, pairs=False):
     the result has x's strides with nsel samples.  Not differentiable (the inference path: lib._utils forward_lowres(frames=)).
     pairs=True: sel is the `image_of` buffer of a pair-list batch (include/lavt_hip.h) -- 1..65535 entries, more than B allowed, entries may repeat, an
     entry outside [0, B) gives a zero sample."""
-    if not x.is_cuda:
-        raise RuntimeError("liblavt_hip operates on GPU memory only (got a CPU tensor for `gather_samples`); there is no CPU fallback")
-    B = int(x.shape[0])
-    sel = _frame_sel(sel, 65535 if pairs else B, "gather_samples")
-    per = x[0].numel()
+    return _gather_samples_fwd(x, sel, 65535 if pairs else int(x.shape[0]), "gather_samples")[0]
+
+
+def _sample_blocks(x, like=None):
+    """x with every sample a dense block of x[0].numel() elements, in whatever dimension order it has (copied to contiguous only when it is not).
+    like (strides): the block layout asked for instead -- a gradient must have the layout of the tensor it belongs to."""
+    B, per = int(x.shape[0]), x[0].numel()
+    if like is not None:
+        if all(st == want for st, want, sz in zip(x.stride(), like, x.shape) if sz > 1):
+            return x
+        return torch.empty_strided(tuple(x.shape), tuple(like), dtype=x.dtype, device=x.device).copy_(x)
     inner, expect = sorted((st, sz) for st, sz in zip(x.stride()[1:], x.shape[1:]) if sz > 1), 1
     for st, sz in inner:                         # a sample is a dense block when its strides, sorted, are the running products of its sizes
         if st != expect:
@@ -3178,10 +3184,51 @@ def gather_samples(x, sel, pairs=False):
         expect *= sz
     if expect != per or (B > 1 and x.stride(0) != per):
         x = x.contiguous()
+    return x
+
+
+def _gather_samples_fwd(x, sel, max_sel, what):
+    """the lavt_gather_samples launch of gather_samples and gather_pairs -> (out, x as dense sample blocks, sel)"""
+    if not x.is_cuda:
+        raise RuntimeError(f"liblavt_hip operates on GPU memory only (got a CPU tensor for `{what}`); there is no CPU fallback")
+    B = int(x.shape[0])
+    sel = _frame_sel(sel, max_sel, what)
+    x = _sample_blocks(x)
+    per = x[0].numel()
     out = torch.empty_strided((sel.numel(),) + tuple(x.shape[1:]), (per,) + tuple(x.stride()[1:]), dtype=x.dtype, device=x.device)
     _note(f"gather-samples {sel.numel()}/{B}x{per}", nbytes=2 * sel.numel() * per * x.element_size())
     K.check(K.lib.lavt_gather_samples(K.dt(x.dtype), K.ptr(x), K.ptr(sel), sel.numel(), B, per, K.ptr(out), K.stream()))
-    return out
+    return out, x, sel
+
+
+@K.scoped
+class _GatherPairs(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, image_of):
+        out, xb, sel = _gather_samples_fwd(x.detach(), image_of, 65535, "gather_pairs")
+        ctx.sel, ctx.x_shape, ctx.x_strides, ctx.out_strides = sel, tuple(xb.shape), tuple(xb.stride()), tuple(out.stride())
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, nsel = ctx.x_shape[0], ctx.sel.numel()
+        dy = _sample_blocks(dy, like=ctx.out_strides)
+        dx = torch.empty_strided(ctx.x_shape, ctx.x_strides, dtype=dy.dtype, device=dy.device)          # every element is written, zeros for an image nobody names
+        per = dx[0].numel()
+        _note(f"gather-samples-bwd {nsel}/{B}x{per}", nbytes=(nsel + B) * per * dy.element_size())
+        K.check(K.lib.lavt_gather_samples_bwd(K.dt(dy.dtype), K.ptr(dy), K.ptr(ctx.sel), nsel, B, per, K.ptr(dx), K.stream()))
+        return dx, None
+
+
+def gather_pairs(x, image_of):
+    """gather_samples(x, image_of, pairs=True) as a differentiable op: out[j] = x[image_of[j]] for whole samples, image_of a device int32 [N] buffer
+    read on the device (a replayed graph follows it), x a dense tensor in any dimension order whose samples are contiguous blocks (the result keeps
+    x's strides).  Backward (lavt_gather_samples_bwd): dx[b] = the sum of dy[j] over the slots that name b, in ascending j with fp32 adds and one
+    rounding -- one fixed order, no atomics, so the op is the same under ops.StepContext(deterministic=True); an image no slot names gets a zero
+    gradient, an entry outside [0, B) a zero sample forward and no gradient backward.
+    image_of is read AGAIN at backward time (it is not copied): it must not be rewritten between the forward and the backward of one step.
+    engine.TrainStep guarantees that -- set_image_of writes between steps, on the stream the step runs on."""
+    return _GatherPairs.apply(x, image_of)
 
 
 # ------------------------------------------------------------------------------------------ fused upsample + argmax (+ I/U counts): inference

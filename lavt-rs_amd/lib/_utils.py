@@ -58,7 +58,7 @@ def _check_frames(module, folded, frames):
 
 
 def _check_image_of(expand, frames, image_of):
-    """image_of= (a pair-list batch, lib/backbone.py: forward; inference only, the backbone refuses it in training mode): one batch arrangement at a time"""
+    """image_of= (a pair-list batch, lib/backbone.py: forward; inference and training alike): one batch arrangement at a time"""
     if image_of is None:
         return
     if expand != 1:
@@ -96,7 +96,8 @@ class _LAVTSimpleDecode(nn.Module):
         Inference (lavt_hip.engine.Predictor): folded = the BatchNorm-folded decoder (eval mode); expand = S > 1 = S expressions per image (l_feats /
         l_mask hold B * S of them), stage 0 of the backbone shared between the expressions of an image; frames: see _decode.
         image_of (device int32 [N]): a pair-list batch, l_feats / l_mask hold N expressions and the result N samples (lib/backbone.py: forward);
-        mutually exclusive with expand != 1 and with frames."""
+        mutually exclusive with expand != 1 and with frames.  Also in training mode (engine.TrainStep(image_of=)): the decoder's BatchNorm then
+        takes its statistics over the N slots, as it does over the N samples of a plain batch."""
         _check_frames(self, folded, frames)          # (raises in front of the backbone)
         _check_image_of(expand, frames, image_of)
         x_c1, x_c2, x_c3, x_c4 = _backbone(self.backbone, x, l_feats, l_mask, expand, image_of)

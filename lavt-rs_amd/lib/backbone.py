@@ -426,30 +426,37 @@ class MultiModalSwinTransformer(nn.Module):
             from lavt_hip.checkpoint import load_swin_checkpoint
             load_swin_checkpoint(self, pretrained)
 
-    def _draw_drop_path(self, B, device):
-        """All DropPath factors of one forward (two per block: attention branch, MLP branch) with 4 launches instead of 4 per draw."""
-        dps = [blk.drop_path for layer in self.layers for blk in layer.blocks]
-        live = [d for d in dps if self.training and d.drop_prob > 0.]
+    def _draw_drop_path(self, B, device, slots=None):
+        """All DropPath factors of one forward (two per block: attention branch, MLP branch) with 4 launches instead of 4 per draw.
+        slots = N (a pair-list train batch: stage 0's blocks see the B images, every later block the N slots): still ONE launch and one tick of the
+        generator -- a draw of width max(B, N) for every live module, of which a module takes the leading B (stage 0) or N (later stages) columns of
+        its two rows.  Reproducible from the generator state alone; the numbers differ from the draw of width B, as those of two batch sizes do."""
+        dps = [(blk.drop_path, B if slots is None or li == 0 else slots) for li, layer in enumerate(self.layers) for blk in layer.blocks]
+        live = [(d, n) for d, n in dps if self.training and d.drop_prob > 0.]
         if not live:
             return
+        width = B if slots is None else max(B, slots)
         keep = getattr(self, "_dp_keep", None)
         if keep is None or keep.device != device or keep.shape[0] != 2 * len(live):
-            keep = torch.tensor([1.0 - d.drop_prob for d in live for _ in (0, 1)], dtype=torch.float32, device=device)[:, None]
+            keep = torch.tensor([1.0 - d.drop_prob for d, _ in live for _ in (0, 1)], dtype=torch.float32, device=device)[:, None]
             self._dp_keep = keep
         if os.environ.get("LAVT_DROPPATH_RNG", "device") == "torch":
-            f = ops.droppath_factors(torch.rand(2 * len(live), B, device=device, dtype=torch.float32), keep)      # floor(keep + u) / keep, one launch
+            f = ops.droppath_factors(torch.rand(2 * len(live), width, device=device, dtype=torch.float32), keep)      # floor(keep + u) / keep, one launch
         else:
-            f = ops.droppath_draw(keep, B)                                                                         # the same with the draw made in the kernel
-        for i, d in enumerate(live):
-            d._batched = [f[2 * i], f[2 * i + 1]]
+            f = ops.droppath_draw(keep, width)                                                                     # the same with the draw made in the kernel
+        for i, (d, n) in enumerate(live):
+            d._batched = [f[2 * i, :n], f[2 * i + 1, :n]]
 
     def forward(self, x, l, l_mask, expand=1, image_of=None):
         """expand = S > 1 (inference: test.py:73-79 runs the whole network once per sentence of an image): x holds B images, l / l_mask B * S
         expressions, expression j of image i at index i * S + j.  Patch embedding and the Swin blocks of stage 0 do not depend on the sentence: they
         run once per image, their rows are repeated S times in front of stage 0's PWAM, and everything after runs on B * S samples.
-        image_of (device int32 [N], inference): a pair-list batch -- x holds B images, l / l_mask N expressions, slot j pairs expression j with image
+        image_of (device int32 [N]): a pair-list batch -- x holds B images, l / l_mask N expressions, slot j pairs expression j with image
         image_of[j]; N may be smaller or larger than B, an entry outside [0, B) is an empty slot (zero rows).  Stage 0's rows are gathered by the
-        buffer on the device (ops.gather_samples), so a captured replay follows a changed buffer; everything after runs on N samples."""
+        buffer on the device (ops.gather_samples), so a captured replay follows a changed buffer; everything after runs on N samples.
+        Training mode takes it too (engine.TrainStep(image_of=)): the gather is ops.gather_pairs, whose backward sums the slots' gradients per image
+        in ascending slot order, and DropPath draws B factors for stage 0's blocks and N for the others (_draw_drop_path).  The buffer is read again
+        in the backward; a trainer has no empty slots (TrainStep.set_image_of refuses them: a zero-row slot would enter the criterion)."""
         dtype = compute_dtype()
         B = x.shape[0]
         S = int(expand)
@@ -458,15 +465,16 @@ class MultiModalSwinTransformer(nn.Module):
         if image_of is not None:
             if S != 1:
                 raise ValueError("image_of names the image of every expression; it cannot be combined with expand != 1")
-            if self.training:
-                raise RuntimeError("image_of shares stage 0 across expressions: inference only (model.eval())")
             if l.shape[0] != image_of.numel():
                 raise ValueError(f"language batch {l.shape[0]} != the {image_of.numel()} entries of image_of")
         if S > 1 and self.training:
             raise RuntimeError("expand > 1 shares stage 0 across expressions: inference only (model.eval())")
         if image_of is None and l.shape[0] != B * S:
             raise ValueError(f"language batch {l.shape[0]} != image batch {B} x expand {S}")
-        self._draw_drop_path(B, x.device)
+        if image_of is None:
+            self._draw_drop_path(B, x.device)
+        else:
+            self._draw_drop_path(B, x.device, slots=int(image_of.numel()))
         lang = _LangCtx.get(l, l_mask, dtype, entry=True)
         lang.set_plan([(layer.fusion.image_lang_att.f_key[0], layer.fusion.image_lang_att.f_value[0]) for layer in self.layers])
         t, Wh, Ww = self.patch_embed.tokens(x, dtype)
@@ -474,7 +482,8 @@ class MultiModalSwinTransformer(nn.Module):
         outs = []
         for i, layer in enumerate(self.layers):
             if i == 0 and image_of is not None:
-                t = ops.gather_samples(layer.run_blocks(t, Wh, Ww), image_of, pairs=True)
+                t = layer.run_blocks(t, Wh, Ww)
+                t = ops.gather_pairs(t, image_of) if torch.is_grad_enabled() and t.requires_grad else ops.gather_samples(t, image_of, pairs=True)
                 B = t.shape[0]
                 f, H, W, t, Wh, Ww = layer.fuse_language(t, Wh, Ww, l, l_mask)
             elif i == 0 and S > 1:
