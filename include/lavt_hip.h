@@ -777,7 +777,7 @@ int lavt_ema_swap(const int64_t* desc, const int64_t* ema, const int32_t* chunks
  *   offset 0 fp32 loss | 4 fp32 I | 8 fp32 U | 12 fp32 lr | 16 fp32 grad_norm | 20 uint32 flags | 24 fp64 iou | 32 int64 it
  *
  * lavt_meter_append: ONE single-writer launch at the end of an iteration, after the optimizer's tick.  stats: the fp32[4] {loss, sum of weights, I, U} of
- * the fused criteria.  ctl: the control block of lavt_grad_norm, or NULL.  step: the optimizer's counter, or NULL.  hyper: the hyper row whose base lr is
+ * the fused cross-entropy, or the row of lavt_upsample_iu below for the criteria that do not count I / U ([1] is not read).  ctl: the control block of lavt_grad_norm, or NULL.  step: the optimizer's counter, or NULL.  hyper: the hyper row whose base lr is
  * logged (fp32[5], [0] = base lr), or NULL.  Nothing at all is stored when header[1] != 0 or ctl[4] != 0.  Otherwise the record is
  *   iou  = (I == 0 || U == 0) ? 0 : (double)I / (double)U  (train.py:64-76), seg_correct compares it in fp64 against the double literals;
  *   lr   = hyper[0] * (total_steps > 0 ? powf(fmaxf(1 - step[0] / total_steps, 0), power) : 1) with the counter as the update's tick left it -- the lr
@@ -804,6 +804,26 @@ int64_t lavt_meter_bytes(int capacity);
 int lavt_meter_append(const float* stats, const float* ctl /* NULL */, const float* step /* NULL */, const float* hyper /* NULL */, float total_steps, float power,
                       void* block, int capacity, void* stream);
 int lavt_grad_norm_tensors(const float* ws, int nchunks, const int32_t* first, int count, const float* ctl, double* out, int32_t* bad, void* stream);
+/* The hard-mask I / U of a training batch for the criteria whose own statistics do not hold them (csrc/meters.hip; three new symbols under ABI v7).
+ * The reference logs IoU(output, masks) in its training loops whatever --loss is (train.py:64-76: pred = output.argmax(1); I = sum(pred * gt);
+ * U = sum(pred + gt) - I, pooled over the batch).  lavt_upsample_ce_fwd leaves these counts in out4[2:4]; the `stats` of the two Dice criteria
+ * hold soft sums at pinned offsets and no argmax counts, so a metered step of those criteria runs this pass behind the criterion's forward:
+ * a fused bilinear upsample (align_corners) + argmax + pooled I / U over the low-resolution 2-class logits x NHWC [B,Hi,Wi,2] (LAVT_F32 / LAVT_BF16),
+ * target int64 [n,Ho,Wo] in {0,1}, n = B (or nsel).  Every pixel is computed exactly as the cross-entropy kernel computes it; pred = up1 > up0 (a tie
+ * is class 0, as argmax), tgt = (t == 1), I = #(pred && tgt), U = #(pred || tgt) over all samples.
+ *   row (device fp32[4]) = {loss_src ? loss_src[0] : 0, 0, I, U} -- exactly the row lavt_meter_append reads as `stats`; loss_src[0] is copied bit for bit.
+ * Counted in integers: per wave with ballot + popcount, one int32 pair per workgroup in ws, then a one-workgroup finish that adds the pairs in a fixed
+ * order in 64-bit integers and converts each total to fp32 once.  Two launches, no floating-point atomics: identical bits from run to run, the same
+ * kernels in deterministic mode.  ws: lavt_upsample_iu_ws(n, Ho, Wo) 32-bit words of scratch (host arithmetic; 0 for n <= 0).
+ * _sel: annotated-frame selection as for the criteria (sel DEVICE int32 [nsel], 0 < nsel <= B, read on the device so a replayed graph follows the
+ * buffer; sample j reads logits frame sel[j] and target j; an entry outside [0, B) is never dereferenced and adds nothing to I or U).
+ * Bad arguments (a null pointer other than loss_src, a non-positive size, nsel outside 1..B, another dtype, ws_words below the query) return
+ * LAVT_ERR_INVALID with row untouched. */
+int64_t lavt_upsample_iu_ws(int n, int Ho, int Wo);
+int lavt_upsample_iu(int dtype, const void* x, const int64_t* target, const float* loss_src /* NULL */, int32_t* ws, int64_t ws_words, float* row, int B, int Hi,
+                     int Wi, int Ho, int Wo, void* stream);
+int lavt_upsample_iu_sel(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, const float* loss_src /* NULL */, int32_t* ws,
+                         int64_t ws_words, float* row, int B, int Hi, int Wi, int Ho, int Wo, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Evaluation meter (csrc/meters.hip; the reference's evaluation log, test.py:84-108: per-sample IoU, cumulative I / U, precision@X) kept on the

@@ -5,7 +5,9 @@
 // hyper row, the schedule -- it reads through optim_protocol.h and the LAVT_CTL_* / LAVT_ADAMW_HYPER_* names of the public header.
 // The evaluation meter (include/lavt_hip.h "Evaluation meter") is its sibling behind a Predictor's mask kernel: the (I, U) rows of a prediction batch
 // go into the accumulators of the reference's evaluation loop (test.py:84-108) and a ring of per-sample records.
-#include "common.h"
+// The hard-mask I / U pass (include/lavt_hip.h "Training meters": lavt_upsample_iu) makes the fp32[4] row the append reads for the criteria whose own
+// statistics do not hold the argmax counts (mc_dice, dice_boundary): the pixel arithmetic of the cross-entropy kernel, counted in integers.
+#include "internal.h"
 #include "optim_protocol.h"
 
 namespace {
@@ -144,6 +146,65 @@ __global__ __launch_bounds__(64) void eval_meter_append_kernel(const int32_t* __
     }
 }
 
+// ---------------------------------------------------------------------------------------------- hard-mask I / U of a training batch (lavt_upsample_iu)
+// train.py:64-76 on the low-resolution logits: every full-resolution pixel is recomputed from its four neighbours exactly as upsample_ce_fwd_kernel
+// does (bl_coord / upce_at, common.h; pred = up1 > up0, a tie is class 0), pred && tgt and pred || tgt are counted per wave with ballot + popcount --
+// wave-uniform integers -- and every workgroup stores ONE int32 pair.  A streaming pass over the int64 labels: consecutive lanes load consecutive
+// 8-byte labels (512 contiguous bytes per wave), the label load is issued before the gather from the (L2-resident) logits map.  The loop bound is
+// uniform over the workgroup, a lane past the end or on an unselected frame is a false predicate, not a branch around the ballots.
+inline int iu_grid(int64_t n) { int64_t b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b)); }
+
+template <typename T, bool SEL>
+__global__ __launch_bounds__(256) void upsample_iu_kernel(const T* __restrict__ x, const int32_t* __restrict__ sel, int nfr, const int64_t* __restrict__ target,
+                                                          int32_t* __restrict__ partial, int ns, int Hi, int Wi, int Ho, int Wo, float sh, float sw) {
+    const int64_t n = (int64_t)ns * Ho * Wo, stride = (int64_t)gridDim.x * 256;
+    int ci = 0, cu = 0;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < n; base += stride) {
+        const int64_t i = base + threadIdx.x;
+        bool pi = false, pu = false;
+        if (i < n) {
+            const int64_t t = target[i];
+            const int xo = (int)(i % Wo), yo = (int)((i / Wo) % Ho), b = sel_frame<SEL>(sel, (int)(i / Wo / Ho), nfr);
+            if (!SEL || b >= 0) {          // an entry of sel outside [0, nfr): no logits are read, the sample counts nothing
+                int y0, y1, x0, x1; float ly, lx;
+                bl_coord(yo, sh, Hi, y0, y1, ly);
+                bl_coord(xo, sw, Wi, x0, x1, lx);
+                const UpCe u = upce_at<T>(x + (int64_t)b * Hi * Wi * 2, Wi, y0, y1, ly, x0, x1, lx);
+                const bool pred = u.up1 > u.up0, tgt = t == 1;          // argmax picks class 0 on ties
+                pi = pred && tgt;
+                pu = pred || tgt;
+            }
+        }
+        ci += __popcll(__ballot(pi));
+        cu += __popcll(__ballot(pu));
+    }
+    __shared__ int red[4][2];
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = ci; red[threadIdx.x >> 6][1] = cu; }
+    __syncthreads();
+    if (threadIdx.x < 2) partial[blockIdx.x * 2 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+// row = {loss_src ? loss_src[0] : 0, 0, I, U}: the pairs added in 64-bit integers in one fixed order (thread t takes pairs t, t + 256, ...; a xor tree
+// joins the lanes, the four waves are added in wave order), each total converted to fp32 once.  The loss is copied as a bit pattern (a NaN keeps its payload).
+__global__ __launch_bounds__(256) void upsample_iu_finish_kernel(const int32_t* __restrict__ partial, int nblk, const uint32_t* __restrict__ loss_src,
+                                                                 float* __restrict__ row) {
+    long long a[2] = {0, 0};
+    for (int b = threadIdx.x; b < nblk; b += 256) { a[0] += partial[b * 2]; a[1] += partial[b * 2 + 1]; }
+    __shared__ long long red[4][2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a[k] += __shfl_xor(a[k], o, 64);
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = a[0]; red[threadIdx.x >> 6][1] = a[1]; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t loss_bits = loss_src ? loss_src[0] : 0u;
+        reinterpret_cast<uint32_t*>(row)[0] = loss_bits;
+        row[1] = 0.f;
+        row[2] = (float)(red[0][0] + red[1][0] + red[2][0] + red[3][0]);
+        row[3] = (float)(red[0][1] + red[1][1] + red[2][1] + red[3][1]);
+    }
+}
+
 }  // namespace
 
 #define ST reinterpret_cast<hipStream_t>(stream)
@@ -172,4 +233,40 @@ extern "C" int lavt_eval_meter_append(const int32_t* iu, const int32_t* image_of
     hipLaunchKernelGGL(eval_meter_append_kernel, dim3(1), dim3(64), 0, ST, iu, image_of, n_images, n, reinterpret_cast<double*>(block), capacity);
     LAVT_CHECK_LAUNCH("lavt_eval_meter_append");
     return LAVT_OK;
+}
+
+extern "C" int64_t lavt_upsample_iu_ws(int n, int Ho, int Wo) {
+    return (n > 0 && Ho > 0 && Wo > 0) ? 2 * (int64_t)iu_grid((int64_t)n * Ho * Wo) : 0;
+}
+
+// SEL = false: B frames = B samples (sel, nsel unused); SEL = true: nsel samples out of the B frames of x
+template <bool SEL>
+static int upsample_iu(const char* who, int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, const float* loss_src, int32_t* ws,
+                       int64_t ws_words, float* row, int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
+    const int ns = SEL ? nsel : B;
+    const int blocks = iu_grid((int64_t)ns * Ho * Wo);
+    LAVT_CHECK_ARG(dtype == LAVT_F32 || dtype == LAVT_BF16, "%s: bad dtype %d", who, dtype);
+    LAVT_CHECK_ARG(ws_words >= lavt_upsample_iu_ws(ns, Ho, Wo), "%s: scratch of %d 32-bit words needed", who, 2 * blocks);
+    LAVT_CHECK_ARG((reinterpret_cast<uintptr_t>(target) & 7) == 0 && ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(row) |
+                                                                       reinterpret_cast<uintptr_t>(loss_src) | reinterpret_cast<uintptr_t>(sel)) & 3) == 0,
+                   "%s: target must be 8-byte aligned; sel, loss_src, ws and row 4-byte", who);
+    const float sh = bl_scale(Hi, Ho), sw = bl_scale(Wi, Wo);
+    if (dtype == LAVT_F32) hipLaunchKernelGGL((upsample_iu_kernel<float, SEL>), dim3(blocks), dim3(256), 0, ST, (const float*)x, sel, B, target, ws, ns, Hi, Wi, Ho, Wo, sh, sw);
+    else hipLaunchKernelGGL((upsample_iu_kernel<bf16, SEL>), dim3(blocks), dim3(256), 0, ST, (const bf16*)x, sel, B, target, ws, ns, Hi, Wi, Ho, Wo, sh, sw);
+    hipLaunchKernelGGL(upsample_iu_finish_kernel, dim3(1), dim3(256), 0, ST, ws, blocks, reinterpret_cast<const uint32_t*>(loss_src), row);
+    LAVT_CHECK_LAUNCH(who);
+    return LAVT_OK;
+}
+
+extern "C" int lavt_upsample_iu(int dtype, const void* x, const int64_t* target, const float* loss_src, int32_t* ws, int64_t ws_words, float* row, int B, int Hi,
+                                int Wi, int Ho, int Wo, void* stream) {
+    LAVT_CHECK_ARG(x && target && ws && row && B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "lavt_upsample_iu: bad arguments");
+    return upsample_iu<false>("lavt_upsample_iu", dtype, x, nullptr, B, target, loss_src, ws, ws_words, row, B, Hi, Wi, Ho, Wo, stream);
+}
+
+extern "C" int lavt_upsample_iu_sel(int dtype, const void* x, const int32_t* sel, int nsel, const int64_t* target, const float* loss_src, int32_t* ws,
+                                    int64_t ws_words, float* row, int B, int Hi, int Wi, int Ho, int Wo, void* stream) {
+    LAVT_CHECK_ARG(x && sel && target && ws && row && B > 0 && nsel > 0 && nsel <= B && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0,
+                   "lavt_upsample_iu_sel: bad arguments (0 < nsel <= B)");
+    return upsample_iu<true>("lavt_upsample_iu_sel", dtype, x, sel, nsel, target, loss_src, ws, ws_words, row, B, Hi, Wi, Ho, Wo, stream);
 }

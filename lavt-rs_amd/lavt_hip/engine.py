@@ -36,7 +36,9 @@ FusedAdamW on the step's context: its update then ends the step's body, inside t
 
 Training meters (TrainStep(meters=) / make_meters(); lavt_hip.meters): one more launch behind the optimizer's tick logs loss, lr, I, U, IoU, the gradient norm
 and the update's verdict of every step() into a ring on the device and moves the epoch accumulators of the reference's log (train.py:463-500); the host reads
-them with TrainMeters.poll(), which never waits.  Off by default: a step built without meters launches what it launched before.
+them with TrainMeters.poll(), which never waits.  The launch reads `meter_stats`, an fp32[4] row {loss, ., I, U}: under loss="ce" the criterion's own `stats`;
+under "mc_dice" / "dice_boundary", whose `stats` hold no argmax counts, the row of lib._utils.fused_iu -- one more kernel pair behind the criterion's forward.
+Off by default: a step built without meters launches what it launched before, for every criterion.
 """
 import os
 import sys
@@ -228,7 +230,9 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
         so the deterministic mode keeps its promise across cycles.
         meters: a lavt_hip.meters.TrainMeters (or make_meters() later, before warmup_and_capture()): the step's body then ends with ONE more launch,
         lavt_meter_append, which logs loss, lr, IoU, gradient norm and the update's verdict of every step() on the device (DESIGN.md "Training meters").
-        None: the launches of a step built without the argument.  Needs a fused criterion (`stats`).
+        None: the launches of a step built without the argument.  Needs a fused criterion (`stats`).  The logged I / U are the argmax counts of
+        train.py:64-76 under every criterion: `meter_stats` is `stats` under loss="ce"; under "mc_dice" / "dice_boundary" a metered step makes it with one
+        more kernel pair behind the criterion's forward (lib._utils.fused_iu), `stats` keeping the criterion's own layout.
         image_of: device int32 [N], a static buffer like image and target -- a PAIR-LIST train batch (include/lavt_hip.h: the image_of contract; DESIGN.md
         "Pair-list training").  `image` holds B images, l_feats / l_mask N expressions, target is (N, H, W); slot j trains expression j on image
         image_of[j].  Patch embedding and stage 0's Swin blocks run forward and backward once per IMAGE, ops.gather_pairs repeats their rows per slot
@@ -285,7 +289,9 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
         self.zero_skip_values = 0                # gradient values left out of the captured zero fill (GradBuckets.set_zero_skip)
         ops.wgrads.enabled = True                # one weight gradient per parameter per step into the zeroed flat buffer: grouped, plainly stored
         self.fused_loss = fused_loss and hasattr(model, "forward_lowres")
-        self.stats = None                        # fused loss: [loss, sum of weights, I, U] of the last step (device tensor)
+        self.stats = None                        # fused loss: the criterion's statistics of the last step (device tensor; "ce": [loss, sum of weights, I, U])
+        self.meter_stats = None                  # the fp32[4] row {loss, ., I, U} the meters log: `stats` itself under "ce"; under the Dice criteria the
+                                                 # row of fused_iu when meters are attached, else None
         # The compute-dtype weight copies are refreshed by the optimizer (FusedAdamW.step re-casts them right after the update).  Set this when
         # the weights are changed by something else between replays of the captured step (a torch.optim optimizer, manual edits): the casts
         # (~0.3 ms for Swin-B) then run at the start of every step, inside the graph.
@@ -529,15 +535,20 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
         ops.dtable_chain.job, ops.dtable_chain.keep = None, None          # (a backward that raised mid-way must not leave its binning job to the next step)
         if fp8_enabled():
             ops.fp8.advance()                    # delayed scaling: last step's |max| values become this step's quantisation scales
-        if self.fused_loss:                       # upsample + criterion (+ I/U) fused: the (B,2,H,W) logits are never written
-            from lib._utils import fused_dice_boundary_loss, fused_dice_loss, fused_loss
+        if self.fused_loss:                       # upsample + criterion fused: the (B,2,H,W) logits are never written
+            from lib._utils import fused_dice_boundary_loss, fused_dice_loss, fused_iu, fused_loss
             y = self.model.forward_lowres(self.x, self.l, self.m) if self.image_of is None else self.model.forward_lowres(self.x, self.l, self.m, image_of=self.image_of)
             if self.criterion == "ce":
                 loss, self.stats = fused_loss(y, self.t, (0.9, 1.1), valid_indices=self.valid_indices)
+                self.meter_stats = self.stats    # the cross-entropy pair counts the hard-mask I / U itself (stats[2:4])
             elif self.criterion == "mc_dice":
                 loss, self.stats = fused_dice_loss(y, self.t, valid_indices=self.valid_indices)
             else:
                 loss, self.stats = fused_dice_boundary_loss(y, self.t, valid_indices=self.valid_indices, dice_rate=self.dice_rate, boundary_rate=self.boundary_rate)
+            if self.criterion != "ce":
+                # the Dice criteria's `stats` hold soft sums at pinned offsets, no argmax counts: a metered step makes the log's row {loss, 0, I, U} with
+                # one more kernel pair directly behind the criterion's forward (train.py:64-76 whatever --loss is); an unmetered step launches nothing
+                self.meter_stats = fused_iu(y, self.t, valid_indices=self.valid_indices, loss=self.stats) if self.meters is not None else None
         else:
             out = self.model(self.x, self.l, self.m)
             if self.valid_indices is not None:
@@ -570,9 +581,9 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
             # the last launch of the iteration, behind the optimizer's tick: the record's lr is the one the NEXT update will use, as the reference logs it
             if self.opt is not None:
                 ctl, cnt, hyper, total, power = self.opt.meter_args()
-                self.meters.append(self.stats, ctl, cnt, hyper, total, power)
+                self.meters.append(self.meter_stats, ctl, cnt, hyper, total, power)
             else:
-                self.meters.append(self.stats)
+                self.meters.append(self.meter_stats)
         return loss.detach()
 
     def warmup_and_capture(self, eager_iters=3):

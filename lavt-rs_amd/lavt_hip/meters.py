@@ -291,7 +291,8 @@ class TrainMeters(DeviceBlock):
 
     # ---- the launch (TrainStep._body ends with it)
     def append(self, stats, ctl=None, step=None, hyper=None, total_steps=0.0, power=0.0):
-        """enqueue lavt_meter_append on the current stream; capturable.  stats / ctl / step: device tensors (ctl, step: None without an optimizer);
+        """enqueue lavt_meter_append on the current stream; capturable.  stats: the device fp32[4] row {loss, ., I, U} (TrainStep.meter_stats: the
+        cross-entropy criterion's stats, or the row of lib._utils.fused_iu under the Dice criteria); ctl / step: device tensors (None without an optimizer);
         hyper: the fp32[5] hyper row whose base lr is logged, as a tensor or as its device address (FusedAdamW.meter_args gives a row of its table)"""
         K.check(K.lib.lavt_meter_append(K.ptr(stats), K.ptr(ctl), K.ptr(step), hyper if isinstance(hyper, int) else K.ptr(hyper), float(total_steps), float(power),
                                         K.ptr(self.block), self.capacity, K.stream()))

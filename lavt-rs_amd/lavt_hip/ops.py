@@ -3160,6 +3160,40 @@ def upsample_dice_boundary_loss(x, target, B, Hi, Wi, Ho, Wo, sel=None, dice_rat
     return _UpsampleDiceBoundary.apply(x, target, B, Hi, Wi, Ho, Wo, float(dice_rate), float(boundary_rate), _frame_sel(sel, B, "upsample_dice_boundary_loss"))
 
 
+def upsample_iu(x, target, B, Hi, Wi, Ho, Wo, sel=None, loss=None):
+    """The hard-mask I / U of train.py:64-76 -- `pred = F.interpolate(y, (Ho, Wo), bilinear, align_corners=True).argmax(1)`; I = sum(pred * gt);
+    U = sum(pred + gt) - I, pooled over the batch -- on the low-resolution 2-class logits rows x [B*Hi*Wi, 2], for the criteria whose `stats` do not
+    hold these counts (mc_dice, dice_boundary).  -> the device fp32[4] row {loss[0] or 0, 0, I, U} that lavt_meter_append reads; the counts are what
+    upsample_cross_entropy leaves in stats[2:4].  Not an autograd op (x is detached).  sel: see _frame_sel, target is [nsel, Ho, Wo] then.
+    loss: an optional device fp32 tensor whose element 0 the kernel copies into row[0] (no torch op: the row is made by the pass's two launches)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or not isinstance(target, torch.Tensor) or not target.is_cuda:
+        raise RuntimeError("liblavt_hip operates on GPU memory only (got a CPU tensor for `upsample_iu`); there is no CPU fallback")
+    sel = _frame_sel(sel, B, "upsample_iu")
+    if loss is not None:
+        if not isinstance(loss, torch.Tensor) or not loss.is_cuda:
+            raise RuntimeError("liblavt_hip operates on GPU memory only (got a CPU tensor for the loss of `upsample_iu`); there is no CPU fallback")
+        if loss.dtype != torch.float32 or loss.numel() < 1 or not loss.is_contiguous():
+            raise ValueError(f"upsample_iu: loss must be a contiguous float32 tensor with at least one element, got {loss.dtype} {tuple(loss.shape)}")
+        loss = loss.detach()
+    ns = B if sel is None else sel.numel()
+    with torch.no_grad():
+        x = x.detach().contiguous()
+        target = target.contiguous()
+        if x.numel() != B * Hi * Wi * 2:
+            raise ValueError(f"upsample_iu: expected {B * Hi * Wi} rows of 2 logits, got {tuple(x.shape)}")
+        if target.dtype != torch.int64 or target.numel() != ns * Ho * Wo:
+            raise ValueError(f"upsample_iu: target must be int64 [{ns}, {Ho}, {Wo}], got {target.dtype} {tuple(target.shape)}")
+        row = torch.empty(4, dtype=torch.float32, device=x.device)
+        ws = _scratch(K.lib.lavt_upsample_iu_ws(ns, Ho, Wo), x.device)          # (int32 pairs in fp32-typed scratch: 32-bit words either way)
+        _note(f"upsample-iu {ns}x{Hi}x{Wi}->{Ho}x{Wo}", nbytes=8 * ns * Ho * Wo + x.numel() * x.element_size())
+        if sel is None:
+            K.check(K.lib.lavt_upsample_iu(K.dt(x.dtype), K.ptr(x), K.ptr(target), K.ptr(loss), K.ptr(ws), ws.numel(), K.ptr(row), B, Hi, Wi, Ho, Wo, K.stream()))
+        else:
+            K.check(K.lib.lavt_upsample_iu_sel(K.dt(x.dtype), K.ptr(x), K.ptr(sel), ns, K.ptr(target), K.ptr(loss), K.ptr(ws), ws.numel(), K.ptr(row), B, Hi, Wi, Ho, Wo,
+                                               K.stream()))
+    return row
+
+
 def gather_samples(x, sel, pairs=False):
     """`torch.index_select(x, 0, sel)` for whole samples with sel on the device (int32 [nsel], see _frame_sel), no layout change: x is a dense tensor in
     ANY dimension order (an NCHW-shaped view of NHWC memory, as the backbone returns its feature maps, included) whose samples are contiguous blocks;

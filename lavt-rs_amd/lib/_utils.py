@@ -51,6 +51,16 @@ def fused_dice_boundary_loss(y, target, valid_indices=None, dice_rate=1.0, bound
                                            dice_rate=dice_rate, boundary_rate=boundary_rate)
 
 
+def fused_iu(y, target, valid_indices=None, loss=None):
+    """The reference's training-log counts `IoU(output, masks)` (train.py:64-76: argmax, I = sum(pred * gt), U = sum(pred + gt) - I, pooled over the
+    batch) on the LOW-resolution decoder output y, for the criteria whose statistics do not hold them (fused_dice_loss, fused_dice_boundary_loss):
+    bilinear upsample + argmax + integer counts in one kernel pair, no gradient.  -> the device fp32[4] row {loss[0] or 0, 0, I, U}, the layout of
+    fused_loss's stats (and the same I, U), which the training meters read.
+    valid_indices: as for fused_loss.  loss: an optional device fp32 tensor (a criterion's stats) whose element 0 the kernel copies into row[0]."""
+    B, _, h, w = y.shape
+    return ops.upsample_iu(nchw_rows(y, y.dtype), target, B, h, w, int(target.shape[-2]), int(target.shape[-1]), sel=valid_indices, loss=loss)
+
+
 def _check_frames(module, folded, frames):
     if frames is not None and (module.training or not folded):
         raise ValueError("forward_lowres: frames= needs the BatchNorm-folded decoder (folded=True, model.eval()); in training mode select in the "

@@ -12,7 +12,10 @@ repetition is a window of iterations between two device events, ended by a synch
 the host's wall time per iteration next to the device's (route (c) is bound by the host's wait, not by the device).  lr = 0 as in bench.py's separate
 optimizer timing: same memory traffic, weights left alone.  Prints one JSON line per route and appends them to profiles/meters_time.jsonl.
 
-    python tools/meters_time.py [--steps 20] [--reps 7] [--warmup 5]
+--loss {ce,mc_dice,dice_boundary} chooses the criterion of all three steps (default ce).  Under the Dice criteria a metered step also runs the hard-mask
+I / U pass (lavt_upsample_iu: two launches behind the criterion's forward), so (b') - (a) is the append plus that pass; every JSON line names the criterion.
+
+    python tools/meters_time.py [--steps 20] [--reps 7] [--warmup 5] [--loss ce]
 """
 import argparse
 import json
@@ -34,6 +37,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7, help="timed windows per route")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--poll-every", type=int, default=10)
+    ap.add_argument("--loss", choices=("ce", "mc_dice", "dice_boundary"), default="ce", help="the criterion of the timed steps")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "meters_time.jsonl"))
     a = ap.parse_args()
 
@@ -55,7 +59,7 @@ def main():
         model = segmentation.lavt("", SimpleNamespace(swin_type="base", window12=True, drop_path_rate=0.3, bert_random_init=True))
         fill_state_dict_(model)
         model = model.to(dev).train()
-        step = TrainStep(model, x, l, m, t, use_graph=True, context=ops.StepContext())
+        step = TrainStep(model, x, l, m, t, use_graph=True, context=ops.StepContext(), loss=a.loss)
         opt = step.make_optimizer(tensor_norms=metered if tensor_norms is None else tensor_norms, **okw)
         meters = step.make_meters() if metered else None
         step.warmup_and_capture()
@@ -103,7 +107,7 @@ def main():
     lines = []
     for name, _ in routes:
         ts, hs = dev_ms[name], host_ms[name]
-        rec = {"tool": "meters_time", "workload": "swin_b_w12_480_b2", "route": name, "ms_median": round(statistics.median(ts), 4), "ms_min": round(min(ts), 4),
+        rec = {"tool": "meters_time", "workload": "swin_b_w12_480_b2", "loss": a.loss, "route": name, "ms_median": round(statistics.median(ts), 4), "ms_min": round(min(ts), 4),
                "ms_max": round(max(ts), 4), "host_ms_median": round(statistics.median(hs), 4), "reps": len(ts), "iterations_per_rep": a.steps,
                "ms_all": [round(v, 4) for v in ts], "device": torch.cuda.get_device_name(0)}
         if name == "replay_meters":
@@ -111,7 +115,7 @@ def main():
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
     med = {name: statistics.median(ts) for name, ts in dev_ms.items()}
-    lines.append(json.dumps({"tool": "meters_time", "workload": "swin_b_w12_480_b2", "route": "comparison",
+    lines.append(json.dumps({"tool": "meters_time", "workload": "swin_b_w12_480_b2", "loss": a.loss, "route": "comparison",
                              "meters_minus_plain_us": round((med["replay_meters"] - med["replay_plain"]) * 1e3, 2),
                              "append_minus_plain_us": round((med["replay_append"] - med["replay_plain"]) * 1e3, 2),
                              "item_minus_plain_us": round((med["replay_item"] - med["replay_plain"]) * 1e3, 2),
