@@ -171,6 +171,34 @@ typedef struct lavt_gemm_nt {
 } lavt_gemm_nt_t;
 
 int lavt_gemm_nt(const lavt_gemm_nt_t* p, void* stream);
+/* The kernel lavt_gemm_nt(p) launches: one instantiation of one of the three NT kernel families and the arguments the library derives for it
+ * (csrc/gemm_nt_plan.hip decides, the families launch from this answer).  A host-side query: nothing is launched and no pointer of p is read
+ * through.  New symbol only: no existing prototype or struct changed, lavt_abi_version() stays 7. */
+#define LAVT_NT_CLASSIC 0 /* csrc/gemm.hip: register-staged double buffer (fp32, and bf16 without a zero page / 16-byte aligned rows) */
+#define LAVT_NT_V2 1      /* csrc/gemm_v2.hip: LDS-DMA ring */
+#define LAVT_NT_PIPE 2    /* csrc/gemm_nt_pipe.hip: LDS-DMA ring with the software-pipelined K loop */
+#define LAVT_NT_WALK_GENERAL 0 /* every K tile decoded from scratch (K tails, conv taps that fit no faster walk); the classic family's only walk */
+#define LAVT_NT_WALK_PLAIN 1   /* no taps, no concat source, K a multiple of the K tile: running pointers */
+#define LAVT_NT_WALK_TAPS 2    /* convolution taps walked with the K loop (conv_kc and a_split multiples of the K tile, <= 32 taps) */
+#define LAVT_NT_WALK_PARTIAL 3 /* the tap walk with a partial last channel block (conv_kc % 64 != 0; pipelined family, k-contiguous bf16 weights) */
+#define LAVT_NT_DACT 1 /* kind bits: fused activation gradient (dact_pre) */
+#define LAVT_NT_LNA 2  /* LayerNorm-folded A operand (ln_wsum) */
+#define LAVT_NT_GD 4   /* the stored-derivative form: with LNA, act = LAVT_ACT_GELU_D; with DACT, dact = LAVT_ACT_STORED and no residual / bias / row map */
+#define LAVT_NT_F8 8   /* e4m3 operands */
+typedef struct lavt_gemm_nt_route {
+    int32_t family;   /* LAVT_NT_CLASSIC / _V2 / _PIPE */
+    int32_t tile;     /* square output tile of a workgroup: 64, 128 or 256 */
+    int32_t stages;   /* K tiles in the LDS ring: 2 or 4 (classic: its 2 buffers) */
+    int32_t waves;    /* waves per workgroup: 4 or 8 */
+    int32_t kwalk;    /* LAVT_NT_WALK_* */
+    int32_t b_kmajor; /* B layout the kernel is built for: 0 = B[N][K], 1 = B[K][N] */
+    int32_t kind;     /* LAVT_NT_DACT / _LNA / _GD / _F8 bits */
+    int32_t lean;     /* epilogue instantiation: 0 full, 1 bias / residual / row scale / row map only, 2 bare store, 3 bare store with C2 kept */
+    int32_t epi_wide; /* the value the launch stores into lavt_gemm_nt_t.epi_wide: bit 0 the 16-byte store form, bit 1 side inputs requested before the K loop */
+    int32_t dtype;    /* element type of the operands (LAVT_F32 / LAVT_BF16 / LAVT_FP8); the classic family's template type */
+} lavt_gemm_nt_route_t;
+/* -> LAVT_OK and *out, or LAVT_ERR_INVALID (lavt_last_error set) exactly where lavt_gemm_nt(p) refuses the problem */
+int lavt_gemm_nt_route(const lavt_gemm_nt_t* p, lavt_gemm_nt_route_t* out);
 /* -> number of row blocks whose partial statistics lavt_gemm_nt(p) would store into p->colstats (0: this problem's kernel has no statistics
  * epilogue -- leave colstats NULL and take the statistics from the output with lavt_colstats_meanrstd); *rows_per_block = rows per block */
 int lavt_gemm_nt_colstats_plan(const lavt_gemm_nt_t* p, int* rows_per_block);

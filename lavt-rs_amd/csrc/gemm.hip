@@ -186,14 +186,8 @@ template <typename T, int BM, int BN, bool BKM> int launch_nt(const lavt_gemm_nt
     constexpr int B_TILE = BKM ? BK * (BN + KM_PAD) : BN * Cfg<T>::KC_LD;
     const size_t lds = 2 * (size_t)(A_TILE + B_TILE) * sizeof(T);
     dim3 grid(cdiv(p.M, BM) * cdiv(p.N, BN), p.batch);
-    static bool attr_set = false;      // > 64 KiB of dynamic LDS must be requested once per kernel
-    if (!attr_set && lds > 65536) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<T, BM, BN, BKM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            lavt_set_error("lavt_gemm_nt: cannot reserve %zu bytes of LDS", lds);
-            return LAVT_ERR_LAUNCH;
-        }
-        attr_set = true;
-    }
+    static bool reserved = false;
+    if (const int rc = lavt_nt_reserve_lds(&reserved, reinterpret_cast<const void*>(&gemm_nt_kernel<T, BM, BN, BKM>), lds, "lavt_gemm_nt")) return rc;
     hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, BKM>), grid, dim3(256), lds, st, p);
     LAVT_CHECK_LAUNCH("lavt_gemm_nt");
     return LAVT_OK;
@@ -202,14 +196,10 @@ template <typename T, int BM, int BN, bool BKM> int launch_nt(const lavt_gemm_nt
 static int forced_tile() {
     return lavt_tuning().gemm_tile;
 }
-template <typename T> int dispatch_nt(const lavt_gemm_nt_t& p, hipStream_t st) {
-    const long tiles128 = (long)cdiv(p.M, 128) * cdiv(p.N, 128) * p.batch;
-    const int force = forced_tile();
-    // measured on MI355X (tools/gemm_bench.py): 64x64 tiles win on every backbone GEMM of the batch-2 step (they are latency-bound:
-    // more workgroups per CU hide it better); 128x128 pays only once there are >= 3 full waves of tiles (decoder convs)
-    const bool big = force ? force == 128 : (tiles128 >= 768 && p.N >= 128);
-    if (p.b_kmajor) return big ? launch_nt<T, 128, 128, true>(p, st) : launch_nt<T, 64, 64, true>(p, st);
-    return big ? launch_nt<T, 128, 128, false>(p, st) : launch_nt<T, 64, 64, false>(p, st);
+// the classic family's instantiation of a route (gemm_nt_plan.hip): element type x tile x B layout
+template <typename T> int launch_nt_route(const lavt_gemm_nt_t& p, const lavt_gemm_nt_route_t& r, hipStream_t st) {
+    if (r.b_kmajor) return r.tile == 128 ? launch_nt<T, 128, 128, true>(p, st) : launch_nt<T, 64, 64, true>(p, st);
+    return r.tile == 128 ? launch_nt<T, 128, 128, false>(p, st) : launch_nt<T, 64, 64, false>(p, st);
 }
 
 // ================================================================================================
@@ -407,61 +397,18 @@ template <typename T> int dispatch_tn(const lavt_gemm_tn_t& p, hipStream_t st) {
 
 }  // namespace
 
+// Every check and every choice of kernel is lavt_gemm_nt_route's (gemm_nt_plan.hip); this launches what the route names.
 extern "C" int lavt_gemm_nt(const lavt_gemm_nt_t* pp, void* stream) {
-    LAVT_CHECK_ARG(pp != nullptr, "lavt_gemm_nt: null params");
+    lavt_gemm_nt_route_t r;
+    const int rc = lavt_gemm_nt_route(pp, &r);
+    if (rc != LAVT_OK) return rc;
     lavt_gemm_nt_t p = *pp;
-    LAVT_CHECK_ARG(p.dtype == LAVT_F32 || p.dtype == LAVT_BF16 || p.dtype == LAVT_FP8, "lavt_gemm_nt: bad dtype %d", p.dtype);
-    const int epc = p.dtype == LAVT_F32 ? 4 : (p.dtype == LAVT_FP8 ? 16 : 8);
-    LAVT_CHECK_ARG(p.M > 0 && p.N > 0 && p.K > 0 && p.batch >= 1, "lavt_gemm_nt: bad shape M=%d N=%d K=%d batch=%d", p.M, p.N, p.K, p.batch);
-    LAVT_CHECK_ARG(p.K % epc == 0, "lavt_gemm_nt: K=%d must be a multiple of %d", p.K, epc);
-    LAVT_CHECK_ARG(p.A && p.B && p.C, "lavt_gemm_nt: null operand");
-    LAVT_CHECK_ARG(p.lda % epc == 0 && p.ldb % epc == 0, "lavt_gemm_nt: lda/ldb must be multiples of %d", epc);
-    LAVT_CHECK_ARG(p.ldc % 4 == 0, "lavt_gemm_nt: ldc must be a multiple of 4");
-    LAVT_CHECK_ARG(!p.b_kmajor || p.N % epc == 0, "lavt_gemm_nt: k-major B needs N %% %d == 0", epc);
-    LAVT_CHECK_ARG(!p.A2 || (p.a_split % epc == 0 && p.lda2 % epc == 0), "lavt_gemm_nt: bad a_split");
-    LAVT_CHECK_ARG(!p.C2 || p.c_split % 4 == 0, "lavt_gemm_nt: bad c_split");
-    if (p.conv_kc > 0) {
-        const int taps = conv_taps_of(p);
-        const int vox = (p.conv_d > 0 ? p.conv_d : 1) * p.conv_h * p.conv_w;
-        if (p.conv_kc_split > 0) {
-            int st_ = 0;
-            LAVT_CHECK_ARG(p.dtype == LAVT_BF16 && p.conv_tap_split == 0 && p.conv_kc_split % 64 == 0 && p.batch * p.conv_kc_split == p.conv_kc && p.K == taps * p.conv_kc_split &&
-                           p.strideB == 0 && taps <= 32 && (!p.A2 || p.a_split % 64 == 0) && p.zeros && lavt_gemm_nt_pipe_tile(p, &st_) == 128,
-                           "lavt_gemm_nt: conv_kc_split needs batch * conv_kc_split == conv_kc, K == taps * conv_kc_split, strideB == 0 and the pipelined tap-walking kernel (bf16, conv_kc %% 64 == 0)");
-        } else if (p.conv_tap_split > 0)
-            LAVT_CHECK_ARG(p.dtype == LAVT_BF16 && p.K == p.conv_tap_split * p.conv_kc && p.batch * p.conv_tap_split == taps && p.conv_kc % 64 == 0 && taps <= 32 &&
-                           (!p.A2 || p.a_split % 64 == 0) && p.zeros, "lavt_gemm_nt: conv_tap_split needs batch * conv_tap_split == taps and the tap-walking path (conv_kc %% 64 == 0)");
-        else
-        LAVT_CHECK_ARG(p.K == taps * p.conv_kc && p.conv_kc % epc == 0 && p.conv_h > 0 && p.conv_w > 0, "lavt_gemm_nt: bad conv geometry");
-        LAVT_CHECK_ARG(p.M % vox == 0, "lavt_gemm_nt: conv rows %d not a multiple of D*H*W", p.M);
-    }
-    LAVT_CHECK_ARG((!p.R || p.ldr % 4 == 0) && (!p.Cpre || p.ldcpre % 4 == 0) && (!p.mul || p.ldmul % 4 == 0), "lavt_gemm_nt: ldr/ldcpre/ldmul must be multiples of 4");
-    LAVT_CHECK_ARG(p.act != LAVT_ACT_GELU_D || (p.ln_wsum && p.Cpre && !p.mul && !p.C2 && !p.R && !p.row_scale && !p.c_rowmap),
-                   "lavt_gemm_nt: LAVT_ACT_GELU_D exists in the LayerNorm-folded launch only (ln_wsum), needs Cpre and takes no multiplier / split / residual / row scale / row map");
-    LAVT_CHECK_ARG(!p.res_first || (p.dact_pre && p.R), "lavt_gemm_nt: res_first orders the residual before the fused activation gradient (needs dact_pre and R)");
+    p.epi_lds = 0;          // (reserved)
+    p.epi_wide = r.epi_wide;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    { p.epi_lds = 0;          // (reserved)
-      // the 16-byte store form where every alignment holds; else the narrow 8-byte stores
-      p.epi_wide = (p.dtype != LAVT_F32 && !p.c_f32 && p.ldc % 8 == 0 && (!p.C2 || (p.ldc2 % 8 == 0 && p.c_split % 8 == 0)) && (!p.R || p.ldr % 4 == 0) &&
-                    (!p.Cpre || p.ldcpre % 8 == 0) && (!p.dact_pre || p.lddact % 4 == 0) && (!p.bias || (p.strideBias % 4 == 0 && ((uintptr_t)p.bias % 16) == 0)) &&
-                    ((uintptr_t)p.C % 16) == 0 && (!p.C2 || ((uintptr_t)p.C2 % 16) == 0) && (!p.Cpre || ((uintptr_t)p.Cpre % 16) == 0) && (p.strideC % 8 == 0)) ? 1 : 0;
-      // bit 1: the epilogue's side inputs are requested before the K loop (gemm_common.h NtSide)
-      if (p.epi_wide && p.batch == 1) p.epi_wide |= 2; }
-    if (p.colstats) {
-        int rpb = 0;
-        LAVT_CHECK_ARG(lavt_gemm_nt_colstats_plan(&p, &rpb) > 0, "lavt_gemm_nt: colstats only where lavt_gemm_nt_colstats_plan accepts the problem (pipelined bf16 tiles, plain epilogue)");
-    }
-    {
-        int pipe_stages = 0;
-        const int pipe_tile = lavt_gemm_nt_pipe_tile(p, &pipe_stages);          // the 256x256 tile and the long-K 128x128 problems (gemm_nt_pipe.hip)
-        if (pipe_tile) return lavt_gemm_nt_pipe(p, pipe_tile, pipe_stages, st);
-    }
-    const int rc2 = lavt_gemm_nt_v2(p, st);          // bf16 LDS-DMA pipeline (gemm_v2.hip); 1 = not applicable
-    if (rc2 != 1) return rc2;
-    LAVT_CHECK_ARG(p.ln_wsum == nullptr, "lavt_gemm_nt: ln_wsum (LayerNorm-folded A operand) exists on the bf16 LDS-DMA path only");
-    LAVT_CHECK_ARG(p.dact_pre == nullptr, "lavt_gemm_nt: dact_pre (fused activation gradient) exists on the bf16 LDS-DMA path only");
-    LAVT_CHECK_ARG(p.dtype != LAVT_FP8, "lavt_gemm_nt: fp8 operands exist on the LDS-DMA path only");
-    return p.dtype == LAVT_F32 ? dispatch_nt<float>(p, st) : dispatch_nt<bf16>(p, st);
+    if (r.family == LAVT_NT_PIPE) return lavt_gemm_nt_pipe(p, r, st);
+    if (r.family == LAVT_NT_V2) return lavt_gemm_nt_v2(p, r, st);
+    return r.dtype == LAVT_F32 ? launch_nt_route<float>(p, r, st) : launch_nt_route<bf16>(p, r, st);
 }
 
 extern "C" int lavt_gemm_tn(const lavt_gemm_tn_t* pp, void* stream) {

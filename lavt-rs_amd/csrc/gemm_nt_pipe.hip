@@ -596,126 +596,49 @@ __global__ __launch_bounds__(512) void gemm_nt_pipe_kernel(const lavt_gemm_nt_t 
     }
 }
 
-template <int BM, int BN, bool BKM, int STAGES, int MODE, int LEAN, bool F8 = false> int launch_pipe_(const lavt_gemm_nt_t& p, hipStream_t st) {
+template <int BM, int BN, bool BKM, int STAGES, int MODE, int LEAN, bool F8> int launch_pipe_(const lavt_gemm_nt_t& p, hipStream_t st) {
     constexpr size_t lds = STAGES * (size_t)(BM * 128 + BN * 128);
-    static bool attr_set = false;
-    if (!attr_set && lds > 65536) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_pipe_kernel<BM, BN, BKM, STAGES, MODE, LEAN, F8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            lavt_set_error("lavt_gemm_nt(pipe): cannot reserve %zu bytes of LDS", lds);
-            return LAVT_ERR_LAUNCH;
-        }
-        attr_set = true;
-    }
+    static bool reserved = false;
+    if (const int rc = lavt_nt_reserve_lds(&reserved, reinterpret_cast<const void*>(&gemm_nt_pipe_kernel<BM, BN, BKM, STAGES, MODE, LEAN, F8>), lds, "lavt_gemm_nt(pipe)")) return rc;
     dim3 grid(cdiv(p.M, BM) * cdiv(p.N, BN), p.batch);
     hipLaunchKernelGGL((gemm_nt_pipe_kernel<BM, BN, BKM, STAGES, MODE, LEAN, F8>), grid, dim3(512), lds, st, p);
     LAVT_CHECK_LAUNCH("lavt_gemm_nt(pipe)");
     return LAVT_OK;
 }
-template <int BM, int BN, bool BKM, int STAGES, int MODE> int launch_pipe_lean(const lavt_gemm_nt_t& p, hipStream_t st) {
-    if constexpr (BM == 256 && BKM && MODE == 2) {          // split-output data gradient of a concat convolution: the plain store with the second output kept (LEAN 3)
-        if (p.C2 && p.act == 0 && !p.mul && !p.Cpre && !p.bias && !p.R && !p.row_scale && !p.c_rowmap)
-            return launch_pipe_<BM, BN, BKM, STAGES, MODE, 3>(p, st);
-    }
-    if (MODE != 0 && p.act == 0 && !p.mul && !p.Cpre && !p.C2) {      // epilogue instantiations without the features a launch does not use (gemm_common.h)
-        if (!p.bias && !p.R && !p.row_scale && !p.c_rowmap) return launch_pipe_<BM, BN, BKM, STAGES, MODE, 2>(p, st);
-        return launch_pipe_<BM, BN, BKM, STAGES, MODE, 1>(p, st);
-    }
-    return launch_pipe_<BM, BN, BKM, STAGES, MODE, 0>(p, st);
-}
-// fp8 operands: the plain and the tap-walking issue only (lavt_gemm_nt_pipe_tile sends everything else to gemm_v2.hip), lean epilogues as above
-template <int BM, int BN, int STAGES, int MODE> int launch_pipe_f8_lean(const lavt_gemm_nt_t& p, hipStream_t st) {
-    if (p.act == 0 && !p.mul && !p.Cpre && !p.C2) {
-        if (!p.bias && !p.R && !p.row_scale && !p.c_rowmap) return launch_pipe_<BM, BN, false, STAGES, MODE, 2, true>(p, st);
-        return launch_pipe_<BM, BN, false, STAGES, MODE, 1, true>(p, st);
-    }
-    return launch_pipe_<BM, BN, false, STAGES, MODE, 0, true>(p, st);
-}
-static inline bool pipe_f8_simple(const lavt_gemm_nt_t& p) { return p.conv_kc <= 0 && p.A2 == nullptr && p.K % 128 == 0; }
-static inline bool pipe_f8_convfast(const lavt_gemm_nt_t& p) {
-    const int64_t lim = (1ll << 31) - (1ll << 24);
-    const int64_t a_rows = (int64_t)p.M + 2 * ((int64_t)(p.conv_h > 0 ? p.conv_h : 1) * p.conv_w + p.conv_w + 1);
-    const bool small = a_rows * p.lda < lim && (p.A2 == nullptr || a_rows * p.lda2 < lim) && (int64_t)p.N * p.ldb + (int64_t)p.batch * p.strideB < lim;
-    return p.conv_kc > 0 && p.conv_kc % 128 == 0 && (p.A2 == nullptr || p.a_split % 128 == 0) && conv_taps_of(p) <= 32 && small;
-}
-template <int BM, int BN, int STAGES> int launch_pipe_f8(const lavt_gemm_nt_t& p, hipStream_t st) {
-    if (pipe_f8_simple(p)) return launch_pipe_f8_lean<BM, BN, STAGES, 1>(p, st);
-    return launch_pipe_f8_lean<BM, BN, STAGES, 2>(p, st);
-}
-template <int BM, int BN, bool BKM, int STAGES> int launch_pipe(const lavt_gemm_nt_t& p, hipStream_t st) {
-    const bool simple = p.conv_kc <= 0 && p.A2 == nullptr && p.K % 64 == 0;
-    // (tap-walking mode: operands through 32-bit buffer offsets -- each of them below 2 GB, the halo margin included)
-    const int64_t lim = (1ll << 31) - (1ll << 24);
-    const int64_t a_rows = (int64_t)p.M + 2 * ((int64_t)(p.conv_h > 0 ? p.conv_h : 1) * p.conv_w + p.conv_w + 1);
-    const int64_t b_rows = p.b_kmajor ? (int64_t)conv_taps_of(p) * p.conv_kc : p.N;
-    const bool small = a_rows * p.lda * 2 < lim && (p.A2 == nullptr || a_rows * p.lda2 * 2 < lim) && b_rows * p.ldb * 2 + (int64_t)p.batch * p.strideB * 2 < lim;
-    const bool convfast = p.conv_kc > 0 && p.conv_kc % 64 == 0 && (p.A2 == nullptr || p.a_split % 64 == 0) && conv_taps_of(p) <= 32 && small;
-    if (simple) return launch_pipe_lean<BM, BN, BKM, STAGES, 1>(p, st);
-    if (convfast) return launch_pipe_lean<BM, BN, BKM, STAGES, 2>(p, st);
-    if constexpr (!BKM) {          // k-contiguous weights [Cout][taps][Cin] with Cin % 64 != 0 (Cin % 8 == 0; a concat boundary on a 64-channel block): the partial-block form
-        const bool convtail = p.conv_kc > 0 && p.conv_kc % 64 != 0 && p.conv_kc % 8 == 0 && (p.A2 == nullptr || p.a_split % 64 == 0) && conv_taps_of(p) <= 32 && small &&
-                              p.conv_kc_split <= 0 && p.conv_tap_split <= 0 && p.batch == 1 && p.K == conv_taps_of(p) * p.conv_kc && p.ldb >= (int64_t)conv_taps_of(p) * p.conv_kc;
-        if (convtail) return launch_pipe_lean<BM, BN, BKM, STAGES, 3>(p, st);
-    }
-    return launch_pipe_lean<BM, BN, BKM, STAGES, 0>(p, st);
-}
 
 }  // namespace
 
-// Which tile of this kernel family a problem takes (0: none -- it goes to gemm_v2.hip / gemm.hip) and the ring depth.  Measured on MI355X
-// (tools/gemm_bench.py, tools/conv_small_probe.py): the 256x256 tile (one workgroup per CU, 128 flop per byte of LDS fill -- every CU ingests ~50 GB/s
-// whatever the tile, so the 128x128 tile is fill-bound at half the rate) only when its tiles fill the 256 CUs well (whole rounds at >= 80 %); the 128x128
-// tile for long reductions (K >= 1024; LAVT_GEMM_PIPE=3: every 128x128 problem) where gemm_v2.hip would take its 8-wave 128x128 form.
-int lavt_gemm_nt_pipe_tile(const lavt_gemm_nt_t& p, int* stages_out) {
-    if ((p.dtype != LAVT_BF16 && p.dtype != LAVT_FP8) || p.zeros == nullptr) return 0;
-    const lavt_tuning_t& tun = lavt_tuning();
-    const int pipe = tun.gemm_pipe;                 // 0: gemm_v2 K loops only; 1: the 256x256 tile; 2: + 128x128 for K >= 1024; 3: + every 128x128 problem
-    if (pipe < 1) return 0;
-    if (p.dtype == LAVT_FP8) {          // e4m3 operands: k-contiguous, 128-element K tiles, plain or tap-walking issue (anything else: gemm_v2.hip's fp8 form)
-        if (p.b_kmajor || p.c_f32 || p.conv_kc_split > 0 || p.conv_tap_split > 0 || p.lda % 16 || p.ldb % 16 || (p.A2 && p.lda2 % 16)) return 0;
-        if (!pipe_f8_simple(p) && !pipe_f8_convfast(p)) return 0;
+// A route of this family (gemm_nt_plan.hip decides it) -> its instantiation; a case that is not here is a kernel that does not exist.  The order of
+// the cases is the order of the kernels in the device image (hipcc emits instantiations in the order they are first named): it is the order the
+// former launchers gave them, kept so that no kernel's address moves.  Nothing tests or enforces that order: it holds the device image
+// byte-identical across this refactor only, and the next change that adds or drops a kernel is free to ignore it.
+int lavt_gemm_nt_pipe(const lavt_gemm_nt_t& p, const lavt_gemm_nt_route_t& r, hipStream_t st) {
+#define PIPE_CASE(BM, ST, KM, MODE, F8, LEAN)                                                                                                  \
+    case lavt_nt_route_key(BM, ST, KM, MODE, (F8) ? LAVT_NT_F8 : 0, LEAN): return launch_pipe_<BM, BM, KM, ST, MODE, LEAN, F8>(p, st);
+// The general walk's lean forms are never launched (the planner gives that walk the full epilogue only), but the device image has always held
+// them: the former launcher named them behind a condition the compiler folds.  They stay instantiated, with no way in, until a change of
+// its own retires them (the announced follow-up, together with the order constraint above).
+#define PIPE_KEPT(BM, ST, KM, LEAN) if (false) return launch_pipe_<BM, BM, KM, ST, LAVT_NT_WALK_GENERAL, LEAN, false>(p, st);
+#define PIPE_LEANS(BM, ST, KM, MODE, F8) PIPE_CASE(BM, ST, KM, MODE, F8, 2) PIPE_CASE(BM, ST, KM, MODE, F8, 1) PIPE_CASE(BM, ST, KM, MODE, F8, 0)
+#define PIPE_GENERAL(BM, ST, KM) PIPE_KEPT(BM, ST, KM, 2) PIPE_KEPT(BM, ST, KM, 1) PIPE_CASE(BM, ST, KM, LAVT_NT_WALK_GENERAL, false, 0)
+// e4m3 operands: k-contiguous B, the plain and the tap walk
+#define PIPE_F8(BM, ST) PIPE_LEANS(BM, ST, false, LAVT_NT_WALK_PLAIN, true) PIPE_LEANS(BM, ST, false, LAVT_NT_WALK_TAPS, true)
+// bf16: k-major B (no partial-block walk; LEAN3 = the 256x256 tile's tap walk with the plain store and the second output kept: the split-output
+// data gradient of a concat convolution), then k-contiguous B with every walk
+#define PIPE_BF16(BM, ST, LEAN3)                                                                                                              \
+    PIPE_LEANS(BM, ST, true, LAVT_NT_WALK_PLAIN, false) LEAN3 PIPE_LEANS(BM, ST, true, LAVT_NT_WALK_TAPS, false) PIPE_GENERAL(BM, ST, true)   \
+    PIPE_LEANS(BM, ST, false, LAVT_NT_WALK_PLAIN, false) PIPE_LEANS(BM, ST, false, LAVT_NT_WALK_TAPS, false)                                  \
+    PIPE_LEANS(BM, ST, false, LAVT_NT_WALK_PARTIAL, false) PIPE_GENERAL(BM, ST, false)
+    switch (lavt_nt_route_key(r.tile, r.stages, r.b_kmajor, r.kwalk, r.kind, r.lean)) {
+        PIPE_F8(256, 2) PIPE_F8(128, 2) PIPE_F8(128, 4)
+        PIPE_BF16(256, 2, PIPE_CASE(256, 2, true, LAVT_NT_WALK_TAPS, false, 3)) PIPE_BF16(128, 2, ) PIPE_BF16(128, 4, )
     }
-    if (p.lda % 8 || p.ldb % 8 || (p.A2 && p.lda2 % 8)) return 0;
-    if (p.ln_wsum || p.dact_pre) return 0;
-    if (p.conv_kc_split > 0) {          // the channel-split reduction exists in this kernel's tap-walking mode only
-        *stages_out = 4;
-        return 128;
-    }
-    const int force = tun.gemm_tile;
-    const long tiles128 = (long)cdiv(p.M, 128) * cdiv(p.N, 128) * p.batch;
-    const long tiles64 = (long)cdiv(p.M, 64) * cdiv(p.N, 64) * p.batch;
-    const bool big = force ? force == 128 : ((tiles128 >= 200 || (p.K >= 64 * 64 && tiles128 >= GEMM_BIG_LONG)) && p.N >= 128);
-    const long wgs = big ? tiles128 : tiles64;
-    const int stages = tun.gemm_stages ? tun.gemm_stages : (wgs >= (big ? S2_MIN128 : 512) ? 2 : 4);
-    const long tiles256x = (long)cdiv(p.M, 256) * cdiv(p.N, 256) * p.batch;
-    const long rounds = (tiles256x + 255) / 256;
-    // (round 5: N within 1/16 of a multiple of 256 also takes the large tile -- Swin-T's 480-column data gradient of the concat convolution ran 439 us on 3600
-    // 128x128 tiles at 0.35 of peak; the columns beyond N are out-of-range offsets in the weight descriptor and masked stores)
-    const bool n_fits = p.N % 256 == 0 || (p.N % 8 == 0 && (long)p.N * 16 >= (long)cdiv(p.N, 256) * 256 * 15);
-    const bool huge = force ? force == 512 : (n_fits && p.K >= 1024 && tiles256x >= 128 && tiles256x * 10 >= rounds * 256 * 8);
-    if (huge) { *stages_out = 2; return 256; }
-    if (big && (pipe >= 3 || (pipe == 2 && p.K >= 1024))) { *stages_out = stages == 2 ? 2 : 4; return 128; }
-    return 0;
-}
-
-// tile: 256 = the 256x256 tile (2-stage ring, 128 KB of LDS), 128 = the 128x128 tile with `stages` (2 or 4) stages
-int lavt_gemm_nt_pipe(const lavt_gemm_nt_t& p, int tile, int stages, hipStream_t st) {
-    if (p.dtype == LAVT_FP8) {
-        if (tile == 256) return launch_pipe_f8<256, 256, 2>(p, st);
-        return stages == 2 ? launch_pipe_f8<128, 128, 2>(p, st) : launch_pipe_f8<128, 128, 4>(p, st);
-    }
-    if (tile == 256) return p.b_kmajor ? launch_pipe<256, 256, true, 2>(p, st) : launch_pipe<256, 256, false, 2>(p, st);
-    if (stages == 2) return p.b_kmajor ? launch_pipe<128, 128, true, 2>(p, st) : launch_pipe<128, 128, false, 2>(p, st);
-    return p.b_kmajor ? launch_pipe<128, 128, true, 4>(p, st) : launch_pipe<128, 128, false, 4>(p, st);
-}
-
-extern "C" int lavt_gemm_nt_colstats_plan(const lavt_gemm_nt_t* pp, int* rows_per_block) {
-    if (!pp || !rows_per_block) return 0;
-    const lavt_gemm_nt_t& p = *pp;
-    *rows_per_block = 0;
-    if (p.batch != 1 || p.bias || p.act || p.R || p.row_scale || p.c_rowmap || p.c_f32 || p.C2 || p.Cpre || p.mul || p.N % 4 || p.M <= 0 || p.N <= 0) return 0;
-    int stages = 0;
-    const int tile = lavt_gemm_nt_pipe_tile(p, &stages);
-    if (!tile) return 0;
-    *rows_per_block = tile / 2;                      // a wave row of the 2 x 4 wave grid
-    return cdiv(p.M, tile) * 2;
+#undef PIPE_BF16
+#undef PIPE_F8
+#undef PIPE_GENERAL
+#undef PIPE_LEANS
+#undef PIPE_KEPT
+#undef PIPE_CASE
+    lavt_set_error("lavt_gemm_nt(pipe): the route names no kernel of this family");
+    return LAVT_ERR_INVALID;
 }

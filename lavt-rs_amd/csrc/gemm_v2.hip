@@ -412,120 +412,54 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_nt_v2_kernel(const lavt_gemm_
     }
 }
 
-template <int BM, int BN, bool BKM, int STAGES, int WAVES, int MODE, bool DACT = false, bool F8 = false, bool LNA = false, bool GD = false, int LEAN = 0> int launch_nt_v2_(const lavt_gemm_nt_t& p, hipStream_t st) {
-    if constexpr (LEAN == 0 && !DACT && !LNA && !F8 && MODE != 0) {      // epilogue instantiations without the features a launch does not use (gemm_common.h)
-        if (p.act == 0 && !p.mul && !p.Cpre && !p.C2) {
-            if (!p.bias && !p.R && !p.row_scale && !p.c_rowmap) return launch_nt_v2_<BM, BN, BKM, STAGES, WAVES, MODE, DACT, F8, LNA, GD, 2>(p, st);
-            return launch_nt_v2_<BM, BN, BKM, STAGES, WAVES, MODE, DACT, F8, LNA, GD, 1>(p, st);
-        }
-    }
+template <int BM, int BN, bool BKM, int STAGES, int WAVES, int MODE, bool DACT, bool F8, bool LNA, bool GD, int LEAN> int launch_nt_v2_(const lavt_gemm_nt_t& p, hipStream_t st) {
     constexpr size_t lds = STAGES * (size_t)(BM * 128 + BN * 128);
-    static bool attr_set = false;
-    if (!attr_set && lds > 65536) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_v2_kernel<BM, BN, BKM, STAGES, WAVES, MODE, DACT, F8, LNA, GD, LEAN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            lavt_set_error("lavt_gemm_nt(v2): cannot reserve %zu bytes of LDS", lds);
-            return LAVT_ERR_LAUNCH;
-        }
-        attr_set = true;
-    }
+    static bool reserved = false;
+    if (const int rc = lavt_nt_reserve_lds(&reserved, reinterpret_cast<const void*>(&gemm_nt_v2_kernel<BM, BN, BKM, STAGES, WAVES, MODE, DACT, F8, LNA, GD, LEAN>), lds, "lavt_gemm_nt(v2)")) return rc;
     dim3 grid(cdiv(p.M, BM) * cdiv(p.N, BN), p.batch);
     hipLaunchKernelGGL((gemm_nt_v2_kernel<BM, BN, BKM, STAGES, WAVES, MODE, DACT, F8, LNA, GD, LEAN>), grid, dim3(WAVES * 64), lds, st, p);
     LAVT_CHECK_LAUNCH("lavt_gemm_nt(v2)");
     return LAVT_OK;
 }
-// LayerNorm-folded A operand (ln_wsum != NULL): plain k-contiguous problems whose workgroups see whole rows (every tile walks all of K)
-int launch_nt_v2_lna(const lavt_gemm_nt_t& p, hipStream_t st) {
-    if (p.b_kmajor || p.conv_kc > 0 || p.A2 || p.a_rowmap || p.K % 64 || p.N % 4 || p.batch != 1 || p.dact_pre || !p.bias || p.alpha != 1.0f) {
-        lavt_set_error("lavt_gemm_nt: ln_wsum (LayerNorm-folded A) needs a plain k-contiguous problem: no taps / concat / row gather / batch, K %% 64 == 0, bias = folded bias, alpha = 1");
-        return LAVT_ERR_INVALID;
-    }
-    const long tiles128 = (long)cdiv(p.M, 128) * cdiv(p.N, 128), tiles64 = (long)cdiv(p.M, 64) * cdiv(p.N, 64);
-    // (LAVT_ACT_GELU_D is its own instantiation: with the branch on p.act inside one kernel, the classic form ran 3 us per launch slower)
-    if (p.act == LAVT_ACT_GELU_D && !p.mul && !p.C2 && !p.R && !p.row_scale && !p.c_rowmap) {
-        if (tiles128 >= 200 && p.N >= 128) return tiles128 >= S2_MIN128 ? launch_nt_v2_<128, 128, false, 2, 8, 1, false, false, true, true>(p, st) : launch_nt_v2_<128, 128, false, 4, 8, 1, false, false, true, true>(p, st);
-        return tiles64 >= 512 ? launch_nt_v2_<64, 64, false, 2, 4, 1, false, false, true, true>(p, st) : launch_nt_v2_<64, 64, false, 4, 4, 1, false, false, true, true>(p, st);
-    }
-    if (tiles128 >= 200 && p.N >= 128) return tiles128 >= S2_MIN128 ? launch_nt_v2_<128, 128, false, 2, 8, 1, false, false, true>(p, st) : launch_nt_v2_<128, 128, false, 4, 8, 1, false, false, true>(p, st);
-    return tiles64 >= 512 ? launch_nt_v2_<64, 64, false, 2, 4, 1, false, false, true>(p, st) : launch_nt_v2_<64, 64, false, 4, 4, 1, false, false, true>(p, st);
-}
-// fp8 operands (LAVT_FP8): k-contiguous A and B, 128-element K tiles; 128x128 / 8 waves when that fills the chip, else 64x64 / 4 waves
-template <int BM, int BN, int STAGES, int WAVES> int launch_nt_v2_f8(const lavt_gemm_nt_t& p, hipStream_t st) {
-    const bool simple = p.conv_kc <= 0 && p.A2 == nullptr && p.K % 128 == 0;
-    const bool convfast = p.conv_kc > 0 && p.conv_kc % 128 == 0 && (p.A2 == nullptr || p.a_split % 128 == 0) && conv_taps_of(p) <= 32;
-    if (simple) return launch_nt_v2_<BM, BN, false, STAGES, WAVES, 1, false, true>(p, st);
-    if (convfast) return launch_nt_v2_<BM, BN, false, STAGES, WAVES, 2, false, true>(p, st);
-    return launch_nt_v2_<BM, BN, false, STAGES, WAVES, 0, false, true>(p, st);
-}
-int launch_nt_v2_fp8(const lavt_gemm_nt_t& p, hipStream_t st) {
-    if (p.b_kmajor || p.dact_pre || p.c_f32 || p.lda % 16 || p.ldb % 16 || (p.A2 && (p.lda2 % 16 || p.a_split % 16)) || p.K % 16 || (p.conv_kc > 0 && p.conv_kc % 16) || !p.zeros) {
-        lavt_set_error("lavt_gemm_nt(fp8): needs k-contiguous e4m3 operands with 16-byte aligned rows (lda, ldb, K, conv_kc, a_split %% 16 == 0), bf16 C, no dact_pre");
-        return LAVT_ERR_INVALID;
-    }
-    const long tiles128 = (long)cdiv(p.M, 128) * cdiv(p.N, 128) * p.batch, tiles64 = (long)cdiv(p.M, 64) * cdiv(p.N, 64) * p.batch;
-    if (tiles128 >= 200 && p.N >= 128) return tiles128 >= S2_MIN128 ? launch_nt_v2_f8<128, 128, 2, 8>(p, st) : launch_nt_v2_f8<128, 128, 4, 8>(p, st);
-    return tiles64 >= 512 ? launch_nt_v2_f8<64, 64, 2, 4>(p, st) : launch_nt_v2_f8<64, 64, 4, 4>(p, st);
-}
-// Fused activation-gradient epilogue (dact_pre): data gradients only (k-major B, plain K walk); the flag is a template parameter so that no
-// other instantiation pays its registers (as a run-time branch in every kernel it cost 12 VGPRs and 0.25 ms per step in round 1).
-int launch_nt_v2_dact(const lavt_gemm_nt_t& p, hipStream_t st) {
-    // (a residual is taken in both orders the header states: C * act'(pre) + R, and with res_first (C + R) * act'(pre))
-    if (!p.b_kmajor || p.conv_kc > 0 || p.A2 || p.K % 64 || p.lddact % 8 || p.c_f32 || p.C2 || p.Cpre || p.act || p.mul) {
-        lavt_set_error("lavt_gemm_nt: dact_pre needs a plain k-major data-gradient problem (no taps / concat / activation / second output, K %% 64 == 0)");
-        return LAVT_ERR_INVALID;
-    }
-    const long tiles128 = (long)cdiv(p.M, 128) * cdiv(p.N, 128) * p.batch, tiles64 = (long)cdiv(p.M, 64) * cdiv(p.N, 64) * p.batch;
-    // the stored-derivative form (dact = LAVT_ACT_STORED, no residual) is its own instantiation (GD): a multiply, none of the transcendental forms
-    if (p.dact == LAVT_ACT_STORED && !p.R && !p.bias && !p.c_rowmap && !p.act && !p.mul && !p.Cpre && !p.C2) {      // (its wide epilogue has none of these: any of them takes the general instantiation)
-        if (tiles128 >= 200 && p.N >= 128) return tiles128 >= S2_MIN128 ? launch_nt_v2_<128, 128, true, 2, 8, 1, true, false, false, true>(p, st) : launch_nt_v2_<128, 128, true, 4, 8, 1, true, false, false, true>(p, st);
-        return tiles64 >= 512 ? launch_nt_v2_<64, 64, true, 2, 4, 1, true, false, false, true>(p, st) : launch_nt_v2_<64, 64, true, 4, 4, 1, true, false, false, true>(p, st);
-    }
-    if (tiles128 >= 200 && p.N >= 128) return tiles128 >= S2_MIN128 ? launch_nt_v2_<128, 128, true, 2, 8, 1, true>(p, st) : launch_nt_v2_<128, 128, true, 4, 8, 1, true>(p, st);
-    return tiles64 >= 512 ? launch_nt_v2_<64, 64, true, 2, 4, 1, true>(p, st) : launch_nt_v2_<64, 64, true, 4, 4, 1, true>(p, st);
-}
-template <int BM, int BN, bool BKM, int STAGES, int WAVES> int launch_nt_v2(const lavt_gemm_nt_t& p, hipStream_t st) {
-    const bool simple = p.conv_kc <= 0 && p.A2 == nullptr && p.K % 64 == 0;
-    const bool convfast = p.conv_kc > 0 && p.conv_kc % 64 == 0 && (p.A2 == nullptr || p.a_split % 64 == 0) && conv_taps_of(p) <= 32;     // (a bit per tap)
-    if (simple) return launch_nt_v2_<BM, BN, BKM, STAGES, WAVES, 1>(p, st);
-    if (convfast) return launch_nt_v2_<BM, BN, BKM, STAGES, WAVES, 2>(p, st);
-    return launch_nt_v2_<BM, BN, BKM, STAGES, WAVES, 0>(p, st);
-}
-
 
 }  // namespace
 
-int lavt_gemm_nt_v2(const lavt_gemm_nt_t& p, hipStream_t st) {
-    if (p.dtype == LAVT_FP8) return launch_nt_v2_fp8(p, st);
-    if (p.dtype != LAVT_BF16 || p.zeros == nullptr) return 1;
-    const lavt_tuning_t& tun = lavt_tuning();
-    if (p.lda % 8 || p.ldb % 8 || (p.A2 && p.lda2 % 8)) return 1;
-    if (p.ln_wsum) return launch_nt_v2_lna(p, st);
-    if (p.dact_pre) return launch_nt_v2_dact(p, st);
-    // Dispatch measured on MI355X (tools/gemm_bench.py, hipGraph-timed): 128x128 tile with 8 waves (2 per SIMD: one wave's DMA issue and
-    // LDS reads hide under the other's MFMAs) and a 2-stage ring (64-80 KiB -> 2 workgroups per CU) once there are >= 200 such tiles;
-    // otherwise 64x64 tiles / 4 waves (5 workgroups per CU).
-    const int force = tun.gemm_tile;
-    const long tiles128 = (long)cdiv(p.M, 128) * cdiv(p.N, 128) * p.batch;
-    const long tiles64 = (long)cdiv(p.M, 64) * cdiv(p.N, 64) * p.batch;
-    // long reductions on few tiles (3-D convolutions of SepTPWAM: K = 27 C on 144 tiles of 128x128) also take the 128x128 tile: a launch lasts as
-    // long as its serial chain of K tiles, and the larger tile moves half the bytes per K tile and flop
-    const bool big = force ? force == 128 : ((tiles128 >= 200 || (p.K >= 64 * 64 && tiles128 >= GEMM_BIG_LONG)) && p.N >= 128);
-
-    // Ring depth.  In isolation (operands L2-resident) 2 stages win everywhere; inside the training step the operands of the small
-    // GEMMs arrive cold from HBM / Infinity Cache and a 4-deep ring is worth 0.8 ms per step.  The many-tile long-K problems (decoder
-    // convolutions: every CU holds 2 workgroups and streams from L2) stay at 2 stages, which keeps two workgroups per CU resident.
-    // Round 5 (second session): for the 128x128 / 8-wave tile the 4-deep ring is 128 KB -- ONE workgroup per CU -- so a launch of 257-600 such workgroups ran in
-    // two or three rounds of single workgroups; from 257 workgroups up (more workgroups than CUs) the 2-deep ring (64 KB, two co-resident workgroups whose
-    // barrier stalls overlap) wins: batch 4 11.70 -> 11.39 ms, Video-Swin-B 19.55 -> 18.77, Swin-T batch 8 10.89 -> 10.73, headline 7.61 -> 7.58
-    // (profiles/r05_zz_ring_depth_threshold_sweep.txt, ..._rule_ab.txt).  Up to 256 workgroups (the M = 1800 GEMMs of batch 2) the 4-deep ring stays.
-    const long wgs = big ? tiles128 : tiles64;
-    const int stages = tun.gemm_stages ? tun.gemm_stages : (wgs >= (big ? S2_MIN128 : 512) ? 2 : 4);
-#define GO(BM_, BN_, KM_, ST_, WV_) return launch_nt_v2<BM_, BN_, KM_, ST_, WV_>(p, st)
-    // (the 256x256 tile and the long-K 128x128 problems are taken by gemm_nt_pipe.hip before this dispatcher: gemm.hip)
-    if (big) {
-        if (stages == 2) { if (p.b_kmajor) GO(128, 128, true, 2, 8); else GO(128, 128, false, 2, 8); }
-        if (p.b_kmajor) GO(128, 128, true, 4, 8); else GO(128, 128, false, 4, 8);
+// A route of this family (gemm_nt_plan.hip decides it) -> its instantiation; a case that is not here is a kernel that does not exist.  The order of
+// the cases is the order of the kernels in the device image (hipcc emits instantiations in the order they are first named): it is the order the
+// former launchers gave them, kept so that no kernel's address moves.  Nothing tests or enforces that order: it holds the device image
+// byte-identical across this refactor only, and the next change that adds or drops a kernel is free to ignore it.
+int lavt_gemm_nt_v2(const lavt_gemm_nt_t& p, const lavt_gemm_nt_route_t& r, hipStream_t st) {
+#define V2_CASE(BM, WV, ST, KM, MODE, KIND, LEAN)                                                                                             \
+    case lavt_nt_route_key(BM, ST, KM, MODE, KIND, LEAN):                                                                                      \
+        return launch_nt_v2_<BM, BM, KM, ST, WV, MODE, ((KIND) & LAVT_NT_DACT) != 0, ((KIND) & LAVT_NT_F8) != 0, ((KIND) & LAVT_NT_LNA) != 0, ((KIND) & LAVT_NT_GD) != 0, LEAN>(p, st);
+// the four (tile / waves, ring depth) forms of X
+#define V2_TILES(X) X(128, 8, 2) X(128, 8, 4) X(64, 4, 2) X(64, 4, 4)
+// LayerNorm-folded A operand: k-contiguous B, plain walk, full epilogue; its stored-derivative form first
+#define V2_LNA_GD(BM, WV, ST) V2_CASE(BM, WV, ST, false, LAVT_NT_WALK_PLAIN, LAVT_NT_LNA | LAVT_NT_GD, 0)
+#define V2_LNA(BM, WV, ST) V2_CASE(BM, WV, ST, false, LAVT_NT_WALK_PLAIN, LAVT_NT_LNA, 0)
+// e4m3 operands: k-contiguous B, every walk but the partial-block one, full epilogue
+#define V2_F8(BM, WV, ST)                                                                                                                     \
+    V2_CASE(BM, WV, ST, false, LAVT_NT_WALK_PLAIN, LAVT_NT_F8, 0) V2_CASE(BM, WV, ST, false, LAVT_NT_WALK_TAPS, LAVT_NT_F8, 0) V2_CASE(BM, WV, ST, false, LAVT_NT_WALK_GENERAL, LAVT_NT_F8, 0)
+// fused activation gradient: k-major B, plain walk, full epilogue
+#define V2_DACT_GD(BM, WV, ST) V2_CASE(BM, WV, ST, true, LAVT_NT_WALK_PLAIN, LAVT_NT_DACT | LAVT_NT_GD, 0)
+#define V2_DACT(BM, WV, ST) V2_CASE(BM, WV, ST, true, LAVT_NT_WALK_PLAIN, LAVT_NT_DACT, 0)
+// plain kind, one B layout: the plain and the tap walk with the lean levels 2, 1, 0, the general walk with the full epilogue only
+#define V2_LEANS(BM, WV, ST, KM, MODE) V2_CASE(BM, WV, ST, KM, MODE, 0, 2) V2_CASE(BM, WV, ST, KM, MODE, 0, 1) V2_CASE(BM, WV, ST, KM, MODE, 0, 0)
+#define V2_LAYOUT(BM, WV, ST, KM) V2_LEANS(BM, WV, ST, KM, LAVT_NT_WALK_PLAIN) V2_LEANS(BM, WV, ST, KM, LAVT_NT_WALK_TAPS) V2_CASE(BM, WV, ST, KM, LAVT_NT_WALK_GENERAL, 0, 0)
+#define V2_PLAIN(BM, WV, ST) V2_LAYOUT(BM, WV, ST, true) V2_LAYOUT(BM, WV, ST, false)
+    switch (lavt_nt_route_key(r.tile, r.stages, r.b_kmajor, r.kwalk, r.kind, r.lean)) {
+        V2_TILES(V2_LNA_GD) V2_TILES(V2_LNA) V2_TILES(V2_F8) V2_TILES(V2_DACT_GD) V2_TILES(V2_DACT) V2_TILES(V2_PLAIN)
     }
-    if (stages == 2) { if (p.b_kmajor) GO(64, 64, true, 2, 4); else GO(64, 64, false, 2, 4); }
-    if (p.b_kmajor) GO(64, 64, true, 4, 4); else GO(64, 64, false, 4, 4);
-#undef GO
+#undef V2_PLAIN
+#undef V2_LAYOUT
+#undef V2_LEANS
+#undef V2_DACT
+#undef V2_DACT_GD
+#undef V2_F8
+#undef V2_LNA
+#undef V2_LNA_GD
+#undef V2_TILES
+#undef V2_CASE
+    lavt_set_error("lavt_gemm_nt(v2): the route names no kernel of this family");
+    return LAVT_ERR_INVALID;
 }

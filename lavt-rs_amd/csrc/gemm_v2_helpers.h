@@ -1,5 +1,5 @@
 // GEMM-specific helpers shared by the LDS-DMA GEMM generations (gemm_v2.hip, gemm_nt_pipe.hip: NT family; gemm_tn_v2.hip, gemm_tn_pipe.hip: TN family;
-// conv_wgrad.hip): dispatch constants, grouped vmcnt waits, the whole-tile transposing read, slot swizzles.  The family-neutral pipeline primitives
+// conv_wgrad.hip): grouped vmcnt waits, the whole-tile transposing read, slot swizzles.  The family-neutral pipeline primitives
 // (DMA issue, counted waits, issue / tie) are in lds_prims.h.  Internal linkage (anonymous namespace) in each translation unit.
 #pragma once
 #include <stdlib.h>
@@ -10,12 +10,6 @@
 using namespace lavt_gemm;
 
 namespace {
-
-// Dispatch constants shared by the NT dispatchers (gemm_v2.hip, gemm_nt_pipe.hip).
-// Workgroups of the 128x128 tile from which the 2-stage ring (two workgroups per CU) replaces the 4-stage one: more workgroups than the 256 CUs.
-constexpr long S2_MIN128 = 257;
-// Long reductions (K >= 4096) take the 128x128 tile from this many tiles up (below the general threshold of 200).
-constexpr long GEMM_BIG_LONG = 128;
 
 template <int G> __device__ __forceinline__ void wait_groups(int g) {      // leave g groups of G vector-memory ops in flight
     if (g <= 0) wait_vmcnt<0>();

@@ -5,12 +5,24 @@
 #include "common.h"
 
 // ---- NT family ----------------------------------------------------------------------------------------------------------------------------------------
-// gemm_v2.hip: bf16 / fp8 LDS-DMA pipeline.  Returns 1 when the problem is not for this kernel (the caller falls back to gemm.hip), else a LAVT status.
-int lavt_gemm_nt_v2(const lavt_gemm_nt_t& p, hipStream_t st);
-// gemm_nt_pipe.hip, software-pipelined K loop: which tile of that family a problem takes (0: none -- it goes to gemm_v2.hip / gemm.hip) and the ring depth.
-int lavt_gemm_nt_pipe_tile(const lavt_gemm_nt_t& p, int* stages_out);
-// tile: 256 = the 256x256 tile (2-stage ring, 128 KB of LDS), 128 = the 128x128 tile with `stages` (2 or 4) stages
-int lavt_gemm_nt_pipe(const lavt_gemm_nt_t& p, int tile, int stages, hipStream_t st);
+// gemm_nt_plan.hip (lavt_gemm_nt_route, include/lavt_hip.h) decides the kernel of a problem; gemm.hip launches the route's family.  The two LDS-DMA
+// families map a route of theirs to its instantiation and launch it (a route naming no instantiation is LAVT_ERR_INVALID: the planner makes none).
+int lavt_gemm_nt_v2(const lavt_gemm_nt_t& p, const lavt_gemm_nt_route_t& r, hipStream_t st);            // gemm_v2.hip
+int lavt_gemm_nt_pipe(const lavt_gemm_nt_t& p, const lavt_gemm_nt_route_t& r, hipStream_t st);          // gemm_nt_pipe.hip
+// the fields of a route that select an instantiation inside a family, as one switch value
+constexpr unsigned lavt_nt_route_key(int tile, int stages, int b_kmajor, int kwalk, int kind, int lean) {
+    return (unsigned)(tile / 64) | (stages == 2 ? 0u : 8u) | (b_kmajor ? 16u : 0u) | (unsigned)kwalk << 5 | (unsigned)lean << 7 | (unsigned)kind << 9;
+}
+// Dynamic LDS above 64 KiB has to be requested once per kernel; `*reserved` is the launcher's flag for its instantiation.
+static inline int lavt_nt_reserve_lds(bool* reserved, const void* kernel, size_t lds, const char* who) {
+    if (*reserved || lds <= 65536) return LAVT_OK;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        lavt_set_error("%s: cannot reserve %zu bytes of LDS", who, lds);
+        return LAVT_ERR_LAUNCH;
+    }
+    *reserved = true;
+    return LAVT_OK;
+}
 
 // ---- TN family ----------------------------------------------------------------------------------------------------------------------------------------
 // gemm_tn_v2.hip: bf16 LDS-DMA kernel.  Returns 1 when the problem is not for this kernel (the caller falls back to gemm.hip).

@@ -121,6 +121,17 @@ class GemmNT(C.Structure):
     ]
 
 
+class GemmNTRoute(C.Structure):
+    """lavt_gemm_nt_route_t: the kernel instantiation lavt_gemm_nt launches for a problem (lavt_gemm_nt_route, csrc/gemm_nt_plan.hip)"""
+    _fields_ = [("family", i32), ("tile", i32), ("stages", i32), ("waves", i32), ("kwalk", i32), ("b_kmajor", i32), ("kind", i32), ("lean", i32),
+                ("epi_wide", i32), ("dtype", i32)]
+
+
+NT_CLASSIC, NT_V2, NT_PIPE = 0, 1, 2                                      # GemmNTRoute.family
+NT_WALK_GENERAL, NT_WALK_PLAIN, NT_WALK_TAPS, NT_WALK_PARTIAL = 0, 1, 2, 3     # .kwalk
+NT_DACT, NT_LNA, NT_GD, NT_F8 = 1, 2, 4, 8                                # .kind bits
+
+
 class DtableJob(C.Structure):
     """lavt_dtable_job_t: the table-gradient binning of one attention-backward launch (chained form)"""
     _fields_ = [("slab", vp), ("part", vp), ("slab_ld", i32), ("wd", i32), ("wh", i32), ("ww", i32), ("nwin", i32), ("N", i32), ("heads", i32),
@@ -150,6 +161,7 @@ class PPItem(C.Structure):
 _PROTOTYPES = {
     "lavt_abi_version": [],
     "lavt_tuning_reload": [],
+    "lavt_gemm_nt_route": [C.POINTER(GemmNT), C.POINTER(GemmNTRoute)],
     "lavt_gemm_nt_colstats_plan": [C.POINTER(GemmNT), C.POINTER(i32)],
     "lavt_colstats_finish_blocks": [vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, f32, vp],
     "lavt_window_attn_bwd_chained": [i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, f32, C.POINTER(DtableJob), C.POINTER(DtableJob), vp],
@@ -322,7 +334,7 @@ _cdll.lavt_upsample_iu_ws.restype = C.c_int64
 _cdll.lavt_reduce_partials_det_stage.restype = C.c_int64
 _cdll.lavt_window_attn_bwd_det_ws.restype = C.c_int64
 _cdll.lavt_last_error.argtypes = []
-for _name in ("lavt_last_error", "lavt_window_attn_bwd_ws", "lavt_window_attn_stream_ok", "lavt_window_attn_stream_bwd_ws", "lavt_attn_uses_table", "lavt_abi_version", "lavt_layernorm_bwd_blocks", "lavt_window_attn_bwd_pieces", "lavt_gemm_tn_pieces", "lavt_pwam_q_parts", "lavt_pwam_words_records", "lavt_pwam_mix1_records", "lavt_adamw_chunk_elems", "lavt_tuning_reload", "lavt_conv3x3_wgrad_ws", "lavt_conv3x3_wgrad_f8_ok", "lavt_gemm_tn_grouped_sk_ws", "lavt_gemm_nt_colstats_plan", "lavt_cls_head_bwd_blocks", "lavt_reduce_partials_column_blocks", "lavt_grad_norm_ws", "lavt_upsample_dice_boundary_ws", "lavt_upsample_iu_ws", "lavt_reduce_partials_det_stage", "lavt_window_attn_bwd_det_ws", "lavt_gemm_tn_v2_eligible", "lavt_meter_bytes", "lavt_eval_meter_bytes"):      # queries, not launches: never timed
+for _name in ("lavt_last_error", "lavt_window_attn_bwd_ws", "lavt_window_attn_stream_ok", "lavt_window_attn_stream_bwd_ws", "lavt_attn_uses_table", "lavt_abi_version", "lavt_layernorm_bwd_blocks", "lavt_window_attn_bwd_pieces", "lavt_gemm_tn_pieces", "lavt_pwam_q_parts", "lavt_pwam_words_records", "lavt_pwam_mix1_records", "lavt_adamw_chunk_elems", "lavt_tuning_reload", "lavt_conv3x3_wgrad_ws", "lavt_conv3x3_wgrad_f8_ok", "lavt_gemm_tn_grouped_sk_ws", "lavt_gemm_nt_colstats_plan", "lavt_gemm_nt_route", "lavt_cls_head_bwd_blocks", "lavt_reduce_partials_column_blocks", "lavt_grad_norm_ws", "lavt_upsample_dice_boundary_ws", "lavt_upsample_iu_ws", "lavt_reduce_partials_det_stage", "lavt_window_attn_bwd_det_ws", "lavt_gemm_tn_v2_eligible", "lavt_meter_bytes", "lavt_eval_meter_bytes"):      # queries, not launches: never timed
     setattr(lib, _name, getattr(_cdll, _name))
 
 EXPORTED = tuple(_PROTOTYPES) + ("lavt_last_error",)

@@ -611,40 +611,50 @@ def _zero_page(device):
 
 
 # ------------------------------------------------------------------------------------------ raw launches
-def gemm_nt(dtype, M, N, Kd, A, lda, B, ldb, Cout, ldc, *, batch=1, strideA=0, strideB=0, strideC=0, A2=None, lda2=0,
-            a_split=0, a_rowmap=None, conv=None, b_kmajor=False, b_tap_stride=0, alpha=1.0, bias=None, strideBias=0,
-            row_scale=None, strideRowScale=0, row_scale_div=1, act=K.ACT_NONE, Cpre=None, ldcpre=0, R=None, ldr=0, C2=None, ldc2=0,
-            c_split=0, c_rowmap=None, c_f32=False, a_off=0, b_off=0, c_off=0, dact_pre=None, lddact=0, dact=K.ACT_NONE, deq=None,
-            mul=None, ldmul=0, res_first=False, conv_tap_split=0, conv_kc_split=0, ln=None, want_colstats=False):
-    """A/B/Cout are tensors; *_off are element offsets into them (column sub-blocks).  dtype torch.uint8 = e4m3 operands (A, B 1 byte per
-    element; C / residual bf16) with the two dequantisation |max| pointers in `deq`.
-    want_colstats: if this problem's kernel has the statistics epilogue (lavt_gemm_nt_colstats_plan), the launch also stores per-row-block column
-    sums / centred second moments of the output; returns (partials, blocks, rows_per_block) then, else None."""
+def gemm_nt_params(dtype, M, N, Kd, A, lda, B, ldb, Cout, ldc, *, batch=1, strideA=0, strideB=0, strideC=0, A2=None, lda2=0,
+                   a_split=0, a_rowmap=None, conv=None, b_kmajor=False, b_tap_stride=0, alpha=1.0, bias=None, strideBias=0,
+                   row_scale=None, strideRowScale=0, row_scale_div=1, act=K.ACT_NONE, Cpre=None, ldcpre=0, R=None, ldr=0, C2=None, ldc2=0,
+                   c_split=0, c_rowmap=None, c_f32=False, a_off=0, b_off=0, c_off=0, dact_pre=None, lddact=0, dact=K.ACT_NONE, deq=None,
+                   mul=None, ldmul=0, res_first=False, conv_tap_split=0, conv_kc_split=0, ln=None, addr=K.ptr, zeros=None):
+    """The lavt_gemm_nt_t of a launch (gemm_nt fills it here and launches it).  A/B/Cout are tensors; *_off are element offsets into them (column
+    sub-blocks).  dtype torch.uint8 = e4m3 operands (A, B 1 byte per element; C / residual bf16) with the two dequantisation |max| pointers in `deq`.
+    addr: operand -> device address (None -> NULL); zeros: address of the zero page (default: the page of A's device).  The host tests that ask
+    lavt_gemm_nt_route about a problem pass made-up addresses through both."""
     f8 = dtype == torch.uint8
     es = 4 if dtype == torch.float32 else (1 if f8 else 2)
     p = K.GemmNT()
     p.dtype, p.M, p.N, p.K, p.batch = (K.FP8 if f8 else K.dt(dtype)), M, N, Kd, batch
-    p.A, p.lda, p.strideA = K.ptr(A) + a_off * es, lda, strideA
-    p.A2, p.lda2, p.a_split = K.ptr(A2), lda2, a_split
-    p.a_rowmap = K.ptr(a_rowmap)
+    p.A, p.lda, p.strideA = addr(A) + a_off * es, lda, strideA
+    p.A2, p.lda2, p.a_split = addr(A2), lda2, a_split
+    p.a_rowmap = addr(a_rowmap)
     if conv is not None:
         p.conv_h, p.conv_w, p.conv_kc, p.conv_flip = conv[:4]
         if len(conv) > 4:
             p.conv_d, p.conv_kd, p.conv_kh, p.conv_kw = conv[4:8]
-    p.B, p.ldb, p.strideB, p.b_kmajor, p.b_tap_stride = K.ptr(B) + b_off * es, ldb, strideB, int(b_kmajor), b_tap_stride
-    p.alpha, p.bias, p.strideBias = alpha, K.ptr(bias), strideBias
-    p.row_scale, p.strideRowScale, p.row_scale_div, p.act = K.ptr(row_scale), strideRowScale, row_scale_div, act
-    p.Cpre, p.ldcpre, p.R, p.ldr = K.ptr(Cpre), ldcpre, K.ptr(R), ldr
-    p.C, p.ldc, p.strideC = K.ptr(Cout) + c_off * (4 if c_f32 else (2 if f8 else es)), ldc, strideC
-    p.C2, p.ldc2, p.c_split = K.ptr(C2), ldc2, c_split
-    p.c_rowmap, p.c_f32 = K.ptr(c_rowmap), int(c_f32)
-    p.zeros = _zero_page(A.device)
-    p.dact_pre, p.lddact, p.dact = K.ptr(dact_pre), lddact, dact
-    p.mul, p.ldmul, p.res_first, p.conv_tap_split, p.conv_kc_split = K.ptr(mul), ldmul, int(res_first), conv_tap_split, conv_kc_split
+    p.B, p.ldb, p.strideB, p.b_kmajor, p.b_tap_stride = addr(B) + b_off * es, ldb, strideB, int(b_kmajor), b_tap_stride
+    p.alpha, p.bias, p.strideBias = alpha, addr(bias), strideBias
+    p.row_scale, p.strideRowScale, p.row_scale_div, p.act = addr(row_scale), strideRowScale, row_scale_div, act
+    p.Cpre, p.ldcpre, p.R, p.ldr = addr(Cpre), ldcpre, addr(R), ldr
+    p.C, p.ldc, p.strideC = addr(Cout) + c_off * (4 if c_f32 else (2 if f8 else es)), ldc, strideC
+    p.C2, p.ldc2, p.c_split = addr(C2), ldc2, c_split
+    p.c_rowmap, p.c_f32 = addr(c_rowmap), int(c_f32)
+    p.zeros = _zero_page(A.device) if zeros is None else zeros
+    p.dact_pre, p.lddact, p.dact = addr(dact_pre), lddact, dact
+    p.mul, p.ldmul, p.res_first, p.conv_tap_split, p.conv_kc_split = addr(mul), ldmul, int(res_first), conv_tap_split, conv_kc_split
     if ln is not None:          # (wsum, mean out, rstd out, eps): LayerNorm-folded A operand
-        p.ln_wsum, p.ln_mean, p.ln_rstd, p.ln_eps = K.ptr(ln[0]), K.ptr(ln[1]), K.ptr(ln[2]), ln[3]
+        p.ln_wsum, p.ln_mean, p.ln_rstd, p.ln_eps = addr(ln[0]), addr(ln[1]), addr(ln[2]), ln[3]
     if deq is not None:
         p.deq_a, p.deq_b = deq
+    return p
+
+
+def gemm_nt(dtype, M, N, Kd, A, lda, B, ldb, Cout, ldc, *, want_colstats=False, **kw):
+    """One lavt_gemm_nt launch; kw: the keyword arguments of gemm_nt_params, which documents them (the address overrides excepted: tensors only).
+    want_colstats: if this problem's kernel has the statistics epilogue (lavt_gemm_nt_colstats_plan), the launch also stores per-row-block column
+    sums / centred second moments of the output; returns (partials, blocks, rows_per_block) then, else None."""
+    if "addr" in kw or "zeros" in kw:
+        raise TypeError("gemm_nt launches on tensors; addr= / zeros= belong to gemm_nt_params")
+    p = gemm_nt_params(dtype, M, N, Kd, A, lda, B, ldb, Cout, ldc, **kw)
     stats = None
     if want_colstats:
         rpb = C.c_int32(0)
@@ -654,8 +664,8 @@ def gemm_nt(dtype, M, N, Kd, A, lda, B, ldb, Cout, ldc, *, batch=1, strideA=0, s
             p.colstats = K.ptr(parts)
             stats = (parts, nblk, int(rpb.value))
     if K.prof.enabled:
-        K.prof.note = {"flops": 2.0 * M * N * Kd * batch, "shape": f"nt {M}x{N}x{Kd}" + (f" b{batch}" if batch > 1 else "") + (" conv" if conv is not None else "")
-                       + (" kmajor" if b_kmajor else "")}
+        K.prof.note = {"flops": 2.0 * M * N * Kd * p.batch, "shape": f"nt {M}x{N}x{Kd}" + (f" b{p.batch}" if p.batch > 1 else "") + (" conv" if p.conv_kc > 0 else "")
+                       + (" kmajor" if p.b_kmajor else "")}
     K.check(K.lib.lavt_gemm_nt(C.byref(p), K.stream()))
     return stats
 

@@ -15,9 +15,9 @@ is not gives an error of the order 1 / 1e-3; NaN / inf in an owned element is an
 
 Gate (`gate`): E(got, ref) <= K_NT[output] * F with F = E(floor, ref) of the same case.
 
-`route(case, tuning)` restates lavt_gemm_nt (csrc/gemm.hip), lavt_gemm_nt_pipe_tile / launch_pipe (csrc/gemm_nt_pipe.hip), lavt_gemm_nt_v2 and its
-launch_nt_v2_* helpers (csrc/gemm_v2.hip) and the epi_wide rule: which kernel family, tile, ring depth, K-walk mode, DACT / GD / LNA instantiation,
-lean level and store form a case takes.  Every row of the table states the route it is there for; the host test holds `route` to it."""
+`route(case, tuning)` restates the planner of the family, lavt_gemm_nt_route (csrc/gemm_nt_plan.hip), and its epi_wide rule: which kernel family,
+tile, ring depth, K-walk mode, DACT / GD / LNA instantiation, lean level and store form a case takes.  Every row of the table states the route it is
+there for; test_gemm_nt_cases_host.py holds `route` to it, and test_gemm_nt_route_host.py holds `route` to the library."""
 import collections
 import functools
 import math
@@ -139,6 +139,10 @@ class Case:
     @property
     def strideC(self):
         return self.Mo * self.ldc + self.stride_x if self.batch > 1 else 0
+
+    @property
+    def ld_side(self):     # leading dimension the tests give R, mul and dact_pre
+        return self.N + 8
 
     @property
     def nrs(self):         # row-scale entries per batch entry
@@ -371,8 +375,27 @@ def rejects(key, got, ref, flo):
     return (not same) and E > 0.0 and E >= 2.0 * K_NT[key] * nt_error(flo, ref)
 
 
+# ------------------------------------------------------------------------------------------------ the launch of a case
+def launch_args(c, buf):
+    """(args, kwargs) of lavt_hip.ops.gemm_nt / gemm_nt_params for a case.  `buf`: name -> operand, absent or None where the case has none -- A, B, C,
+    C2, Cpre, bias (at bias_off already), row_scale, R, mul, dact_pre (rows of c.ld_side elements), a_map, c_map, wsum, ln_mean, ln_rstd.  The GPU test
+    passes device tensors, the host route test made-up addresses: one statement of how a case becomes a lavt_gemm_nt_t."""
+    g = buf.get
+    dt = BF if c.dtype == "bf16" else torch.float32
+    strideA, strideB = (c.Ma * c.lda, (c.K if c.kmajor else c.N) * c.ldb) if c.batch > 1 else (0, 0)
+    ld_side = c.ld_side
+    kw = dict(batch=c.batch, strideA=strideA, strideB=strideB, strideC=c.strideC, a_rowmap=g("a_map"), b_kmajor=c.kmajor, alpha=c.alpha, bias=g("bias"),
+              strideBias=c.N if c.batch > 1 else 0, row_scale=g("row_scale"), strideRowScale=c.nrs if c.batch > 1 else 0, row_scale_div=c.row_scale_div, act=c.act,
+              Cpre=g("Cpre"), ldcpre=c.ldcpre if c.cpre else 0, R=g("R"), ldr=ld_side if c.R else 0, C2=g("C2"), ldc2=c.ldc2 if c.c_split else 0, c_split=c.c_split,
+              c_rowmap=g("c_map"), c_f32=c.c_f32, dact_pre=g("dact_pre"), lddact=ld_side if c.dact is not None else 0, dact=c.dact if c.dact is not None else 0,
+              mul=g("mul"), ldmul=ld_side if c.mul else 0, res_first=c.res_first, ln=(g("wsum"), g("ln_mean"), g("ln_rstd"), EPS) if c.ln else None)
+    return (dt, c.M, c.N, c.K, buf["A"], c.lda, buf["B"], c.ldb, buf["C"], c.ldc), kw
+
+
 # ------------------------------------------------------------------------------------------------ the dispatch, restated
-S2_MIN128, GEMM_BIG_LONG = 257, 128          # csrc/gemm_v2_helpers.h
+# The library decides all of this in ONE place, lavt_gemm_nt_route (csrc/gemm_nt_plan.hip); test_gemm_nt_route_host.py holds `route`, `epi_wide` and
+# `colstats_plan` below to its answers, row by row, so a threshold edited there and not here fails on the CPU.
+S2_MIN128, GEMM_BIG_LONG = 257, 128          # csrc/gemm_nt_plan.hip
 DEFAULT = dict(tile=0, stages=0, pipe=2)      # LAVT_GEMM_TILE / LAVT_GEMM_STAGES / LAVT_GEMM_PIPE as csrc/tuning.hip reads them
 INVALID = "invalid"
 
@@ -407,7 +430,7 @@ def _forms(c, span, bf16_kernel=True):
 
 
 def _lean(c, kmode):
-    """launch_nt_v2_ / launch_pipe_lean: epilogue instantiations without the features a launch does not use (plain and tap-walking K walks only)"""
+    """the planner's nt_lean: epilogue instantiations without the features a launch does not use (plain and tap-walking K walks only)"""
     if kmode == 0 or c.act != ACT_NONE or c.mul or c.cpre or c.c_split:
         return 0
     return 2 if not (c.bias or c.R or c.row_scale or c.c_map) else 1
@@ -425,7 +448,7 @@ def _contract_ok(c):
 
 
 def _plain_choice(c, t):
-    """(big, stages) of lavt_gemm_nt_v2 / lavt_gemm_nt_pipe_tile"""
+    """(big, stages) of the planner's nt_tile_rule with both clauses (forced configuration, long K)"""
     tiles128, tiles64 = cdiv(c.M, 128) * cdiv(c.N, 128) * c.batch, cdiv(c.M, 64) * cdiv(c.N, 64) * c.batch
     big = (t["tile"] == 128) if t["tile"] else ((tiles128 >= 200 or (c.K >= 64 * 64 and tiles128 >= GEMM_BIG_LONG)) and c.N >= 128)
     wgs = tiles128 if big else tiles64
@@ -433,7 +456,7 @@ def _plain_choice(c, t):
 
 
 def pipe_tile(c, t):
-    """lavt_gemm_nt_pipe_tile: (tile, stages) of csrc/gemm_nt_pipe.hip, or None"""
+    """the planner's nt_pipe_tile: (tile, stages) of csrc/gemm_nt_pipe.hip, or None"""
     if c.dtype != "bf16" or t["pipe"] < 1 or c.ln or c.dact is not None:
         return None
     big, stages = _plain_choice(c, t)
@@ -465,15 +488,15 @@ def route(case, tuning=None):
     p = pipe_tile(c, t)
     if p:
         return Route("pipe", p[0], p[1], kmode, "", _lean(c, kmode), _forms(c, 64 if p[0] == 256 else 32), False)
-    if c.dtype == "bf16":          # lavt_gemm_nt_v2 (the zero page is always given; lda, ldb % 8 hold by the contract)
+    if c.dtype == "bf16":          # csrc/gemm_v2.hip (the zero page is always given; lda, ldb % 8 hold by the contract)
         tiles128, tiles64 = cdiv(c.M, 128) * cdiv(c.N, 128), cdiv(c.M, 64) * cdiv(c.N, 64)
         pick = lambda a, b: (128, 2 if a >= S2_MIN128 else 4) if (a >= 200 and c.N >= 128) else (64, 2 if b >= 512 else 4)          # ignores the forced tile / stages
-        if c.ln:          # launch_nt_v2_lna
+        if c.ln:          # the LayerNorm-folded operand
             if c.kmajor or c.a_map or c.K % 64 or c.N % 4 or c.batch != 1 or c.dact is not None or not c.bias or c.alpha != 1.0:
                 return INVALID
             tile, st = pick(tiles128, tiles64)
             return Route("v2", tile, st, 1, "LNA+GD" if c.act == ACT_GELU_D else "LNA", 0, _forms(c, 32), False)
-        if c.dact is not None:          # launch_nt_v2_dact
+        if c.dact is not None:          # the fused activation gradient
             if not c.kmajor or c.K % 64 or c.N % 8 or c.c_f32 or c.c_split or c.cpre or c.act or c.mul:
                 return INVALID
             tile, st = pick(tiles128 * c.batch, tiles64 * c.batch)
@@ -589,7 +612,7 @@ DEFAULT_RULES = [
     Case("k960-v2-128", 3073, 1024, 960, route="v2/128/s4/k1/-/L1/wide", bias=True, why="the same tiles under K = 1024 stay in gemm_v2"),
 ]
 
-# the four sizes whose tile counts pick the four kernels of launch_nt_v2_dact / launch_nt_v2_lna
+# the four sizes whose tile counts pick the four kernels (tile x ring depth) of the DACT and the LNA kind
 SIZES = [(77, 136, "v2/64/s4"), (2053, 1024, "v2/64/s2"), (3190, 1024, "v2/128/s4"), (4217, 1024, "v2/128/s2")]
 
 

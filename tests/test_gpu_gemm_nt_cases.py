@@ -26,7 +26,7 @@ every instantiation of the dispatcher outside convolutions and fp8):
   * DEFAULT_RULES: 200 tiles of 128x128 at K = 1024 (the pipelined kernel at the default LAVT_GEMM_PIPE=2) and at K = 960 (gemm_v2).
   * DACT: dact_pre with GELU / RELU / TANH, each without residual, with it, and with res_first; bias, row_scale and c_rowmap present;
     LAVT_ACT_STORED in its own instantiation and (with R) in the general one; at the four sizes whose tile counts pick the four kernels of
-    launch_nt_v2_dact (77 x 136, 2053 x 1024, 3190 x 1024, 4217 x 1024), K = 64 and 192; plus the narrow form of each kernel (ldc = N + 4).
+    the planner for dact_pre (77 x 136, 2053 x 1024, 3190 x 1024, 4217 x 1024), K = 64 and 192; plus the narrow form of each kernel (ldc = N + 4).
   * LNA: the LayerNorm-folded operand at the same sizes and K: act NONE / GELU + Cpre / LAVT_ACT_GELU_D + Cpre, statistics requested and NULL, one row
     with R + row_scale + c_rowmap, one whose rows have a mean of 10 sigma, the narrow form of each kernel.
   * REFUSALS: the combinations the header declares invalid return LAVT_ERR_INVALID, set lavt_last_error and leave the outputs untouched.
@@ -103,7 +103,6 @@ class Launch:
             unused = (~used).repeat(c.batch)
         self.A = _padded(i["A"], c.lda, dt, unused)
         self.B = _padded(i["W"].transpose(1, 2) if c.kmajor else i["W"], c.ldb, dt)
-        self.strideA, self.strideB = (c.Ma * c.lda, (c.K if c.kmajor else c.N) * c.ldb) if c.batch > 1 else (0, 0)
         self.written = torch.ones(c.Mo, dtype=torch.bool)
         if c.c_map:
             self.written[:] = False
@@ -114,7 +113,7 @@ class Launch:
             b[c.bias_off:] = i["bias"].float().reshape(-1)
             self.bias = b.to(dev())[c.bias_off:]
         self.row_scale = i["row_scale"].float().contiguous().to(dev()) if c.row_scale else None
-        self.ld_side = c.N + 8
+        self.ld_side = c.ld_side
         side = lambda k: _padded(i[k], self.ld_side, dt, ~self.written) if k in i else None
         self.R, self.mul, self.dact_pre = side("R"), side("mul"), side("dact_pre")
         self.a_map = i["a_map"].to(dev()) if c.a_map else None
@@ -135,13 +134,10 @@ class Launch:
 
     def run(self):
         from lavt_hip import ops
-        c, o = self.c, self.outputs()
-        ops.gemm_nt(self.dt, c.M, c.N, c.K, self.A, c.lda, self.B, c.ldb, o["C"], c.ldc, batch=c.batch, strideA=self.strideA, strideB=self.strideB, strideC=c.strideC,
-                    a_rowmap=self.a_map, b_kmajor=c.kmajor, alpha=c.alpha, bias=self.bias, strideBias=c.N if c.batch > 1 else 0, row_scale=self.row_scale,
-                    strideRowScale=c.nrs if c.batch > 1 else 0, row_scale_div=c.row_scale_div, act=c.act, Cpre=o.get("Cpre"), ldcpre=c.ldcpre if c.cpre else 0,
-                    R=self.R, ldr=self.ld_side if c.R else 0, C2=o.get("C2"), ldc2=c.ldc2 if c.c_split else 0, c_split=c.c_split, c_rowmap=self.c_map, c_f32=c.c_f32,
-                    dact_pre=self.dact_pre, lddact=self.ld_side if c.dact is not None else 0, dact=c.dact if c.dact is not None else 0, mul=self.mul,
-                    ldmul=self.ld_side if c.mul else 0, res_first=c.res_first, ln=(self.wsum, o.get("ln_mean"), o.get("ln_rstd"), G.EPS) if c.ln else None)
+        o = self.outputs()
+        args, kw = G.launch_args(self.c, dict(o, A=self.A, B=self.B, bias=self.bias, row_scale=self.row_scale, R=self.R, mul=self.mul, dact_pre=self.dact_pre,
+                                              a_map=self.a_map, c_map=self.c_map, wsum=self.wsum))
+        ops.gemm_nt(*args, **kw)
         torch.cuda.synchronize()
         return o
 
@@ -239,14 +235,14 @@ def test_default_rules(case, monkeypatch, request):
 
 @pytest.mark.parametrize("case", G.DACT, ids=repr)
 def test_dact(case, monkeypatch, request):
-    """the fused activation gradient; the sizes pick all four kernels of launch_nt_v2_dact, which ignores the forced tile"""
+    """the fused activation gradient; the sizes pick all four kernels of its kind, whose tile rule ignores the forced tile"""
     _tuning(monkeypatch, request, {})
     check_case(case)
 
 
 @pytest.mark.parametrize("case", G.LNA, ids=repr)
 def test_lna(case, monkeypatch, request):
-    """the LayerNorm-folded A operand; the sizes pick all four kernels of launch_nt_v2_lna"""
+    """the LayerNorm-folded A operand; the sizes pick all four kernels of its kind"""
     _tuning(monkeypatch, request, {})
     check_case(case)
 

@@ -68,7 +68,7 @@ def test_struct_layout_matches_header():
     """ctypes mirrors of the parameter structs have one field per header member, in order."""
     from lavt_hip import _capi
     header = open(os.path.join(ROOT, "include", "lavt_hip.h")).read()
-    for cname, st in (("lavt_gemm_nt", _capi.GemmNT), ("lavt_gemm_tn", _capi.GemmTN)):
+    for cname, st in (("lavt_gemm_nt", _capi.GemmNT), ("lavt_gemm_tn", _capi.GemmTN), ("lavt_gemm_nt_route", _capi.GemmNTRoute)):
         body = re.search(r"typedef struct %s \{(.*?)\} %s_t;" % (cname, cname), header, re.S).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         names = []
