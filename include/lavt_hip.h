@@ -980,6 +980,26 @@ int lavt_bert_embed_bwd(int dtype, const void* dy, const int64_t* ids, const int
                         int rows, int N, int H, void* stream);
 int lavt_dropout(int dtype, const void* x, const uint8_t* keep, float scale, const void* residual, void* y, int64_t n, void* stream);
 
+/* Sentence attention: the BertSelfAttention core, softmax(q k^T / sqrt(hd) + keybias) -> dropout -> . v, fused for sentence-length sequences (new
+ * symbols only: no existing prototype or struct changed, lavt_abi_version() stays 7).
+ *   qkv      token-major [B*N][3H] in `dtype` (LAVT_BF16 / LAVT_F32), columns q | k | v, each heads x hd: the output of one GEMM over the stacked
+ *            query / key / value weights, read as it is (no head-major copy)
+ *   keybias  fp32 [B][N] = (1 - attention_mask) * -10000: a masked key is biased by -10000, not -inf, so a fully masked row is uniform over its keys
+ *            (HF's behaviour); rows of padded QUERY tokens are computed like any other
+ *   keep     uint8 [B][heads][N][N], the dropout keep mask of the probabilities (drawn by the caller), or NULL for no dropout; drop_scale = 1 / (1 - p)
+ *            multiplies the kept ones (ignored when keep is NULL; keep of all ones with drop_scale 1 gives the bits of NULL)
+ * lavt_sentence_attn_fwd writes out [B*N][H] token-major in `dtype` and nothing else (no probabilities, no scratch).
+ * lavt_sentence_attn_bwd takes the same qkv / keybias / keep and dout [B*N][H], recomputes the probabilities with the forward's own arithmetic and
+ *   writes EVERY element of dqkv [B*N][3H] in `dtype`.
+ * One workgroup per (sample, head) with all its operands in LDS as fp32; fp32 accumulation in index order, one rounding to `dtype` at the store; no
+ * atomics, no reduction across workgroups: the same bits on every run, so the kernels are their own deterministic form.
+ * Geometry: hd == 64 and 1 <= N <= 64; anything else is LAVT_ERR_INVALID with a message and no launch (the caller keeps its composed route:
+ * lavt_gemm_nt / lavt_attn_softmax_* / lavt_gemm_tn).  The backward asks for up to 99,072 bytes of LDS (N = 64). */
+int lavt_sentence_attn_fwd(int dtype, const void* qkv, const float* keybias, const uint8_t* keep, float drop_scale, void* out, int B, int N, int heads,
+                           int hd, void* stream);
+int lavt_sentence_attn_bwd(int dtype, const void* qkv, const float* keybias, const uint8_t* keep, float drop_scale, const void* dout, void* dqkv, int B,
+                           int N, int heads, int hd, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Deterministic forms (DESIGN.md "Deterministic mode"; new symbols only: no existing prototype or struct changed, lavt_abi_version() stays 7).
  * Every entry point below computes what its sibling above computes WITHOUT float atomics: the same bits on every run from the same inputs.  The

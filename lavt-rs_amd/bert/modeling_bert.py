@@ -4,7 +4,8 @@ Same constructor / `from_pretrained` / `forward(input_ids, attention_mask=None, 
 reference's call sites use (lib/_utils.py:38-52, train.py:216-218, 595-602: `BertModel.from_pretrained(args.ck_bert)`, `.pooler = None`,
 `model(sentences, attention_mask=attentions)[0]`), and the same module tree, so a HF `pytorch_model.bin` (or the `bert_model` entry of a
 LAVT checkpoint, train.py:612) loads key for key.  All arithmetic runs through lavt_hip.ops (GEMMs with fused bias / GELU / residual,
-LayerNorm, the batched masked attention, the embedding-sum and dropout kernels of csrc/text.hip); nothing falls back to torch math.
+LayerNorm, the batched masked attention or, with `fused_attention`, the sentence-attention kernels, the embedding-sum and dropout kernels of
+csrc/text.hip); nothing falls back to torch math.
 """
 import json
 import os
@@ -65,9 +66,10 @@ class BertSelfAttention(nn.Module):
         self.value = nn.Linear(config.hidden_size, config.hidden_size)
         self.dropout = nn.Dropout(config.attention_probs_dropout_prob)
 
-    def forward(self, x, keybias, B, N):
+    def forward(self, x, keybias, B, N, fused=False):
         qkv = ops.linear_cat(x, (self.query, self.key, self.value))          # one GEMM over the stacked [3H, H] weight
-        return ops.masked_self_attention(qkv, keybias, B, N, self.num_attention_heads, self.dropout.p if self.training else 0.0)
+        attend = ops.sentence_attention if fused else ops.masked_self_attention          # (BertModel.fused_attention, read at every call)
+        return attend(qkv, keybias, B, N, self.num_attention_heads, self.dropout.p if self.training else 0.0)
 
 
 class _DenseDropAddNorm(nn.Module):
@@ -98,8 +100,8 @@ class BertAttention(nn.Module):
         self.self = BertSelfAttention(config)
         self.output = BertSelfOutput(config)
 
-    def forward(self, x, keybias, B, N):
-        return self.output(self.self(x, keybias, B, N), x)
+    def forward(self, x, keybias, B, N, fused=False):
+        return self.output(self.self(x, keybias, B, N, fused), x)
 
 
 class BertIntermediate(nn.Module):
@@ -123,8 +125,8 @@ class BertLayer(nn.Module):
         self.intermediate = BertIntermediate(config)
         self.output = BertOutput(config)
 
-    def forward(self, x, keybias, B, N):
-        a = self.attention(x, keybias, B, N)
+    def forward(self, x, keybias, B, N, fused=False):
+        a = self.attention(x, keybias, B, N, fused)
         return self.output(self.intermediate(a), a)
 
 
@@ -143,20 +145,25 @@ class BertPooler(nn.Module):
 
 
 class BertModel(nn.Module):
-    def __init__(self, config=None, add_pooling_layer=True):
+    """fused_attention (a plain attribute, also a constructor / from_pretrained keyword; default False): the attention core of every layer runs as
+    ops.sentence_attention -- one kernel per direction -- instead of the composed ops.masked_self_attention.  Read at every forward, so it may be set
+    at any time before a step is captured.  With attention dropout on, the two routes draw different masks (ops.sentence_attention)."""
+
+    def __init__(self, config=None, add_pooling_layer=True, fused_attention=False):
         super().__init__()
+        self.fused_attention = bool(fused_attention)
         self.config = config if config is not None else BertConfig()
         self.embeddings = BertEmbeddings(self.config)
         self.encoder = BertEncoder(self.config)
         self.pooler = BertPooler(self.config) if add_pooling_layer else None
 
     @classmethod
-    def from_pretrained(cls, path, *unused, **unused_kw):
+    def from_pretrained(cls, path, *unused, fused_attention=False, **unused_kw):
         """`path`: a directory with config.json and pytorch_model.bin (what `args.ck_bert` points at).  There is no hub download."""
         cfg = os.path.join(str(path), "config.json")
         if not os.path.isfile(cfg):
             raise OSError(f"BertModel.from_pretrained: {path!r} is not a directory with config.json / pytorch_model.bin (no network download here)")
-        model = cls(BertConfig.from_json_file(cfg))
+        model = cls(BertConfig.from_json_file(cfg), fused_attention=fused_attention)
         wfile = os.path.join(str(path), "pytorch_model.bin")
         sfile = os.path.join(str(path), "model.safetensors")
         if os.path.isfile(wfile):
@@ -192,6 +199,6 @@ class BertModel(nn.Module):
         keybias = (1.0 - attention_mask.reshape(B, N).to(torch.float32)) * -10000.0          # get_extended_attention_mask of 3.0.2
         x = self.embeddings(input_ids, token_type_ids)
         for layer in self.encoder.layer:
-            x = layer(x, keybias, B, N)
+            x = layer(x, keybias, B, N, self.fused_attention)
         out = ops.cast_ad(x, torch.float32).view(B, N, self.config.hidden_size)
         return (out,)

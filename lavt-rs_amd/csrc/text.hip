@@ -1,7 +1,8 @@
 // Text side of lavt_one / lavt_video: the BERT-base encoder the reference builds with
 // `BertModel.from_pretrained(args.ck_bert)` (lib/_utils.py:38-52; train.py:595-602; HF transformers 3.0.2 `modeling_bert.py`).
 // Its Linear / LayerNorm / GELU / attention GEMMs run on the kernels of the visual path; this file adds what only the text side needs:
-// the embedding sum (word + position + token type) with its scatter-add backward, and inverted dropout with a caller-drawn keep mask.
+// the embedding sum (word + position + token type) with its scatter-add backward, inverted dropout with a caller-drawn keep mask, and the fused
+// attention core for sentence-length sequences (lavt_sentence_attn_fwd / _bwd: one workgroup per (sample, head), one launch per direction).
 // 20-22 tokens per sentence: latency-bound, a wave per token row, 16-byte accesses.
 #include "common.h"
 
@@ -74,9 +75,130 @@ __global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, c
     }
 }
 
+// ---- sentence attention: the BertSelfAttention core for one (sample, head) per workgroup, everything in LDS as fp32 ---------------------------------
+// qkv token-major [B*N][3H] (q | k | v, each heads x 64), N <= 64 tokens.  A wave owns a query row: lane j holds key j's score, the row's max / sum are
+// wave reductions, and the lanes turn into the 64 output columns for the value product.  Plain fp32 FMA: the problem is 20 x 20 x 64 per head.
+constexpr int SA_HD = 64;            // head_dim the kernels are written for (a lane per column)
+constexpr int SA_LDK = SA_HD + 1;    // row stride of the operands read with a lane per ROW (k, and v in the backward): odd, so 32 rows hit 32 banks
+
+__host__ __device__ constexpr size_t sattn_fwd_lds(int N) { return ((size_t)N * (2 * SA_HD + SA_LDK) + 64) * sizeof(float); }
+__host__ __device__ constexpr size_t sattn_bwd_lds(int N) { return ((size_t)N * (2 * SA_HD + 2 * SA_LDK + 2 * N) + 64) * sizeof(float); }
+
+// head h of the token rows of sample b, column block `which` (0 q, 1 k, 2 v) -> dst[n * ld + d] as fp32
+template <typename T>
+__device__ __forceinline__ void sattn_stage(const T* __restrict__ src, int64_t row_stride, float* dst, int ld, int N) {
+    for (int e = threadIdx.x; e < N * SA_HD; e += blockDim.x) {
+        const int n = e >> 6, d = e & 63;
+        dst[n * ld + d] = to_f<T>(src[n * row_stride + d]);
+    }
+}
+
+// P[i][j] for lane j of the wave that owns query row i: softmax_j(q_i . k_j / sqrt(hd) + keybias[j]).  ONE function for forward and backward, so that the
+// backward's recomputed probabilities are the forward's bits.  Lanes j >= N return 0.  A fully masked row keeps -10000 on every key (uniform), as HF does.
+__device__ __forceinline__ float sattn_prob(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ kb, int i, int j, int N,
+                                            float scale) {
+    float s = -INFINITY;
+    if (j < N) {
+        float a = 0.f;
+#pragma unroll 16
+        for (int d = 0; d < SA_HD; ++d) a = fmaf(q[i * SA_HD + d], k[j * SA_LDK + d], a);
+        s = fmaf(a, scale, kb[j]);
+    }
+    const float m = wave_max(s);
+    const float e = j < N ? expf(s - m) : 0.f;
+    return e / wave_sum(e);
+}
+
+__device__ __forceinline__ float sattn_drop(float x, const uint8_t* __restrict__ keep_row, int j, float drop_scale) {
+    return keep_row ? (keep_row[j] ? x * drop_scale : 0.f) : x;
+}
+
+template <typename T>
+__global__ __launch_bounds__(512) void sentence_attn_fwd_kernel(const T* __restrict__ qkv, const float* __restrict__ keybias, const uint8_t* __restrict__ keep,
+                                                                float drop_scale, T* __restrict__ out, int N, int heads, float scale) {
+    extern __shared__ float sa_lds[];
+    const int b = blockIdx.x / heads, h = blockIdx.x % heads, H = heads * SA_HD;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nwaves = blockDim.x >> 6;
+    float* q = sa_lds;                       // [N][64]
+    float* k = q + N * SA_HD;                // [N][65]
+    float* v = k + N * SA_LDK;               // [N][64]
+    float* kb = v + N * SA_HD;               // [64]
+    const T* base = qkv + (int64_t)b * N * 3 * H + h * SA_HD;
+    sattn_stage<T>(base, 3 * H, q, SA_HD, N);
+    sattn_stage<T>(base + H, 3 * H, k, SA_LDK, N);
+    sattn_stage<T>(base + 2 * H, 3 * H, v, SA_HD, N);
+    if (threadIdx.x < N) kb[threadIdx.x] = keybias[b * N + threadIdx.x];
+    __syncthreads();
+    for (int i = wave; i < N; i += nwaves) {
+        const float p = sattn_prob(q, k, kb, i, lane, N, scale);
+        const uint8_t* keep_row = keep ? keep + ((int64_t)blockIdx.x * N + i) * N : nullptr;
+        const float pd = lane < N ? sattn_drop(p, keep_row, lane, drop_scale) : 0.f;
+        float o = 0.f;
+        for (int j = 0; j < N; ++j) o = fmaf(__shfl(pd, j, 64), v[j * SA_HD + lane], o);          // lane = output column
+        out[((int64_t)b * N + i) * H + h * SA_HD + lane] = from_f<T>(o);
+    }
+}
+
+// dqkv of the same (sample, head): P is recomputed (sattn_prob), dP = dO V^T through the dropout mask, dS = P (dP - sum_j dP P); then
+// dQ = dS K / sqrt(hd), dK = dS^T Q / sqrt(hd), dV = Pd^T dO with a wave per output row and a lane per column.  Every sum runs in index order.
+template <typename T>
+__global__ __launch_bounds__(512) void sentence_attn_bwd_kernel(const T* __restrict__ qkv, const float* __restrict__ keybias, const uint8_t* __restrict__ keep,
+                                                                float drop_scale, const T* __restrict__ dout, T* __restrict__ dqkv, int N, int heads,
+                                                                float scale) {
+    extern __shared__ float sa_lds[];
+    const int b = blockIdx.x / heads, h = blockIdx.x % heads, H = heads * SA_HD;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nwaves = blockDim.x >> 6;
+    float* q = sa_lds;                       // [N][64]
+    float* k = q + N * SA_HD;                // [N][65]
+    float* v = k + N * SA_LDK;               // [N][65]
+    float* dO = v + N * SA_LDK;              // [N][64]
+    float* dS = dO + N * SA_HD;              // [N][N]
+    float* Pd = dS + N * N;                  // [N][N]   P after dropout
+    float* kb = Pd + N * N;                  // [64]
+    const T* base = qkv + (int64_t)b * N * 3 * H + h * SA_HD;
+    sattn_stage<T>(base, 3 * H, q, SA_HD, N);
+    sattn_stage<T>(base + H, 3 * H, k, SA_LDK, N);
+    sattn_stage<T>(base + 2 * H, 3 * H, v, SA_LDK, N);
+    sattn_stage<T>(dout + (int64_t)b * N * H + h * SA_HD, H, dO, SA_HD, N);
+    if (threadIdx.x < N) kb[threadIdx.x] = keybias[b * N + threadIdx.x];
+    __syncthreads();
+    for (int i = wave; i < N; i += nwaves) {
+        const float p = sattn_prob(q, k, kb, i, lane, N, scale);
+        const uint8_t* keep_row = keep ? keep + ((int64_t)blockIdx.x * N + i) * N : nullptr;
+        float dp = 0.f;
+        if (lane < N) {
+            float a = 0.f;
+#pragma unroll 16
+            for (int d = 0; d < SA_HD; ++d) a = fmaf(dO[i * SA_HD + d], v[lane * SA_LDK + d], a);
+            dp = sattn_drop(a, keep_row, lane, drop_scale);
+        }
+        const float delta = wave_sum(dp * p);
+        if (lane < N) {
+            dS[i * N + lane] = p * (dp - delta);
+            Pd[i * N + lane] = sattn_drop(p, keep_row, lane, drop_scale);
+        }
+    }
+    __syncthreads();
+    T* gbase = dqkv + (int64_t)b * N * 3 * H + h * SA_HD;
+    for (int t = wave; t < 3 * N; t += nwaves) {
+        const int which = t / N, r = t - which * N;
+        float a = 0.f;
+        if (which == 0) {
+            for (int j = 0; j < N; ++j) a = fmaf(dS[r * N + j], k[j * SA_LDK + lane], a);
+            a *= scale;
+        } else if (which == 1) {
+            for (int i = 0; i < N; ++i) a = fmaf(dS[i * N + r], q[i * SA_HD + lane], a);
+            a *= scale;
+        } else {
+            for (int i = 0; i < N; ++i) a = fmaf(Pd[i * N + r], dO[i * SA_HD + lane], a);
+        }
+        gbase[(int64_t)r * 3 * H + which * H + lane] = from_f<T>(a);
+    }
+}
+
 }  // namespace
 
-#define DISPATCH_T(dtype, NAME, ...)                                   \
+#define DISPATCH_T(dtype, NAME, ...)                                 \
     if (dtype == LAVT_F32) { using T = float; __VA_ARGS__; }           \
     else if (dtype == LAVT_BF16) { using T = bf16; __VA_ARGS__; }      \
     else { lavt_set_error(NAME ": bad dtype %d", dtype); return LAVT_ERR_INVALID; }
@@ -103,6 +225,50 @@ extern "C" int lavt_bert_embed_bwd_det(int dtype, const void* dy, const int64_t*
     LAVT_CHECK_ARG(dy && ids && dword && dpos && dtype_ && rows > 0 && N > 0 && H > 0, "lavt_bert_embed_bwd_det: bad arguments");
     DISPATCH_T(dtype, "lavt_bert_embed_bwd_det", hipLaunchKernelGGL(bert_embed_bwd_det_kernel<T>, dim3(rows, 3), dim3(256), 0, ST, (const T*)dy, ids, token_type, dword, dpos, dtype_, rows, N, H));
     LAVT_CHECK_LAUNCH("lavt_bert_embed_bwd_det");
+    return LAVT_OK;
+}
+
+// the geometry the sentence-attention kernels are written for; everything else is the caller's composed route (lavt_hip.ops.sentence_attention)
+#define SATTN_CHECK(NAME, ...)                                                                                                                   \
+    LAVT_CHECK_ARG(__VA_ARGS__, NAME ": bad arguments");                                                                                         \
+    LAVT_CHECK_ARG(hd == SA_HD && N >= 1 && N <= 64, NAME ": head_dim %d, %d tokens: the kernel covers head_dim 64 and 1..64 tokens", hd, N);    \
+    LAVT_CHECK_ARG(B >= 1 && heads >= 1 && (int64_t)B * heads <= 0x7fffffff, NAME ": B = %d, heads = %d", B, heads)
+
+extern "C" int lavt_sentence_attn_fwd(int dtype, const void* qkv, const float* keybias, const uint8_t* keep, float drop_scale, void* out, int B, int N,
+                                      int heads, int hd, void* stream) {
+    SATTN_CHECK("lavt_sentence_attn_fwd", qkv && keybias && out);
+    const size_t lds = sattn_fwd_lds(N);          // <= 49,664 bytes
+    const float scale = 0.125f;                   // 1 / sqrt(64)
+    DISPATCH_T(dtype, "lavt_sentence_attn_fwd", hipLaunchKernelGGL(sentence_attn_fwd_kernel<T>, dim3(B * heads), dim3(512), lds, ST, (const T*)qkv, keybias, keep,
+                                                                   drop_scale, (T*)out, N, heads, scale));
+    LAVT_CHECK_LAUNCH("lavt_sentence_attn_fwd");
+    return LAVT_OK;
+}
+
+template <typename T>
+static int sattn_bwd_launch(const void* qkv, const float* keybias, const uint8_t* keep, float drop_scale, const void* dout, void* dqkv, int B, int N, int heads,
+                            hipStream_t st) {
+    const size_t lds = sattn_bwd_lds(N);          // 99,072 bytes at N = 64: past 64 KB (N >= 48) the kernel needs the attribute, as attention_mfma.hip's do
+    static size_t reserved = 0;
+    if (lds > 65536 && lds > reserved) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sentence_attn_bwd_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+            lavt_set_error("lavt_sentence_attn_bwd: cannot reserve %zu bytes of LDS", lds);
+            return LAVT_ERR_LAUNCH;
+        }
+        reserved = lds;
+    }
+    hipLaunchKernelGGL(sentence_attn_bwd_kernel<T>, dim3(B * heads), dim3(512), lds, st, (const T*)qkv, keybias, keep, drop_scale, (const T*)dout, (T*)dqkv, N, heads,
+                       0.125f);
+    return LAVT_OK;
+}
+
+extern "C" int lavt_sentence_attn_bwd(int dtype, const void* qkv, const float* keybias, const uint8_t* keep, float drop_scale, const void* dout, void* dqkv,
+                                      int B, int N, int heads, int hd, void* stream) {
+    SATTN_CHECK("lavt_sentence_attn_bwd", qkv && keybias && dout && dqkv);
+    int rc = LAVT_OK;
+    DISPATCH_T(dtype, "lavt_sentence_attn_bwd", rc = sattn_bwd_launch<T>(qkv, keybias, keep, drop_scale, dout, dqkv, B, N, heads, ST));
+    if (rc != LAVT_OK) return rc;
+    LAVT_CHECK_LAUNCH("lavt_sentence_attn_bwd");
     return LAVT_OK;
 }
 

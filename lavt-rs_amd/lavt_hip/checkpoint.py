@@ -139,6 +139,9 @@ def load_lavt2d_into_video(video_model, filename, drop_fusion=False, map_locatio
 # ------------------------------------------------------------------------------------------------ training state (engine.TrainStep)
 TRAIN_STATE_FORMAT = 1
 TRAIN_STATE_KEYS = ("model", "optimizer", "lavt_train_state")
+# one more top-level entry, exactly when the step trains a separate text encoder (TrainStep(text_encoder=)): its state_dict() under the reference's key
+# (train.py:612, 752-757).  Not in TRAIN_STATE_KEYS: a step without encoder writes the three keys above and nothing else.
+TEXT_ENCODER_KEY = "bert_model"
 # the fields of the fingerprint, in the order they are compared
 CONFIG_FIELDS = ("criterion", "dice_rate", "boundary_rate", "accumulate", "amsgrad", "max_grad_norm", "skip_nonfinite", "deterministic", "compute_dtype",
                  "fp8", "world", "param_groups")
@@ -245,13 +248,17 @@ def save_train_state(path, step, **extra):
     for k in extra:
         if k in TRAIN_STATE_KEYS:
             raise ValueError(f"save_train_state: '{k}' is written by the step itself")
+        if k == TEXT_ENCODER_KEY:
+            raise ValueError(f"save_train_state: '{k}' is the entry of a step that trains its text encoder (TrainStep(text_encoder=) writes it itself; "
+                             "a step without one would refuse the file)")
     state = step.state_dict()
     state.update(extra)
     write_atomic(path, state)
 
 
 def load_train_state(path, step):
-    """Read a file of save_train_state into `step` (TrainStep.load_state_dict: after warmup_and_capture(), in place) -> the extra keys"""
+    """Read a file of save_train_state into `step` (TrainStep.load_state_dict: after warmup_and_capture(), in place) -> the extra keys (the text
+    encoder's 'bert_model' entry is the step's, not metadata)"""
     state = torch.load(os.fspath(path), map_location="cpu", weights_only=True)
     step.load_state_dict(state)
-    return {k: v for k, v in state.items() if k not in TRAIN_STATE_KEYS}
+    return {k: v for k, v in state.items() if k not in TRAIN_STATE_KEYS and k != TEXT_ENCODER_KEY}

@@ -39,6 +39,13 @@ and the update's verdict of every step() into a ring on the device and moves the
 them with TrainMeters.poll(), which never waits.  The launch reads `meter_stats`, an fp32[4] row {loss, ., I, U}: under loss="ce" the criterion's own `stats`;
 under "mc_dice" / "dice_boundary", whose `stats` hold no argmax counts, the row of lib._utils.fused_iu -- one more kernel pair behind the criterion's forward.
 Off by default: a step built without meters launches what it launched before, for every criterion.
+
+The separate text encoder of `--model lavt` (TrainStep(text_encoder=bert_model); DESIGN.md "Text encoder in the step"): the reference computes the language
+features in every iteration, lets gradients flow back into `bert_model`, updates its encoder layers 0..9 with the same AdamW and saves it as the checkpoint's
+'bert_model' entry (train.py:217-221, 612, 623-632, 752-757).  With the argument the static language buffers hold token ids and the attention mask, the body
+starts with the encoder's forward, and everything the step owns spans both modules: the flat gradient buffer and its buckets, the zero fill, the all-reduce
+sequence, the weight-copy refresh and stamp, make_optimizer()'s groups, the names handed out ('bert_model.' + the encoder's own) and the checkpoint.
+None (the default): the step as it is without the argument.
 """
 import os
 import sys
@@ -48,6 +55,7 @@ import torch.nn.functional as F
 
 from . import ops
 from . import _capi as K
+from .checkpoint import TEXT_ENCODER_KEY
 from .ddp import GradBuckets
 from .runtime import compute_dtype, fp8_enabled
 
@@ -209,9 +217,48 @@ class _BatchInput:
         self.commit_batch()
 
 
+TEXT_ENCODER_PREFIX = TEXT_ENCODER_KEY + "."          # 'bert_model.': the encoder's parameters wherever a step names parameters; 'bert_model' is the reference's checkpoint key (train.py:612)
+
+
+class _StepModules(torch.nn.Module):
+    """The two trainable modules of `--model lavt` as ONE module for GradBuckets and for every name the step hands out: the model's parameters under
+    their own names, the separate text encoder's under 'bert_model.'.  The encoder comes first: its gradients are the last that backward produces, and
+    GradBuckets lays the flat buffer out in reverse registration order."""
+
+    def __init__(self, model, text_encoder):
+        super().__init__()
+        self.bert_model = text_encoder
+        self.model = model
+
+    def named_parameters(self, prefix="", recurse=True, remove_duplicate=True):
+        yield from self.bert_model.named_parameters(prefix=prefix + TEXT_ENCODER_PREFIX[:-1], recurse=recurse, remove_duplicate=remove_duplicate)
+        yield from self.model.named_parameters(prefix=prefix, recurse=recurse, remove_duplicate=remove_duplicate)
+
+
+def _check_text_encoder(model, image, l_feats, l_mask, text_encoder, valid_indices):
+    """the refusals of TrainStep(text_encoder=), before anything is built"""
+    if valid_indices is not None:
+        raise ValueError("TrainStep: text_encoder cannot be combined with valid_indices (the clip models carry their own encoder: LAVTVideo.text_encoder)")
+    for name, t in (("l_feats", l_feats), ("l_mask", l_mask)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 2:
+            what = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"TrainStep: with text_encoder the step computes the language features itself: {name} must be the static int64 (B, N_l) buffer of "
+                             f"{'token ids' if name == 'l_feats' else 'the attention mask'}, got {what}" + (" (precomputed features belong to a step without text_encoder)"
+                                                                                                              if name == "l_feats" and isinstance(t, torch.Tensor) and t.dtype.is_floating_point else ""))
+    if tuple(l_feats.shape) != tuple(l_mask.shape):
+        raise ValueError(f"TrainStep: l_feats (token ids) is {tuple(l_feats.shape)}, l_mask (attention mask) {tuple(l_mask.shape)}")
+    devs = {p.device for p in text_encoder.parameters()}
+    if devs != {image.device}:
+        raise ValueError(f"TrainStep: text_encoder lives on {sorted(str(d) for d in devs)}, the step's buffers on {image.device}")
+    if model.training and not text_encoder.training:
+        raise ValueError("TrainStep: text_encoder is in eval mode while the model trains (the reference calls bert_model.train() beside model.train(): its dropout "
+                         "is part of the iteration); call text_encoder.train()")
+
+
 class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
     def __init__(self, model, image, l_feats, l_mask, target, world=1, use_graph=True, bucket_mib=32.0, fused_loss=True, refresh_weights_in_step=False, context=None,
-                 *, loss="ce", valid_indices=None, dice_rate=1.0, boundary_rate=0.05, deterministic=None, accumulate=1, meters=None, image_of=None):
+                 *, loss="ce", valid_indices=None, dice_rate=1.0, boundary_rate=0.05, deterministic=None, accumulate=1, meters=None, image_of=None,
+                 text_encoder=None):
         """context: the ops.StepContext this harness keeps its state in (gradient sinks, deferred-launch queues, weight copies, scratch).  None = the
         process-wide default context -- what the drop-in path and a single harness use.  Give every further model in the process its own
         `ops.StepContext()` (and its optimizer the same one: FusedAdamW(..., context=)): their steps can then alternate freely.
@@ -239,7 +286,15 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
         and sums the slots' gradients per image (ascending slot order, fp32, no atomics: the same kernel in deterministic mode); everything behind runs
         on N samples, and loss, `stats` and the meters cover the N slots.  Fill it with set_image_of(pairs), before capture or between replays: every
         entry names one of the B images (no empty slots in training).  Needs a fused criterion and a backbone that shares stage 0; cannot be combined
-        with valid_indices.  None (the default): the launches of a step built without the argument."""
+        with valid_indices.  None (the default): the launches of a step built without the argument.
+        text_encoder: the separate `bert_model` of `--model lavt` (train.py:595-602), trained INSIDE the step.  l_feats / l_mask are then the static int64
+        (B, N_l) buffers of token ids and attention mask (N expressions under image_of), and the body starts with train.py:217-221 literally:
+        `l = text_encoder(ids, attention_mask=mask)[0].permute(0, 2, 1)`, `m = mask.unsqueeze(-1)`.  Everything the step owns spans both modules: one flat
+        gradient buffer and one bucket sequence, one zero fill; the encoder's parameters are named 'bert_model.<name>' wherever names appear (gradient norms,
+        last_nonfinite(), the fingerprint, fp8 sites); make_optimizer() builds the reference's groups with the encoder's (train.py:623-632: encoder layers
+        0..9 -- the other encoder parameters receive gradients and no update); state_dict() carries the reference's 'bert_model' entry.  Set
+        text_encoder.fused_attention = True for the one-kernel attention core (bert/modeling_bert.py).  ValueError for floating-point l_feats, an encoder on
+        another device or in eval mode while the model trains, or together with valid_indices.  None (the default): the step as it is without the argument."""
         import operator
         try:
             k = operator.index(accumulate)
@@ -250,6 +305,9 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
         self.accumulate = k
         if loss not in ("ce", "mc_dice", "dice_boundary"):
             raise ValueError(f"TrainStep: loss must be 'ce', 'mc_dice' or 'dice_boundary', got {loss!r}")
+        if text_encoder is not None:
+            _check_text_encoder(model, image, l_feats, l_mask, text_encoder, valid_indices)
+        self.text_encoder = text_encoder
         if image_of is not None:
             if valid_indices is not None:
                 raise ValueError("TrainStep: image_of (pair-list batches) cannot be combined with valid_indices (annotated frames of clips)")
@@ -280,7 +338,9 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
         # 32 MiB: the bucket that holds the earliest layers is reduced after backward has ended -- its all-reduce is the exposed tail of the step
         # (64 MiB ~ 0.4-0.8 ms over xGMI), while ~15 collectives of this size still run at full ring bandwidth.  LAVT_BUCKET_MIB overrides.
         bucket_mib = float(os.environ.get("LAVT_BUCKET_MIB", bucket_mib))
-        self.buckets = GradBuckets(model, bucket_mib=bucket_mib, fused_accumulation=True)
+        # what the step trains, as one module: the model itself, or the model and the separate text encoder (its names prefixed 'bert_model.')
+        self.trained = model if self.text_encoder is None else _StepModules(model, self.text_encoder)
+        self.buckets = GradBuckets(self.trained, bucket_mib=bucket_mib, fused_accumulation=True)
         self.world = world
         self.graph = None
         self.loss = None
@@ -300,7 +360,7 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
         # the parameters' version counters / storage addresses with what the compute copies were made from and re-casts them (eagerly, in front of
         # the replay) when anything but FusedAdamW has touched them: torch.optim optimizers, load_state_dict, manual edits all bump p._version.
         # FusedAdamW writes through raw pointers (versions do not move) and refreshes the copies itself.
-        self._params = [p for p in model.parameters()]
+        self._params = [p for p in self.trained.parameters()]
         self._seen = None
         self._one = None
         self.opt = None                          # the owned optimizer (make_optimizer / attach_optimizer): its step ends _body
@@ -324,17 +384,19 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
         self.context.deterministic = mode
 
     # ---- owned optimizer ----
-    def make_optimizer(self, param_groups=None, **adamw_kwargs):
-        """Build a FusedAdamW on THIS step's context, attach it and return it.  param_groups=None: lavt_param_groups(model) when the model has a
-        `backbone` and a `classifier` (the reference's groups), else all its parameters.  adamw_kwargs go to FusedAdamW (lr, weight_decay,
+    def make_optimizer(self, param_groups=None, *, text_encoder_layers=10, lang_enc_params="encoder-10", **adamw_kwargs):
+        """Build a FusedAdamW on THIS step's context, attach it and return it.  param_groups=None: lavt_param_groups(model, text_encoder=the step's) when
+        the model has a `backbone` and a `classifier` (the reference's groups; text_encoder_layers / lang_enc_params choose the language encoder's, as
+        `--lang_enc_params` does), else all parameters the step trains.  adamw_kwargs go to FusedAdamW (lr, weight_decay,
         total_steps, power, max_grad_norm, skip_nonfinite, amsgrad, ...).  Before warmup_and_capture() only."""
         from .optim import FusedAdamW, lavt_param_groups
         self._check_attach_window()
         if "context" in adamw_kwargs:
             raise TypeError("TrainStep.make_optimizer: the optimizer is built on the step's own context")
         if param_groups is None:
-            param_groups = (lavt_param_groups(self.model) if hasattr(self.model, "backbone") and hasattr(self.model, "classifier")
-                            else [p for p in self.model.parameters() if p.requires_grad])
+            param_groups = (lavt_param_groups(self.model, text_encoder_layers, lang_enc_params=lang_enc_params, text_encoder=self.text_encoder)
+                            if hasattr(self.model, "backbone") and hasattr(self.model, "classifier")
+                            else [p for p in self.trained.parameters() if p.requires_grad])
         return self.attach_optimizer(FusedAdamW(param_groups, context=self.context, **adamw_kwargs))
 
     def attach_optimizer(self, opt):
@@ -394,10 +456,16 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
             return
         self.opt.reset_phase()
 
+    text_encoder = None               # the separate `bert_model` the step trains beside the model (TrainStep(text_encoder=)); None = the model alone
+
+    def _named_parameters(self):
+        """(name, parameter) of everything the step trains: the model's own names, the text encoder's prefixed 'bert_model.'"""
+        return self.model.named_parameters() if self.text_encoder is None else self.trained.named_parameters()
+
     # ---- checkpoint and resume (DESIGN.md "Checkpoint and resume") ----
     def _config(self):
         """the fingerprint a checkpoint is compared by (checkpoint.CONFIG_FIELDS): what decides the captured launch sequence and the layout of the state"""
-        names = {id(p): n for n, p in self.model.named_parameters()}
+        names = {id(p): n for n, p in self._named_parameters()}
         dtype, fp8 = self._dtype if self._dtype is not None else (compute_dtype(), fp8_enabled())
         groups = [[[names.get(id(p), f"<group {gi} entry {pi}: not a parameter of the model>"), [int(s) for s in p.shape]] for pi, p in enumerate(g["params"])]
                   for gi, g in enumerate(self.opt.param_groups)]
@@ -408,7 +476,7 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
 
     def _acc_layout(self):
         """[name, offset] of every parameter's gradient in the flat buffer `acc` mirrors, in offset order"""
-        names = {id(p): n for n, p in self.model.named_parameters()}
+        names = {id(p): n for n, p in self._named_parameters()}
         return sorted(([names.get(id(p), "?"), int(self.buckets.offset_of[id(p)])] for p in self.buckets.params), key=lambda e: e[1])
 
     def _fp8_sites(self):
@@ -417,7 +485,7 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
         f8 = self.context.fp8
         if not self._config()["fp8"] or f8.prev is None:
             return {}
-        return fp8_site_slots(f8.slots, {id(p): n for n, p in self.model.named_parameters()})
+        return fp8_site_slots(f8.slots, {id(p): n for n, p in self._named_parameters()})
 
     def _needs_owned_optimizer(self, who):
         if self.opt is None:
@@ -437,6 +505,7 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
           'lavt_train_state'  format, config (the fingerprint load_state_dict compares), guard (the optimizer's control block; hold saved as 0), acc (+
                               its layout; only inside a cycle, micro_step() != 0 -- at a boundary it is dead), droppath (ops.droppath_state_dict() of the
                               step's context), fp8 ({'<consuming parameter>|act' or '|dy': [prev, cur]}; {} without fp8), torch_cuda_rng.
+          'bert_model'        text_encoder.state_dict() -- the reference's key (train.py:612) -- exactly when the step has a text encoder
         Not state: gradients, the static input buffers, compute copies (re-made from the parameters), scratch.  checkpoint.save_train_state writes it."""
         from .checkpoint import TRAIN_STATE_FORMAT, to_host
         self._needs_owned_optimizer("TrainStep.state_dict")
@@ -453,7 +522,10 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
         if sites:
             prev, cur = self.context.fp8.prev.cpu(), self.context.fp8.cur.cpu()
             train["fp8"] = {n: torch.stack([prev[i], cur[i]]) for n, i in sites.items()}
-        return {"model": to_host(self.model.state_dict()), "optimizer": to_host(self.opt.state_dict()), "lavt_train_state": train}
+        state = {"model": to_host(self.model.state_dict()), "optimizer": to_host(self.opt.state_dict()), "lavt_train_state": train}
+        if self.text_encoder is not None:          # the reference's key (train.py:612, 752-757): single_bert_model.load_state_dict(ckpt['bert_model'])
+            state[TEXT_ENCODER_KEY] = to_host(self.text_encoder.state_dict())
+        return state
 
     @_in_context
     def load_state_dict(self, state):
@@ -477,16 +549,21 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
         train = state["lavt_train_state"]
         if train.get("format") != TRAIN_STATE_FORMAT:
             raise ValueError(f"{who}: format {train.get('format')!r} of 'lavt_train_state' is not {TRAIN_STATE_FORMAT}")
+        if (TEXT_ENCODER_KEY in state) != (self.text_encoder is not None):
+            raise ValueError(f"{who}: " + (f"this step trains a text encoder (TrainStep(text_encoder=)) and the checkpoint has no '{TEXT_ENCODER_KEY}' entry"
+                                           if self.text_encoder is not None else
+                                           f"the checkpoint has a '{TEXT_ENCODER_KEY}' entry (it was written by a step with text_encoder=) and this step has no text encoder"))
         compare_fingerprints(train["config"], self._config(), who)
-        own = self.model.state_dict()
-        for k, v in state["model"].items():
-            if k not in own:
-                raise ValueError(f"{who}: 'model' has an entry {k} that this model does not have")
-            if tuple(v.shape) != tuple(own[k].shape):
-                raise ValueError(f"{who}: 'model' entry {k} is {tuple(v.shape)} in the checkpoint, {tuple(own[k].shape)} in this model")
-        for k in own:
-            if k not in state["model"]:
-                raise ValueError(f"{who}: 'model' has no entry {k}")
+        for key, module in (("model", self.model),) + (((TEXT_ENCODER_KEY, self.text_encoder),) if self.text_encoder is not None else ()):
+            own = module.state_dict()
+            for k, v in state[key].items():
+                if k not in own:
+                    raise ValueError(f"{who}: '{key}' has an entry {k} that this {'model' if key == 'model' else 'text encoder'} does not have")
+                if tuple(v.shape) != tuple(own[k].shape):
+                    raise ValueError(f"{who}: '{key}' entry {k} is {tuple(v.shape)} in the checkpoint, {tuple(own[k].shape)} in this {'model' if key == 'model' else 'text encoder'}")
+            for k in own:
+                if k not in state[key]:
+                    raise ValueError(f"{who}: '{key}' has no entry {k}")
         plan = self.opt.check_state_dict_in_place(state["optimizer"])
         guard, acc = train.get("guard"), train.get("acc")
         self.opt.check_control_state(guard, who)
@@ -504,6 +581,8 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
         torch.cuda.synchronize(dev)
         with torch.no_grad():
             self.model.load_state_dict(state["model"], strict=True)          # copies into the parameters and buffers
+            if self.text_encoder is not None:
+                self.text_encoder.load_state_dict(state[TEXT_ENCODER_KEY], strict=True)
             self.opt.load_state_dict_in_place(state["optimizer"], plan)
             self.opt.load_control_state(guard, keep_phase=acc is not None)
             if acc is not None:
@@ -524,6 +603,12 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
     def _param_stamp(self):
         return sum(p._version for p in self._params), sum(p.data_ptr() for p in self._params)
 
+    def _language(self):
+        """(l_feats, l_mask) as the model takes them: the static buffers, or -- with a text encoder -- train.py:217-221 on the id / attention-mask buffers"""
+        if self.text_encoder is None:
+            return self.l, self.m
+        return self.text_encoder(self.l, attention_mask=self.m)[0].permute(0, 2, 1), self.m.unsqueeze(-1)
+
     @_in_context
     def _body(self):
         if self.acc is not None and (self.opt is None or self.opt._grad_source is None):
@@ -537,7 +622,8 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
             ops.fp8.advance()                    # delayed scaling: last step's |max| values become this step's quantisation scales
         if self.fused_loss:                       # upsample + criterion fused: the (B,2,H,W) logits are never written
             from lib._utils import fused_dice_boundary_loss, fused_dice_loss, fused_iu, fused_loss
-            y = self.model.forward_lowres(self.x, self.l, self.m) if self.image_of is None else self.model.forward_lowres(self.x, self.l, self.m, image_of=self.image_of)
+            l, m = self._language()
+            y = self.model.forward_lowres(self.x, l, m) if self.image_of is None else self.model.forward_lowres(self.x, l, m, image_of=self.image_of)
             if self.criterion == "ce":
                 loss, self.stats = fused_loss(y, self.t, (0.9, 1.1), valid_indices=self.valid_indices)
                 self.meter_stats = self.stats    # the cross-entropy pair counts the hard-mask I / U itself (stats[2:4])
@@ -550,7 +636,7 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
                 # one more kernel pair directly behind the criterion's forward (train.py:64-76 whatever --loss is); an unmetered step launches nothing
                 self.meter_stats = fused_iu(y, self.t, valid_indices=self.valid_indices, loss=self.stats) if self.meters is not None else None
         else:
-            out = self.model(self.x, self.l, self.m)
+            out = self.model(self.x, *self._language())
             if self.valid_indices is not None:
                 out = torch.index_select(out, 0, self.valid_indices)          # train.py:284, literally
             if self.criterion == "ce":
@@ -678,7 +764,7 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
             bad = [by_start[v.data_ptr()] for v, f in zip(self.buckets._skip_views, flags) if f]
             cand -= {id(p) for p in bad}
             if os.environ.get("LAVT_ZERO_SKIP_VERBOSE"):
-                names = {id(p): n for n, p in self.model.named_parameters()}
+                names = {id(p): n for n, p in self._named_parameters()}
                 print(f"[lavt_hip.engine] zero-fill skip: {len(bad)} candidates are accumulated into or not fully written (e.g. {', '.join(names.get(id(p), '?') for p in bad[:4])}); "
                       "they stay in the fill, capturing again", file=sys.stderr)
             self.graph = None

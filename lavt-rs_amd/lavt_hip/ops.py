@@ -2581,6 +2581,59 @@ def masked_self_attention(qkv, keybias, B, N, heads, p_drop=0.0):
     return _MaskedSelfAttn.apply(qkv, keybias, B, N, heads, float(p_drop))
 
 
+def sentence_attention_ok(N, hd):
+    """the geometry lavt_sentence_attn_fwd / _bwd cover (include/lavt_hip.h): a lane per column of a 64-wide head, a lane per key of <= 64 tokens"""
+    return hd == 64 and 1 <= N <= 64
+
+
+@K.scoped
+class _SentenceAttn(torch.autograd.Function):
+    """The same core as _MaskedSelfAttn as ONE launch per direction (csrc/text.hip): qkv is read token-major as linear_cat wrote it, out / dqkv are
+    written token-major, the probabilities are recomputed in the backward -- nothing is saved but qkv, keybias and the keep mask."""
+
+    @staticmethod
+    def forward(ctx, qkv, keybias, B, N, heads, drop_scale, keep):
+        qkv, keybias = qkv.contiguous(), keybias.contiguous()
+        H = qkv.shape[1] // 3
+        out = torch.empty(B * N, H, dtype=qkv.dtype, device=qkv.device)
+        K.check(K.lib.lavt_sentence_attn_fwd(K.dt(qkv.dtype), K.ptr(qkv), K.ptr(keybias), K.ptr(keep), drop_scale, K.ptr(out), B, N, heads, H // heads, K.stream()))
+        ctx.save_for_backward(qkv, keybias, keep)
+        ctx.dims = (B, N, heads, H // heads, drop_scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, keybias, keep = ctx.saved_tensors
+        B, N, heads, hd, drop_scale = ctx.dims
+        dout = dout.contiguous()
+        dqkv = torch.empty_like(qkv)
+        K.check(K.lib.lavt_sentence_attn_bwd(K.dt(qkv.dtype), K.ptr(qkv), K.ptr(keybias), K.ptr(keep), drop_scale, K.ptr(dout), K.ptr(dqkv), B, N, heads, hd, K.stream()))
+        return dqkv, None, None, None, None, None, None
+
+
+def sentence_attention(qkv, keybias, B, N, heads, p_drop=0.0, keep=None):
+    """masked_self_attention for sentence-length sequences, fused: one kernel forward, one backward (lavt_sentence_attn_fwd / _bwd), no atomics -- the
+    same bits from run to run, so it is its own deterministic form.  qkv [B*N, 3H] and keybias fp32 [B, N] as for masked_self_attention.
+    keep: the uint8 [B, heads, N, N] keep mask of the probabilities, kept ones scaled by 1 / (1 - p_drop); None with p_drop > 0 draws it with torch's
+    generator (bernoulli_, as the composed route does: torch.manual_seed and a checkpoint's torch_cuda_rng govern it).  The mask has B*heads*N*N
+    entries where the composed route draws its padded B*heads*Np*Np: the two routes consume DIFFERENT random streams, so with dropout on they agree in
+    distribution, not sample by sample.
+    Outside sentence_attention_ok (head_dim 64, <= 64 tokens) this IS masked_self_attention(qkv, keybias, B, N, heads, p_drop): a caller's keep mask
+    cannot be honoured there and is refused."""
+    hd = qkv.shape[1] // (3 * heads)
+    if not sentence_attention_ok(N, hd):
+        if keep is not None:
+            raise ValueError(f"sentence_attention: a caller-drawn keep mask needs the fused geometry (head_dim 64, <= 64 tokens), got head_dim {hd}, {N} tokens")
+        return masked_self_attention(qkv, keybias, B, N, heads, p_drop)
+    if keep is None and p_drop > 0.0:
+        keep = torch.empty(B, heads, N, N, dtype=torch.uint8, device=qkv.device).bernoulli_(1.0 - p_drop)
+    if keep is not None:
+        if keep.dtype != torch.uint8 or tuple(keep.shape) != (B, heads, N, N):
+            raise ValueError(f"sentence_attention: keep must be uint8 {(B, heads, N, N)}, got {keep.dtype} {tuple(keep.shape)}")
+        keep = keep.contiguous()
+    return _SentenceAttn.apply(qkv, keybias, B, N, heads, 1.0 / (1.0 - p_drop) if keep is not None else 1.0, keep)
+
+
 # ------------------------------------------------------------------------------------------ layout changes
 @K.scoped
 class _Transpose(torch.autograd.Function):

@@ -284,7 +284,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if self._tn is None:
             raise RuntimeError("FusedAdamW: per-tensor norms exist with tensor_norms=True, after the first step()")
         owner = self._owner_step()
-        names = {id(p): k for k, p in owner.model.named_parameters()} if owner is not None else {}
+        names = {id(p): k for k, p in owner._named_parameters()} if owner is not None else {}
         return [names.get(id(p), i) for i, p in enumerate(self._tn[2])]
 
     def grad_norms(self):
