@@ -17,7 +17,9 @@ Gate (`gate`): E(got, ref) <= K_NT[output] * F with F = E(floor, ref) of the sam
 
 `route(case, tuning)` restates the planner of the family, lavt_gemm_nt_route (csrc/gemm_nt_plan.hip), and its epi_wide rule: which kernel family,
 tile, ring depth, K-walk mode, DACT / GD / LNA instantiation, lean level and store form a case takes.  Every row of the table states the route it is
-there for; test_gemm_nt_cases_host.py holds `route` to it, and test_gemm_nt_route_host.py holds `route` to the library."""
+there for; test_gemm_nt_cases_host.py holds `route` to it, and test_gemm_nt_route_host.py holds `route` to the library.  `route` restates the
+convolution clauses of the planner too (nt_kwalk, lean level 3, the channel-split clause of nt_pipe_tile, the contract checks of both splits); the
+convolution cases themselves, their reference and their table are gemm_nt_conv_cases.py's.  fp8 is restated nowhere."""
 import collections
 import functools
 import math
@@ -357,14 +359,15 @@ def nt_error(got, ref):
     return max(_axis_error(g, r), _axis_error(g.T, r.T))
 
 
-def gate(key, got, ref, flo, case="", report=False):
-    """E(got, ref) <= K_NT[key] * E(floor, ref).  Raises AssertionError on a miss and returns (E, F); with report it raises nothing and returns
-    (E, F, ok).  A floor of exactly 0 admits E = 0 only."""
+def gate(key, got, ref, flo, case="", report=False, factors=None):
+    """E(got, ref) <= K[key] * E(floor, ref), K = K_NT or the `factors` of another table of the family.  Raises AssertionError on a miss and returns
+    (E, F); with report it raises nothing and returns (E, F, ok).  A floor of exactly 0 admits E = 0 only."""
+    K = K_NT if factors is None else factors
     E, Fl = nt_error(got, ref), nt_error(flo, ref)
-    ok = E <= K_NT[key] * Fl
+    ok = E <= K[key] * Fl
     if report:
         return E, Fl, ok
-    assert ok, f"{case} {key}: error {E:.3e} > {K_NT[key]:g} x floor {Fl:.3e} (E / F = {E / Fl if Fl > 0 else math.inf:.2f})"
+    assert ok, f"{case} {key}: error {E:.3e} > {K[key]:g} x floor {Fl:.3e} (E / F = {E / Fl if Fl > 0 else math.inf:.2f})"
     return E, Fl
 
 
@@ -429,17 +432,68 @@ def _forms(c, span, bf16_kernel=True):
     return frozenset(f)
 
 
-def _lean(c, kmode):
-    """the planner's nt_lean: epilogue instantiations without the features a launch does not use (plain and tap-walking K walks only)"""
-    if kmode == 0 or c.act != ACT_NONE or c.mul or c.cpre or c.c_split:
+WALK_GENERAL, WALK_PLAIN, WALK_TAPS, WALK_PARTIAL = 0, 1, 2, 3          # LAVT_NT_WALK_*
+
+
+def _cv(c, name, default=0):
+    """a convolution field of a case (gemm_nt_conv_cases.ConvCase has them; the plain rows of this file do not)"""
+    return getattr(c, name, default)
+
+
+def fits(c):
+    """the 2 GB bound of the pipelined family's 32-bit descriptor offsets, halo margin included (restated for the route comparison only)"""
+    lim = (1 << 31) - (1 << 24)
+    a_rows = c.M + 2 * ((c.conv_h if c.conv_h > 0 else 1) * c.conv_w + c.conv_w + 1)
+    b_rows = c.taps * c.conv_kc if c.kmajor else c.N
+    return a_rows * c.lda * 2 < lim and (not c.C2src or a_rows * c.lda2 * 2 < lim) and b_rows * c.ldb * 2 + c.batch * c.strideB * 2 < lim
+
+
+def kwalk(c, descriptors):
+    """the planner's nt_kwalk for bf16 operands; descriptors: the pipelined family (the 2 GB bound, the only home of the partial-block walk)"""
+    kc = _cv(c, "conv_kc")
+    if kc <= 0:
+        return WALK_PLAIN if c.K % 64 == 0 else WALK_GENERAL          # (no row of the plain table has a concat source)
+    walkable = (not c.C2src or c.a_split % 64 == 0) and c.taps <= 32 and (not descriptors or fits(c))
+    if kc % 64 == 0 and walkable:
+        return WALK_TAPS
+    if (descriptors and not c.kmajor and kc % 8 == 0 and walkable and c.conv_kc_split <= 0 and c.conv_tap_split <= 0 and c.batch == 1
+            and c.K == c.taps * kc and c.ldb >= c.taps * kc):
+        return WALK_PARTIAL
+    return WALK_GENERAL
+
+
+def _lean(c, kmode, tile=0):
+    """the planner's nt_lean: epilogue instantiations without the features a launch does not use (every K walk but the general decode); 3: the bare
+    store with C2 kept, on the 256x256 tile with k-major weights and the tap walk only"""
+    if kmode == WALK_GENERAL or c.act != ACT_NONE or c.mul or c.cpre:
         return 0
-    return 2 if not (c.bias or c.R or c.row_scale or c.c_map) else 1
+    bare = not (c.bias or c.R or c.row_scale or c.c_map)
+    if not c.c_split:
+        return 2 if bare else 1
+    return 3 if bare and tile == 256 and c.kmajor and kmode == WALK_TAPS else 0
 
 
-def _contract_ok(c):
+def _contract_ok(c, t):
     """the argument checks of lavt_gemm_nt itself"""
     if c.K % c.es or (c.kmajor and c.N % c.es) or c.lda % c.es or c.ldb % c.es or c.ldc % 4 or (c.c_split and c.c_split % 4):
         return False
+    if _cv(c, "C2src") and (c.a_split % c.es or c.lda2 % c.es):
+        return False
+    kc = _cv(c, "conv_kc")
+    if kc > 0:
+        a2_ok = not c.C2src or c.a_split % 64 == 0
+        if c.conv_kc_split > 0:
+            p = pipe_tile(c, t)
+            if not (c.dtype == "bf16" and c.conv_tap_split == 0 and c.conv_kc_split % 64 == 0 and c.batch * c.conv_kc_split == kc and c.K == c.taps * c.conv_kc_split
+                    and c.strideB == 0 and c.taps <= 32 and a2_ok and p is not None and p[0] == 128):
+                return False
+        elif c.conv_tap_split > 0:
+            if not (c.dtype == "bf16" and c.K == c.conv_tap_split * kc and c.batch * c.conv_tap_split == c.taps and kc % 64 == 0 and c.taps <= 32 and a2_ok):
+                return False
+        elif not (c.K == c.taps * kc and kc % c.es == 0 and c.conv_h > 0 and c.conv_w > 0):
+            return False
+        if c.M % c.vox:
+            return False
     if c.act == ACT_GELU_D and not (c.ln and c.cpre and not (c.mul or c.c_split or c.R or c.row_scale or c.c_map)):
         return False
     if c.res_first and not (c.dact is not None and c.R):
@@ -459,6 +513,10 @@ def pipe_tile(c, t):
     """the planner's nt_pipe_tile: (tile, stages) of csrc/gemm_nt_pipe.hip, or None"""
     if c.dtype != "bf16" or t["pipe"] < 1 or c.ln or c.dact is not None:
         return None
+    if c.lda % 8 or c.ldb % 8 or (_cv(c, "C2src") and c.lda2 % 8):
+        return None
+    if _cv(c, "conv_kc_split") > 0:          # the channel-split reduction exists in this family's tap-walking mode only
+        return 128, 4
     big, stages = _plain_choice(c, t)
     tiles256 = cdiv(c.M, 256) * cdiv(c.N, 256) * c.batch
     rounds = cdiv(tiles256, 256)
@@ -482,12 +540,13 @@ def colstats_plan(c, t):
 def route(case, tuning=None):
     """-> Route, or INVALID where the launch returns LAVT_ERR_INVALID"""
     c, t = case, dict(DEFAULT, **(tuning or {}))
-    if not _contract_ok(c) or (c.colstats and not colstats_plan(c, t)):
+    if not _contract_ok(c, t) or (c.colstats and not colstats_plan(c, t)):
         return INVALID
-    kmode = 1 if c.K % 64 == 0 else 0          # SIMPLE: no taps, no concat source, K % 64 == 0; else the general decode
     p = pipe_tile(c, t)
     if p:
-        return Route("pipe", p[0], p[1], kmode, "", _lean(c, kmode), _forms(c, 64 if p[0] == 256 else 32), False)
+        kmode = kwalk(c, True)
+        return Route("pipe", p[0], p[1], kmode, "", _lean(c, kmode, p[0]), _forms(c, 64 if p[0] == 256 else 32), False)
+    kmode = kwalk(c, False)          # plain: no taps, no concat source, K % 64 == 0; taps: the tap walk; else the general decode
     if c.dtype == "bf16":          # csrc/gemm_v2.hip (the zero page is always given; lda, ldb % 8 hold by the contract)
         tiles128, tiles64 = cdiv(c.M, 128) * cdiv(c.N, 128), cdiv(c.M, 64) * cdiv(c.N, 64)
         pick = lambda a, b: (128, 2 if a >= S2_MIN128 else 4) if (a >= 200 and c.N >= 128) else (64, 2 if b >= 512 else 4)          # ignores the forced tile / stages
@@ -504,7 +563,7 @@ def route(case, tuning=None):
             pf = bool(epi_wide(c) & 2) and "wide" in _forms(c, 32) and (tile == 64 or gd)
             return Route("v2", tile, st, 1, "DACT+GD" if gd else "DACT", 0, _forms(c, 32), pf)
         big, stages = _plain_choice(c, t)
-        tile, lean = (128 if big else 64), _lean(c, kmode)
+        tile, lean = (128 if big else 64), _lean(c, kmode, 128 if big else 64)
         pf = tile == 64 and lean < 2 and bool(epi_wide(c) & 2) and "wide" in _forms(c, 32) and bool(c.R or c.mul)
         return Route("v2", tile, stages, kmode, "", lean, _forms(c, 32), pf)
     if c.ln or c.dact is not None:          # fp32: both exist on the bf16 LDS-DMA path only

@@ -5,7 +5,8 @@
     LayerNorm-folded operand (the fold of W, gamma, beta included), and the autograd gradient through GELU, tanh and ReLU for dact_pre, with the
     residual joining after or (res_first) before it.
 (2) `route` returns the route every row of the table states, under every forced configuration the row runs in, and the table reaches every
-    instantiation the dispatcher can reach outside convolutions and fp8 (gemm_nt_cases.reachable enumerates them).
+    instantiation the dispatcher can reach outside convolutions and fp8 (gemm_nt_cases.reachable enumerates them; the convolution
+    instantiations are gemm_nt_conv_cases.reachable_conv's, held by test_gemm_nt_conv_cases_host.py).
 (3) Planted faults: the "kernel" is the floor evaluation (fp32, bf16 roundings of the contract) with one defect injected, at the smallest case of the
     table that has the feature.  The gate, with K_NT as committed, must reject every defect with a factor 2 to spare and pass the unmutated floor."""
 import pytest

@@ -10,15 +10,19 @@ The planner never reads through an address; no struct of this file is ever passe
     `prefetch` of the Python Route are decided inside the kernel (per wave span, from epi_wide and the column range) and stay outside the comparison.
   * refusals: lavt_last_error names the feature the row is refused for.
   * lavt_gemm_nt_colstats_plan equals colstats_plan() for the same rows.
-  * ROWS: what route() does not restate -- convolutions, fp8, the thresholds' boundaries -- written by hand from the rules, the route stated per row.
+  * the convolution table (tests/gemm_nt_conv_cases.py): every (row, forced configuration) field by field, as for PLAIN; its refusals name the feature.
+  * ROWS: fp8 (which route() does not restate), the benchmark's convolutions, the 2 GB descriptor bound and the thresholds' boundaries, written by hand
+    from the rules, the route stated per row; every row but the fp8 ones must equal route() too.
   * forced configurations: the LayerNorm-folded and the activation-gradient rows (and gemm_v2's fp8 form) ignore LAVT_GEMM_TILE / LAVT_GEMM_STAGES
     and have no long-K clause; pinned here as today's behaviour."""
 import ctypes
+import types
 
 import pytest
 import torch
 
 import gemm_nt_cases as G
+import gemm_nt_conv_cases as V
 
 ENV = ("LAVT_GEMM_TILE", "LAVT_GEMM_STAGES", "LAVT_GEMM_PIPE")
 BF, F8 = torch.bfloat16, torch.uint8
@@ -156,7 +160,64 @@ def test_forced_configurations_do_not_reach_lna_and_dact(tuning):
             assert f"{f[0]}/{f[1]}/s{f[2]}/k{f[3]}/{f[4]}/L{f[5]}" == c.route.rsplit("/", 1)[0], (name, c.name, f, c.route)
 
 
-# ------------------------------------------------------------------------------------------------ rows route() does not restate
+# ------------------------------------------------------------------------------------------------ the convolution table
+def conv_params(c):
+    """the lavt_gemm_nt_t of a convolution row, through the helper the GPU test launches with"""
+    K, ops = _capi()
+    new = Addresses()
+    buf = dict(A_big=new(), B=new(), C=new())
+    buf.update({k: new() for k, v in dict(A2=c.C2, C2=c.c_split, Cpre=c.cpre, bias=c.bias).items() if v})
+    args, kw = V.launch_args(c, buf)
+    p = ops.gemm_nt_params(*args, **kw, addr=lambda a: a, zeros=new())
+    if c.colstats:
+        p.colstats = new()
+    return p
+
+
+def _conv_tuning(c, name, tuning):
+    env = G.tuning_env(name) if name else {}
+    tuning(dict(env, **(c.env or {})))
+    t = G.tuning_dict(name) if name else {}
+    return dict(t, pipe=int(c.env["LAVT_GEMM_PIPE"])) if c.env else t
+
+
+@pytest.mark.parametrize("name", [None] + sorted({t for _, t in V.launches() if t}))
+def test_conv_rows_route_as_restated(name, tuning):
+    """every row of the convolution table that runs under this configuration; under the default tuning, every row"""
+    rows = [c for c, t in V.launches() if t == name] if name else V.TABLE
+    assert rows
+    bad = []
+    for c in rows:
+        t = _conv_tuning(c, name, tuning)
+        want = G.route(c, t)
+        rc, r, nblk, rpb = ask(conv_params(c))
+        if want == G.INVALID:          # (the colstats rows at the default tuning: 64x64 tiles have no statistics epilogue)
+            if rc != -22:
+                bad.append((c.name, "INVALID", rc, fields(r)))
+            continue
+        exp = (want.family, want.tile, want.stages, want.kmode, want.kind, want.lean, G.epi_wide(c))
+        waves = 8 if want.family == "pipe" or (want.family == "v2" and want.tile == 128) else 4
+        if rc != 0 or fields(r) != exp or r.waves != waves or r.b_kmajor != int(c.kmajor) or r.dtype != (1 if c.dtype == "bf16" else 0):
+            bad.append((c.name, exp, rc, fields(r), r.waves, r.b_kmajor))
+        blocks = G.colstats_plan(c, dict(G.DEFAULT, **t))
+        if (nblk, rpb) != (blocks, G.pipe_tile(c, dict(G.DEFAULT, **t))[0] // 2 if blocks else 0):
+            bad.append((c.name, "colstats", blocks, nblk, rpb))
+        if name and V.route_key(c, want) != V.stated_route(c, name):
+            bad.append((c.name, "stated", V.route_key(c, want), V.stated_route(c, name)))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("case", V.REFUSALS, ids=repr)
+def test_conv_refusals_say_why(case, tuning):
+    K, _ = _capi()
+    t = _conv_tuning(case, None, tuning)
+    assert G.route(case, t) == G.INVALID
+    rc, _, _, _ = ask(conv_params(case))
+    msg = K.lib.lavt_last_error().decode()
+    assert rc == -22 and msg.startswith("lavt_gemm_nt") and case.word in msg, (rc, msg)
+
+
+# ------------------------------------------------------------------------------------------------ rows written by hand
 # Written by hand from the rules (the comment block of csrc/gemm_nt_plan.hip); per row the tile counts that decide it.
 #   t128 / t64 / t256 = tiles of that size x batch.  128x128 tile: t128 >= 200, or K >= 4096 and t128 >= 128 (N >= 128); ring of 2 from 257 / 512
 #   workgroups.  pipe: 256x256 where N fits, K >= 1024, t256 >= 128 and the last round of 256 is >= 80 % full; else the 128x128 tile with K >= 1024.
@@ -250,6 +311,21 @@ def row_params(args, kw):
     return ops.gemm_nt_params(dtype, M, N, Kd, new(), lda, new(), ldb, new(), ldc, **kw, addr=lambda a: a, zeros=new())
 
 
+def row_case(args, kw):
+    """a hand-written row as route() reads a case (no fp8)"""
+    dtype, M, N, Kd, lda, ldb, ldc = args
+    kw = dict(kw)
+    lda, Kd = kw.pop("lda", lda), kw.pop("Kd", Kd)
+    H, W, kc, flip = kw.get("conv", (0, 0, 0, 0))
+    c = types.SimpleNamespace(
+        dtype="bf16" if dtype == BF else "f32", es=8 if dtype == BF else 4, M=M, N=N, K=Kd, batch=kw.get("batch", 1), lda=lda, ldb=ldb, ldc=ldc, kmajor=bool(kw.get("b_kmajor")),
+        C2src=bool(kw.get("A2")), lda2=kw.get("lda2", 0), a_split=kw.get("a_split", 0), conv_kc=kc, conv_h=H, conv_w=W, taps=9, vox=max(H * W, 1),
+        conv_tap_split=kw.get("conv_tap_split", 0), conv_kc_split=kw.get("conv_kc_split", 0), strideB=kw.get("strideB", 0), strideC=kw.get("strideC", 0),
+        c_split=kw.get("c_split", 0) if kw.get("C2") else 0, ldc2=kw.get("ldc2", 0), c_f32=bool(kw.get("c_f32")), bias=bool(kw.get("bias")), bias_off=0, act=0, cpre=False,
+        ldcpre=0, mul=False, R=False, row_scale=False, c_map=False, a_map=False, ln=False, dact=None, res_first=False, colstats=False, alpha=1.0)
+    return c
+
+
 @pytest.mark.parametrize("name,call,t,want", ROWS, ids=[r[0] for r in ROWS])
 def test_hand_written_rows(name, call, t, want, tuning):
     full = dict(G.DEFAULT, **t)
@@ -258,3 +334,7 @@ def test_hand_written_rows(name, call, t, want, tuning):
     K, _ = _capi()
     assert rc == 0, K.lib.lavt_last_error()
     assert fields(r) == want, (name, fields(r), want)
+    if call[0][0] != F8:          # route() restates everything but fp8
+        c = row_case(*call)
+        got = G.route(c, full)
+        assert got != G.INVALID and (got.family, got.tile, got.stages, got.kmode, got.kind, got.lean, G.epi_wide(c)) == want, (name, got, want)

@@ -12,7 +12,7 @@ same error of the fp32 / bf16 floor of the case.  Every figure is printed before
   * a case the table says runs and that returns LAVT_ERR_INVALID fails (ops.gemm_nt raises); no case is skipped.
 
 Cases (gemm_nt_cases.py states, per row, the route it is there for; test_gemm_nt_cases_host.py holds `route` to it and shows that the rows reach
-every instantiation of the dispatcher outside convolutions and fp8):
+every instantiation of the dispatcher outside convolutions -- gemm_nt_conv_cases.py -- and fp8):
   * PLAIN, run under all twelve settings of LAVT_GEMM_TILE 64 / 128 / 512 x LAVT_GEMM_STAGES 2 / 4 x LAVT_GEMM_PIPE 0 / 3 (seven distinct kernels:
     gemm_v2 64x64 and 128x128 with a 2- and a 4-deep ring, the pipelined 128x128 with both rings, the pipelined 256x256):
       edges  M = tile k + {1, 15, 17, 63} and M < 16; N in {8, 24, 72, 136, 328} and 132 with an fp32 output; K in {8, 56, 64, 72, 264}: the general
@@ -31,7 +31,8 @@ every instantiation of the dispatcher outside convolutions and fp8):
     with R + row_scale + c_rowmap, one whose rows have a mean of 10 sigma, the narrow form of each kernel.
   * REFUSALS: the combinations the header declares invalid return LAVT_ERR_INVALID, set lavt_last_error and leave the outputs untouched.
 
-Out of scope: the implicit-GEMM convolution modes (tap-walking K walks, LEAN 3, conv_tap_split / conv_kc_split), fp8, the TN family.
+Elsewhere: the implicit-GEMM convolution modes (tap-walking K walks, LEAN 3, conv_tap_split / conv_kc_split) in test_gpu_gemm_nt_conv_cases.py, the TN
+family in test_gpu_gemm_tn_cases.py.  Out of scope: fp8.
 
 Measured E / F on MI355X, the largest over the cases of this file (gemm_nt_cases.K_NT = 2 x that, rounded up, never under 1): MEASURED below.
 Every bf16 output sits at 1.000 in every case and under every forced configuration: its error IS the final bf16 rounding, and the kernel rounds the
