@@ -292,6 +292,57 @@ int lavt_gemm_tn_grouped_ln(const lavt_gemm_tn_t* probs, int n, const void* dy, 
  * (conv taps, batch > 1, too little work): call lavt_gemm_tn_grouped then.  Members' `partials` fields are ignored. */
 int64_t lavt_gemm_tn_grouped_sk_ws(const lavt_gemm_tn_t* probs, int n);
 int lavt_gemm_tn_grouped_sk(const lavt_gemm_tn_t* probs, int n, float* scratch, int64_t scratch_floats, void* stream);
+/* What lavt_gemm_tn(p) launches: the kernel family, its instantiation, the K pieces and how they meet in C (csrc/gemm_tn_plan.hip decides, the
+ * families launch from this answer).  A host-side query: nothing is launched and no pointer of p is read through.  New symbols only: no existing
+ * prototype or struct changed, lavt_abi_version() stays 7. */
+#define LAVT_TN_CLASSIC 0 /* csrc/gemm.hip: register-staged double buffer (fp32, and bf16 problems the LDS-DMA kernels decline); always adds atomically */
+#define LAVT_TN_V2 1      /* csrc/gemm_tn_v2.hip: LDS-DMA ring, bf16 */
+#define LAVT_TN_STORE 0   /* one writer per output element, stored plainly */
+#define LAVT_TN_ATOMIC 1  /* fp32 atomics (K pieces meeting in C, or accumulate) */
+#define LAVT_TN_PARTS 2   /* K pieces stored as plain tiles into `partials`, added into C by tn_reduce_pieces */
+typedef struct lavt_gemm_tn_route {
+    int32_t family;       /* LAVT_TN_CLASSIC / _V2 */
+    int32_t dtype;        /* element type of the operands; the classic family's template type */
+    int32_t tile, waves;  /* square output tile of a workgroup (64 / 128) and its waves (4 / 8) */
+    int32_t maps;         /* the K loop that carries row maps / the row mask (V2) */
+    int32_t colsum_form;  /* V2: 0 none, 1 scalar walk of the LDS tile, 2 on the matrix cores */
+    int32_t convp;        /* V2: the kernel with the tap state of a convolution weight gradient */
+    int32_t kt_per_piece; /* K tiles (64 rows; classic fp32: 16) per piece */
+    int32_t pieces;       /* K pieces = grid z, none of them empty */
+    int32_t write;        /* LAVT_TN_STORE / _ATOMIC / _PARTS */
+} lavt_gemm_tn_route_t;
+/* -> LAVT_OK and *out, or LAVT_ERR_INVALID (lavt_last_error set) exactly where lavt_gemm_tn(p) refuses the problem */
+int lavt_gemm_tn_route(const lavt_gemm_tn_t* p, lavt_gemm_tn_route_t* out);
+/* What a grouped entry launches for n problems.  entry: LAVT_TN_ENTRY_GROUPED (lavt_gemm_tn_grouped; with ln_rows > 0 lavt_gemm_tn_grouped_ln
+ * offering a LayerNorm backward over [ln_rows][ln_C]) or LAVT_TN_ENTRY_SK (lavt_gemm_tn_grouped_sk).  A host-side query, as above. */
+#define LAVT_TN_GROUP_MAX 6
+#define LAVT_TN_ENTRY_GROUPED 0
+#define LAVT_TN_ENTRY_SK 1
+#define LAVT_TN_EACH 0    /* the group does not form: one lavt_gemm_tn per problem */
+#define LAVT_TN_GROUP64 1 /* csrc/gemm_tn_v2.hip: 64x64 tiles, gemm_tn_v2_grouped_kernel / _grouped_ln_kernel */
+#define LAVT_TN_PIPE 2    /* csrc/gemm_tn_pipe.hip: 128x128 software-pipelined tiles */
+#define LAVT_TN_SK 3      /* csrc/gemm_tn_v2.hip: stream-K on 128x128 tiles + tn_streamk_fixup */
+#define LAVT_TN_REDUCE_NONE 0
+#define LAVT_TN_REDUCE_GROUP 1     /* tn_reduce_pieces_group */
+#define LAVT_TN_REDUCE_PIPE 2      /* tnp_reduce_pieces */
+#define LAVT_TN_REDUCE_PIPE_DEEP 3 /* tnp_reduce_pieces_deep */
+#define LAVT_TN_RIDER_NONE 0  /* no LayerNorm was offered */
+#define LAVT_TN_RIDER_RIDES 1 /* it runs as extra workgroups of the launch */
+#define LAVT_TN_RIDER_AFTER 2 /* the entry launches it on its own after the weight gradients */
+typedef struct lavt_gemm_tn_group_route {
+    int32_t launch;      /* LAVT_TN_EACH / _GROUP64 / _PIPE / _SK */
+    int32_t stages;      /* ring depth: 2, the pipelined launch 3 / 4 (EACH: 0) */
+    int32_t maps;        /* some member carries row maps / a row mask (GROUP64, SK: the kernel's MAPS) */
+    int32_t colsum_form; /* 0 none, 1 scalar (SK), 2 matrix cores (GROUP64, PIPE) */
+    int32_t workgroups;  /* workgroups of the weight gradients (riders not counted; SK: the persistent workgroups; EACH: 0) */
+    int32_t pieces[LAVT_TN_GROUP_MAX], kt_per_piece[LAVT_TN_GROUP_MAX]; /* per member (EACH: of its own lavt_gemm_tn_route) */
+    int32_t parts[LAVT_TN_GROUP_MAX]; /* per member: its pieces go through its partials scratch */
+    int32_t any_parts, reducer, reducer_grid_x; /* LAVT_TN_REDUCE_* and the x size of its grid (y = n) */
+    int32_t rider, rider_lpr, rider_blocks, rider_wgs; /* LAVT_TN_RIDER_*; RIDES: lanes per row, LayerNorm units and the workgroups they occupy */
+    int64_t scratch_floats; /* SK: floats of scratch (what lavt_gemm_tn_grouped_sk_ws answers) */
+} lavt_gemm_tn_group_route_t;
+/* -> LAVT_OK and *out, or LAVT_ERR_INVALID: a member lavt_gemm_tn refuses (EACH), a group the stream-K entry does not take */
+int lavt_gemm_tn_group_route(const lavt_gemm_tn_t* probs, int n, int entry, int ln_rows, int ln_C, lavt_gemm_tn_group_route_t* out);
 
 /* 3x3 / pad 1 / no-bias convolution weight gradient with the nine taps fused (ABI v5; bf16; csrc/conv_wgrad.hip) -- the gradient autograd computes for
  * SimpleDecoding's conv1_4 .. conv2_2 (lib/mask_predictor.py:60-97):  dW[co][ci][tap] += sum_p dY[p][co] * X[p + (dy, dx)][ci],

@@ -192,10 +192,6 @@ template <typename T, int BM, int BN, bool BKM> int launch_nt(const lavt_gemm_nt
     LAVT_CHECK_LAUNCH("lavt_gemm_nt");
     return LAVT_OK;
 }
-// LAVT_GEMM_TILE=128|64 forces a tile configuration (tests exercise both); unset = shape heuristic.
-static int forced_tile() {
-    return lavt_tuning().gemm_tile;
-}
 // the classic family's instantiation of a route (gemm_nt_plan.hip): element type x tile x B layout
 template <typename T> int launch_nt_route(const lavt_gemm_nt_t& p, const lavt_gemm_nt_route_t& r, hipStream_t st) {
     if (r.b_kmajor) return r.tile == 128 ? launch_nt<T, 128, 128, true>(p, st) : launch_nt<T, 64, 64, true>(p, st);
@@ -360,23 +356,10 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const lavt_gemm_tn_t p, in
     if (do_colsum && i0 + tid < p.I) atomicAdd(p.colsum + (int64_t)bz * p.strideColsum + i0 + tid, csum * p.alpha);
 }
 
-template <typename T, int BI, int BJ> int launch_tn(const lavt_gemm_tn_t& p, hipStream_t st) {
+template <typename T, int BI, int BJ> int launch_tn(const lavt_gemm_tn_t& p, const lavt_gemm_tn_route_t& r, hipStream_t st) {
     constexpr int BK = Cfg<T>::BK;
     const size_t lds = 2 * (size_t)(BK * (BI + KM_PAD) + BK * (BJ + KM_PAD)) * sizeof(T);
-    const int tiles = cdiv(p.I, BI) * cdiv(p.J, BJ);
-    const int ktiles = cdiv(p.K, BK);
-    int split = p.split_k;
-    if (split <= 0) {
-        split = (int)(768 / ((long)tiles * p.batch));
-        if (split < 1) split = 1;
-        const int max_split = (ktiles + 3) / 4;        // at least 4 K tiles per workgroup
-        if (split > max_split) split = max_split;
-        if (split < 1) split = 1;
-    }
-    if (split > ktiles) split = ktiles;
-    const int per = cdiv(ktiles, split);
-    split = cdiv(ktiles, per);
-    dim3 grid(tiles, p.batch, split);
+    dim3 grid(cdiv(p.I, BI) * cdiv(p.J, BJ), p.batch, r.pieces);
     static bool attr_set = false;
     if (!attr_set && lds > 65536) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_kernel<T, BI, BJ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
@@ -385,14 +368,12 @@ template <typename T, int BI, int BJ> int launch_tn(const lavt_gemm_tn_t& p, hip
         }
         attr_set = true;
     }
-    hipLaunchKernelGGL((gemm_tn_kernel<T, BI, BJ>), grid, dim3(256), lds, st, p, per);
+    hipLaunchKernelGGL((gemm_tn_kernel<T, BI, BJ>), grid, dim3(256), lds, st, p, r.kt_per_piece);
     LAVT_CHECK_LAUNCH("lavt_gemm_tn");
     return LAVT_OK;
 }
-template <typename T> int dispatch_tn(const lavt_gemm_tn_t& p, hipStream_t st) {
-    const int force = forced_tile();
-    const bool big = force ? force == 128 : (p.I >= 256 && p.J >= 1024 && p.K >= 8192);
-    return big ? launch_tn<T, 128, 128>(p, st) : launch_tn<T, 64, 64>(p, st);
+template <typename T> int dispatch_tn(const lavt_gemm_tn_t& p, const lavt_gemm_tn_route_t& r, hipStream_t st) {
+    return r.tile == 128 ? launch_tn<T, 128, 128>(p, r, st) : launch_tn<T, 64, 64>(p, r, st);
 }
 
 }  // namespace
@@ -411,88 +392,64 @@ extern "C" int lavt_gemm_nt(const lavt_gemm_nt_t* pp, void* stream) {
     return r.dtype == LAVT_F32 ? launch_nt_route<float>(p, r, st) : launch_nt_route<bf16>(p, r, st);
 }
 
+// Every check and every choice of kernel, piece count and rider is gemm_tn_plan.hip's; these launch what the route names.
 extern "C" int lavt_gemm_tn(const lavt_gemm_tn_t* pp, void* stream) {
-    LAVT_CHECK_ARG(pp != nullptr, "lavt_gemm_tn: null params");
-    lavt_gemm_tn_t p = *pp;
-    LAVT_CHECK_ARG(p.dtype == LAVT_F32 || p.dtype == LAVT_BF16, "lavt_gemm_tn: bad dtype %d", p.dtype);
-    const int epc = p.dtype == LAVT_F32 ? 4 : 8;
-    LAVT_CHECK_ARG(p.I > 0 && p.J > 0 && p.K > 0 && p.batch >= 1, "lavt_gemm_tn: bad shape");
-    LAVT_CHECK_ARG(p.I % epc == 0 && p.J % epc == 0, "lavt_gemm_tn: I=%d, J=%d must be multiples of %d", p.I, p.J, epc);
-    LAVT_CHECK_ARG(p.A && p.B && p.C, "lavt_gemm_tn: null operand");
-    LAVT_CHECK_ARG(p.lda % epc == 0 && p.ldb % epc == 0, "lavt_gemm_tn: lda/ldb must be multiples of %d", epc);
-    LAVT_CHECK_ARG(!p.B2 || (p.b_split % epc == 0 && p.ldb2 % epc == 0), "lavt_gemm_tn: bad b_split");
-    if (p.conv_kc > 0)
-        LAVT_CHECK_ARG(p.J == conv_taps_of(p) * p.conv_kc &&
-                       p.conv_kc % epc == 0 && p.conv_h > 0 && p.conv_w > 0, "lavt_gemm_tn: bad conv geometry");
+    lavt_gemm_tn_route_t r;
+    const int rc = lavt_gemm_tn_route(pp, &r);
+    if (rc != LAVT_OK) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int rc2 = lavt_gemm_tn_v2(p, st);          // bf16 LDS-DMA kernel (gemm_v2.hip); 1 = not applicable
-    if (rc2 != 1) return rc2;
-    LAVT_CHECK_ARG(!p.colsum_atomic, "lavt_gemm_tn: colsum_atomic needs the bf16 LDS-DMA kernel (bf16 operands, 16-byte aligned rows, zeros page)");
-    return p.dtype == LAVT_F32 ? dispatch_tn<float>(p, st) : dispatch_tn<bf16>(p, st);
+    if (r.family == LAVT_TN_V2) return lavt_gemm_tn_v2(*pp, r, st);
+    return r.dtype == LAVT_F32 ? dispatch_tn<float>(*pp, r, st) : dispatch_tn<bf16>(*pp, r, st);
 }
 
-// upper bound of the K pieces of lavt_gemm_tn (>= 8 K tiles of 64 rows per piece)
-extern "C" int lavt_gemm_tn_pieces(const lavt_gemm_tn_t* p) {
-    if (!p || p->K <= 0) return 1;
-    const int ktiles = cdiv(p->K, 64);
-    // (batched problems -- the per-sample word-side reductions of the fused PWAM node: 2-4 output tiles -- are cut down to 2 K tiles per piece:
-    // a piece is a serial chain of ~1 us per K tile on the 2-stage ring, and the launch sits on the critical chain)
-    const int min_kt = p->batch > 1 ? 2 : 8;
-    int n = cdiv(ktiles, min_kt);
-    if (n > ktiles) n = ktiles;
-    return n < 1 ? 1 : n;
+// the argument checks the grouped entries share, then the group's route
+static int tn_group_route(const char* who, const lavt_gemm_tn_t* probs, int n, int entry, int ln_rows, int ln_C, lavt_gemm_tn_group_route_t* r) {
+    LAVT_CHECK_ARG(probs != nullptr && n >= 1, "%s: bad arguments", who);
+    bool ok = true;
+    for (int i = 0; i < n; ++i) ok = ok && probs[i].A && probs[i].B && probs[i].C && probs[i].I > 0 && probs[i].J > 0 && probs[i].K > 0;
+    LAVT_CHECK_ARG(ok, "%s: null operand / bad shape", who);
+    return lavt_gemm_tn_group_route(probs, n, entry, ln_rows, ln_C, r);
 }
 
 // n independent weight-gradient problems issued together: one grouped launch without split-K when they qualify (bf16, plain / row-mapped
 // operands, >= 256 output tiles in total), else one lavt_gemm_tn call each.  Results are identical either way up to fp32 summation order.
-// The stream-K form of the same launch: lavt_gemm_tn_grouped_sk_ws_v2 / _sk_v2 (internal.h).
-extern "C" int64_t lavt_gemm_tn_grouped_sk_ws(const lavt_gemm_tn_t* probs, int n) {
-    if (probs == nullptr || n < 1) return 0;
-    for (int i = 0; i < n; ++i)
-        if (!(probs[i].A && probs[i].B && probs[i].C && probs[i].I > 0 && probs[i].J > 0 && probs[i].K > 0)) return 0;
-    return lavt_gemm_tn_grouped_sk_ws_v2(probs, n);
-}
 extern "C" int lavt_gemm_tn_grouped_sk(const lavt_gemm_tn_t* probs, int n, float* scratch, int64_t scratch_floats, void* stream) {
-    LAVT_CHECK_ARG(probs != nullptr && n >= 1 && scratch != nullptr, "lavt_gemm_tn_grouped_sk: bad arguments");
-    const int rc = lavt_gemm_tn_grouped_sk_v2(probs, n, scratch, scratch_floats, reinterpret_cast<hipStream_t>(stream));
-    LAVT_CHECK_ARG(rc != 1, "lavt_gemm_tn_grouped_sk: the group does not qualify or the scratch is too small (ask lavt_gemm_tn_grouped_sk_ws first)");
-    return rc;
+    lavt_gemm_tn_group_route_t r;
+    const int rc = tn_group_route("lavt_gemm_tn_grouped_sk", probs, n, LAVT_TN_ENTRY_SK, 0, 0, &r);
+    if (rc != LAVT_OK) return rc;
+    LAVT_CHECK_ARG(scratch != nullptr && scratch_floats >= r.scratch_floats, "lavt_gemm_tn_grouped_sk: the scratch is too small (ask lavt_gemm_tn_grouped_sk_ws first)");
+    return lavt_gemm_tn_grouped_sk_v2(probs, n, r, scratch, reinterpret_cast<hipStream_t>(stream));
+}
+// the weight gradients as the route names them; the LayerNorm it does not carry is the caller's
+static int tn_group_launch(const lavt_gemm_tn_t* probs, int n, const lavt_gemm_tn_group_route_t& r, void* stream, const lavt_ln_rider_t* ln) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (r.launch == LAVT_TN_PIPE) return lavt_gemm_tn_grouped_pipe(probs, n, r, st, ln);
+    if (r.launch == LAVT_TN_GROUP64) return lavt_gemm_tn_grouped_v2(probs, n, r, st, ln);
+    for (int i = 0; i < n; ++i) {
+        const int rc = lavt_gemm_tn(&probs[i], stream);
+        if (rc != LAVT_OK) return rc;
+    }
+    return LAVT_OK;
 }
 // lavt_gemm_tn_grouped + ONE LayerNorm backward (the partial-sum form of lavt_layernorm_bwd_partial, bf16, no gather) that rides as extra workgroups of the
-// grouped launch when the group runs on the 64x64 launch with column sums; in every other case the two are issued one after the other -- the result is
-// the same either way.  ws / ws_floats: the LayerNorm's partial-sum scratch (lavt_layernorm_bwd_blocks(...) * 2 * C floats).
+// grouped launch where the route says so; in every other case the two are issued one after the other -- the result is the same either way.
+// ws / ws_floats: the LayerNorm's partial-sum scratch (lavt_layernorm_bwd_blocks(...) * 2 * C floats).
 extern "C" int lavt_gemm_tn_grouped_ln(const lavt_gemm_tn_t* probs, int n, const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
                                        void* dx, float* ws, int64_t ws_floats, const void* dres, int rows, int C, void* stream) {
-    LAVT_CHECK_ARG(probs != nullptr && n >= 1 && dy && x && gamma && mean && rstd && dx && ws && rows > 0 && C > 0 && C % 8 == 0, "lavt_gemm_tn_grouped_ln: bad arguments");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    bool ok = true;
-    for (int i = 0; i < n; ++i) ok = ok && probs[i].A && probs[i].B && probs[i].C && probs[i].I > 0 && probs[i].J > 0 && probs[i].K > 0;
-    LAVT_CHECK_ARG(ok, "lavt_gemm_tn_grouped_ln: null operand / bad shape");
+    LAVT_CHECK_ARG(dy && x && gamma && mean && rstd && dx && ws && rows > 0 && C > 0 && C % 8 == 0, "lavt_gemm_tn_grouped_ln: bad arguments");
+    lavt_gemm_tn_group_route_t r;
+    int rc = tn_group_route("lavt_gemm_tn_grouped_ln", probs, n, LAVT_TN_ENTRY_GROUPED, rows, C, &r);
+    if (rc != LAVT_OK) return rc;
     int lpr, cpl, waves;
     const int blocks = lavt_ln_bwd_geometry(LAVT_BF16, rows, C, &lpr, &cpl, &waves);
     LAVT_CHECK_ARG(ws_floats >= (int64_t)blocks * 2 * C, "lavt_gemm_tn_grouped_ln: LayerNorm scratch of %ld floats needed", (long)blocks * 2 * C);
     lavt_ln_rider_t ln{dy, x, gamma, mean, rstd, dx, ws, dres, rows, C};
-    int rc = lavt_gemm_tn_grouped_v2(probs, n, st, &ln);
-    if (rc == LAVT_OK) return rc;                                  // both launched, the LayerNorm as riders
-    if (rc == 1) {                                                 // the group does not form: one launch per problem
-        for (int i = 0; i < n; ++i) {
-            const int r = lavt_gemm_tn(&probs[i], stream);
-            if (r != LAVT_OK) return r;
-        }
-    } else if (rc != 3) return rc;
+    rc = tn_group_launch(probs, n, r, stream, &ln);
+    if (rc != LAVT_OK || r.rider == LAVT_TN_RIDER_RIDES) return rc;
     return lavt_layernorm_bwd_partial_impl(LAVT_BF16, dy, x, gamma, mean, rstd, dx, ws, ws_floats, dres, rows, C, stream);
 }
 extern "C" int lavt_gemm_tn_grouped(const lavt_gemm_tn_t* probs, int n, void* stream) {
-    LAVT_CHECK_ARG(probs != nullptr && n >= 1, "lavt_gemm_tn_grouped: bad arguments");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    bool ok = true;
-    for (int i = 0; i < n; ++i) ok = ok && probs[i].A && probs[i].B && probs[i].C && probs[i].I > 0 && probs[i].J > 0 && probs[i].K > 0;
-    LAVT_CHECK_ARG(ok, "lavt_gemm_tn_grouped: null operand / bad shape");
-    const int rc = lavt_gemm_tn_grouped_v2(probs, n, st, nullptr);
-    if (rc != 1) return rc;
-    for (int i = 0; i < n; ++i) {
-        const int r = lavt_gemm_tn(&probs[i], stream);
-        if (r != LAVT_OK) return r;
-    }
-    return LAVT_OK;
+    lavt_gemm_tn_group_route_t r;
+    const int rc = tn_group_route("lavt_gemm_tn_grouped", probs, n, LAVT_TN_ENTRY_GROUPED, 0, 0, &r);
+    return rc != LAVT_OK ? rc : tn_group_launch(probs, n, r, stream, nullptr);
 }

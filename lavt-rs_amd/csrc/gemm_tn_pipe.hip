@@ -505,27 +505,15 @@ template <int STAGES, int LPR> void tnp_launch(const TnpGroup& g, const TnpRider
 
 }  // namespace
 
-// The grouped weight-gradient launch on 128x128 pipelined tiles.  Returns 1 when the group does not qualify (the caller takes gemm_tn_v2.hip's
-// launch), LAVT_OK when it was launched (with the LayerNorm rider if `ln` was given), 3 when it was launched WITHOUT the rider it was offered.
-int lavt_gemm_tn_grouped_pipe(const lavt_gemm_tn_t* probs, int n, hipStream_t st, const lavt_ln_rider_t* ln) {
-    const lavt_tuning_t& tun = lavt_tuning();
-    if (tun.tn_pipe == 0 || n < 2 || n > TNP_MAX) return 1;
+// The grouped weight-gradient launch on 128x128 pipelined tiles, as lavt_gemm_tn_group_route (gemm_tn_plan.hip) names it: the pieces of every member,
+// the reducer, the ring depth and the rider are the route's; this fills TnpGroup / TnpRider from it and picks tnp_launch<STAGES, LPR>.
+int lavt_gemm_tn_grouped_pipe(const lavt_gemm_tn_t* probs, int n, const lavt_gemm_tn_group_route_t& r, hipStream_t st, const lavt_ln_rider_t* ln) {
+    static_assert(TNP_MAX == LAVT_TN_GROUP_MAX, "the route's per-member arrays");
     TnpGroup g;
-    int base_tiles = 0;
-    long work = 0;                                                // (output tile, K tile) pairs of the launch
+    int tiles = 0;
     for (int i = 0; i < n; ++i) {
         const lavt_gemm_tn_t& p = probs[i];
         const bool no_b = p.ldb == 0;                             // (the column-sum-only side member: B = the zero page)
-        if (p.dtype != LAVT_BF16 || p.batch != 1 || p.conv_kc > 0 || p.B2 || p.c_conv_permute) return 1;
-        if (p.I % 8 || p.J % 4 || p.lda % 8 || p.ldb % 8 || p.K < 8) return 1;
-        if ((int64_t)(p.K + 1024) * p.lda * 2 >= (1LL << 30) || (int64_t)(p.K + 1024) * p.ldb * 2 >= (1LL << 30)) return 1;          // 32-bit byte offsets inside a 2 GB descriptor, with room for the tiles issued beyond K
-        // a MAPPED operand is addressed by source row: the rows its map may name must stay inside the descriptor as well (unknown extent: the K + 1024 rows
-        // bounded above; a padded-window source or a large clip can be several times the reduction length -- beyond 2^31 bytes the hardware returns zeros)
-        if (p.a_rowmap && p.a_src_rows > 0 && (p.a_src_rows + 1) * p.lda * 2 + 256 >= (1LL << 31)) return 1;
-        if (p.b_rowmap && p.b_src_rows > 0 && (p.b_src_rows + 1) * p.ldb * 2 + 256 >= (1LL << 31)) return 1;
-        if (p.a_rowscale && (!p.a_rowscale_binary || p.a_rowscale_div < 64 || (p.K + p.a_rowscale_div - 1) / p.a_rowscale_div > 64)) return 1;
-        if (no_b && !p.colsum) return 1;
-        if (!no_b && p.J % 8) return 1;
         TnpMember& m = g.m[i];
         m.A = (const bf16*)p.A; m.B = (const bf16*)p.B; m.C = p.C; m.colsum = p.colsum;
         m.a_map = p.a_rowmap; m.b_map = p.b_rowmap; m.a_rs = p.a_rowscale;
@@ -537,98 +525,32 @@ int lavt_gemm_tn_grouped_pipe(const lavt_gemm_tn_t* probs, int n, hipStream_t st
         m.flags = (p.accumulate ? TNP_ACCUMULATE : 0) | (p.colsum_atomic ? TNP_COLSUM_ATOMIC : 0) | (no_b ? TNP_NO_B : 0) |
                   ((((uintptr_t)p.C & 15) == 0 && p.ldc % 4 == 0) ? TNP_VEC4 : 0) | TNP_WT;
         m.alpha = p.alpha;
-        m.part = nullptr; m.pieces = 1; m.kt_per = cdiv(p.K, 64);
-        base_tiles += m.tiles;
-        work += (long)m.tiles * cdiv(p.K, 64);
-    }
-    // K pieces.  A group whose 128x128 tiles fill the chip (>= tn_pipe_min_tiles: the stage-2 / stage-3 Swin-block groups) runs uncut: one writer per output,
-    // chains of <= 128 K tiles.  Otherwise (long reductions on few tiles: stage 0 / 1, PWAM's 1x1 convolutions) every member is cut into pieces of about
-    // work / 248 K tiles -- one round of workgroups of equal length -- through its partials scratch; a member without one keeps the group on the 64x64 launch.
-    int tiles = 0;
-    bool any_pieces = false, drop_rider = false;
-    int64_t max_total = 0;
-    if (base_tiles >= tun.tn_pipe_min_tiles) {
-        // (short reductions stay on the 64x64 launch: at 8 K tiles -- the last stage's 450 tokens, 792 tiles -- a workgroup that holds a CU alone spends more
-        // on its ring prologue and its 64 KB epilogue than on its K loop, and nothing else runs on the CU meanwhile: 54 us against 49)
-        if (work < (long)base_tiles * tun.tn_pipe_min_ktiles) return 1;
-        for (int i = 0; i < n; ++i) {
-            if (cdiv(probs[i].K, 64) > 128) return 1;
-            tiles += g.m[i].tiles;
-            g.m[i].tile_end = tiles;
-        }
-    } else {
-        if (tun.tn_pipe < 2) return 1;                            // LAVT_TN_PIPE=1: the uncut groups only
-        // ONE round of workgroups (a workgroup holds a CU: 128 KB of LDS), of equal length: the smallest piece length whose workgroup count stays inside the
-        // chip -- and leaves a fifth of it to the LayerNorm riders when the launch carries them (they would otherwise queue behind the tiles: +13 us at stage 0)
-        auto piece_len = [&](int budget) {
-            int l = (int)((work + budget - 1) / budget);
-            if (l < 8) l = 8;
-            for (;; ++l) {
-                long wgs = 0;
-                for (int i = 0; i < n; ++i) wgs += (long)g.m[i].tiles * cdiv(cdiv(probs[i].K, 64), l);
-                if (wgs <= budget || l >= 128) break;
-            }
-            return l;
-        };
-        int len = piece_len(ln ? 208 : 250);
-        if (ln != nullptr) {
-            // ... unless giving the riders their fifth costs more than their own launch: with the measured 0.8 us per K tile, a LayerNorm launch of
-            // ~4 us + its bytes at ~3 TB/s (Swin-T's stage 2 at 8 images: 117 tiles of 113 K tiles stay uncut under the rider budget -- 96 us -- and take
-            // 57 K tiles + the reduction without riders: 63 + 16 us).  The caller then launches the LayerNorm itself (return code 3).
-            const int len_free = piece_len(250);
-            const double ln_us = 4.0 + 6.0 * (double)ln->rows * ln->C / 3.0e6;
-            if (0.8 * len > 0.8 * len_free + ln_us + 1.0) { len = len_free; drop_rider = true; }
-        }
-        for (int i = 0; i < n; ++i) {
-            const lavt_gemm_tn_t& p = probs[i];
-            TnpMember& m = g.m[i];
-            const int kt = cdiv(p.K, 64);
-            int ns = cdiv(kt, len);
-            const int per = cdiv(kt, ns);
-            ns = cdiv(kt, per);                                   // no empty pieces
-            if (per > 128) return 1;
-            if (ns > 1) {
-                const int64_t need = (int64_t)ns * ((int64_t)p.I * m.J + p.I);
-                if (p.partials == nullptr || p.partials_floats < need) return 1;
-                m.part = p.partials; m.pieces = ns; m.kt_per = per;
-                if ((((uintptr_t)p.partials & 15) == 0) && ((int64_t)p.I * m.J) % 4 == 0 && m.J % 4 == 0) m.flags |= TNP_PART_VEC4;
-                any_pieces = true;
-                const int64_t tot = (int64_t)p.I * m.J + p.I;
-                max_total = max_total > tot ? max_total : tot;
-            }
-            tiles += m.tiles * ns;
-            m.tile_end = tiles;
-        }
-        if (tiles < 96 || tiles > 256) return 1;
+        m.part = r.parts[i] ? p.partials : nullptr; m.pieces = r.pieces[i]; m.kt_per = r.kt_per_piece[i];
+        if (r.parts[i] && (((uintptr_t)p.partials & 15) == 0) && ((int64_t)p.I * m.J) % 4 == 0 && m.J % 4 == 0) m.flags |= TNP_PART_VEC4;
+        tiles += m.tiles * m.pieces;
+        m.tile_end = tiles;
     }
     for (int i = n; i < TNP_MAX; ++i) { g.m[i] = g.m[0]; g.m[i].tile_end = tiles; g.m[i].pieces = 1; }
     g.n = n; g.tiles = tiles;
-    TnpRider r{};
-    int rider_wgs = 0, lpr = 0;
-    if (ln != nullptr && !drop_rider) {
-        int cpl, waves;
-        const int blocks = lavt_ln_bwd_geometry(LAVT_BF16, ln->rows, ln->C, &lpr, &cpl, &waves);
-        if (waves == 4 && cpl == 1 && (lpr == 16 || lpr == 32 || lpr == 64) && blocks > 0) {
-            r = TnpRider{(const bf16*)ln->dy, (const bf16*)ln->x, ln->gamma, ln->mean, ln->rstd, (bf16*)ln->dx, ln->partials, (const bf16*)ln->dres, ln->rows, ln->C, blocks};
-            rider_wgs = (blocks + 1) / 2;
-        } else lpr = 0;
+    LAVT_CHECK_ARG(r.launch == LAVT_TN_PIPE && tiles == r.workgroups && (r.rider != LAVT_TN_RIDER_RIDES || ln != nullptr),
+                   "lavt_gemm_tn_grouped(pipe): the route does not name this launch");
+    TnpRider lr{};
+    int lpr = 0;
+    if (r.rider == LAVT_TN_RIDER_RIDES) {
+        lr = TnpRider{(const bf16*)ln->dy, (const bf16*)ln->x, ln->gamma, ln->mean, ln->rstd, (bf16*)ln->dx, ln->partials, (const bf16*)ln->dres, ln->rows, ln->C, r.rider_blocks};
+        lpr = r.rider_lpr;
     }
-    const int stages = tun.tn_pipe_stages == 3 ? 3 : 4;
 #define TNP_GO(S_)                                                                                                    \
     do {                                                                                                              \
-        if (lpr == 64) tnp_launch<S_, 64>(g, r, rider_wgs, st);                                                       \
-        else if (lpr == 32) tnp_launch<S_, 32>(g, r, rider_wgs, st);                                                  \
-        else if (lpr == 16) tnp_launch<S_, 16>(g, r, rider_wgs, st);                                                  \
-        else tnp_launch<S_, 0>(g, r, 0, st);                                                                          \
+        if (lpr == 64) tnp_launch<S_, 64>(g, lr, r.rider_wgs, st);                                                    \
+        else if (lpr == 32) tnp_launch<S_, 32>(g, lr, r.rider_wgs, st);                                               \
+        else if (lpr == 16) tnp_launch<S_, 16>(g, lr, r.rider_wgs, st);                                               \
+        else tnp_launch<S_, 0>(g, lr, 0, st);                                                                         \
     } while (0)
-    if (stages == 3) TNP_GO(3); else TNP_GO(4);
+    if (r.stages == 3) TNP_GO(3); else TNP_GO(4);
 #undef TNP_GO
-    if (any_pieces) {
-        int max_ns = 1;
-        for (int i = 0; i < n; ++i) max_ns = max_ns > g.m[i].pieces ? max_ns : g.m[i].pieces;
-        if (max_ns > 8) hipLaunchKernelGGL(tnp_reduce_pieces_deep, dim3((unsigned)cdiv(max_total, 64), n), dim3(256), 0, st, g);
-        else hipLaunchKernelGGL(tnp_reduce_pieces, dim3((unsigned)cdiv(max_total, 1024), n), dim3(256), 0, st, g);
-    }
+    if (r.reducer == LAVT_TN_REDUCE_PIPE_DEEP) hipLaunchKernelGGL(tnp_reduce_pieces_deep, dim3((unsigned)r.reducer_grid_x, n), dim3(256), 0, st, g);
+    else if (r.reducer == LAVT_TN_REDUCE_PIPE) hipLaunchKernelGGL(tnp_reduce_pieces, dim3((unsigned)r.reducer_grid_x, n), dim3(256), 0, st, g);
     LAVT_CHECK_LAUNCH("lavt_gemm_tn_grouped(pipe)");
-    return (ln != nullptr && lpr == 0) ? 3 : LAVT_OK;
+    return LAVT_OK;
 }

@@ -544,9 +544,11 @@ __global__ __launch_bounds__(256) void tn_reduce_pieces(const float* __restrict_
     }
 }
 
-template <int BI, int BJ, int WAVES, int STAGES, bool MAPS, int CS, bool CONVP = !MAPS> int launch_tn_v2_(const lavt_gemm_tn_t& p, int split, hipStream_t st) {
-    if constexpr (CONVP && !MAPS) {          // (mapped problems are never convolutions: tn_v2_eligible) the map-free kernel without the tap state for plain problems
-        if (p.conv_kc <= 0 && !p.c_conv_permute) return launch_tn_v2_<BI, BJ, WAVES, STAGES, MAPS, CS, false>(p, split, st);
+// The launchers below decide nothing: lavt_gemm_tn_route / lavt_gemm_tn_group_route (gemm_tn_plan.hip) name tile, K loop, column-sum form, pieces,
+// write form and rider; here a route is mapped to its instantiation and the device structs are filled from it.
+template <int BI, int BJ, int WAVES, int STAGES, bool MAPS, int CS, bool CONVP = !MAPS> int launch_tn_v2_(const lavt_gemm_tn_t& p, const lavt_gemm_tn_route_t& r, hipStream_t st) {
+    if constexpr (CONVP && !MAPS) {          // the map-free kernel without the tap state for plain problems
+        if (!r.convp) return launch_tn_v2_<BI, BJ, WAVES, STAGES, MAPS, CS, false>(p, r, st);
     }
     constexpr size_t lds = STAGES * (size_t)(64 * (BI + BJ) * 2) + (MAPS ? (2 * (STAGES - 1) + 1) * 768 + 256 : 0);
     static bool attr_set = false;
@@ -557,34 +559,26 @@ template <int BI, int BJ, int WAVES, int STAGES, bool MAPS, int CS, bool CONVP =
         }
         attr_set = true;
     }
-    const int ktiles = cdiv(p.K, 64);
-    const int per = cdiv(ktiles, split);
-    dim3 grid(cdiv(p.I, BI) * cdiv(p.J, BJ), p.batch, cdiv(ktiles, per));
-    const int pieces = (int)grid.z;
-    // partial tiles instead of atomics when the caller lent scratch for them (plain problems only: no conv column permutation, batch 1)
-    const bool parts = pieces > 1 && p.partials && !p.c_conv_permute && p.partials_floats >= (int64_t)p.batch * pieces * ((int64_t)p.I * p.J + p.I);
-    if (!parts) {
-        lavt_gemm_tn_t q = p;
-        q.partials = nullptr;
-        hipLaunchKernelGGL((gemm_tn_v2_kernel<BI, BJ, WAVES, STAGES, MAPS, CS, CONVP>), grid, dim3(WAVES * 64), lds, st, q, per);
-    } else {
-        hipLaunchKernelGGL((gemm_tn_v2_kernel<BI, BJ, WAVES, STAGES, MAPS, CS, CONVP>), grid, dim3(WAVES * 64), lds, st, p, per);
+    dim3 grid(cdiv(p.I, BI) * cdiv(p.J, BJ), p.batch, r.pieces);
+    lavt_gemm_tn_t q = p;
+    if (r.write != LAVT_TN_PARTS) q.partials = nullptr;          // (the kernel stores partial tiles wherever it sees a scratch)
+    hipLaunchKernelGGL((gemm_tn_v2_kernel<BI, BJ, WAVES, STAGES, MAPS, CS, CONVP>), grid, dim3(WAVES * 64), lds, st, q, r.kt_per_piece);
+    if (r.write == LAVT_TN_PARTS) {
         const int64_t total = (int64_t)p.I * p.J + (p.colsum ? p.I : 0);
-        hipLaunchKernelGGL(tn_reduce_pieces, dim3((unsigned)cdiv(total, 64), p.batch), dim3(256), 0, st, p.partials, pieces, p.I, p.J, p.C, p.ldc, p.colsum, p.strideC, p.strideColsum);
+        hipLaunchKernelGGL(tn_reduce_pieces, dim3((unsigned)cdiv(total, 64), p.batch), dim3(256), 0, st, p.partials, r.pieces, p.I, p.J, p.C, p.ldc, p.colsum, p.strideC, p.strideColsum);
     }
     LAVT_CHECK_LAUNCH("lavt_gemm_tn(v2)");
     return LAVT_OK;
 }
-// two-stage ring only (3 / 4 stages cost a resident workgroup per CU and lost end to end in round 1: those instantiations are gone)
-template <int BI, int BJ, int WAVES> int launch_tn_v2(const lavt_gemm_tn_t& p, int split, hipStream_t st) {
-    const bool maps = p.a_rowmap || p.a_rowscale || p.b_rowmap;
-    // colsum on the matrix cores when the workgroups carrying it are a minority (>= 4 column tiles), the scalar walk otherwise; 128x128: scalar
-    const int cs = !p.colsum ? 0 : ((BI == 64 && cdiv(p.J, BJ) >= 4) ? 2 : 1);
+template <int BI, int BJ, int WAVES> int launch_tn_v2(const lavt_gemm_tn_t& p, const lavt_gemm_tn_route_t& r, hipStream_t st) {
+    const bool maps = r.maps;
     if constexpr (BI == 64) {
-        if (cs == 2) return maps ? launch_tn_v2_<BI, BJ, WAVES, 2, true, 2>(p, split, st) : launch_tn_v2_<BI, BJ, WAVES, 2, false, 2>(p, split, st);
+        if (r.colsum_form == 2) return maps ? launch_tn_v2_<BI, BJ, WAVES, 2, true, 2>(p, r, st) : launch_tn_v2_<BI, BJ, WAVES, 2, false, 2>(p, r, st);
     }
-    if (cs) return maps ? launch_tn_v2_<BI, BJ, WAVES, 2, true, 1>(p, split, st) : launch_tn_v2_<BI, BJ, WAVES, 2, false, 1>(p, split, st);
-    return maps ? launch_tn_v2_<BI, BJ, WAVES, 2, true, 0>(p, split, st) : launch_tn_v2_<BI, BJ, WAVES, 2, false, 0>(p, split, st);
+    if (r.colsum_form == 1) return maps ? launch_tn_v2_<BI, BJ, WAVES, 2, true, 1>(p, r, st) : launch_tn_v2_<BI, BJ, WAVES, 2, false, 1>(p, r, st);
+    if (r.colsum_form == 0) return maps ? launch_tn_v2_<BI, BJ, WAVES, 2, true, 0>(p, r, st) : launch_tn_v2_<BI, BJ, WAVES, 2, false, 0>(p, r, st);
+    lavt_set_error("lavt_gemm_tn(v2): the route names no instantiation (tile %d, column-sum form %d)", r.tile, r.colsum_form);
+    return LAVT_ERR_INVALID;
 }
 
 // the same for the members of a grouped launch that were cut into pieces through partial tiles: blockIdx.y = member
@@ -617,159 +611,66 @@ __global__ __launch_bounds__(256) void tn_reduce_pieces_group(const TnGroup g) {
 
 }  // namespace
 
-static bool tn_v2_eligible(const lavt_gemm_tn_t& p) {
-    if (p.dtype != LAVT_BF16 || p.zeros == nullptr) return false;
-    if (p.lda % 8 || p.ldb % 8 || (p.B2 && p.ldb2 % 8)) return false;
-    if (p.a_rowscale && !p.a_rowscale_binary) return false;
-    if ((p.a_rowmap || p.a_rowscale || p.b_rowmap) && (p.conv_kc > 0 || p.B2)) return false;      // the mapped K loop has no taps / second source
-    if ((int64_t)p.K * (p.lda > p.ldb ? p.lda : p.ldb) >= (1LL << 31)) return false;                // 32-bit element offsets
-    return true;
+// fills the group's device struct from its route; -> workgroups
+static int tn_fill_group(TnGroup& g, const lavt_gemm_tn_t* probs, int n, const lavt_gemm_tn_group_route_t& r, int tile) {
+    int tiles = 0;
+    for (int i = 0; i < TN_GROUP_MAX; ++i) {
+        g.p[i] = probs[i < n ? i : 0];
+        if (i >= n || !r.parts[i]) g.p[i].partials = nullptr;
+        g.split[i] = i < n ? r.pieces[i] : 1;
+        if (i < n) tiles += cdiv(g.p[i].I, tile) * cdiv(g.p[i].J, tile) * r.pieces[i];
+        g.tile_end[i] = tiles;
+    }
+    g.n = n;
+    return tiles;
 }
 
-// 1 when lavt_gemm_tn runs this problem on the LDS-DMA kernels of this file -- the only ones that honour a lent `partials` scratch.  Deterministic mode asks
-// before it lends one (lavt_hip.ops.gemm_tn): a problem that falls to gemm_tn_kernel must be told split_k = 1 instead.
-extern "C" int lavt_gemm_tn_v2_eligible(const lavt_gemm_tn_t* p) { return p != nullptr && tn_v2_eligible(*p) ? 1 : 0; }
-
-// returns 1 when the group cannot run as one launch (the caller then issues the problems one by one)
-// ln != NULL: a LayerNorm backward to run as rider workgroups of the launch; returns 3 when the group was launched WITHOUT it (the caller launches it)
-int lavt_gemm_tn_grouped_v2(const lavt_gemm_tn_t* probs, int n, hipStream_t st, const lavt_ln_rider_t* ln) {
-    if (n < 2 || n > TN_GROUP_MAX) return 1;
-    {   // short reductions on enough 128x128 tiles (the Swin-block groups of stages 2 / 3): the software-pipelined launch of gemm_tn_pipe.hip
-        const int rc = lavt_gemm_tn_grouped_pipe(probs, n, st, ln);
-        if (rc != 1) return rc;
-    }
+int lavt_gemm_tn_grouped_v2(const lavt_gemm_tn_t* probs, int n, const lavt_gemm_tn_group_route_t& r, hipStream_t st, const lavt_ln_rider_t* ln) {
+    static_assert(TN_GROUP_MAX == LAVT_TN_GROUP_MAX, "the route's per-member arrays");
     TnGroup g;
-    bool maps = false;
-    int tiles = 0;
-    // Tile configuration of the grouped launch: 64x64 tiles, 4 waves, 2-stage ring.
-    // (rectangular 64 x 128 / 128 x 64 tiles, 4 waves -- 24 KB per K tile for 1.05 MFLOP -- measured level with the square tile in round 4: 39.0 / 41.2 vs
-    // 39.0 us per stage-2 launch, 8.66 / 8.74 vs 8.56 ms per step; the instantiations are gone)
-    constexpr int TBI = 64, TBJ = 64;
-    bool any_colsum = false;
-    // Pieces per member.  A member with a partials scratch (lavt_gemm_tn_t.partials: its pieces are stored as plain tiles and added into C by one
-    // small second kernel) may be cut as finely as its K allows -- the long-K weight gradients of PWAM (K = 28 800 rows = 450 K tiles on 4
-    // output tiles each) then run as ONE launch of ~1000 workgroups instead of four launches of ~230 at one workgroup per CU; a member
-    // without one is cut into at most 4 pieces that meet through atomics (only if its C holds zeros: split_k < 0), and a chain of more than
-    // 128 K tiles without a scratch keeps the group from forming (it would run serially while the short members supply the tile count).
-    constexpr int chain = 48;          // 32 / 48 / 64 / 128: video step 23.16 / 22.93 / 22.82 / 22.87 ms, image step level
-    constexpr int piece_tiles = 8;
-    bool any_parts = false;
-    int64_t max_total = 0;
-    // ... and only where cutting pays: a group whose uncut 64x64 tiles already give every CU two workgroups (>= 512: the Swin-block launch at
-    // 4 images per GPU, K = 3600 = 57 K tiles) runs faster uncut -- 64.9 vs 88.4 us (tools/wgrad_sk_time.py) -- unless a chain exceeds 128 K tiles
-    long uncut = 0;
-    for (int i = 0; i < n; ++i) uncut += (long)cdiv(probs[i].I, TBI) * cdiv(probs[i].J, TBJ);
-    const bool cut_pays = uncut < 512;
-    for (int per_piece = piece_tiles; ; per_piece *= 2) {
-        tiles = 0; maps = false; any_colsum = false; any_parts = false; max_total = 0;
-        for (int i = 0; i < n; ++i) {
-            const lavt_gemm_tn_t& p = probs[i];
-            if (!tn_v2_eligible(p) || p.batch != 1 || p.conv_kc > 0 || p.B2 || p.I % 8 || p.J % 8) return 1;
-            const int ktiles = cdiv(p.K, 64);
-            maps = maps || p.a_rowmap || p.a_rowscale || p.b_rowmap;
-            any_colsum = any_colsum || p.colsum != nullptr;
-            g.p[i] = p;
-            int ns = 1;
-            const int want = cdiv(ktiles, per_piece);
-            const bool parts = p.partials != nullptr && !p.c_conv_permute && ktiles > chain && (cut_pays || ktiles > 128) && want > 1 &&
-                               p.partials_floats >= (int64_t)want * ((int64_t)p.I * p.J + p.I);
-            if (parts) ns = want;
-            else {
-                g.p[i].partials = nullptr;
-                if (ktiles > 128) return 1;
-                // (a group whose uncut tiles already give every CU two workgroups is not cut through atomics either: at 4 images per GPU -- K = 3600 = 57 K tiles --
-                // two atomic pieces per tile cost 12.60 vs 12.34 ms per step, and a plainly stored gradient needs no zero fill: engine.TrainStep)
-                ns = (p.split_k < 0 && cut_pays) ? cdiv(ktiles, chain) : 1;
-                if (ns > 4) ns = 4;
-            }
-            const int per = cdiv(ktiles, ns);
-            ns = cdiv(ktiles, per);                      // no empty pieces
-            if (parts && ns > 1) { any_parts = true; max_total = max_total > (int64_t)p.I * p.J + p.I ? max_total : (int64_t)p.I * p.J + p.I; }
-            if (ns <= 1) g.p[i].partials = nullptr;
-            g.split[i] = ns;
-            tiles += cdiv(p.I, TBI) * cdiv(p.J, TBJ) * ns;
-            g.tile_end[i] = tiles;
-        }
-        if (tiles <= 2048 || !any_parts || per_piece >= 64) break;      // too many workgroups: longer pieces
-    }
-    for (int i = n; i < TN_GROUP_MAX; ++i) { g.p[i] = probs[0]; g.p[i].partials = nullptr; g.tile_end[i] = tiles; g.split[i] = 1; }
-    g.n = n;
-    if (tiles < 256) return 1;   // too few workgroups to fill the chip
-    // (round 2: an XCD-contiguous tile order inside each member -- it cuts the 152 MB of fabric traffic -- and a 3-stage ring were both measured
-    // on the step: 10.63 vs 10.64 ms and 10.81 vs 10.62 ms; neither is kept)
+    const int tiles = tn_fill_group(g, probs, n, r, 64);
+    const bool maps = r.maps;
     const size_t lds = 2 * (size_t)(64 * (64 + 64) * 2) + (maps ? 3 * 768 + 256 : 0);
-    if (ln != nullptr && any_colsum) {
-        int lpr, cpl, waves;
-        const int blocks = lavt_ln_bwd_geometry(LAVT_BF16, ln->rows, ln->C, &lpr, &cpl, &waves);
-        LnRider r{(const bf16*)ln->dy, (const bf16*)ln->x, ln->gamma, ln->mean, ln->rstd, (bf16*)ln->dx, ln->partials, (const bf16*)ln->dres, ln->rows, ln->C, blocks};
-        bool rode = true;
+    const bool rides = r.rider == LAVT_TN_RIDER_RIDES;
+    LAVT_CHECK_ARG(r.launch == LAVT_TN_GROUP64 && tiles == r.workgroups && (rides ? ln && r.colsum_form == 2 && (r.rider_lpr == 16 || r.rider_lpr == 32 || r.rider_lpr == 64)
+                                                                                   : r.colsum_form == 0 || r.colsum_form == 2),
+                   "lavt_gemm_tn_grouped(v2): the route names no instantiation");
+    if (rides) {
+        const int blocks = r.rider_blocks;
+        LnRider lr{(const bf16*)ln->dy, (const bf16*)ln->x, ln->gamma, ln->mean, ln->rstd, (bf16*)ln->dx, ln->partials, (const bf16*)ln->dres, ln->rows, ln->C, blocks};
 #define TNG_LN(LPR_, CPL_)                                                                                                                            \
     do {                                                                                                                                               \
-        if (maps) hipLaunchKernelGGL((gemm_tn_v2_grouped_ln_kernel<true, 2, LPR_, CPL_>), dim3(tiles + blocks), dim3(256), lds, st, g, tiles, r);      \
-        else hipLaunchKernelGGL((gemm_tn_v2_grouped_ln_kernel<false, 2, LPR_, CPL_>), dim3(tiles + blocks), dim3(256), lds, st, g, tiles, r);          \
+        if (maps) hipLaunchKernelGGL((gemm_tn_v2_grouped_ln_kernel<true, 2, LPR_, CPL_>), dim3(tiles + blocks), dim3(256), lds, st, g, tiles, lr);     \
+        else hipLaunchKernelGGL((gemm_tn_v2_grouped_ln_kernel<false, 2, LPR_, CPL_>), dim3(tiles + blocks), dim3(256), lds, st, g, tiles, lr);         \
     } while (0)
-        if (waves != 4 || (size_t)3 * lpr * cpl * 8 * 4 > lds) rode = false;
-        else if (lpr == 16 && cpl == 1) TNG_LN(16, 1);
-        else if (lpr == 32 && cpl == 1) TNG_LN(32, 1);
-        else if (lpr == 64 && cpl == 1) TNG_LN(64, 1);
-        else rode = false;          // (C = 1024: two chunks per lane need 164 registers -- a fourth workgroup per CU no longer fits; the two stage-3 blocks launch it on its own)
+        if (r.rider_lpr == 16) TNG_LN(16, 1);
+        else if (r.rider_lpr == 32) TNG_LN(32, 1);
+        else TNG_LN(64, 1);
 #undef TNG_LN
-        if (rode) {
-            if (any_parts) hipLaunchKernelGGL(tn_reduce_pieces_group, dim3((unsigned)cdiv(max_total, 64), n), dim3(256), 0, st, g);
-            LAVT_CHECK_LAUNCH("lavt_gemm_tn_grouped_ln(v2)");
-            return LAVT_OK;
-        }
-    }
-    if (any_colsum) {
+    } else if (r.colsum_form == 2) {
         if (maps) hipLaunchKernelGGL((gemm_tn_v2_grouped_kernel<64, 64, 4, 2, true, 2>), dim3(tiles), dim3(256), lds, st, g);
         else hipLaunchKernelGGL((gemm_tn_v2_grouped_kernel<64, 64, 4, 2, false, 2>), dim3(tiles), dim3(256), lds, st, g);
     } else {
         if (maps) hipLaunchKernelGGL((gemm_tn_v2_grouped_kernel<64, 64, 4, 2, true, 0>), dim3(tiles), dim3(256), lds, st, g);
         else hipLaunchKernelGGL((gemm_tn_v2_grouped_kernel<64, 64, 4, 2, false, 0>), dim3(tiles), dim3(256), lds, st, g);
     }
-    if (any_parts) hipLaunchKernelGGL(tn_reduce_pieces_group, dim3((unsigned)cdiv(max_total, 64), n), dim3(256), 0, st, g);
+    if (r.reducer == LAVT_TN_REDUCE_GROUP) hipLaunchKernelGGL(tn_reduce_pieces_group, dim3((unsigned)r.reducer_grid_x, n), dim3(256), 0, st, g);
     LAVT_CHECK_LAUNCH("lavt_gemm_tn_grouped(v2)");
-    return ln ? 3 : LAVT_OK;
+    return LAVT_OK;
 }
 
-// ---- stream-K grouped launch: host side.  sk_plan fills g / sk and returns the scratch floats needed (0 = the group does not qualify).
-static int64_t sk_plan(const lavt_gemm_tn_t* probs, int n, TnGroup& g, TnSk& sk, bool& maps, bool& any_colsum) {
-    constexpr int TB = 128;
-    if (n < 2 || n > TN_GROUP_MAX) return 0;
-    maps = false; any_colsum = false;
-    int its = 0, tiles = 0;
-    for (int i = 0; i < n; ++i) {
-        const lavt_gemm_tn_t& p = probs[i];
-        if (!tn_v2_eligible(p) || p.batch != 1 || p.conv_kc > 0 || p.B2 || p.I % 8 || p.J % 8 || p.c_conv_permute) return 0;
-        const int kt = cdiv(p.K, 64), t = cdiv(p.I, TB) * cdiv(p.J, TB);
-        maps = maps || p.a_rowmap || p.a_rowscale || p.b_rowmap;
-        any_colsum = any_colsum || p.colsum != nullptr;
-        g.p[i] = p;
-        g.p[i].partials = nullptr;
-        g.split[i] = 1;
-        its += t * kt; tiles += t;
-        sk.it_end[i] = its; sk.kt[i] = kt; sk.tiles_end[i] = tiles;
-        g.tile_end[i] = tiles;
+// ---- stream-K grouped launch: host side
+int lavt_gemm_tn_grouped_sk_v2(const lavt_gemm_tn_t* probs, int n, const lavt_gemm_tn_group_route_t& r, float* scratch, hipStream_t st) {
+    TnGroup g; TnSk sk;
+    int its = 0;
+    const int tiles = tn_fill_group(g, probs, n, r, 128);          // (r.pieces = 1, r.parts = 0: members' `partials` are ignored)
+    for (int i = 0; i < TN_GROUP_MAX; ++i) {
+        sk.kt[i] = i < n ? r.kt_per_piece[i] : 1;
+        if (i < n) its += (g.tile_end[i] - (i ? g.tile_end[i - 1] : 0)) * sk.kt[i];
+        sk.it_end[i] = its; sk.tiles_end[i] = g.tile_end[i];
     }
-    for (int i = n; i < TN_GROUP_MAX; ++i) { g.p[i] = probs[0]; g.p[i].partials = nullptr; g.tile_end[i] = tiles; g.split[i] = 1; sk.it_end[i] = its; sk.kt[i] = 1; sk.tiles_end[i] = tiles; }
-    g.n = n;
-    // worth it when the 128x128 tiles alone cannot fill the chip in whole rounds but there is enough work for every run to amortise its ring
-    // prologue (>= 6 K tiles per run) -- the Swin-block launches of stages 1-3; many-tile members (stage 0: K = 28 800) keep the piece form
-    int nw = 512;
-    if (its / nw < 6) nw = its / 6;
-    if (nw < 128 || tiles < 32) return 0;
-    sk.total = its; sk.nw = nw;
-    return (int64_t)nw * 2 * (TB * TB + TB);
-}
-int64_t lavt_gemm_tn_grouped_sk_ws_v2(const lavt_gemm_tn_t* probs, int n) {
-    TnGroup g; TnSk sk; bool maps, cs;
-    return sk_plan(probs, n, g, sk, maps, cs);
-}
-int lavt_gemm_tn_grouped_sk_v2(const lavt_gemm_tn_t* probs, int n, float* scratch, int64_t scratch_floats, hipStream_t st) {
-    TnGroup g; TnSk sk; bool maps, any_colsum;
-    const int64_t need = sk_plan(probs, n, g, sk, maps, any_colsum);
-    if (need == 0 || scratch == nullptr || scratch_floats < need) return 1;
-    sk.slots = scratch;
+    sk.total = its; sk.nw = r.workgroups; sk.slots = scratch;
+    const bool maps = r.maps;
     const size_t lds = 2 * (size_t)(64 * (128 + 128) * 2) + (maps ? 3 * 768 + 256 : 0);
 #define SK_GO(MAPS_, CS_)                                                                                                                              \
     do {                                                                                                                                               \
@@ -780,40 +681,16 @@ int lavt_gemm_tn_grouped_sk_v2(const lavt_gemm_tn_t* probs, int n, float* scratc
         }                                                                                                                                              \
         hipLaunchKernelGGL((gemm_tn_v2_streamk_kernel<128, 128, 8, 2, MAPS_, CS_>), dim3(sk.nw), dim3(512), lds, st, g, sk);                           \
     } while (0)
-    if (any_colsum) { if (maps) SK_GO(true, 1); else SK_GO(false, 1); }          // (scalar column sums: the matrix-core form costs 16 accumulator registers the 128-register tile does not have)
+    LAVT_CHECK_ARG(r.launch == LAVT_TN_SK && r.colsum_form <= 1 && sk.nw >= 1, "lavt_gemm_tn_grouped_sk: the route names no instantiation");
+    if (r.colsum_form == 1) { if (maps) SK_GO(true, 1); else SK_GO(false, 1); }
     else { if (maps) SK_GO(true, 0); else SK_GO(false, 0); }
 #undef SK_GO
-    hipLaunchKernelGGL((tn_streamk_fixup<128, 128>), dim3(sk.tiles_end[n - 1], 4), dim3(256), 0, st, g, sk);
+    hipLaunchKernelGGL((tn_streamk_fixup<128, 128>), dim3(tiles, 4), dim3(256), 0, st, g, sk);
     LAVT_CHECK_LAUNCH("lavt_gemm_tn_grouped_sk");
     return LAVT_OK;
 }
 
-int lavt_gemm_tn_v2(const lavt_gemm_tn_t& p, hipStream_t st) {
-    if (p.dtype != LAVT_BF16 || p.zeros == nullptr) return 1;
-    if (!tn_v2_eligible(p)) return 1;                            // (only 0 / constant row masks can be folded into the row fetch)
-    // Measured (tools/gemm_bench.py tn): the 64x64 / 4-wave tile wins on every weight-gradient shape of the step, the conv wgrads included
-    // (369 vs 230 TF/s for 128x128); the split-K factor trades workgroup count (latency hiding) against fp32 atomic traffic.
-    const int force = lavt_tuning().gemm_tile;
-    const int ktiles = cdiv(p.K, 64);
-    const long tiles64 = (long)cdiv(p.I, 64) * cdiv(p.J, 64) * p.batch;
-    const long tiles128 = (long)cdiv(p.I, 128) * cdiv(p.J, 128) * p.batch;
-    // conv weight gradients (long K, >= 48 tiles of 128x128 -- the Swin-T decoder's 384-channel convolutions have 102): the larger tile halves the
-    // L2->LDS bytes per MFMA (measured 303 vs 357 us on Swin-B's; 16.9 -> 16.1 ms per Swin-T step)
-    constexpr int TN_BIG_MIN = 48;
-    const bool big = force ? force == 128 : (p.conv_kc > 0 && tiles128 >= TN_BIG_MIN && ktiles >= 64);
-    const long tiles = big ? tiles128 : tiles64;
-    int split = p.split_k;
-    if (split <= 0) {
-        constexpr int target = 768;
-        split = big ? (int)((384 + tiles / 2) / tiles) : (int)((target + tiles / 2) / tiles);      // ~3 (64-tile) / ~1.5 (128-tile) workgroups per CU
-        const int long_k = (ktiles + 127) / 128;          // no workgroup walks more than ~128 K tiles
-        if (split < long_k) split = long_k;
-        const int min_kt = p.batch > 1 ? 2 : 8;          // (as lavt_gemm_tn_pieces: batched problems down to 2 K tiles per piece)
-        const int max_split = (ktiles + min_kt - 1) / min_kt;           // >= 8 K tiles per workgroup (2 for batched problems)
-        if (split > max_split) split = max_split;
-        if (split < 1) split = 1;
-    }
-    if (split > ktiles) split = ktiles;
-    if (big) return launch_tn_v2<128, 128, 8>(p, split, st);
-    return launch_tn_v2<64, 64, 4>(p, split, st);
+int lavt_gemm_tn_v2(const lavt_gemm_tn_t& p, const lavt_gemm_tn_route_t& r, hipStream_t st) {
+    if (r.tile == 128) return launch_tn_v2<128, 128, 8>(p, r, st);
+    return launch_tn_v2<64, 64, 4>(p, r, st);
 }

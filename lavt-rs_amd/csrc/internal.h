@@ -25,25 +25,18 @@ static inline int lavt_nt_reserve_lds(bool* reserved, const void* kernel, size_t
 }
 
 // ---- TN family ----------------------------------------------------------------------------------------------------------------------------------------
-// gemm_tn_v2.hip: bf16 LDS-DMA kernel.  Returns 1 when the problem is not for this kernel (the caller falls back to gemm.hip).
-int lavt_gemm_tn_v2(const lavt_gemm_tn_t& p, hipStream_t st);
+// gemm_tn_plan.hip (lavt_gemm_tn_route / lavt_gemm_tn_group_route, include/lavt_hip.h) decides kernel, pieces, write form and rider; gemm.hip launches
+// what the route names.  The launchers below fill their device structs from a route of theirs and map it to an instantiation (a route naming no
+// instantiation is LAVT_ERR_INVALID: the planner makes none).
+int lavt_gemm_tn_v2(const lavt_gemm_tn_t& p, const lavt_gemm_tn_route_t& r, hipStream_t st);          // gemm_tn_v2.hip: LAVT_TN_V2
 
-// A LayerNorm backward (the partial-sum form of lavt_layernorm_bwd_partial, bf16, no gather) offered to a grouped weight-gradient launch to run as
-// rider workgroups.  Passed by pointer between gemm.hip, gemm_tn_v2.hip and gemm_tn_pipe.hip.
+// A LayerNorm backward (the partial-sum form of lavt_layernorm_bwd_partial, bf16, no gather) offered to a grouped weight-gradient launch; it runs as
+// rider workgroups of the launch where the route says LAVT_TN_RIDER_RIDES.  Passed by pointer between gemm.hip, gemm_tn_v2.hip and gemm_tn_pipe.hip.
 struct lavt_ln_rider_t { const void* dy; const void* x; const float* gamma; const float* mean; const float* rstd; void* dx; float* partials; const void* dres; int rows, C; };
 
-// gemm_tn_v2.hip: n independent weight-gradient problems as one grouped launch without split-K when they qualify (bf16, plain / row-mapped operands,
-// >= 256 output tiles in total).  Returns 1 when the group cannot run as one launch (the caller then issues the problems one by one).
-// ln != NULL: a LayerNorm backward to run as rider workgroups of the launch; returns 3 when the group was launched WITHOUT it (the caller launches it).
-int lavt_gemm_tn_grouped_v2(const lavt_gemm_tn_t* probs, int n, hipStream_t st, const lavt_ln_rider_t* ln);
-// gemm_tn_pipe.hip: the grouped weight-gradient launch on 128x128 pipelined tiles.  Returns 1 when the group does not qualify (the caller takes
-// gemm_tn_v2.hip's launch), LAVT_OK when it was launched (with the LayerNorm rider if `ln` was given), 3 when it was launched WITHOUT the rider it was offered.
-int lavt_gemm_tn_grouped_pipe(const lavt_gemm_tn_t* probs, int n, hipStream_t st, const lavt_ln_rider_t* ln);
-// The stream-K form of the grouped launch (gemm_tn_v2.hip): 128x128 tiles, the K-tile iterations of all members dealt in equal runs to persistent
-// workgroups, split tiles through `scratch`.  _ws: floats of scratch the group wants, 0 = the group does not qualify (use lavt_gemm_tn_grouped).
-// _sk_v2 returns 1 when the group does not qualify or the scratch is too small.
-int64_t lavt_gemm_tn_grouped_sk_ws_v2(const lavt_gemm_tn_t* probs, int n);
-int lavt_gemm_tn_grouped_sk_v2(const lavt_gemm_tn_t* probs, int n, float* scratch, int64_t scratch_floats, hipStream_t st);
+int lavt_gemm_tn_grouped_v2(const lavt_gemm_tn_t* probs, int n, const lavt_gemm_tn_group_route_t& r, hipStream_t st, const lavt_ln_rider_t* ln);          // gemm_tn_v2.hip: LAVT_TN_GROUP64
+int lavt_gemm_tn_grouped_pipe(const lavt_gemm_tn_t* probs, int n, const lavt_gemm_tn_group_route_t& r, hipStream_t st, const lavt_ln_rider_t* ln);        // gemm_tn_pipe.hip: LAVT_TN_PIPE
+int lavt_gemm_tn_grouped_sk_v2(const lavt_gemm_tn_t* probs, int n, const lavt_gemm_tn_group_route_t& r, float* scratch, hipStream_t st);                  // gemm_tn_v2.hip: LAVT_TN_SK
 
 // ---- LayerNorm backward (norm.hip) --------------------------------------------------------------------------------------------------------------------
 // geometry of the plain (no gather, no xn output) partial-sum form, for the grouped weight-gradient launch that runs it in rider workgroups

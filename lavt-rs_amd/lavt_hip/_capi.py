@@ -151,6 +151,30 @@ class GemmTN(C.Structure):
     ]
 
 
+class GemmTNRoute(C.Structure):
+    """lavt_gemm_tn_route_t: what lavt_gemm_tn launches for a problem (lavt_gemm_tn_route, csrc/gemm_tn_plan.hip)"""
+    _fields_ = [("family", i32), ("dtype", i32), ("tile", i32), ("waves", i32), ("maps", i32), ("colsum_form", i32), ("convp", i32), ("kt_per_piece", i32),
+                ("pieces", i32), ("write", i32)]
+
+
+TN_GROUP_MAX = 6
+
+
+class GemmTNGroupRoute(C.Structure):
+    """lavt_gemm_tn_group_route_t: what a grouped weight-gradient entry launches for n problems (lavt_gemm_tn_group_route)"""
+    _fields_ = [("launch", i32), ("stages", i32), ("maps", i32), ("colsum_form", i32), ("workgroups", i32), ("pieces", i32 * TN_GROUP_MAX),
+                ("kt_per_piece", i32 * TN_GROUP_MAX), ("parts", i32 * TN_GROUP_MAX), ("any_parts", i32), ("reducer", i32), ("reducer_grid_x", i32),
+                ("rider", i32), ("rider_lpr", i32), ("rider_blocks", i32), ("rider_wgs", i32), ("scratch_floats", i64)]
+
+
+TN_CLASSIC, TN_V2 = 0, 1                                                   # GemmTNRoute.family
+TN_STORE, TN_ATOMIC, TN_PARTS = 0, 1, 2                                    # .write
+TN_ENTRY_GROUPED, TN_ENTRY_SK = 0, 1                                       # lavt_gemm_tn_group_route(entry)
+TN_EACH, TN_GROUP64, TN_PIPE, TN_SK = 0, 1, 2, 3                           # GemmTNGroupRoute.launch
+TN_REDUCE_NONE, TN_REDUCE_GROUP, TN_REDUCE_PIPE, TN_REDUCE_PIPE_DEEP = 0, 1, 2, 3     # .reducer
+TN_RIDER_NONE, TN_RIDER_RIDES, TN_RIDER_AFTER = 0, 1, 2                    # .rider
+
+
 class PPItem(C.Structure):
     """lavt_pp_item_t: one output frame of the batched input stage (64 bytes; lavt_hip.preprocess.ITEM_DTYPE is the numpy form the blob is packed with)"""
     _fields_ = [("src_off", i64), ("mask_off", i64), ("Hs", i32), ("Ws", i32), ("coef_x", i32), ("bounds_x", i32), ("ksize_x", i32),
@@ -170,6 +194,8 @@ _PROTOTYPES = {
     "lavt_droppath_factors": [vp, vp, vp, i32, i32, vp],
     "lavt_droppath_draw": [vp, vp, vp, i32, i32, vp],
     "lavt_conv3x3_wgrad_ws": [i32, i32, i32, i32, i32, i32],
+    "lavt_gemm_tn_route": [C.POINTER(GemmTN), C.POINTER(GemmTNRoute)],
+    "lavt_gemm_tn_group_route": [C.POINTER(GemmTN), i32, i32, i32, i32, C.POINTER(GemmTNGroupRoute)],
     "lavt_gemm_tn_grouped_ln": [C.POINTER(GemmTN), i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, vp],
     "lavt_gemm_tn_grouped_sk_ws": [C.POINTER(GemmTN), i32],
     "lavt_gemm_tn_grouped_sk": [C.POINTER(GemmTN), i32, vp, i64, vp],
@@ -336,7 +362,7 @@ _cdll.lavt_upsample_iu_ws.restype = C.c_int64
 _cdll.lavt_reduce_partials_det_stage.restype = C.c_int64
 _cdll.lavt_window_attn_bwd_det_ws.restype = C.c_int64
 _cdll.lavt_last_error.argtypes = []
-for _name in ("lavt_last_error", "lavt_window_attn_bwd_ws", "lavt_window_attn_stream_ok", "lavt_window_attn_stream_bwd_ws", "lavt_attn_uses_table", "lavt_abi_version", "lavt_layernorm_bwd_blocks", "lavt_window_attn_bwd_pieces", "lavt_gemm_tn_pieces", "lavt_pwam_q_parts", "lavt_pwam_words_records", "lavt_pwam_mix1_records", "lavt_adamw_chunk_elems", "lavt_tuning_reload", "lavt_conv3x3_wgrad_ws", "lavt_conv3x3_wgrad_f8_ok", "lavt_gemm_tn_grouped_sk_ws", "lavt_gemm_nt_colstats_plan", "lavt_gemm_nt_route", "lavt_cls_head_bwd_blocks", "lavt_reduce_partials_column_blocks", "lavt_grad_norm_ws", "lavt_upsample_dice_boundary_ws", "lavt_upsample_iu_ws", "lavt_reduce_partials_det_stage", "lavt_window_attn_bwd_det_ws", "lavt_gemm_tn_v2_eligible", "lavt_meter_bytes", "lavt_eval_meter_bytes"):      # queries, not launches: never timed
+for _name in ("lavt_last_error", "lavt_window_attn_bwd_ws", "lavt_window_attn_stream_ok", "lavt_window_attn_stream_bwd_ws", "lavt_attn_uses_table", "lavt_abi_version", "lavt_layernorm_bwd_blocks", "lavt_window_attn_bwd_pieces", "lavt_gemm_tn_pieces", "lavt_pwam_q_parts", "lavt_pwam_words_records", "lavt_pwam_mix1_records", "lavt_adamw_chunk_elems", "lavt_tuning_reload", "lavt_conv3x3_wgrad_ws", "lavt_conv3x3_wgrad_f8_ok", "lavt_gemm_tn_grouped_sk_ws", "lavt_gemm_nt_colstats_plan", "lavt_gemm_nt_route", "lavt_gemm_tn_route", "lavt_gemm_tn_group_route", "lavt_cls_head_bwd_blocks", "lavt_reduce_partials_column_blocks", "lavt_grad_norm_ws", "lavt_upsample_dice_boundary_ws", "lavt_upsample_iu_ws", "lavt_reduce_partials_det_stage", "lavt_window_attn_bwd_det_ws", "lavt_gemm_tn_v2_eligible", "lavt_meter_bytes", "lavt_eval_meter_bytes"):      # queries, not launches: never timed
     setattr(lib, _name, getattr(_cdll, _name))
 
 EXPORTED = tuple(_PROTOTYPES) + ("lavt_last_error",)

@@ -670,29 +670,48 @@ def gemm_nt(dtype, M, N, Kd, A, lda, B, ldb, Cout, ldc, *, want_colstats=False, 
     return stats
 
 
-def gemm_tn(dtype, I, J, Kd, A, lda, B, ldb, Cout, ldc, *, batch=1, strideA=0, strideB=0, strideC=0, a_rowmap=None,
-            a_rowscale=None, a_rowscale_div=1, a_rowscale_binary=False, accumulate=False, B2=None, ldb2=0, b_split=0, b_rowmap=None, conv=None, alpha=1.0, c_conv_permute=False, colsum=None,
-            strideColsum=0, a_off=0, b_off=0, c_off=0, defer=None, colsum_atomic=False, extra=False, rider=None):
+def gemm_tn_params(dtype, I, J, Kd, A, lda, B, ldb, Cout, ldc, *, batch=1, strideA=0, strideB=0, strideC=0, a_rowmap=None,
+                   a_rowscale=None, a_rowscale_div=1, a_rowscale_binary=False, accumulate=False, B2=None, ldb2=0, b_split=0, b_rowmap=None, conv=None, alpha=1.0,
+                   c_conv_permute=False, colsum=None, strideColsum=0, a_off=0, b_off=0, c_off=0, colsum_atomic=False, a_src_rows=None, b_src_rows=None,
+                   addr=K.ptr, zeros=None):
+    """The lavt_gemm_tn_t of a launch, without the split plan (split_k = 0, no partials: gemm_tn sets them).  A/B/Cout are tensors; *_off are element
+    offsets into them.  a_src_rows / b_src_rows: rows a row map may name (default: the rows of the tensor).  addr: operand -> device address
+    (None -> NULL); zeros: address of the zero page (default: the page of A's device).  The host tests that ask lavt_gemm_tn_route /
+    lavt_gemm_tn_group_route about a problem pass made-up addresses through both, and the row counts."""
     es = 4 if dtype == torch.float32 else 2
-    assert Cout.dtype == torch.float32
     p = K.GemmTN()
     p.dtype, p.I, p.J, p.K, p.batch = K.dt(dtype), I, J, Kd, batch
-    p.A, p.lda, p.strideA, p.a_rowmap = K.ptr(A) + a_off * es, lda, strideA, K.ptr(a_rowmap)
-    p.a_rowscale, p.a_rowscale_div = K.ptr(a_rowscale), a_rowscale_div
+    p.A, p.lda, p.strideA, p.a_rowmap = addr(A) + a_off * es, lda, strideA, addr(a_rowmap)
+    p.a_rowscale, p.a_rowscale_div = addr(a_rowscale), a_rowscale_div
     p.a_rowscale_binary, p.accumulate = int(a_rowscale_binary), int(accumulate)
-    p.B, p.ldb, p.strideB = K.ptr(B) + b_off * es, ldb, strideB
-    p.B2, p.ldb2, p.b_split, p.b_rowmap = K.ptr(B2), ldb2, b_split, K.ptr(b_rowmap)
+    p.B, p.ldb, p.strideB = addr(B) + b_off * es, ldb, strideB
+    p.B2, p.ldb2, p.b_split, p.b_rowmap = addr(B2), ldb2, b_split, addr(b_rowmap)
     if conv is not None:
         p.conv_h, p.conv_w, p.conv_kc = conv[:3]
         if len(conv) > 3:
             p.conv_d, p.conv_kd, p.conv_kh, p.conv_kw = conv[3:7]
-    p.alpha, p.C, p.ldc, p.strideC = alpha, K.ptr(Cout) + c_off * 4, ldc, strideC
-    p.c_conv_permute = int(c_conv_permute)          # (split_k: tn_plan below -- deferred = into the zeroed flat gradient buffer: a grouped launch may split K)
-    p.colsum, p.strideColsum, p.colsum_atomic = K.ptr(colsum), strideColsum, int(colsum_atomic)
+    p.alpha, p.C, p.ldc, p.strideC = alpha, addr(Cout) + c_off * 4, ldc, strideC
+    p.c_conv_permute = int(c_conv_permute)
+    p.colsum, p.strideColsum, p.colsum_atomic = addr(colsum), strideColsum, int(colsum_atomic)
     # rows a row map may name (the pipelined grouped kernel bounds its 32-bit descriptor offsets with them)
-    p.a_src_rows = (A.shape[0] if A.dim() >= 2 else A.numel() // max(lda, 1)) if a_rowmap is not None else 0
-    p.b_src_rows = (B.shape[0] if B.dim() >= 2 else B.numel() // max(ldb, 1)) if b_rowmap is not None else 0
-    p.zeros = _zero_page(A.device)
+    rows_of = lambda t, ld: t.shape[0] if t.dim() >= 2 else t.numel() // max(ld, 1)
+    if a_rowmap is not None:
+        p.a_src_rows = rows_of(A, lda) if a_src_rows is None else a_src_rows
+    if b_rowmap is not None:
+        p.b_src_rows = rows_of(B, ldb) if b_src_rows is None else b_src_rows
+    p.zeros = _zero_page(A.device) if zeros is None else zeros
+    return p
+
+
+def gemm_tn(dtype, I, J, Kd, A, lda, B, ldb, Cout, ldc, *, batch=1, conv=None, a_rowmap=None, a_rowscale=None, b_rowmap=None, colsum=None, defer=None, extra=False,
+            rider=None, **kw):
+    """One lavt_gemm_tn launch, or (defer) one member queued for a grouped launch; kw: the keyword arguments of gemm_tn_params, which documents them (the
+    address overrides excepted: tensors only).  split_k and the partials scratch follow tn_plan (deferred = into the zeroed flat gradient buffer: a
+    grouped launch may split K)."""
+    if "addr" in kw or "zeros" in kw:
+        raise TypeError("gemm_tn launches on tensors; addr= / zeros= belong to gemm_tn_params")
+    assert Cout.dtype == torch.float32
+    p = gemm_tn_params(dtype, I, J, Kd, A, lda, B, ldb, Cout, ldc, batch=batch, conv=conv, a_rowmap=a_rowmap, a_rowscale=a_rowscale, b_rowmap=b_rowmap, colsum=colsum, **kw)
     det = deterministic()
     v2_ok = bool(K.lib.lavt_gemm_tn_v2_eligible(C.byref(p))) if det else False          # the launches that honour a lent scratch: the library's own rule
     # scratch for split reductions through partial tiles (long-K weight gradients on few output tiles: PWAM's 1x1 convolutions over 28 800 rows;

@@ -24,9 +24,11 @@ powers of two (or 0), so that rounding is exact and the floor needs no model of 
 source rows no map entry names, the rows at and beyond K, the gap between batch entries; C and colsum carry NaN in everything the kernel does not own.
 Rows masked by a zero row scale hold finite values (a kernel may read and multiply them).
 
-`tn_route(case_or_group, tuning)` restates lavt_gemm_tn / dispatch_tn / launch_tn (csrc/gemm.hip), tn_v2_eligible / lavt_gemm_tn_v2 / launch_tn_v2 /
-lavt_gemm_tn_grouped_v2 / sk_plan (csrc/gemm_tn_v2.hip), lavt_gemm_tn_grouped_pipe (csrc/gemm_tn_pipe.hip) and cw_supported / cw_pieces and the fp8
-launcher's piece rounding (csrc/conv_wgrad.hip).  Every row of the table states the route it is there for; the host test holds `tn_route` to it."""
+`tn_route(case_or_group, tuning)` restates the family's planner, csrc/gemm_tn_plan.hip: lavt_gemm_tn_route (the contract checks, tn_v2_eligible, both
+tile and split rules) and lavt_gemm_tn_group_route (tn_route_pipe, tn_route_group64, tn_route_sk), and cw_supported / cw_pieces and the fp8 launcher's
+piece rounding (csrc/conv_wgrad.hip).  Every row of the table states the route it is there for; test_gemm_tn_cases_host.py holds `tn_route` to it and
+test_gemm_tn_route_host.py holds it to the library's own answer.  `launch_args(case, buf)` is the one way both the GPU test and that host test fill
+a lavt_gemm_tn_t from a row."""
 import collections
 import math
 import re
@@ -71,12 +73,12 @@ class Case:
 
     def __init__(self, name, route, *, I, K, J=0, mode="int", dtype="bf16", batch=1, a_map=False, b_map=False, scale=None, div=1, v=1.0, alpha=1.0,
                  accumulate=False, colsum=False, colsum_atomic=False, split_k=0, partials=None, zeros=True, conv=None, b_split=0, permute=False,
-                 tuning=None, no_b=False, c_off=0, part_off=0, ld_pad=(8, 16, 4), lda=None, invalid=False, share=None):
+                 tuning=None, no_b=False, c_off=0, part_off=0, ld_pad=(8, 16, 4), lda=None, invalid=False, share=None, src_rows=(None, None)):
         self.name, self.route, self.mode, self.dtype, self.I, self.K, self.batch = name, route, mode, dtype, I, K, batch
         self.a_map, self.b_map, self.scale, self.div, self.v, self.alpha = a_map, b_map, scale, div, v, alpha
         self.accumulate, self.colsum, self.colsum_atomic, self.split_k, self.partials, self.zeros = accumulate, colsum, colsum_atomic, split_k, partials, zeros
         self.conv, self.b_split, self.permute, self.tuning, self.no_b = conv, b_split, permute, dict(tuning or {}), no_b
-        self.c_off, self.part_off, self.invalid, self.share = c_off, part_off, invalid, share
+        self.c_off, self.part_off, self.invalid, self.share, self.src_rows = c_off, part_off, invalid, share, src_rows
         self.J = taps_of(conv) * conv["kc"] if conv else ((J or 8) if no_b else J)
         self.bcols = conv["kc"] if conv else self.J                      # logical columns of the B source (channels under taps)
         self.b1 = b_split if b_split else self.bcols                     # columns held by B (the rest by B2)
@@ -107,6 +109,17 @@ class Case:
     @property
     def tdtype(self):
         return torch.float32 if self.dtype == "f32" else BF
+
+    @property
+    def a_src_rows(self):
+        """lavt_gemm_tn_t.a_src_rows: the rows of the A buffer `build` lays out (what a_rowmap may name), or the row's own statement; 0 without a map"""
+        rows = ((self.batch - 1) * self.strideA + self.Ra_buf * self.lda + 8) // self.lda
+        return 0 if not self.a_map else (rows if self.src_rows[0] is None else self.src_rows[0])
+
+    @property
+    def b_src_rows(self):
+        rows = ((self.batch - 1) * self.strideB + self.Rb_buf * self.ldb + 8) // max(self.ldb, 1)
+        return 0 if not self.b_map else (rows if self.src_rows[1] is None else self.src_rows[1])
 
     @property
     def pieces_bound(self):
@@ -237,6 +250,30 @@ def extract(c, Cflat, csflat):
     C = torch.stack([Cflat[b * c.strideC:b * c.strideC + c.I * c.ldc].view(c.I, c.ldc)[:, :c.J] for b in range(c.batch)])
     cs = torch.stack([csflat[b * c.strideColsum:b * c.strideColsum + c.I] for b in range(c.batch)]) if csflat is not None else None
     return C, cs
+
+
+def launch_args(c, buf):
+    """-> (args, kw, finish): lavt_hip.ops.gemm_tn_params(*args, **kw) fills the lavt_gemm_tn_t of a case and finish(p, addr) sets what the tests decide
+    per row on the filled struct: split_k, the lent partials scratch (at its offset) and a missing zero page.  buf: the operands A, B (the zero page for
+    a column-sum-only member), C and, where the case has them, B2, a_map, b_map, scale, colsum, parts -- device tensors (GPU test, addr = the tensor's
+    address) or made-up addresses (host test, addr = identity)"""
+    cv = None
+    if c.conv:
+        v = c.conv
+        cv = (v["h"], v["w"], v["kc"]) + ((v["d"], v["kd"], v["kh"], v["kw"]) if (v["d"], v["kd"], v["kh"], v["kw"]) != (1, 1, 3, 3) else ())
+    args = (c.tdtype, c.I, c.J, c.K, buf["A"], c.lda, buf["B"], c.ldb, buf["C"], c.ldc)
+    kw = dict(batch=c.batch, strideA=c.strideA, strideB=c.strideB, strideC=c.strideC, a_rowmap=buf.get("a_map"), a_rowscale=buf.get("scale"), a_rowscale_div=c.div,
+              a_rowscale_binary=c.scale == "binary", accumulate=c.accumulate, B2=buf.get("B2"), ldb2=c.ldb2, b_split=c.b_split if c.b2 else 0, b_rowmap=buf.get("b_map"),
+              conv=cv, alpha=c.alpha, c_conv_permute=c.permute, colsum=buf.get("colsum"), strideColsum=c.strideColsum, c_off=c.c_off, colsum_atomic=c.colsum_atomic,
+              a_src_rows=c.a_src_rows, b_src_rows=c.b_src_rows)
+
+    def finish(p, addr):
+        p.split_k = c.split_k
+        p.partials, p.partials_floats = (addr(buf["parts"]) + 4 * c.part_off, c.partials_floats) if buf.get("parts") is not None else (None, 0)
+        if not c.zeros:
+            p.zeros = None
+        return p
+    return args, kw, finish
 
 
 # ------------------------------------------------------------------------------------------------ the contract
@@ -442,7 +479,7 @@ def _maps(c):
 
 
 def contract_ok(c):
-    """the argument checks of lavt_gemm_tn"""
+    """the argument checks of lavt_gemm_tn_route"""
     e = c.epc
     if c.I % e or c.J % e or c.lda % e or c.ldb % e:
         return False
@@ -518,7 +555,7 @@ def ln_geometry(rows, C):
 
 
 def _route_pipe(ms, t, ln):
-    """lavt_gemm_tn_grouped_pipe: None when the group does not qualify"""
+    """tn_route_pipe: None when the group does not qualify"""
     if t["tn_pipe"] == 0 or not 2 <= len(ms) <= 6:
         return None
     base, work, geo = 0, 0, []
@@ -529,6 +566,8 @@ def _route_pipe(ms, t, ln):
             return None
         if (c.K + 1024) * c.lda * 2 >= 1 << 30 or (c.K + 1024) * c.ldb * 2 >= 1 << 30:
             return None
+        if (c.a_src_rows > 0 and (c.a_src_rows + 1) * c.lda * 2 + 256 >= 1 << 31) or (c.b_src_rows > 0 and (c.b_src_rows + 1) * c.ldb * 2 + 256 >= 1 << 31):
+            return None          # the rows a map may name stay inside the 2 GB descriptor
         if c.scale and (c.scale != "binary" or c.div < 64 or cdiv(c.K, c.div) > 64):
             return None
         if (c.no_b and not c.colsum) or (not c.no_b and c.J % 8):
@@ -575,7 +614,7 @@ def _route_pipe(ms, t, ln):
 
 
 def _route_group64(ms, t, ln):
-    """lavt_gemm_tn_grouped_v2 after the pipelined launch declined: None when the group does not form"""
+    """tn_route_group64, asked after the pipelined launch declined: None when the group does not form"""
     if not 2 <= len(ms) <= 6:
         return None
     uncut = sum(cdiv(c.I, 64) * cdiv(c.J, 64) for c in ms)
@@ -613,7 +652,7 @@ def _route_group64(ms, t, ln):
 
 
 def sk_plan(ms):
-    """sk_plan: (workgroups, scratch floats) or None"""
+    """tn_route_sk: (workgroups, scratch floats) or None"""
     if not 2 <= len(ms) <= 6:
         return None
     its = tiles = 0
@@ -745,7 +784,7 @@ CLASSIC = [
     Case("c-maps-taps", "classic/bf16/64/p1", I=72, K=150, conv=conv(3, 9, 7, 8), b_map=True, a_map=True, alpha=1.25, permute=True, **_cs),
     Case("c-maps-b2", "classic/bf16/64/p1", I=72, J=72, K=129, b_split=8, a_map=True, alpha=-0.5, **_cs),
     Case("c-mask-taps-b2", "classic/bf16/64/p1", I=8, K=189, conv=conv(3, 9, 7, 72), b_split=64, scale="binary", div=63, v=1.25, alpha=1.25, **_cs),
-    # the default big rule of dispatch_tn: I >= 256, J >= 1024, K >= 8192
+    # the default big rule of the classic family: I >= 256, J >= 1024, K >= 8192
     Case("c-big-default", "classic/bf16/128/p32", I=256, J=1024, K=8192, zeros=False, alpha=1.25, **_cs),
 ]
 TAPS = [

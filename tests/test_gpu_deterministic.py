@@ -122,7 +122,7 @@ def test_table_gradient(dtype, window, dims, heads):
 
 @pytest.mark.parametrize("dtype,M", [(torch.float32, 1000), (torch.bfloat16, 1024)])
 def test_weight_gradient_split(dtype, M):
-    """fp32: gemm.hip gemm_tn_kernel `atomicAdd(C + ii * p.ldc + col, ...)` from launch_tn's `split = 768 / (tiles * batch)` pieces (capped at one per 4 K
+    """fp32: gemm.hip gemm_tn_kernel `atomicAdd(C + ii * p.ldc + col, ...)` from the classic split rule of lavt_gemm_tn_route (gemm_tn_plan.hip), `split = 768 / (tiles * batch)` pieces (capped at one per 4 K
     tiles): 1000 rows on one 64x64 tile split, and fp32 is never lent scratch.  bf16: gemm_tn_v2.hip tn_tile_range `if (atomic) atomicAdd(dst, ...)`,
     `o.atomic = !to_parts && (nsplit > 1 || p.accumulate)`: 1024 rows = 16 K tiles = 2 pieces (>= 8 K tiles each), below _TN_PARTIALS_MINK = 2048 no
     scratch.  Reference and gate: test_gpu_ops.test_linear_plain (run_pair defaults)."""

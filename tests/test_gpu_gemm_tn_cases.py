@@ -1,7 +1,7 @@
 """The TN weight-gradient family, one direct launch per case, against its statement in tests/gemm_tn_cases.py: lavt_gemm_tn, lavt_gemm_tn_grouped,
 _grouped_ln, _grouped_sk, lavt_conv3x3_wgrad, lavt_conv3x3_wgrad_f8 and lavt_unpack_conv_grad.
 
-A test builds the operands on the CPU, fills a lavt_gemm_tn_t through ops.gemm_tn(..., defer=collector), sets split_k, partials and zeros on the struct and
+A test builds the operands on the CPU, fills a lavt_gemm_tn_t through gemm_tn_cases.launch_args -> ops.gemm_tn_params (split_k, partials and zeros set on the struct) and
 calls the entry point itself.  Integer mode (small-integer operands: every partial sum exact in fp32, see gemm_tn_cases.py) holds C and colsum to the
 integer reference with torch.equal -- on every route, whatever the tile, the K pieces, the order atomics land in.  Real mode holds them to
 E <= K_TN x F (E: the larger of the row and the column relative error against fp64, F: the same error of the fp32 floor evaluated by torch); every figure
@@ -75,14 +75,6 @@ def _ratio(E, F):
     return E / F if F > 0 else (0.0 if E == 0 else float("inf"))
 
 
-class _Collect:
-    def __init__(self):
-        self.p, self.keep = None, None
-
-    def add(self, p, keep, extra=False, rider=None):
-        self.p, self.keep = p, keep
-
-
 class Member:
     """the device buffers of one problem and its struct"""
 
@@ -110,21 +102,11 @@ class Member:
 
     def struct(self):
         from lavt_hip import _capi as K, ops
-        c, q = self.c, _Collect()
-        cv = None
-        if c.conv:
-            v = c.conv
-            cv = (v["h"], v["w"], v["kc"]) + ((v["d"], v["kd"], v["kh"], v["kw"]) if (v["d"], v["kd"], v["kh"], v["kw"]) != (1, 1, 3, 3) else ())
-        ops.gemm_tn(c.tdtype, c.I, c.J, c.K, self.A, c.lda, self.B, c.ldb, self.C, c.ldc, batch=c.batch, strideA=c.strideA, strideB=c.strideB, strideC=c.strideC,
-                    a_rowmap=self.a_map, a_rowscale=self.scale, a_rowscale_div=c.div, a_rowscale_binary=c.scale == "binary", accumulate=c.accumulate, B2=self.B2,
-                    ldb2=c.ldb2, b_split=c.b_split if c.b2 else 0, b_rowmap=self.b_map, conv=cv, alpha=c.alpha, c_conv_permute=c.permute, colsum=self.cs,
-                    strideColsum=c.strideColsum, c_off=c.c_off, defer=q, colsum_atomic=c.colsum_atomic, extra=c.no_b)
-        p = q.p
-        p.split_k = c.split_k
-        p.partials, p.partials_floats = (K.ptr(self.parts) + 4 * c.part_off, c.partials_floats) if self.parts is not None else (None, 0)
-        if not c.zeros:
-            p.zeros = None
-        self.keep = q.keep
+        c = self.c
+        buf = dict(A=self.A, B=self.B, B2=self.B2, a_map=self.a_map, b_map=self.b_map, scale=self.scale, C=self.C, colsum=self.cs, parts=self.parts)
+        args, kw, finish = G.launch_args(c, buf)
+        p = finish(ops.gemm_tn_params(*args, **kw), K.ptr)
+        assert (p.a_src_rows, p.b_src_rows) == (self.A.numel() // c.lda if c.a_map else 0, self.B.numel() // max(c.ldb, 1) if c.b_map else 0)
         return p
 
     def owned(self):
