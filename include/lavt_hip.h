@@ -1051,6 +1051,25 @@ int lavt_sentence_attn_fwd(int dtype, const void* qkv, const float* keybias, con
 int lavt_sentence_attn_bwd(int dtype, const void* qkv, const float* keybias, const uint8_t* keep, float drop_scale, const void* dout, void* dqkv, int B,
                            int N, int heads, int hd, void* stream);
 
+/* The opening of the encoder in inference as one launch (DESIGN.md "Text encoder in the prediction"; a new symbol only: no existing prototype or
+ * struct changed, lavt_abi_version() stays 7).  What lavt_bert_embed_fwd + lavt_layernorm_fwd + the three element-wise steps of
+ * `(1.0 - attention_mask.float()) * -10000.0` compute, without the rounding to `dtype` between the embedding sum and the LayerNorm:
+ *   out[r]     = dtype(LayerNorm((word[ids[r]] + type[token_type ? token_type[r] : 0]) + pos[r % N]) * gamma + beta)      [rows][H], LAVT_F32 / LAVT_BF16
+ *   keybias[r] = (1.f - (float)attn_mask[r]) * -10000.f                                                                    fp32 [rows]
+ * ids / token_type / attn_mask int64 [rows]; tables, gamma, beta fp32.  The sum is formed in BertEmbeddings.forward's order and stays fp32; the
+ * statistics are two-pass in fp32 (the mean, then the mean of squared deviations ABOUT it -- never E[x^2] - mean^2: BERT's eps is 1e-12 and its rows
+ * are not centred); one rounding to `dtype`, at the store.  keybias is evaluated literally, so it holds the bits of the torch expression for any
+ * integer mask; token_type NULL = type 0 everywhere; attn_mask and keybias are both given or both NULL.
+ * The kernel cannot raise and reads nothing outside its tables: an id outside [0, vocab) reads word row 0 (the pad row), a type outside
+ * [0, n_types) reads type row 0, and r % N lies inside [0, n_pos) because the entry refuses N > n_pos.  Range checks with a message belong to the
+ * host, where the values come from the host (lavt_hip.engine.check_sentences).
+ * A wave per row holding its H / 64 elements in registers between the passes; no LDS, no atomics, no scratch: the same bits on every run.
+ * LAVT_ERR_INVALID with a message and no launch: a null pointer (token_type and the attn_mask / keybias pair excepted), rows / N / H or a table's
+ * row count <= 0, H % 4 != 0, H > 2048, N > n_pos, keybias without attn_mask or the reverse, a dtype other than LAVT_F32 / LAVT_BF16. */
+int lavt_bert_embed_ln_fwd(int dtype, const int64_t* ids, const int64_t* token_type, const int64_t* attn_mask, const float* word, const float* pos,
+                           const float* type, const float* gamma, const float* beta, float eps, void* out, float* keybias, int rows, int N, int H,
+                           int vocab, int n_pos, int n_types, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Deterministic forms (DESIGN.md "Deterministic mode"; new symbols only: no existing prototype or struct changed, lavt_abi_version() stays 7).
  * Every entry point below computes what its sibling above computes WITHOUT float atomics: the same bits on every run from the same inputs.  The

@@ -5,7 +5,7 @@ reference's call sites use (lib/_utils.py:38-52, train.py:216-218, 595-602: `Ber
 `model(sentences, attention_mask=attentions)[0]`), and the same module tree, so a HF `pytorch_model.bin` (or the `bert_model` entry of a
 LAVT checkpoint, train.py:612) loads key for key.  All arithmetic runs through lavt_hip.ops (GEMMs with fused bias / GELU / residual,
 LayerNorm, the batched masked attention or, with `fused_attention`, the sentence-attention kernels, the embedding-sum and dropout kernels of
-csrc/text.hip); nothing falls back to torch math.
+csrc/text.hip and, with `fused_embeddings` in inference, its one-launch embedding + LayerNorm + key-bias opening); nothing falls back to torch math.
 """
 import json
 import os
@@ -147,23 +147,28 @@ class BertPooler(nn.Module):
 class BertModel(nn.Module):
     """fused_attention (a plain attribute, also a constructor / from_pretrained keyword; default False): the attention core of every layer runs as
     ops.sentence_attention -- one kernel per direction -- instead of the composed ops.masked_self_attention.  Read at every forward, so it may be set
-    at any time before a step is captured.  With attention dropout on, the two routes draw different masks (ops.sentence_attention)."""
+    at any time before a step is captured.  With attention dropout on, the two routes draw different masks (ops.sentence_attention).
+    fused_embeddings (the same kind of attribute and keyword; default False): with grad mode off, the opening of forward -- embedding sum, LayerNorm and
+    the key bias of the attention mask -- runs as ONE launch, ops.bert_embed_ln, instead of five; there is no rounding to the compute dtype between sum
+    and norm, so in bf16 its rows differ from the composed opening's by that rounding.  With grad mode on the composed opening runs whatever the
+    attribute says (the fused kernel has no backward).  Dropout is off in every inference the fused route serves: in training mode it is applied as before."""
 
-    def __init__(self, config=None, add_pooling_layer=True, fused_attention=False):
+    def __init__(self, config=None, add_pooling_layer=True, fused_attention=False, fused_embeddings=False):
         super().__init__()
         self.fused_attention = bool(fused_attention)
+        self.fused_embeddings = bool(fused_embeddings)
         self.config = config if config is not None else BertConfig()
         self.embeddings = BertEmbeddings(self.config)
         self.encoder = BertEncoder(self.config)
         self.pooler = BertPooler(self.config) if add_pooling_layer else None
 
     @classmethod
-    def from_pretrained(cls, path, *unused, fused_attention=False, **unused_kw):
+    def from_pretrained(cls, path, *unused, fused_attention=False, fused_embeddings=False, **unused_kw):
         """`path`: a directory with config.json and pytorch_model.bin (what `args.ck_bert` points at).  There is no hub download."""
         cfg = os.path.join(str(path), "config.json")
         if not os.path.isfile(cfg):
             raise OSError(f"BertModel.from_pretrained: {path!r} is not a directory with config.json / pytorch_model.bin (no network download here)")
-        model = cls(BertConfig.from_json_file(cfg), fused_attention=fused_attention)
+        model = cls(BertConfig.from_json_file(cfg), fused_attention=fused_attention, fused_embeddings=fused_embeddings)
         wfile = os.path.join(str(path), "pytorch_model.bin")
         sfile = os.path.join(str(path), "model.safetensors")
         if os.path.isfile(wfile):
@@ -196,8 +201,13 @@ class BertModel(nn.Module):
         B, N = input_ids.shape
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
-        keybias = (1.0 - attention_mask.reshape(B, N).to(torch.float32)) * -10000.0          # get_extended_attention_mask of 3.0.2
-        x = self.embeddings(input_ids, token_type_ids)
+        if self.fused_embeddings and not torch.is_grad_enabled():          # (read at every call, like fused_attention)
+            emb = self.embeddings
+            x, keybias = ops.bert_embed_ln(input_ids, token_type_ids, attention_mask.reshape(B, N), emb, N, compute_dtype())
+            x = ops.dropout(x, emb.dropout.p, emb.training)
+        else:
+            keybias = (1.0 - attention_mask.reshape(B, N).to(torch.float32)) * -10000.0          # get_extended_attention_mask of 3.0.2
+            x = self.embeddings(input_ids, token_type_ids)
         for layer in self.encoder.layer:
             x = layer(x, keybias, B, N, self.fused_attention)
         out = ops.cast_ad(x, torch.float32).view(B, N, self.config.hidden_size)

@@ -1,7 +1,8 @@
 // Text side of lavt_one / lavt_video: the BERT-base encoder the reference builds with
 // `BertModel.from_pretrained(args.ck_bert)` (lib/_utils.py:38-52; train.py:595-602; HF transformers 3.0.2 `modeling_bert.py`).
 // Its Linear / LayerNorm / GELU / attention GEMMs run on the kernels of the visual path; this file adds what only the text side needs:
-// the embedding sum (word + position + token type) with its scatter-add backward, inverted dropout with a caller-drawn keep mask, and the fused
+// the embedding sum (word + position + token type) with its scatter-add backward, the same sum with its LayerNorm and the attention mask's key bias as one
+// inference launch (lavt_bert_embed_ln_fwd), inverted dropout with a caller-drawn keep mask, and the fused
 // attention core for sentence-length sequences (lavt_sentence_attn_fwd / _bwd: one workgroup per (sample, head), one launch per direction).
 // 20-22 tokens per sentence: latency-bound, a wave per token row, 16-byte accesses.
 #include "common.h"
@@ -24,6 +25,67 @@ __global__ __launch_bounds__(256) void bert_embed_fwd_kernel(const int64_t* __re
         // (word + type) + position: the order of BertEmbeddings.forward
         o[0] = from_f<T>((a.x + d.x) + b.x); o[1] = from_f<T>((a.y + d.y) + b.y); o[2] = from_f<T>((a.z + d.z) + b.z); o[3] = from_f<T>((a.w + d.w) + b.w);
     }
+}
+
+// The opening of the encoder in inference as ONE launch (lavt_bert_embed_ln_fwd):
+//   out[r][:] = T(LayerNorm((word[ids[r]][:] + type[tt ? tt[r] : 0][:]) + pos[r % N][:]) * gamma + beta),  keybias[r] = (1 - mask[r]) * -10000.
+// A wave per token row, 4 rows per workgroup; lane l holds the float4 chunks l, l + 64, ... of its row (MAXC of them: H <= 256 * MAXC) in registers
+// between the two statistics passes -- mean first, then the mean of squared deviations about it -- so the row is read once and nothing goes through LDS.
+// The sum stays fp32 from the tables to the store: one rounding to T.  The kernel cannot raise: an id outside [0, vocab) reads word row 0 (the pad
+// row), a type outside [0, n_types) type row 0; r % N < N <= n_pos is the entry's check.
+template <typename T, int MAXC>
+__global__ __launch_bounds__(256) void bert_embed_ln_fwd_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ tt, const int64_t* __restrict__ amask,
+                                                                const float* __restrict__ word, const float* __restrict__ pos, const float* __restrict__ type,
+                                                                const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                                T* __restrict__ out, float* __restrict__ keybias, int rows, int N, int H, int vocab, int n_types) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;                               // (uniform over the wave: the reductions below are wave-local)
+    int64_t id = ids[row], ty = tt ? tt[row] : 0;
+    if ((uint64_t)id >= (uint64_t)vocab) id = 0;
+    if ((uint64_t)ty >= (uint64_t)n_types) ty = 0;
+    const float* w = word + id * (int64_t)H;
+    const float* p = pos + (int64_t)(row % N) * H;
+    const float* t = type + ty * (int64_t)H;
+    const int nchunk = H >> 2;
+    float4 v[MAXC];
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        const int ch = lane + 64 * c;
+        v[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ch < nchunk) {
+            const float4 a = *reinterpret_cast<const float4*>(w + 4 * ch), b = *reinterpret_cast<const float4*>(p + 4 * ch),
+                         d = *reinterpret_cast<const float4*>(t + 4 * ch);
+            // (word + type) + position: the order of BertEmbeddings.forward
+            v[c] = make_float4((a.x + d.x) + b.x, (a.y + d.y) + b.y, (a.z + d.z) + b.z, (a.w + d.w) + b.w);
+            s += (v[c].x + v[c].y) + (v[c].z + v[c].w);
+        }
+    }
+    const float mu = wave_sum(s) / (float)H;
+    float q = 0.f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (lane + 64 * c < nchunk) {
+            const float dx = v[c].x - mu, dy = v[c].y - mu, dz = v[c].z - mu, dw = v[c].w - mu;
+            q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+        }
+    const float rs = 1.f / sqrtf(wave_sum(q) / (float)H + eps);
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        const int ch = lane + 64 * c;
+        if (ch < nchunk) {
+            const float4 g = *reinterpret_cast<const float4*>(gamma + 4 * ch), be = *reinterpret_cast<const float4*>(beta + 4 * ch);
+            const float y0 = (v[c].x - mu) * rs * g.x + be.x, y1 = (v[c].y - mu) * rs * g.y + be.y, y2 = (v[c].z - mu) * rs * g.z + be.z,
+                        y3 = (v[c].w - mu) * rs * g.w + be.w;
+            T* o = out + (int64_t)row * H + 4 * ch;
+            if constexpr (std::is_same<T, float>::value) {
+                *reinterpret_cast<float4*>(o) = make_float4(y0, y1, y2, y3);
+            } else {
+                *reinterpret_cast<uint2*>(o) = make_uint2(pack_bf16x2(y0, y1), pack_bf16x2(y2, y3));          // (H % 4 == 0: a chunk of a bf16 row starts on 8 bytes)
+            }
+        }
+    }
+    if (amask && lane == 0) keybias[row] = (1.f - (float)amask[row]) * -10000.f;          // get_extended_attention_mask of 3.0.2, literally
 }
 
 // dword[ids[r]] += dy[r], dpos[r % N] += dy[r], dtype[tt[r]] += dy[r]  (fp32 atomics: a few dozen rows, repeated ids / positions collide)
@@ -209,6 +271,23 @@ extern "C" int lavt_bert_embed_fwd(int dtype, const int64_t* ids, const int64_t*
     LAVT_CHECK_ARG(ids && word && pos && type && out && rows > 0 && N > 0 && H > 0 && H % 4 == 0, "lavt_bert_embed_fwd: bad arguments");
     DISPATCH_T(dtype, "lavt_bert_embed_fwd", hipLaunchKernelGGL(bert_embed_fwd_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, ST, ids, token_type, word, pos, type, (T*)out, rows, N, H));
     LAVT_CHECK_LAUNCH("lavt_bert_embed_fwd");
+    return LAVT_OK;
+}
+
+extern "C" int lavt_bert_embed_ln_fwd(int dtype, const int64_t* ids, const int64_t* token_type, const int64_t* attn_mask, const float* word, const float* pos,
+                                      const float* type, const float* gamma, const float* beta, float eps, void* out, float* keybias, int rows, int N, int H,
+                                      int vocab, int n_pos, int n_types, void* stream) {
+    LAVT_CHECK_ARG(ids && word && pos && type && gamma && beta && out, "lavt_bert_embed_ln_fwd: null pointer");
+    LAVT_CHECK_ARG(rows > 0 && N > 0 && H > 0 && vocab > 0 && n_pos > 0 && n_types > 0, "lavt_bert_embed_ln_fwd: rows = %d, N = %d, H = %d, tables of %d / %d / %d rows",
+                   rows, N, H, vocab, n_pos, n_types);
+    LAVT_CHECK_ARG(H % 4 == 0 && H <= 2048, "lavt_bert_embed_ln_fwd: unsupported H=%d (a multiple of 4, at most 2048)", H);
+    LAVT_CHECK_ARG(N <= n_pos, "lavt_bert_embed_ln_fwd: %d tokens but only %d positions", N, n_pos);
+    LAVT_CHECK_ARG((keybias != nullptr) == (attn_mask != nullptr), "lavt_bert_embed_ln_fwd: keybias and attn_mask go together (both or neither)");
+    const int nchunk = H / 4;
+#define EMBED_LN(MAXC_) hipLaunchKernelGGL((bert_embed_ln_fwd_kernel<T, MAXC_>), dim3((rows + 3) / 4), dim3(256), 0, ST, ids, token_type, attn_mask, word, pos, type, gamma, beta, eps, (T*)out, keybias, rows, N, H, vocab, n_types)
+    DISPATCH_T(dtype, "lavt_bert_embed_ln_fwd", if (nchunk <= 64) EMBED_LN(1); else if (nchunk <= 128) EMBED_LN(2); else if (nchunk <= 256) EMBED_LN(4); else EMBED_LN(8));
+#undef EMBED_LN
+    LAVT_CHECK_LAUNCH("lavt_bert_embed_ln_fwd");
     return LAVT_OK;
 }
 

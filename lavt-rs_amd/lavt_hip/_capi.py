@@ -242,6 +242,7 @@ _PROTOTYPES = {
     "lavt_act_bwd": [i32, i32, vp, vp, vp, i64, vp],
     "lavt_bert_embed_fwd": [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "lavt_bert_embed_bwd": [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    "lavt_bert_embed_ln_fwd": [i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "lavt_dropout": [i32, vp, vp, f32, vp, vp, i64, vp],
     "lavt_sentence_attn_fwd": [i32, vp, vp, vp, f32, vp, i32, i32, i32, i32, vp],
     "lavt_sentence_attn_bwd": [i32, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, vp],

@@ -255,6 +255,55 @@ def _check_text_encoder(model, image, l_feats, l_mask, text_encoder, valid_indic
                          "is part of the iteration); call text_encoder.train()")
 
 
+def check_sentences(ids, mask, shape, vocab_size, max_positions, who="Predictor.set_sentences"):
+    """The refusals of Predictor.set_sentences as a pure function: token ids and attention mask for static int64 buffers of `shape` = (N, N_l), read by an
+    encoder with `vocab_size` word rows and `max_positions` position rows and by PWAM, whose word axis holds ops.KV_LD tokens.  ValueError, naming the
+    argument: a tensor of another shape or dtype than the buffers, N_l > max_positions, N_l > ops.KV_LD and -- for HOST tensors only -- an id outside
+    [0, vocab_size).  Range is checked where the values come from the host (the rule of set_image_of); device tensors are the caller's promise: the
+    kernels cannot raise and read word row 0 for an id out of range (include/lavt_hip.h: lavt_bert_embed_ln_fwd)."""
+    shape = tuple(int(v) for v in shape)
+    for name, t in (("ids", ids), ("mask", mask)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or tuple(t.shape) != shape:
+            what = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{who}: {name} must be an int64 tensor of shape {shape} ({'token ids' if name == 'ids' else 'attention mask'}), got {what}")
+    n_l = shape[1]
+    if n_l > int(max_positions):
+        raise ValueError(f"{who}: ids hold {n_l} tokens per sentence, the encoder has max_position_embeddings = {int(max_positions)}")
+    if n_l > ops.KV_LD:
+        raise ValueError(f"{who}: ids hold {n_l} tokens per sentence, the model's word axis holds ops.KV_LD = {ops.KV_LD}")
+    if not ids.is_cuda and ids.numel():
+        lo, hi = int(ids.min()), int(ids.max())
+        if lo < 0 or hi >= int(vocab_size):
+            bad = [(int(i), int(j), int(ids[i, j])) for i, j in ((ids < 0) | (ids >= int(vocab_size))).nonzero()[:4].tolist()]
+            raise ValueError(f"{who}: ids (sentence, token, id) {bad} outside the vocabulary [0, {int(vocab_size)})")
+
+
+def _check_predictor_text_encoder(model, image, lang, l_mask, text_encoder, valid_indices):
+    """the refusals of Predictor(text_encoder=), after the existing checks and before anything is built"""
+    for name, t in (("lang", lang), ("l_mask", l_mask)):
+        if t.dtype != torch.int64 or t.dim() != 2:
+            raise ValueError(f"Predictor: with text_encoder the predictor computes the language features itself: {name} must be the static int64 (N, N_l) buffer of "
+                             f"{'token ids' if name == 'lang' else 'the attention mask'}, got {t.dtype} {tuple(t.shape)} (precomputed features belong to a predictor "
+                             "without text_encoder)")
+    if tuple(lang.shape) != tuple(l_mask.shape):
+        raise ValueError(f"Predictor: lang (token ids) is {tuple(lang.shape)}, l_mask (attention mask) {tuple(l_mask.shape)}")
+    if hasattr(model, "text_encoder"):
+        raise ValueError(f"Predictor: text_encoder given, but {type(model).__name__} carries its own encoder (model.text_encoder runs inside forward_lowres): "
+                         "feed it token ids without the argument")
+    if valid_indices is not None:
+        raise ValueError("Predictor: text_encoder cannot be combined with valid_indices (the clip models carry their own encoder: LAVTVideo.text_encoder)")
+    devs = {p.device for p in text_encoder.parameters()}
+    if devs != {image.device}:
+        raise ValueError(f"Predictor: text_encoder lives on {sorted(str(d) for d in devs)}, the predictor's buffers on {image.device}")
+    if text_encoder.training:
+        raise RuntimeError("Predictor: text_encoder is in training mode -- call text_encoder.eval() first (dropout is not part of a prediction)")
+    cfg = getattr(text_encoder, "config", None)
+    n_l = int(lang.shape[1])
+    if n_l > ops.KV_LD or (cfg is not None and n_l > cfg.max_position_embeddings):
+        raise ValueError(f"Predictor: lang holds {n_l} tokens per sentence; the model's word axis holds ops.KV_LD = {ops.KV_LD}"
+                         + (f", the encoder has max_position_embeddings = {cfg.max_position_embeddings}" if cfg is not None else ""))
+
+
 class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
     def __init__(self, model, image, l_feats, l_mask, target, world=1, use_graph=True, bucket_mib=32.0, fused_loss=True, refresh_weights_in_step=False, context=None,
                  *, loss="ce", valid_indices=None, dice_rate=1.0, boundary_rate=0.05, deterministic=None, accumulate=1, meters=None, image_of=None,
@@ -832,12 +881,20 @@ class Predictor(_ValidIndices, _ImageOf, _BatchInput):
                   images and N target masks.
       meter       optional lavt_hip.metrics.DeviceEvalMeter (or make_meter() / attach_meter() later, before warmup_and_capture()): the body ends with
                   one more launch that does EvalMeter.update(pred.iu) on the device, for the live slots only.  Needs a target.
+      text_encoder    optional: the separate `bert_model` of `--model lavt` (test.py:60-83 evaluates with it), in eval mode, run INSIDE the prediction
+                  (DESIGN.md "Text encoder in the prediction").  lang / l_mask are then the static int64 (N, N_l) buffers of token ids and attention mask
+                  (N = B * expressions_per_image, or the slot count under image_of; an empty slot's ids are encoded and its logits never read), and the
+                  body opens with `l = text_encoder(ids, attention_mask=mask)[0].permute(0, 2, 1)`, `m = mask.unsqueeze(-1)`.  The stamp step() compares
+                  covers the encoder's parameters and buffers too.  set_sentences(ids, mask) fills the buffers, also between replays.  Set
+                  text_encoder.fused_attention / .fused_embeddings for the one-kernel attention core and opening (bert/modeling_bert.py): the
+                  predictor sets neither.  ValueError for floating-point lang or a non-integer l_mask, a model that carries its own encoder, together
+                  with valid_indices, an encoder on another device; RuntimeError for an encoder in training mode.
     step() never synchronises: it returns the static mask tensor, the caller decides when to read it (EvalMeter.update(pred.iu) reads `.iu` with one
-    copy per call; a DeviceEvalMeter reads nothing until poll() / read()).  Built with neither image_of nor meter, the launches are those of a
-    predictor without the two arguments."""
+    copy per call; a DeviceEvalMeter reads nothing until poll() / read()).  Built with none of image_of, meter and text_encoder, the launches are those
+    of a predictor without the three arguments."""
 
     def __init__(self, model, image, lang, l_mask, *, target=None, out_size=None, via_size=None, expressions_per_image=1, use_graph=True, context=None,
-                 valid_indices=None, image_of=None, meter=None):
+                 valid_indices=None, image_of=None, meter=None, text_encoder=None):
         if model.training:
             raise RuntimeError("Predictor: the model is in training mode -- call model.eval() first (BatchNorm is folded from the running statistics, DropPath is off)")
         for name, t in (("image", image), ("lang", lang), ("l_mask", l_mask), ("target", target)):
@@ -866,6 +923,9 @@ class Predictor(_ValidIndices, _ImageOf, _BatchInput):
             raise NotImplementedError(f"Predictor: expressions_per_image > 1 needs a backbone that shares stage 0 between expressions; {type(model.backbone).__name__} does not")
         if image_of is None and lang.shape[0] != image.shape[0] * S:
             raise ValueError(f"Predictor: {lang.shape[0]} expressions for {image.shape[0]} images x {S} expressions per image")
+        if text_encoder is not None:
+            _check_predictor_text_encoder(model, image, lang, l_mask, text_encoder, valid_indices)
+        self.text_encoder = text_encoder
         self.context = context if context is not None else ops.default_context()
         self.model, self.x, self.l, self.m, self.t = model, image, lang, l_mask, target
         self.S = S
@@ -881,6 +941,8 @@ class Predictor(_ValidIndices, _ImageOf, _BatchInput):
         # a replay runs no Python: neither the weight cache's version checks nor the BatchNorm fold's.  step() compares this stamp over parameters AND
         # buffers (the running statistics are folded into weights) and re-casts / re-folds eagerly, into the same storage, when anything moved
         self._state = [t for t in list(model.parameters()) + list(model.buffers())]
+        if text_encoder is not None:          # the encoder's compute copies live in the same context and are read by the same graph
+            self._state += list(text_encoder.parameters()) + list(text_encoder.buffers())
         self._seen = None
         self._warmed = False
         self.meter = None
@@ -918,12 +980,15 @@ class Predictor(_ValidIndices, _ImageOf, _BatchInput):
     @_in_context
     def _body(self):
         with torch.no_grad():
+            l, m = self.l, self.m
+            if self.text_encoder is not None:          # the text stage of TrainStep._language and LAVTOne.forward_lowres, on the id / attention-mask buffers
+                l, m = self.text_encoder(l, attention_mask=m)[0].permute(0, 2, 1), m.unsqueeze(-1)
             if self.image_of is not None:
-                y = self.model.forward_lowres(self.x, self.l, self.m, folded=True, image_of=self.image_of)
+                y = self.model.forward_lowres(self.x, l, m, folded=True, image_of=self.image_of)
             elif self.valid_indices is None:
-                y = self.model.forward_lowres(self.x, self.l, self.m, folded=True, expand=self.S)
+                y = self.model.forward_lowres(self.x, l, m, folded=True, expand=self.S)
             else:
-                y = self.model.forward_lowres(self.x, self.l, self.m, folded=True, frames=self.valid_indices)
+                y = self.model.forward_lowres(self.x, l, m, folded=True, frames=self.valid_indices)
             n, _, h, w = y.shape
             from lib.mask_predictor import nchw_rows
             n_images = int(self.x.shape[0]) if self.image_of is not None else None
@@ -971,6 +1036,19 @@ class Predictor(_ValidIndices, _ImageOf, _BatchInput):
             self.graph = None
             torch.cuda.synchronize()
 
+    def set_sentences(self, ids, mask):
+        """Copy token ids and attention mask (int64 (N, N_l), host or device tensors) into the static `lang` / `l_mask` buffers of a predictor built with
+        text_encoder; usable between replays -- the captured text stage reads the buffers on the device.  check_sentences() runs first and refuses
+        (ValueError) before any copy: another shape or dtype than the buffers, and, for host tensors, an id outside the encoder's vocabulary.  Host
+        tensors go through pinned memory on the current stream, nothing synchronises."""
+        who = "Predictor.set_sentences"
+        if self.text_encoder is None:
+            raise ValueError(f"{who}: built without text_encoder (lang / l_mask hold the caller's features: copy into them yourself)")
+        cfg = self.text_encoder.config
+        check_sentences(ids, mask, self.l.shape, cfg.vocab_size, cfg.max_position_embeddings, who=who)
+        for dst, src in ((self.l, ids), (self.m, mask)):
+            dst.copy_(src if src.is_cuda else src.contiguous().pin_memory(), non_blocking=True)
+
     def load_frames(self, frames_u8, targets_u8=None):
         """Fill the static `image` buffer (and `target`) from uint8 frames: the reference's Resize -> ToTensor -> Normalize (test.py:70-76,
         test_ytvos.py:236-243) on the device, with PIL's pixels (lavt_hip.preprocess.FramePreprocessor: what it accepts is accepted here).
@@ -1005,6 +1083,8 @@ class Predictor(_ValidIndices, _ImageOf, _BatchInput):
         """-> the mask tensor (static when captured).  No host synchronisation."""
         if self.model.training:
             raise RuntimeError("Predictor.step: the model was put back into training mode")
+        if self.text_encoder is not None and self.text_encoder.training:
+            raise RuntimeError("Predictor.step: the text_encoder was put back into training mode")
         stamp = self._stamp()
         if stamp != self._seen:
             if self._seen is not None:

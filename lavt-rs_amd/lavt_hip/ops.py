@@ -2497,6 +2497,35 @@ def bert_embed(ids, token_type_ids, word, pos, typ, N, dtype):
     return _BertEmbed.apply(ids, token_type_ids, word, pos, typ, N, dtype)
 
 
+def bert_embed_ln(ids, token_type_ids, attention_mask, emb_module, N, dtype):
+    """The opening of the encoder in inference as ONE launch (lavt_bert_embed_ln_fwd): -> (x [rows, H] in `dtype`, keybias fp32 [B, N] or None without
+    a mask).  x = LayerNorm(bert_embed(...)) of `emb_module` (a BertEmbeddings: the three tables and the LayerNorm) without the rounding to `dtype`
+    between sum and norm; keybias holds the bits of `(1.0 - attention_mask.float()) * -10000.0`.  Inference only: there is no autograd node, so a
+    table or LayerNorm parameter that requires grad while grad mode is on is refused (RuntimeError) -- train through bert_embed + layer_norm.
+    attention_mask: integer or bool (a floating-point mask is a ValueError: the kernel reads integers)."""
+    word, pos, typ = emb_module.word_embeddings.weight, emb_module.position_embeddings.weight, emb_module.token_type_embeddings.weight
+    ln = emb_module.LayerNorm
+    if torch.is_grad_enabled() and any(p.requires_grad for p in (word, pos, typ, ln.weight, ln.bias)):
+        raise RuntimeError("bert_embed_ln: the fused embedding + LayerNorm has no backward; call it under torch.no_grad() (or train through bert_embed + layer_norm)")
+    ids = ids.contiguous().view(-1).long()
+    tt = token_type_ids.contiguous().view(-1).long() if token_type_ids is not None else None
+    rows, H = ids.numel(), word.shape[1]
+    if N < 1 or rows % N:
+        raise ValueError(f"bert_embed_ln: {rows} token ids are not whole sentences of {N} tokens")
+    mask = keybias = None
+    if attention_mask is not None:
+        if attention_mask.dtype.is_floating_point or attention_mask.numel() != rows:
+            raise ValueError(f"bert_embed_ln: attention_mask must be an integer mask with one entry per token ({rows}), got {attention_mask.dtype} {tuple(attention_mask.shape)}")
+        mask = attention_mask.contiguous().view(-1).long()
+        keybias = torch.empty(rows // N, N, dtype=torch.float32, device=word.device)
+    out = torch.empty(rows, H, dtype=dtype, device=word.device)
+    _note(f"embed+ln {rows}x{H}", nbytes=rows * H * (12.0 + out.element_size()))
+    K.check(K.lib.lavt_bert_embed_ln_fwd(K.dt(dtype), K.ptr(ids), K.ptr(tt), K.ptr(mask), K.ptr(_f32(word)), K.ptr(_f32(pos)), K.ptr(_f32(typ)),
+                                         K.ptr(_f32(ln.weight)), K.ptr(_f32(ln.bias)), ln.eps, K.ptr(out), K.ptr(keybias), rows, N, H,
+                                         word.shape[0], pos.shape[0], typ.shape[0], K.stream()))
+    return out, keybias
+
+
 @K.scoped
 class _Dropout(torch.autograd.Function):
     """y = dropout(x) (+ residual): the keep mask is drawn with torch's generator (so torch.manual_seed governs it, as for nn.Dropout),

@@ -26,7 +26,16 @@ and the decoder's launch count per call (profiler records in the "decoder" scope
                 are milliseconds PER PAIR, the median over --calls repetitions of the whole loop (host wall clock, a synchronise on both sides):
   pairs_batch1_eval_meter       N batch-1 replays, each followed by EvalMeter.update(pred.iu) -- the evaluation loop as it stands: one device-to-host
                                 read per prediction
-  pairs_image_of_device_meter   ONE replay of Predictor(image_of=) with the DeviceEvalMeter appended to its body, and a single meter.read() at the end"""
+  pairs_image_of_device_meter   ONE replay of Predictor(image_of=) with the DeviceEvalMeter appended to its body, and a single meter.read() at the end
+
+    --text-encoder   (opt-in, runs ONLY this) lavt's separate BERT inside the prediction, on the --pairs 12 geometry (12 expressions over 4 images, one
+                     image_of replay) with a bert-base encoder (random init) on 20 tokens.  Milliseconds per CALL, median over --calls device-synchronised
+                     calls; the four regions alternate call by call; ms_p10 / ms_p90 / ms_min / ms_max give the spread; launches_eager_body is the K.prof
+                     launch count of one eager body (for the first region: the eager encoder's launches plus the body's):
+  text_eager_then_replay                         the evaluation loop as it stands: enc(ids, mask) eagerly, two copies, the image_of replay
+  text_in_predictor                              Predictor(text_encoder=) replay
+  text_in_predictor_fused_attention              ... with enc.fused_attention
+  text_in_predictor_fused_attention_embeddings   ... and enc.fused_embeddings"""
 import argparse
 import json
 import os
@@ -168,6 +177,89 @@ def pairs(a, report):
            ms_per_pair_max=round(hi_b / N, 4), overall_iou=round(got["overall_iou"], 4), speedup=round(med_a / med_b, 3), **common)
 
 
+def text_encoder(a, report):
+    import lavt_hip
+    from bert.modeling_bert import BertConfig, BertModel
+    from lavt_hip import _capi as K
+    from lavt_hip import ops
+    from lavt_hip.detweights import det_inputs
+    from lavt_hip.detweights import fill_state_dict_
+    from lavt_hip.engine import Predictor
+    from lib import segmentation
+    dev, N, B, n_l = "cuda:0", 12, 4, 20
+    image_of = [j // 3 for j in range(N)]
+    lavt_hip.set_compute_dtype(torch.bfloat16 if a.dtype == "bf16" else torch.float32)
+    model = segmentation.lavt("", SimpleNamespace(swin_type=a.variant, window12=a.variant == "base", drop_path_rate=0.3))
+    fill_state_dict_(model)
+    model.to(dev).eval()
+    torch.manual_seed(1234)
+    enc = BertModel(BertConfig()).to(dev).eval()          # bert-base geometry, random init
+    enc.pooler = None
+    x = det_inputs(B, a.size, n_l, seed=1234)[0].to(dev)
+    _, _, m, tgt = (t.to(dev) for t in det_inputs(N, a.size, n_l, seed=77))
+    mask = m.squeeze(-1).long().contiguous()
+    ids = (torch.randint(1, enc.config.vocab_size, mask.shape, generator=torch.Generator().manual_seed(77)).to(dev) * mask).contiguous()
+    io = torch.tensor(image_of, dtype=torch.int32, device=dev)
+
+    def features():
+        with torch.no_grad():
+            return enc(ids, attention_mask=mask)[0].permute(0, 2, 1).contiguous(), mask.unsqueeze(-1).contiguous()
+    enc.fused_attention = enc.fused_embeddings = False
+    l0, m0 = features()
+    outer = Predictor(model, x.clone(), l0.clone(), m0.clone(), target=tgt.clone(), image_of=io.clone(), context=ops.StepContext())
+    outer.warmup_and_capture()
+
+    def today():          # test.py:60-83 on this stack: the encoder eagerly in front of every replay, its output copied into the static buffers
+        enc.fused_attention = enc.fused_embeddings = False
+        l, mm = features()
+        outer.l.copy_(l)
+        outer.m.copy_(mm)
+        outer.step()
+    regions, launches, captured = [("text_eager_then_replay", today)], {}, {"text_eager_then_replay": outer.captured}
+    for name, fa, fe in (("text_in_predictor", False, False), ("text_in_predictor_fused_attention", True, False),
+                         ("text_in_predictor_fused_attention_embeddings", True, True)):
+        enc.fused_attention, enc.fused_embeddings = fa, fe          # read at capture: the graph keeps the route it was captured with
+        p = Predictor(model, x.clone(), ids.clone(), mask.clone(), target=tgt.clone(), image_of=io.clone(), text_encoder=enc, context=ops.StepContext())
+        p.warmup_and_capture()
+        captured[name] = p.captured
+        with ops.use_context(p.context):
+            K.prof.start()
+            try:
+                p._body()
+            finally:
+                launches[name] = len(K.prof.stop())
+        regions.append((name, p.step))
+    enc.fused_attention = enc.fused_embeddings = False
+    K.prof.start()
+    try:
+        features()
+    finally:
+        n_text = len(K.prof.stop())
+    with ops.use_context(outer.context):
+        K.prof.start()
+        try:
+            outer._body()
+        finally:
+            launches["text_eager_then_replay"] = n_text + len(K.prof.stop())
+    for _ in range(a.warmup):
+        for _, fn in regions:
+            fn()
+    ts = {name: [] for name, _ in regions}
+    for _ in range(a.calls):          # the regions alternate: drift of the machine lands on all of them alike
+        for name, fn in regions:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts[name].append((time.perf_counter() - t0) * 1e3)
+    base = statistics.median(ts["text_eager_then_replay"])
+    for name, _ in regions:
+        v = sorted(ts[name])
+        report(path=name, pairs=N, images=B, tokens=n_l, captured=captured[name], ms_median=round(statistics.median(v), 3), ms_min=round(v[0], 3),
+               ms_max=round(v[-1], 3), ms_p10=round(v[len(v) // 10], 3), ms_p90=round(v[(9 * len(v)) // 10], 3), launches_eager_body=launches[name],
+               text_launches_eager=n_text if name == "text_eager_then_replay" else None, speedup=round(base / statistics.median(v), 4))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=30)
@@ -179,9 +271,22 @@ def main():
     ap.add_argument("--frames-u8", default=None, metavar="HxW", help="also time the input stage for a uint8 frame of this size: CPU pipeline vs Predictor.load_frames")
     ap.add_argument("--video-select", default=None, metavar="IND", help="run ONLY the annotated-frame comparison on Video-Swin-B, T=8, 384^2: all frames + index vs valid_indices=[IND]")
     ap.add_argument("--pairs", type=int, default=None, metavar="N", help="run ONLY the pair-list comparison: N batch-1 replays + EvalMeter.update vs one image_of replay + device meter")
+    ap.add_argument("--text-encoder", action="store_true", help="run ONLY the text-stage comparison: eager BERT in front of an image_of replay vs Predictor(text_encoder=)")
     a = ap.parse_args()
     if a.calls < 20:
         ap.error("--calls must be at least 20")
+    if a.text_encoder:
+        lines = []
+
+        def report_text(**kw):
+            kw.update(variant=a.variant, size=a.size, dtype=a.dtype, calls=a.calls)
+            lines.append(json.dumps(kw))
+            print(lines[-1], flush=True)
+        text_encoder(a, report_text)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if a.pairs is not None:
         lines = []
 
