@@ -1017,6 +1017,42 @@ int lavt_resize_norm_u8_batch(const lavt_pp_item_t* items, const lavt_pp_item_t*
 int lavt_resize_nearest_u8_batch(const lavt_pp_item_t* items, const lavt_pp_item_t* items_host, int n, const int32_t* tables, const int32_t* tables_host,
                                  int64_t table_elems, const uint8_t* masks, int64_t mask_bytes, int64_t* out, int Ho, int Wo, void* stream);
 
+/* Pseudo-video augmentation (`--pseudo_video_aug weak-rotate-translate-shear-crop`, args.py:132-137): affine warps of uint8 sources into uint8 frames
+ * of the same size, which the batched resize entries above then read.  New symbols only, added under ABI v7.  The contract is Pillow's, pixel for
+ * pixel: `Image.transform((Ws, Hs), Image.AFFINE, a, resample=BILINEAR)` for RGB, `resample=NEAREST` for masks, both with fill 0.
+ *
+ * lavt_pp_warp_t: one descriptor per WARPED frame, 128 bytes.  src_off / dst_off: byte offsets of the Hs x Ws (x 3) source in `src` and of the
+ *   warped frame of the same size in `dst`; any alignment; several descriptors may name one source, destinations must not overlap (not checked).
+ *   a[6]: Pillow's coefficients, output pixel (x, y) reads the source at (a0 (x + .5) + a1 (y + .5) + a2, a3 (x + .5) + a4 (y + .5) + a5).
+ *   The image entry reads a only; the mask entry reads, by `mode`,
+ *     LAVT_WARP_FIXED: A[6], Pillow's 16.16 fixed-point form of a (A0, A1, A3, A4 = floor(a * 65536 + .5); A2, A5 = the same of a2 + a0 / 2 + a1 / 2,
+ *       a5 + a3 / 2 + a4 / 2): out[y][x] = src[(A5 + A4 y + A3 x) >> 16][(A2 + A1 y + A0 x) >> 16] where that lies inside, else 0;
+ *     LAVT_WARP_TABLES (what Pillow does when a1 == 0 and a3 == 0): idx_x [Ws], idx_y [Hs], element offsets into the int32 table buffer:
+ *       out[y][x] = src[idx_y[y]][idx_x[x]], an index of -1 = outside = 0 (lavt_hip/preprocess.py: warp_axis_table builds them as Pillow does,
+ *       by repeated fp64 addition).
+ * lavt_affine_u8_batch: n descriptors, RGB bilinear in fp64 without contraction, the operations of Pillow's bilinear filter in its order; the result is
+ *   truncated to uint8.  warps is device memory, warps_host the same descriptors in HOST memory.  Checked from the host copy before launching:
+ *   1 <= n <= 65535, 1 <= Hs, Ws <= 8192, every source inside src_bytes and every destination inside dst_bytes, every coefficient finite.
+ * lavt_affine_nearest_u8_batch: n descriptors, single-channel nearest.  Checked as above (a is not read), and: mode is one of the two; FIXED: the
+ *   fixed-point coordinates at the four corners (0, 0), (Ws, 0), (0, Hs), (Ws, Hs) fit int32 (where Pillow's own `int` would overflow); TABLES: both
+ *   tables inside table_elems, every entry in [-1, size).  tables / tables_host may be null when table_elems is 0 and no descriptor is TABLES.
+ * LAVT_ERR_INVALID with a message, and no launch, when a check fails.  The kernels repeat the range checks on what they read from device memory: a
+ * descriptor or table that does not belong causes no read outside the buffers and no write. */
+#define LAVT_WARP_FIXED 0
+#define LAVT_WARP_TABLES 1
+typedef struct lavt_pp_warp {
+    int64_t src_off, dst_off;
+    int32_t Hs, Ws;
+    int32_t mode, idx_x, idx_y, reserved0;
+    double a[6];
+    int32_t A[6];
+    int32_t reserved1[4];
+} lavt_pp_warp_t;
+int lavt_affine_u8_batch(const lavt_pp_warp_t* warps, const lavt_pp_warp_t* warps_host, int n, const uint8_t* src, int64_t src_bytes, uint8_t* dst,
+                         int64_t dst_bytes, void* stream);
+int lavt_affine_nearest_u8_batch(const lavt_pp_warp_t* warps, const lavt_pp_warp_t* warps_host, int n, const int32_t* tables, const int32_t* tables_host,
+                                 int64_t table_elems, const uint8_t* src, int64_t src_bytes, uint8_t* dst, int64_t dst_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Text side (lavt_one / lavt_video carry BERT inside the model: lib/_utils.py:38-52; train.py:595-602; the encoder is HF transformers
  * 3.0.2 `BertModel`, absent from the reference tree).  Its Linear / LayerNorm / GELU / attention GEMMs use the entry points above.

@@ -128,7 +128,151 @@ __global__ __launch_bounds__(256) void resize_nearest_u8_batch_kernel(const lavt
     }
 }
 
+// ---- pseudo-video augmentation: Pillow's affine transform of uint8 sources into uint8 frames of the same size (lavt_pp_warp_t) ----
+static_assert(sizeof(lavt_pp_warp_t) == 128 && alignof(lavt_pp_warp_t) == 8, "lavt_pp_warp_t is 128 bytes (lavt_hip/_capi.py: PPWarp, lavt_hip/preprocess.py: WARP_DTYPE)");
+constexpr int PP_SIDE_MAX = 8192;
+constexpr int PP_WARP_ROWS = 4;                   // output rows of a work-group: one per wave, lane = x
+
+__host__ __device__ __forceinline__ bool pp_finite(double v) { return v - v == 0.0; }          // false for NaN and both infinities
+
+__host__ __device__ __forceinline__ bool pp_warp_inside(const lavt_pp_warp_t& w, int channels, int64_t src_bytes, int64_t dst_bytes) {
+    return w.Hs > 0 && w.Ws > 0 && w.Hs <= PP_SIDE_MAX && w.Ws <= PP_SIDE_MAX && pp_inside(w.src_off, (int64_t)w.Hs * w.Ws * channels, src_bytes) &&
+           pp_inside(w.dst_off, (int64_t)w.Hs * w.Ws * channels, dst_bytes);
+}
+
+__host__ __device__ __forceinline__ bool pp_warp_finite(const lavt_pp_warp_t& w) {
+    return pp_finite(w.a[0]) && pp_finite(w.a[1]) && pp_finite(w.a[2]) && pp_finite(w.a[3]) && pp_finite(w.a[4]) && pp_finite(w.a[5]);
+}
+
+// Pillow's fixed-point source coordinate of output (x, y), in 64 bits: what its 32-bit `int` holds wherever that does not overflow
+__host__ __device__ __forceinline__ int64_t pp_fixed(int32_t c, int32_t cy, int32_t cx, int x, int y) { return (int64_t)c + (int64_t)cy * y + (int64_t)cx * x; }
+
+__host__ __device__ __forceinline__ bool pp_fits_i32(int64_t v) { return v >= INT32_MIN && v <= INT32_MAX; }
+
+__host__ __device__ __forceinline__ bool pp_warp_fixed_fits(const lavt_pp_warp_t& w) {
+    for (int cy = 0; cy < 2; ++cy)
+        for (int cx = 0; cx < 2; ++cx)
+            if (!pp_fits_i32(pp_fixed(w.A[2], w.A[1], w.A[0], cx * w.Ws, cy * w.Hs)) || !pp_fits_i32(pp_fixed(w.A[5], w.A[4], w.A[3], cx * w.Ws, cy * w.Hs))) return false;
+    return true;
+}
+
+// Pillow's bilinear_filter32RGB behind affine_transform (Geometry.c), fp64.  Every product and sum is rounded on its own, as Pillow's build does:
+// hipcc would contract a * b + c into one fma, which moves isolated pixels by one.
+// Grid (x tiles of 64, row groups of 4, descriptor); lanes of a wave are neighbours along x, so their gathers fall into the same few source rows.
+__global__ __launch_bounds__(256) void affine_u8_batch_kernel(const lavt_pp_warp_t* __restrict__ warps, const uint8_t* __restrict__ src, int64_t src_bytes,
+                                                              uint8_t* __restrict__ dst, int64_t dst_bytes) {
+#pragma clang fp contract(off)
+    const lavt_pp_warp_t w = warps[blockIdx.z];
+    if (!pp_warp_inside(w, 3, src_bytes, dst_bytes) || !pp_warp_finite(w)) return;          // a descriptor that does not belong to these buffers: nothing is read, nothing written
+    const int x = blockIdx.x * PP_TW + (threadIdx.x & 63), y = blockIdx.y * PP_WARP_ROWS + (threadIdx.x >> 6);
+    if (x >= w.Ws || y >= w.Hs) return;
+    const uint8_t* p = src + w.src_off;
+    uint8_t* q = dst + w.dst_off + ((int64_t)y * w.Ws + x) * 3;
+    const double xc = x + 0.5, yc = y + 0.5;
+    double xin = w.a[0] * xc + w.a[1] * yc + w.a[2];
+    double yin = w.a[3] * xc + w.a[4] * yc + w.a[5];
+    if (xin < 0.0 || xin >= (double)w.Ws || yin < 0.0 || yin >= (double)w.Hs) {
+        q[0] = 0; q[1] = 0; q[2] = 0;
+        return;
+    }
+    xin -= 0.5;
+    yin -= 0.5;
+    const double fx = floor(xin), fy = floor(yin);          // xin, yin lie in [-0.5, 8192): the casts are exact
+    const int x0 = (int)fx, y0 = (int)fy;
+    const double dx = xin - fx, dy = yin - fy;
+    const int xa = min(max(x0, 0), w.Ws - 1), xb = min(max(x0 + 1, 0), w.Ws - 1);          // columns clamp ...
+    const uint8_t* r1 = p + (int64_t)min(max(y0, 0), w.Hs - 1) * w.Ws * 3;
+    const bool below = y0 + 1 >= 0 && y0 + 1 < w.Hs;                                        // ... the second row does not: past the last row v2 = v1
+    const uint8_t* r2 = p + (int64_t)(below ? y0 + 1 : 0) * w.Ws * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double a1 = r1[xa * 3 + c], b1 = r1[xb * 3 + c];
+        const double v1 = a1 + (b1 - a1) * dx;
+        double v2 = v1;
+        if (below) {
+            const double a2 = r2[xa * 3 + c], b2 = r2[xb * 3 + c];
+            v2 = a2 + (b2 - a2) * dx;
+        }
+        q[c] = (uint8_t)(int)(v1 + (v2 - v1) * dy);          // (UINT8) of Pillow: truncation
+    }
+}
+
+// Pillow's affine_fixed (general) and ImagingScaleAffine (axis-aligned, through the host's index tables) for single-channel masks
+__global__ __launch_bounds__(256) void affine_nearest_u8_batch_kernel(const lavt_pp_warp_t* __restrict__ warps, const int32_t* __restrict__ tables, int64_t table_elems,
+                                                                      const uint8_t* __restrict__ src, int64_t src_bytes, uint8_t* __restrict__ dst, int64_t dst_bytes) {
+    const lavt_pp_warp_t w = warps[blockIdx.z];
+    if (!pp_warp_inside(w, 1, src_bytes, dst_bytes)) return;
+    const bool by_tables = w.mode == LAVT_WARP_TABLES;
+    if (by_tables ? !(pp_inside(w.idx_x, w.Ws, table_elems) && pp_inside(w.idx_y, w.Hs, table_elems)) : (w.mode != LAVT_WARP_FIXED || !pp_warp_fixed_fits(w))) return;
+    const int x = blockIdx.x * PP_TW + (threadIdx.x & 63), y = blockIdx.y * PP_WARP_ROWS + (threadIdx.x >> 6);
+    if (x >= w.Ws || y >= w.Hs) return;
+    int64_t xi, yi;
+    if (by_tables) {
+        xi = tables[w.idx_x + x];
+        yi = tables[w.idx_y + y];
+    } else {
+        xi = pp_fixed(w.A[2], w.A[1], w.A[0], x, y) >> 16;
+        yi = pp_fixed(w.A[5], w.A[4], w.A[3], x, y) >> 16;
+    }
+    const bool in = xi >= 0 && xi < w.Ws && yi >= 0 && yi < w.Hs;          // (also what keeps a table entry that does not belong from being followed)
+    dst[w.dst_off + (int64_t)y * w.Ws + x] = in ? src[w.src_off + yi * w.Ws + xi] : (uint8_t)0;
+}
+
 }  // namespace
+
+extern "C" int lavt_affine_u8_batch(const lavt_pp_warp_t* warps, const lavt_pp_warp_t* warps_host, int n, const uint8_t* src, int64_t src_bytes, uint8_t* dst,
+                                    int64_t dst_bytes, void* stream) {
+    LAVT_CHECK_ARG(warps && warps_host && src && dst, "lavt_affine_u8_batch: null pointer");
+    LAVT_CHECK_ARG(n > 0 && n <= 65535 && src_bytes > 0 && dst_bytes > 0, "lavt_affine_u8_batch: bad sizes (1 <= n <= 65535)");
+    int Hmax = 0, Wmax = 0;
+    for (int i = 0; i < n; ++i) {
+        const lavt_pp_warp_t& w = warps_host[i];
+        LAVT_CHECK_ARG(w.Hs > 0 && w.Ws > 0 && w.Hs <= PP_SIDE_MAX && w.Ws <= PP_SIDE_MAX, "lavt_affine_u8_batch: warp %d: source %d x %d: sides are 1..%d", i, w.Hs, w.Ws, PP_SIDE_MAX);
+        LAVT_CHECK_ARG(pp_inside(w.src_off, (int64_t)w.Hs * w.Ws * 3, src_bytes), "lavt_affine_u8_batch: warp %d: a %d x %d x 3 source at byte offset %lld lies outside the %lld bytes of pixels", i,
+                       w.Hs, w.Ws, (long long)w.src_off, (long long)src_bytes);
+        LAVT_CHECK_ARG(pp_inside(w.dst_off, (int64_t)w.Hs * w.Ws * 3, dst_bytes), "lavt_affine_u8_batch: warp %d: a %d x %d x 3 frame at byte offset %lld lies outside the %lld bytes of the destination",
+                       i, w.Hs, w.Ws, (long long)w.dst_off, (long long)dst_bytes);
+        LAVT_CHECK_ARG(pp_warp_finite(w), "lavt_affine_u8_batch: warp %d: a coefficient is not finite", i);
+        Hmax = w.Hs > Hmax ? w.Hs : Hmax;
+        Wmax = w.Ws > Wmax ? w.Ws : Wmax;
+    }
+    hipLaunchKernelGGL(affine_u8_batch_kernel, dim3(cdiv(Wmax, PP_TW), cdiv(Hmax, PP_WARP_ROWS), n), dim3(256), 0, ST, warps, src, src_bytes, dst, dst_bytes);
+    LAVT_CHECK_LAUNCH("lavt_affine_u8_batch");
+    return LAVT_OK;
+}
+
+extern "C" int lavt_affine_nearest_u8_batch(const lavt_pp_warp_t* warps, const lavt_pp_warp_t* warps_host, int n, const int32_t* tables, const int32_t* tables_host,
+                                            int64_t table_elems, const uint8_t* src, int64_t src_bytes, uint8_t* dst, int64_t dst_bytes, void* stream) {
+    LAVT_CHECK_ARG(warps && warps_host && src && dst, "lavt_affine_nearest_u8_batch: null pointer");
+    LAVT_CHECK_ARG(n > 0 && n <= 65535 && src_bytes > 0 && dst_bytes > 0 && table_elems >= 0, "lavt_affine_nearest_u8_batch: bad sizes (1 <= n <= 65535)");
+    LAVT_CHECK_ARG(table_elems == 0 || (tables && tables_host), "lavt_affine_nearest_u8_batch: %lld table elements, but no tables", (long long)table_elems);
+    int Hmax = 0, Wmax = 0;
+    for (int i = 0; i < n; ++i) {
+        const lavt_pp_warp_t& w = warps_host[i];
+        LAVT_CHECK_ARG(w.Hs > 0 && w.Ws > 0 && w.Hs <= PP_SIDE_MAX && w.Ws <= PP_SIDE_MAX, "lavt_affine_nearest_u8_batch: warp %d: mask %d x %d: sides are 1..%d", i, w.Hs, w.Ws, PP_SIDE_MAX);
+        LAVT_CHECK_ARG(pp_inside(w.src_off, (int64_t)w.Hs * w.Ws, src_bytes), "lavt_affine_nearest_u8_batch: warp %d: a %d x %d mask at byte offset %lld lies outside the %lld bytes of masks", i, w.Hs,
+                       w.Ws, (long long)w.src_off, (long long)src_bytes);
+        LAVT_CHECK_ARG(pp_inside(w.dst_off, (int64_t)w.Hs * w.Ws, dst_bytes), "lavt_affine_nearest_u8_batch: warp %d: a %d x %d mask at byte offset %lld lies outside the %lld bytes of the destination", i,
+                       w.Hs, w.Ws, (long long)w.dst_off, (long long)dst_bytes);
+        LAVT_CHECK_ARG(w.mode == LAVT_WARP_FIXED || w.mode == LAVT_WARP_TABLES, "lavt_affine_nearest_u8_batch: warp %d: mode %d is neither LAVT_WARP_FIXED nor LAVT_WARP_TABLES", i, w.mode);
+        if (w.mode == LAVT_WARP_FIXED) {
+            LAVT_CHECK_ARG(pp_warp_fixed_fits(w), "lavt_affine_nearest_u8_batch: warp %d: the 16.16 fixed-point coordinates overflow int32 at a corner of the %d x %d frame", i, w.Hs, w.Ws);
+        } else {
+            LAVT_CHECK_ARG(pp_inside(w.idx_x, w.Ws, table_elems) && pp_inside(w.idx_y, w.Hs, table_elems),
+                           "lavt_affine_nearest_u8_batch: warp %d: an index table (idx_x %d, idx_y %d) lies outside the %lld table elements", i, w.idx_x, w.idx_y, (long long)table_elems);
+            const int32_t *ix = tables_host + w.idx_x, *iy = tables_host + w.idx_y;
+            for (int x = 0; x < w.Ws; ++x)
+                LAVT_CHECK_ARG(ix[x] >= -1 && ix[x] < w.Ws, "lavt_affine_nearest_u8_batch: warp %d: idx_x[%d] = %d is neither -1 nor a column of a %d-column mask", i, x, ix[x], w.Ws);
+            for (int y = 0; y < w.Hs; ++y)
+                LAVT_CHECK_ARG(iy[y] >= -1 && iy[y] < w.Hs, "lavt_affine_nearest_u8_batch: warp %d: idx_y[%d] = %d is neither -1 nor a row of a %d-row mask", i, y, iy[y], w.Hs);
+        }
+        Hmax = w.Hs > Hmax ? w.Hs : Hmax;
+        Wmax = w.Ws > Wmax ? w.Ws : Wmax;
+    }
+    hipLaunchKernelGGL(affine_nearest_u8_batch_kernel, dim3(cdiv(Wmax, PP_TW), cdiv(Hmax, PP_WARP_ROWS), n), dim3(256), 0, ST, warps, tables, table_elems, src, src_bytes, dst, dst_bytes);
+    LAVT_CHECK_LAUNCH("lavt_affine_nearest_u8_batch");
+    return LAVT_OK;
+}
 
 extern "C" int lavt_resize_norm_u8_batch(const lavt_pp_item_t* items, const lavt_pp_item_t* items_host, int n, const int32_t* tables, const int32_t* tables_host,
                                          int64_t table_elems, const uint8_t* pixels, int64_t pixel_bytes, float* out, int Ho, int Wo, float mean0, float mean1,

@@ -181,6 +181,15 @@ class PPItem(C.Structure):
                 ("coef_y", i32), ("bounds_y", i32), ("ksize_y", i32), ("idx_y", i32), ("idx_x", i32), ("reserved0", i32), ("reserved1", i32)]
 
 
+WARP_FIXED, WARP_TABLES = 0, 1                                             # PPWarp.mode (LAVT_WARP_FIXED, LAVT_WARP_TABLES)
+
+
+class PPWarp(C.Structure):
+    """lavt_pp_warp_t: one warped frame of the pseudo-video augmentation (128 bytes; lavt_hip.preprocess.WARP_DTYPE is the numpy form the blob is packed with)"""
+    _fields_ = [("src_off", i64), ("dst_off", i64), ("Hs", i32), ("Ws", i32), ("mode", i32), ("idx_x", i32), ("idx_y", i32), ("reserved0", i32),
+                ("a", C.c_double * 6), ("A", i32 * 6), ("reserved1", i32 * 4)]
+
+
 # every symbol include/lavt_hip.h declares, with its argument types (tests check this list against the header)
 _PROTOTYPES = {
     "lavt_abi_version": [],
@@ -332,6 +341,8 @@ _PROTOTYPES = {
     "lavt_resize_nearest_u8": [vp, i64, i32, i32, i32, vp, vp, vp, i32, i32, vp],
     "lavt_resize_norm_u8_batch": [vp, vp, i32, vp, vp, i64, vp, i64, vp, i32, i32, f32, f32, f32, f32, f32, f32, vp],
     "lavt_resize_nearest_u8_batch": [vp, vp, i32, vp, vp, i64, vp, i64, vp, i32, i32, vp],
+    "lavt_affine_u8_batch": [vp, vp, i32, vp, i64, vp, i64, vp],
+    "lavt_affine_nearest_u8_batch": [vp, vp, i32, vp, vp, i64, vp, i64, vp, i64, vp],
     # deterministic forms (no float atomics): the host calls them instead of their siblings in deterministic mode
     "lavt_gemm_tn_v2_eligible": [C.POINTER(GemmTN)],
     "lavt_reduce_partials_det_stage": [i32],

@@ -149,6 +149,7 @@ class _ValidIndices:
         if self.valid_indices is None:
             raise ValueError(f"{type(self).__name__}.set_valid_indices: built without a valid_indices buffer")
         flat = torch.tensor(flat_valid_indices(per_clip, frames_per_clip, self._n_frames(), count=self.valid_indices.numel()), dtype=torch.int32)
+        self._valid_per_clip = [int(v) for v in per_clip]          # (stage_batch(augment=): the mask of a clip moves with its annotated frame)
         if self.valid_indices.is_cuda:
             flat = flat.pin_memory()
         self.valid_indices.copy_(flat, non_blocking=True)
@@ -168,7 +169,7 @@ class _BatchInput:
             self.batch_preprocessor = BatchPreprocessor((int(self.x.shape[-2]), int(self.x.shape[-1])), device=self.x.device)
         return self.batch_preprocessor
 
-    def stage_batch(self, images, targets=None, repeat=None, *, frame_map=None, target_map=None):
+    def stage_batch(self, images, targets=None, repeat=None, *, frame_map=None, target_map=None, augment=None):
         """Pack the batch and start its upload; writes neither `image` nor `target`, so it may be called while the previous replay is still running.
         images: host list of PIL images / uint8 (Hs, Ws, 3) arrays, one per frame of the image buffer (B, or B*T for a clip buffer (B, T, 3, H, W),
         which is written as B*T frames); repeat=T: B still images, each repeated into a T-frame clip (`--pseudo_video_aug vanilla`, args.py:132-134).
@@ -177,12 +178,29 @@ class _BatchInput:
         images.  frame_map / target_map: the source of every output frame / mask, for any other arrangement.  Frames are counted against the image
         buffer and masks against the target buffer separately, so a pair-list batch (image_of=) brings its B images and its N masks, mask j for slot
         j, as they are: every image is decoded, resized and uploaded once, however many slots name it.
+        augment: a lavt_hip.preprocess.PseudoVideoAugment (`--pseudo_video_aug weak-rotate-translate-shear-crop`, args.py:134-137), with repeat=T on a
+        clip buffer: every frame of a clip gets its own affine motion of the still image, drawn from the augmenter, warped on the device with
+        Pillow's pixels before the resize; each image is still uploaded once.  A mask moves with its frame; one mask per clip (valid_indices) moves
+        with the clip's annotated frame, which set_valid_indices must have named.
         ValueError for wrong counts or a target buffer of another size, TypeError for CUDA input, RuntimeError inside a graph capture: in every case
         before anything is written."""
-        from .preprocess import _BatchPlan
         who = f"{type(self).__name__}.stage_batch"
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError(f"{who}: the input stage runs eagerly in front of step() (a host-side pack and an upload): call it outside the graph capture")
+        if augment is not None:
+            if repeat is None or self.x.dim() != 5 or target_map is not None:
+                raise ValueError(f"{who}: augment= makes clips of still images: it needs repeat=T on a clip buffer (B, T, 3, H, W) and no target_map (the image buffer "
+                                 f"is {tuple(self.x.shape)}, repeat is {repeat})")
+            saved = augment.state_dict()
+            try:
+                return self._stage_batch(who, images, targets, repeat, frame_map, target_map, augment)
+            except Exception:
+                augment.load_state_dict(saved)          # a refused batch draws nothing
+                raise
+        return self._stage_batch(who, images, targets, repeat, frame_map, target_map, None)
+
+    def _stage_batch(self, who, images, targets, repeat, frame_map, target_map, augment):
+        from .preprocess import _BatchPlan, _host_list
         H, W = int(self.x.shape[-2]), int(self.x.shape[-1])
         if targets is not None:
             if self.t is None:
@@ -192,7 +210,25 @@ class _BatchInput:
                                  "targets at the original frame size): copy those into `target` yourself")
             if repeat is not None and target_map is None and isinstance(targets, (list, tuple)) and len(targets) == self.t.shape[0]:
                 target_map = range(len(targets))          # one mask per target sample already (valid_indices: the annotated frame of every clip)
-        plan = _BatchPlan(images, targets, (H, W), frame_map, target_map, repeat)
+        warps = target_warps = None
+        if augment is not None:
+            T = int(repeat)
+            images = _host_list(images, True, "pack_batch: images")
+            clips = augment.draw([a.shape[:2] for a in images], T)
+            warps = [w for clip in clips for w in clip]
+            if targets is not None:
+                n = len(_host_list(targets, False, "pack_batch: targets"))
+                if n == len(warps):                        # one mask per frame
+                    target_warps = warps
+                elif target_map is not None:               # one mask per clip (set above): that of the annotated frame
+                    per_clip = getattr(self, "_valid_per_clip", None)
+                    if getattr(self, "valid_indices", None) is None or per_clip is None or len(per_clip) != n:
+                        raise ValueError(f"{who}: augment= with one mask per clip needs the annotated frame of every clip: call set_valid_indices(per_clip, T) first")
+                    target_warps = [clip[f] for clip, f in zip(clips, per_clip)]
+                elif n == len(clips):                      # B masks for a target buffer of B*T: repeated like the images
+                    target_warps = warps
+                # (any other count is refused below, by the plan or against the target buffer)
+        plan = _BatchPlan(images, targets, (H, W), frame_map, target_map, repeat, warps, target_warps)
         L = plan.layout
         if L.n_frames != self._n_frames():
             raise ValueError(f"{who}: {L.n_frames} frames for an image buffer of {self._n_frames()} ({tuple(self.x.shape)})")
@@ -211,9 +247,9 @@ class _BatchInput:
             raise RuntimeError(f"{who}: no staged batch (call stage_batch() first; a batch is committed once)")
         pp.commit(self.x, self.t if pp._staged[1].n_targets else None)
 
-    def load_batch(self, images, targets=None, repeat=None, *, frame_map=None, target_map=None):
+    def load_batch(self, images, targets=None, repeat=None, *, frame_map=None, target_map=None, augment=None):
         """stage_batch + commit_batch"""
-        self.stage_batch(images, targets, repeat, frame_map=frame_map, target_map=target_map)
+        self.stage_batch(images, targets, repeat, frame_map=frame_map, target_map=target_map, augment=augment)
         self.commit_batch()
 
 

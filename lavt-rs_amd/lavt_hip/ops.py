@@ -3471,25 +3471,71 @@ def _packed_batch(who, blob, blob_host, layout, out, n, shape, dtype):
     return blob.data_ptr(), blob_host.ctypes.data
 
 
-def resize_normalize_u8_batch(blob, blob_host, layout, out, mean, std):
+def _warped_extent(who, blob, layout, warp_layout, section_off, section_bytes):
+    """the bytes a resize launch may read from its section's start: the section itself, or, for a batch packed with warps, everything up to the end of
+    the device scratch behind the blob, where the warped frames lie (`blob` must hold warp_layout.device_bytes)"""
+    if warp_layout is None:
+        return section_bytes
+    if blob.numel() < warp_layout.device_bytes:
+        raise ValueError(f"{who}: the device buffer holds {blob.numel()} bytes, the warped batch needs {warp_layout.device_bytes} (blob + scratch)")
+    return warp_layout.device_bytes - section_off
+
+
+def resize_normalize_u8_batch(blob, blob_host, layout, out, mean, std, warp_layout=None):
     """resize_normalize_u8 for sources of mixed sizes, one launch: `blob` is a packed batch (lavt_hip.preprocess.pack_batch: descriptors, int32 tables,
     pixels) on the device, `blob_host` the same bytes on the host (a uint8 numpy array: the C entry validates descriptors and tables from it before it
-    launches), `layout` the record pack_batch returned -> out fp32 (n_frames, 3, Ho, Wo), written in place."""
+    launches), `layout` the record pack_batch returned -> out fp32 (n_frames, 3, Ho, Wo), written in place.  warp_layout: the batch was packed with
+    warps, some descriptors name frames that affine_u8_batch wrote into the scratch behind the blob."""
     Ho, Wo = layout.out_size
     d, h = _packed_batch("resize_normalize_u8_batch", blob, blob_host, layout, out, layout.n_frames, (3, Ho, Wo), torch.float32)
+    pixel_bytes = _warped_extent("resize_normalize_u8_batch", blob, layout, warp_layout, layout.pixels_off, layout.pixel_bytes)
     _note(f"resize-norm-batch {layout.n_frames}->{Ho}x{Wo}", nbytes=layout.pixel_bytes + layout.n_frames * 12 * Ho * Wo)
     K.check(K.lib.lavt_resize_norm_u8_batch(d + layout.items_off, h + layout.items_off, layout.n_frames, d + layout.tables_off, h + layout.tables_off, layout.table_elems,
-                                            d + layout.pixels_off, layout.pixel_bytes, K.ptr(out), Ho, Wo, *(float(v) for v in mean), *(float(v) for v in std), K.stream()))
+                                            d + layout.pixels_off, pixel_bytes, K.ptr(out), Ho, Wo, *(float(v) for v in mean), *(float(v) for v in std), K.stream()))
     return out
 
 
-def resize_nearest_u8_batch(blob, blob_host, layout, out):
+def resize_nearest_u8_batch(blob, blob_host, layout, out, warp_layout=None):
     """resize_nearest_u8 for masks of mixed sizes, one launch, from the same packed batch -> out int64 (n_targets, Ho, Wo), written in place"""
     Ho, Wo = layout.out_size
     if layout.n_targets < 1:
         raise ValueError("resize_nearest_u8_batch: the batch was packed without targets")
     d, h = _packed_batch("resize_nearest_u8_batch", blob, blob_host, layout, out, layout.n_targets, (Ho, Wo), torch.int64)
+    mask_bytes = _warped_extent("resize_nearest_u8_batch", blob, layout, warp_layout, layout.masks_off, layout.mask_bytes)
     _note(f"resize-nearest-batch {layout.n_targets}->{Ho}x{Wo}", nbytes=layout.mask_bytes + layout.n_targets * 8 * Ho * Wo)
     K.check(K.lib.lavt_resize_nearest_u8_batch(d + layout.titems_off, h + layout.titems_off, layout.n_targets, d + layout.tables_off, h + layout.tables_off, layout.table_elems,
-                                               d + layout.masks_off, layout.mask_bytes, K.ptr(out), Ho, Wo, K.stream()))
+                                               d + layout.masks_off, mask_bytes, K.ptr(out), Ho, Wo, K.stream()))
     return out
+
+
+def _warp_buffers(who, blob, blob_host, layout, warp_layout):
+    if not isinstance(blob, torch.Tensor) or not blob.is_cuda:
+        raise RuntimeError(f"liblavt_hip operates on GPU memory only (got a CPU tensor for `{who}`); there is no CPU fallback")
+    if blob.dtype != torch.uint8 or not blob.is_contiguous() or blob.numel() < warp_layout.device_bytes or blob_host.dtype != np.uint8 or blob_host.size < layout.nbytes or not blob_host.flags.c_contiguous:
+        raise ValueError(f"{who}: the device buffer must be contiguous uint8 of at least {warp_layout.device_bytes} bytes (blob + scratch) and the host copy of at least "
+                         f"{layout.nbytes}, got {tuple(blob.shape)} on the device and {blob_host.shape} on the host")
+    return blob.data_ptr(), blob_host.ctypes.data
+
+
+def affine_u8_batch(blob, blob_host, layout, warp_layout):
+    """The image half of the pseudo-video augmentation, one launch: every image warp descriptor of a batch packed with `warps=` (lavt_hip.preprocess
+    .pack_batch) reads its source in the pixel section and writes Pillow's `transform(AFFINE, BILINEAR)` of it, uint8 HWC of the same size, into the
+    scratch that follows the blob in `blob` (warp_layout.scratch_off .. device_bytes).  The resize launch then reads those frames."""
+    W = warp_layout
+    if W.n_image_warps < 1:
+        raise ValueError("affine_u8_batch: the batch was packed without image warps")
+    d, h = _warp_buffers("affine_u8_batch", blob, blob_host, layout, W)
+    _note(f"affine-batch {W.n_image_warps}", nbytes=2 * W.image_scratch_bytes)
+    K.check(K.lib.lavt_affine_u8_batch(d + W.image_warps_off, h + W.image_warps_off, W.n_image_warps, d + layout.pixels_off, layout.pixel_bytes, d + W.scratch_off,
+                                       W.scratch_bytes, K.stream()))
+
+
+def affine_nearest_u8_batch(blob, blob_host, layout, warp_layout):
+    """The mask half: Pillow's `transform(AFFINE, NEAREST)` of the masks named by the mask warp descriptors, into the same scratch"""
+    W = warp_layout
+    if W.n_mask_warps < 1:
+        raise ValueError("affine_nearest_u8_batch: the batch was packed without mask warps")
+    d, h = _warp_buffers("affine_nearest_u8_batch", blob, blob_host, layout, W)
+    _note(f"affine-nearest-batch {W.n_mask_warps}", nbytes=2 * W.mask_scratch_bytes)
+    K.check(K.lib.lavt_affine_nearest_u8_batch(d + W.mask_warps_off, h + W.mask_warps_off, W.n_mask_warps, d + layout.tables_off, h + layout.tables_off, layout.table_elems,
+                                               d + layout.masks_off, layout.mask_bytes, d + W.scratch_off, W.scratch_bytes, K.stream()))
