@@ -931,6 +931,56 @@ int64_t lavt_eval_meter_bytes(int capacity);
 int lavt_eval_meter_append(const int32_t* iu, const int32_t* image_of /* NULL: every slot live */, int n_images, int n, void* block, int capacity, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * J&F measure (csrc/jf_measure.hip, csrc/meters.hip): the video measure of Refer-YouTube-VOS / Ref-DAVIS -- J, region similarity; F, the boundary
+ * F-measure of the DAVIS 2017 evaluation; J&F, their mean -- as the toolkit's db_eval_iou, db_eval_boundary and _seg2bmap compute them WITHOUT void
+ * pixels.  The recall and decay statistics of the toolkit are not computed.  Five new symbols under ABI v7.
+ *
+ * A frame is a predicted mask P and a ground truth G, both H x W, nonzero = foreground.
+ *   Region       I = |P and G|, U = |P or G|;  J = 1 if U == 0 (two empty masks agree -- unlike the evaluation meter above), else I / U.
+ *   Boundary map b = bmap(S):  e[y,x] = S[y,x+1], s[y,x] = S[y+1,x], se[y,x] = S[y+1,x+1], zero where the source lies outside the frame;
+ *                b = (S^e) | (S^s) | (S^se); then the last row is S^e, the last column S^s and the bottom-right pixel 0.
+ *   Radius       bound_pix = ceil(0.008 * sqrt(H*H + W*W)) in fp64 is the toolkit's (8 at 480x854, 12 at 720x1280); the caller passes it.
+ *   Disk         {(dy,dx) : dy*dy + dx*dx <= r*r};  dil(b)[y,x] = OR of b[y+dy,x+dx] over the disk, positions outside the frame ignored.
+ *   Counts       n_fg = |bmap(P)|, n_gt = |bmap(G)|, m_fg = |bmap(P) and dil(bmap(G))|, m_gt = |bmap(G) and dil(bmap(P))|.
+ *   F            n_fg == 0 and n_gt > 0: precision 1, recall 0;  n_fg > 0 and n_gt == 0: precision 0, recall 1;  both zero: 1 and 1;
+ *                otherwise precision = m_fg / n_fg, recall = m_gt / n_gt.  F = 0 if precision + recall == 0, else ((2.0 * p) * r) / (p + r),
+ *                every step one fp64 rounding.
+ *   A sequence   one object or expression over its frames: J_seq, F_seq = the sum over its frames in frame order, divided by their number.
+ *   Dataset      J, F = the means of J_seq, F_seq over the sequences;  J&F = (J + F) / 2.
+ *
+ * lavt_boundary_counts: pred uint8 [n][H][W] (the mask of lavt_upsample_mask), and exactly one of target_u8 (uint8) / target_i64 (int64) [n][H][W];
+ * nonzero = foreground for all three, whatever the value (255, 7 and 1 << 32 are foreground).  counts int32 [n][8]: row j =
+ * {I, U, n_fg, n_gt, m_fg, m_gt, 0, 0} of frame j.  Every call overwrites every row (a zero-fill kernel, then integer atomic adds -- order-independent,
+ * no floating point anywhere), so a replayed graph needs nothing from what the buffer held.  Frames adjacent in memory never see each other's pixels.
+ * Three kernels (fill, pack, boundary), capturable, no host synchronisation.  ws: lavt_boundary_counts_ws(n, H, W) 64-bit words of scratch (host
+ * arithmetic: 2 * n * H * ceil(W / 64), the two masks as bit rows; 0 for a non-positive size), 8-byte aligned.
+ * LAVT_ERR_INVALID with counts untouched and nothing launched: a null pred, ws or counts, both or neither target, a non-positive size, bound_pix outside
+ * 1 .. LAVT_BOUNDARY_MAX_RADIUS, ws_words below the query.
+ *
+ * The J&F meter block: lavt_jf_meter_bytes(capacity) = 8 * LAVT_JF_METER_HEADER_DOUBLES + capacity * LAVT_JF_METER_RECORD_BYTES bytes of device
+ * memory, 8-byte aligned, zero-filled by the caller except header[0].  Header: fp64[LAVT_JF_METER_HEADER_DOUBLES], counts exact up to 2^53:
+ *   [0] capacity (host; informational)      [1] hold: written by the HOST only, non-zero = an append stores nothing
+ *   [2] the running sequence number of the next record
+ *   the accumulators, zeroed by the host's reset:
+ *   [3] sequences      [4] sum of J_seq      [5] sum of F_seq      [6] frames      [7] sum of J over frames      [8] sum of F over frames
+ *   [9..15] reserved, zero
+ * Ring: capacity records of LAVT_JF_METER_RECORD_BYTES bytes behind the header, sequence `q` in slot q % capacity:
+ *   offset 0 int32 frames | 4 int32 0 | 8 fp64 J_seq | 16 fp64 F_seq | 24 int64 running sequence number
+ *
+ * lavt_jf_meter_append: ONE single-writer launch behind the counts.  n must be a multiple of frames_per_seq; sequence k is the frames
+ * k*T .. k*T + T - 1, taken in ascending order.  live: device int32 [n], live[j] == 0 = frame j is not read; NULL = every frame is live.  Inside a
+ * sequence the live frames are taken in ascending order with the arithmetic above in fp64; [6], [7], [8] move with every live frame; a sequence
+ * with no live frame stores nothing.  `capacity` must be the block's. */
+#define LAVT_BOUNDARY_MAX_RADIUS 40
+#define LAVT_JF_METER_HEADER_DOUBLES 16
+#define LAVT_JF_METER_RECORD_BYTES 32
+int64_t lavt_boundary_counts_ws(int n, int H, int W);
+int lavt_boundary_counts(const uint8_t* pred, const uint8_t* target_u8, const int64_t* target_i64, int n, int H, int W, int bound_pix, uint64_t* ws,
+                         int64_t ws_words, int32_t* counts /* [n][8] */, void* stream);
+int64_t lavt_jf_meter_bytes(int capacity);
+int lavt_jf_meter_append(const int32_t* counts, const int32_t* live /* NULL: every frame */, int n, int frames_per_seq, void* block, int capacity, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Inference path (csrc/infer.hip; reference test.py:60-110 and test_ytvos.py:230-260: batch-1 forward under model.eval() / torch.no_grad(), argmax,
  * I / U).  New symbols only, added under ABI v7: no existing prototype or struct changed.
  *

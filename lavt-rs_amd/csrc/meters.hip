@@ -146,6 +146,83 @@ __global__ __launch_bounds__(64) void eval_meter_append_kernel(const int32_t* __
     }
 }
 
+// ---------------------------------------------------------------------------------------------- J&F meter (include/lavt_hip.h "J&F measure")
+// The DAVIS 2017 sequence means over the count rows of lavt_boundary_counts.  One wave, as the evaluation meter: every lane loads one frame's six counts
+// and liveness (a chunk of 64 frames in flight at once), lane 0 walks the frames in order -- every fp64 sum is sequential -- and closes a sequence
+// behind every frames_per_seq-th frame.
+enum { J_CAPACITY = 0, J_HOLD, J_N, J_SEQS, J_JSEQ_SUM, J_FSEQ_SUM, J_FRAMES, J_JFRAME_SUM, J_FFRAME_SUM, J_END };
+
+struct jf_record {
+    int32_t frames, zero;
+    double J, F;
+    int64_t seq;
+};
+static_assert(sizeof(jf_record) == LAVT_JF_METER_RECORD_BYTES, "the record layout is the contract of include/lavt_hip.h");
+static_assert(J_END <= LAVT_JF_METER_HEADER_DOUBLES, "the header holds the accumulators");
+
+__global__ __launch_bounds__(64) void jf_meter_append_kernel(const int32_t* __restrict__ counts, const int32_t* __restrict__ live_of, int n, int T,
+                                                             double* __restrict__ block, int capacity) {
+    __shared__ int32_t sc[64][6];
+    const int lane = threadIdx.x;
+    double h[J_END];
+#pragma unroll
+    for (int i = 0; i < J_END; ++i) h[i] = block[i];
+    // hold (host-written), or a block that was never initialised: nothing is stored (uniform over the wave, so the barriers below are safe)
+    if (h[J_HOLD] != 0.0 || !(h[J_N] >= 0.0 && h[J_N] < 9.0e15) || capacity <= 0) return;
+    jf_record* ring = reinterpret_cast<jf_record*>(block + LAVT_JF_METER_HEADER_DOUBLES);
+    double js = 0.0, fs = 0.0;          // the open sequence: sums of J and F over its live frames, and their number
+    int cnt = 0;
+    for (int base = 0; base < n; base += 64) {
+        const int s = base + lane;
+        const bool live = s < n && (!live_of || live_of[s] != 0);
+        if (live) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) sc[lane][k] = counts[(int64_t)s * 8 + k];
+        }
+        const unsigned long long mask = __ballot(live);
+        __syncthreads();
+        if (lane == 0) {
+            const int m = min(64, n - base);
+            for (int j = 0; j < m; ++j) {
+                if ((mask >> j) & 1ull) {
+                    const int32_t I = sc[j][0], U = sc[j][1], nfg = sc[j][2], ngt = sc[j][3], mfg = sc[j][4], mgt = sc[j][5];
+                    const double J = U == 0 ? 1.0 : (double)I / (double)U;          // db_eval_iou: two empty masks agree
+                    double p, r;
+                    if (nfg == 0 && ngt > 0) { p = 1.0; r = 0.0; }
+                    else if (nfg > 0 && ngt == 0) { p = 0.0; r = 1.0; }
+                    else if (nfg == 0 && ngt == 0) { p = 1.0; r = 1.0; }
+                    else { p = (double)mfg / (double)nfg; r = (double)mgt / (double)ngt; }
+                    const double F = (p + r == 0.0) ? 0.0 : ((2.0 * p) * r) / (p + r);
+                    js += J;
+                    fs += F;
+                    cnt += 1;
+                    h[J_FRAMES] += 1.0;
+                    h[J_JFRAME_SUM] += J;
+                    h[J_FFRAME_SUM] += F;
+                }
+                if ((base + j + 1) % T == 0) {          // the sequence ends here; one without a live frame stores nothing
+                    if (cnt > 0) {
+                        const int64_t seq = (int64_t)h[J_N];
+                        jf_record rec;
+                        rec.frames = cnt; rec.zero = 0; rec.J = js / (double)cnt; rec.F = fs / (double)cnt; rec.seq = seq;
+                        ring[seq % capacity] = rec;
+                        h[J_N] += 1.0;
+                        h[J_SEQS] += 1.0;
+                        h[J_JSEQ_SUM] += rec.J;
+                        h[J_FSEQ_SUM] += rec.F;
+                    }
+                    js = 0.0; fs = 0.0; cnt = 0;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int i = J_N; i < J_END; ++i) block[i] = h[i];
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- hard-mask I / U of a training batch (lavt_upsample_iu)
 // train.py:64-76 on the low-resolution logits: every full-resolution pixel is recomputed from its four neighbours exactly as upsample_ce_fwd_kernel
 // does (bl_coord / upce_at, common.h; pred = up1 > up0, a tie is class 0), pred && tgt and pred || tgt are counted per wave with ballot + popcount --
@@ -232,6 +309,19 @@ extern "C" int lavt_eval_meter_append(const int32_t* iu, const int32_t* image_of
     LAVT_CHECK_ARG((reinterpret_cast<uintptr_t>(block) & 7) == 0, "lavt_eval_meter_append: the block must be 8-byte aligned");
     hipLaunchKernelGGL(eval_meter_append_kernel, dim3(1), dim3(64), 0, ST, iu, image_of, n_images, n, reinterpret_cast<double*>(block), capacity);
     LAVT_CHECK_LAUNCH("lavt_eval_meter_append");
+    return LAVT_OK;
+}
+
+extern "C" int64_t lavt_jf_meter_bytes(int capacity) {
+    return capacity > 0 ? (int64_t)LAVT_JF_METER_HEADER_DOUBLES * 8 + (int64_t)capacity * LAVT_JF_METER_RECORD_BYTES : 0;
+}
+
+extern "C" int lavt_jf_meter_append(const int32_t* counts, const int32_t* live, int n, int frames_per_seq, void* block, int capacity, void* stream) {
+    LAVT_CHECK_ARG(counts && block && n > 0 && capacity > 0, "lavt_jf_meter_append: bad arguments (counts, block, n > 0, capacity > 0)");
+    LAVT_CHECK_ARG(frames_per_seq > 0 && n % frames_per_seq == 0, "lavt_jf_meter_append: %d frames are not whole sequences of %d", n, frames_per_seq);
+    LAVT_CHECK_ARG((reinterpret_cast<uintptr_t>(block) & 7) == 0, "lavt_jf_meter_append: the block must be 8-byte aligned");
+    hipLaunchKernelGGL(jf_meter_append_kernel, dim3(1), dim3(64), 0, ST, counts, live, n, frames_per_seq, reinterpret_cast<double*>(block), capacity);
+    LAVT_CHECK_LAUNCH("lavt_jf_meter_append");
     return LAVT_OK;
 }
 

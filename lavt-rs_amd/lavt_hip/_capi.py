@@ -301,6 +301,10 @@ _PROTOTYPES = {
     "lavt_upsample_iu_sel": [i32, vp, vp, i32, vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, vp],
     "lavt_eval_meter_bytes": [i32],
     "lavt_eval_meter_append": [vp, vp, i32, i32, vp, i32, vp],
+    "lavt_boundary_counts_ws": [i32, i32, i32],
+    "lavt_boundary_counts": [vp, vp, vp, i32, i32, i32, i32, vp, i64, vp, vp],
+    "lavt_jf_meter_bytes": [i32],
+    "lavt_jf_meter_append": [vp, vp, i32, i32, vp, i32, vp],
     "lavt_ln_fold_multi": [vp, i32, vp],
     "lavt_upsample_ce_fwd": [i32, vp, vp, f32, f32, vp, i64, vp, i32, i32, i32, i32, i32, vp],
     "lavt_upsample_ce_bwd": [i32, vp, vp, f32, f32, vp, vp, vp, i32, i32, i32, i32, i32, vp],
@@ -369,12 +373,14 @@ _cdll.lavt_gemm_tn_grouped_sk_ws.restype = C.c_int64
 _cdll.lavt_grad_norm_ws.restype = C.c_int64
 _cdll.lavt_meter_bytes.restype = C.c_int64
 _cdll.lavt_eval_meter_bytes.restype = C.c_int64
+_cdll.lavt_boundary_counts_ws.restype = C.c_int64
+_cdll.lavt_jf_meter_bytes.restype = C.c_int64
 _cdll.lavt_upsample_dice_boundary_ws.restype = C.c_int64
 _cdll.lavt_upsample_iu_ws.restype = C.c_int64
 _cdll.lavt_reduce_partials_det_stage.restype = C.c_int64
 _cdll.lavt_window_attn_bwd_det_ws.restype = C.c_int64
 _cdll.lavt_last_error.argtypes = []
-for _name in ("lavt_last_error", "lavt_window_attn_bwd_ws", "lavt_window_attn_stream_ok", "lavt_window_attn_stream_bwd_ws", "lavt_attn_uses_table", "lavt_abi_version", "lavt_layernorm_bwd_blocks", "lavt_window_attn_bwd_pieces", "lavt_gemm_tn_pieces", "lavt_pwam_q_parts", "lavt_pwam_words_records", "lavt_pwam_mix1_records", "lavt_adamw_chunk_elems", "lavt_tuning_reload", "lavt_conv3x3_wgrad_ws", "lavt_conv3x3_wgrad_f8_ok", "lavt_gemm_tn_grouped_sk_ws", "lavt_gemm_nt_colstats_plan", "lavt_gemm_nt_route", "lavt_gemm_tn_route", "lavt_gemm_tn_group_route", "lavt_cls_head_bwd_blocks", "lavt_reduce_partials_column_blocks", "lavt_grad_norm_ws", "lavt_upsample_dice_boundary_ws", "lavt_upsample_iu_ws", "lavt_reduce_partials_det_stage", "lavt_window_attn_bwd_det_ws", "lavt_gemm_tn_v2_eligible", "lavt_meter_bytes", "lavt_eval_meter_bytes"):      # queries, not launches: never timed
+for _name in ("lavt_last_error", "lavt_window_attn_bwd_ws", "lavt_window_attn_stream_ok", "lavt_window_attn_stream_bwd_ws", "lavt_attn_uses_table", "lavt_abi_version", "lavt_layernorm_bwd_blocks", "lavt_window_attn_bwd_pieces", "lavt_gemm_tn_pieces", "lavt_pwam_q_parts", "lavt_pwam_words_records", "lavt_pwam_mix1_records", "lavt_adamw_chunk_elems", "lavt_tuning_reload", "lavt_conv3x3_wgrad_ws", "lavt_conv3x3_wgrad_f8_ok", "lavt_gemm_tn_grouped_sk_ws", "lavt_gemm_nt_colstats_plan", "lavt_gemm_nt_route", "lavt_gemm_tn_route", "lavt_gemm_tn_group_route", "lavt_cls_head_bwd_blocks", "lavt_reduce_partials_column_blocks", "lavt_grad_norm_ws", "lavt_upsample_dice_boundary_ws", "lavt_upsample_iu_ws", "lavt_reduce_partials_det_stage", "lavt_window_attn_bwd_det_ws", "lavt_gemm_tn_v2_eligible", "lavt_meter_bytes", "lavt_eval_meter_bytes", "lavt_boundary_counts_ws", "lavt_jf_meter_bytes"):      # queries, not launches: never timed
     setattr(lib, _name, getattr(_cdll, _name))
 
 EXPORTED = tuple(_PROTOTYPES) + ("lavt_last_error",)

@@ -890,6 +890,10 @@ class TrainStep(_ValidIndices, _ImageOf, _BatchInput):
         return self.loss
 
 
+_JF_WHOLE_SEQUENCES = ("Predictor: the J&F meter takes the frames of a step as whole sequences in frame order; it cannot be combined with "
+                       "valid_indices, image_of or expressions_per_image > 1")
+
+
 class Predictor(_ValidIndices, _ImageOf, _BatchInput):
     """The inference sibling of TrainStep: the reference's evaluation loop body (test.py:60-83, test_ytvos.py:230-260)
 
@@ -925,12 +929,18 @@ class Predictor(_ValidIndices, _ImageOf, _BatchInput):
                   text_encoder.fused_attention / .fused_embeddings for the one-kernel attention core and opening (bert/modeling_bert.py): the
                   predictor sets neither.  ValueError for floating-point lang or a non-integer l_mask, a model that carries its own encoder, together
                   with valid_indices, an encoder on another device; RuntimeError for an encoder in training mode.
+      jf_meter    optional lavt_hip.metrics.DeviceJFMeter (or make_jf_meter() / attach_jf_meter() later, before warmup_and_capture()): the video
+                  measure J&F of the DAVIS 2017 evaluation on the device.  Behind the mask kernel, and behind the evaluation meter's append if there
+                  is one, the body runs ops.boundary_counts(mask, target) into the static `jf` (int32 (frames, 8)) and one append of its sequence
+                  means.  Needs a target; the target is at out_size, so with out_size / via_size the measure runs at the original frame size.
+                  jf_frames_per_sequence: frames of one sequence, default T of a 5-D (B, T, 3, H, W) image, else all frames of the batch.
+                  ValueError together with valid_indices, image_of or expressions_per_image > 1.  Paused during warm-up and capture like `meter`.
     step() never synchronises: it returns the static mask tensor, the caller decides when to read it (EvalMeter.update(pred.iu) reads `.iu` with one
-    copy per call; a DeviceEvalMeter reads nothing until poll() / read()).  Built with none of image_of, meter and text_encoder, the launches are those
-    of a predictor without the three arguments."""
+    copy per call; a DeviceEvalMeter reads nothing until poll() / read()).  Built with none of image_of, meter, text_encoder and jf_meter, the launches
+    are those of a predictor without the four arguments."""
 
     def __init__(self, model, image, lang, l_mask, *, target=None, out_size=None, via_size=None, expressions_per_image=1, use_graph=True, context=None,
-                 valid_indices=None, image_of=None, meter=None, text_encoder=None):
+                 valid_indices=None, image_of=None, meter=None, text_encoder=None, jf_meter=None, jf_frames_per_sequence=None):
         if model.training:
             raise RuntimeError("Predictor: the model is in training mode -- call model.eval() first (BatchNorm is folded from the running statistics, DropPath is off)")
         for name, t in (("image", image), ("lang", lang), ("l_mask", l_mask), ("target", target)):
@@ -941,6 +951,8 @@ class Predictor(_ValidIndices, _ImageOf, _BatchInput):
         S = int(expressions_per_image)
         if S < 1:
             raise ValueError("Predictor: expressions_per_image must be >= 1")
+        if jf_meter is not None and (valid_indices is not None or image_of is not None or S > 1):
+            raise ValueError(_JF_WHOLE_SEQUENCES)
         if valid_indices is not None:
             if S > 1:
                 raise ValueError("Predictor: valid_indices selects frames of clips; it cannot be combined with expressions_per_image > 1")
@@ -984,8 +996,50 @@ class Predictor(_ValidIndices, _ImageOf, _BatchInput):
         self.meter = None
         if meter is not None:
             self.attach_meter(meter)
+        self.jf = None                           # int32 (frames, 8) with a J&F meter: {I, U, n_fg, n_gt, m_fg, m_gt, 0, 0} per frame at out_size
+        self.jf_meter = None
+        self.jf_frames_per_sequence = None if jf_frames_per_sequence is None else int(jf_frames_per_sequence)
+        if jf_meter is not None:
+            self.attach_jf_meter(jf_meter)
+        elif jf_frames_per_sequence is not None and target is not None:
+            self._jf_sequence_length()           # (refuse a bad length at construction, with or without a meter yet)
 
     _empty_slots = True          # pair-list batches (_ImageOf.set_image_of): -1 marks an empty slot
+
+    # ---- J&F on the device ----
+    def _jf_sequence_length(self):
+        """frames per sequence of the J&F meter: jf_frames_per_sequence, else T of a 5-D (B, T, 3, H, W) image, else all frames of the batch"""
+        frames = int(self.t.shape[0])          # (the mask has a frame per target frame: B*T for a video model)
+        T = self.jf_frames_per_sequence
+        if T is None:
+            T = int(self.x.shape[1]) if self.x.dim() == 5 else frames
+        if T < 1 or frames % T:
+            raise ValueError(f"Predictor: the {frames} frames of a step are not whole sequences of {T} (jf_frames_per_sequence)")
+        return T
+
+    def make_jf_meter(self, **kw):
+        """Build a lavt_hip.metrics.DeviceJFMeter(**kw) on the predictor's device, attach it and return it.  Before warmup_and_capture() only."""
+        from .metrics import DeviceJFMeter
+        kw.setdefault("device", self.x.device)
+        return self.attach_jf_meter(DeviceJFMeter(**kw))
+
+    def attach_jf_meter(self, meter):
+        """Make an existing DeviceJFMeter part of the prediction step: behind the mask kernel (and the evaluation meter's append) the body runs
+        ops.boundary_counts(mask, target) into `jf` and lavt_jf_meter_append on it: every step() adds its sequences.  Before warmup_and_capture()
+        only; needs a `target`; refused with valid_indices, image_of and expressions_per_image > 1 (the frames of a step must be whole sequences)."""
+        if self._warmed:
+            raise RuntimeError("Predictor: a J&F meter must be attached before warmup_and_capture() (the captured launch sequence is frozen)")
+        if self.jf_meter is not None:
+            raise RuntimeError("Predictor: a J&F meter is already attached")
+        if self.t is None:
+            raise ValueError("Predictor: the J&F meter compares `mask` with a ground truth; this predictor was built without a target")
+        if self.valid_indices is not None or self.image_of is not None or self.S > 1:
+            raise ValueError(_JF_WHOLE_SEQUENCES)
+        if meter.block.device != self.x.device:
+            raise ValueError(f"Predictor: the J&F meter lives on {meter.block.device}, the predictor on {self.x.device}")
+        self._jf_sequence_length()
+        self.jf_meter = meter
+        return meter
 
     # ---- the evaluation log on the device ----
     def make_meter(self, **kw):
@@ -1032,6 +1086,9 @@ class Predictor(_ValidIndices, _ImageOf, _BatchInput):
                                                    n_images=n_images)
             if self.meter is not None:          # the last launch of the step
                 self.meter.append(self.iu, self.image_of, n_images or 0)
+            if self.jf_meter is not None:       # the J&F counts at out_size, then their sequence means
+                self.jf = ops.boundary_counts(self.mask, self.t)
+                self.jf_meter.append(self.jf, self._jf_sequence_length())
         return self.mask
 
     def warmup_and_capture(self, eager_iters=2):
@@ -1039,13 +1096,16 @@ class Predictor(_ValidIndices, _ImageOf, _BatchInput):
         torch.cuda.CUDAGraph on that stream: a straight-line sequence, no forked branches.  A failed capture is reported and the eager path kept.
         An attached meter is on hold (DeviceEvalMeter.pause) for the eager runs and the capture and released at the end: its count is what it was."""
         self._warmed = True
-        if self.meter is None:
+        meters = [m for m in (self.meter, self.jf_meter) if m is not None]
+        if not meters:
             return self._warmup_and_capture(eager_iters)
-        self.meter.pause()
+        for m in meters:
+            m.pause()
         try:
             return self._warmup_and_capture(eager_iters)
         finally:
-            self.meter.resume()
+            for m in meters:
+                m.resume()
 
     @_in_context
     def _warmup_and_capture(self, eager_iters):

@@ -3411,6 +3411,34 @@ def upsample_mask(rows, B, Hi, Wi, out_size, via_size=None, target=None, image_o
     return mask, iu
 
 
+# ------------------------------------------------------------------------------------------ J&F pixel counts (DAVIS 2017 boundary measure)
+def boundary_counts(pred, target, bound_pix=None, out=None):
+    """The integers of the J&F measure (include/lavt_hip.h "J&F measure"; lavt_hip.metrics has the measure itself) for n frames: pred uint8
+    (n, H, W) -- what upsample_mask returns --, target uint8 or int64 (n, H, W), nonzero = foreground for both -> int32 (n, 8), row j =
+    {I, U, n_fg, n_gt, m_fg, m_gt, 0, 0} of frame j.  bound_pix: the disk radius, default metrics.davis_bound_pix(H, W).  out: an int32 (n, 8) tensor
+    to write instead of a fresh one; every row is overwritten completely.  Capturable, no host synchronisation."""
+    from .metrics import davis_bound_pix
+    if not isinstance(pred, torch.Tensor) or not pred.is_cuda or not isinstance(target, torch.Tensor) or not target.is_cuda:
+        raise RuntimeError("liblavt_hip operates on GPU memory only (got a CPU tensor for `boundary_counts`); there is no CPU fallback")
+    if pred.dtype != torch.uint8 or pred.dim() != 3 or pred.numel() == 0:
+        raise ValueError(f"boundary_counts: pred must be a non-empty uint8 (n, H, W), got {pred.dtype} {tuple(pred.shape)}")
+    if target.dtype not in (torch.uint8, torch.int64) or target.shape != pred.shape:
+        raise ValueError(f"boundary_counts: target must be uint8 or int64 {tuple(pred.shape)}, got {target.dtype} {tuple(target.shape)}")
+    n, H, W = (int(v) for v in pred.shape)
+    r = davis_bound_pix(H, W) if bound_pix is None else int(bound_pix)
+    pred, target = pred.contiguous(), target.contiguous()
+    if out is None:
+        out = torch.empty(n, 8, dtype=torch.int32, device=pred.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (n, 8) or not out.is_contiguous() or out.device != pred.device:
+        raise ValueError(f"boundary_counts: out must be a contiguous int32 ({n}, 8) on {pred.device}, got {out.dtype} {tuple(out.shape)}")
+    ws = torch.empty(int(K.lib.lavt_boundary_counts_ws(n, H, W)), dtype=torch.int64, device=pred.device)
+    u8 = target.dtype == torch.uint8
+    _note(f"boundary-counts {n}x{H}x{W} r={r}", nbytes=n * H * W * (1 + target.element_size()))
+    K.check(K.lib.lavt_boundary_counts(K.ptr(pred), K.ptr(target) if u8 else None, None if u8 else K.ptr(target), n, H, W, r, K.ptr(ws), ws.numel(), K.ptr(out),
+                                       K.stream()))
+    return out
+
+
 def _u8_frames(src, inner, what):
     """(N, Hs, Ws[, 3]) uint8 on the GPU whose frames are contiguous (the frame stride is free) -> the tensor and that stride in elements"""
     if not src.is_cuda:

@@ -35,7 +35,16 @@ and the decoder's launch count per call (profiler records in the "decoder" scope
   text_eager_then_replay                         the evaluation loop as it stands: enc(ids, mask) eagerly, two copies, the image_of replay
   text_in_predictor                              Predictor(text_encoder=) replay
   text_in_predictor_fused_attention              ... with enc.fused_attention
-  text_in_predictor_fused_attention_embeddings   ... and enc.fused_embeddings"""
+  text_in_predictor_fused_attention_embeddings   ... and enc.fused_embeddings
+
+    --jf   (opt-in, runs ONLY this) the J&F measure on the device.  MICROSECONDS per call from device events, median over --calls with p10 / p90 / min / max,
+           the regions of a comparison alternating call by call:
+  jf_boundary_counts        ops.boundary_counts alone (int64 target) at 8 x 384x384 (r = 5), 8 x 480x854 (r = 8), 36 x 720x1280 (r = 12), for object-like
+                            masks (one ellipse per frame) and for pixel noise (every pixel a boundary pixel); bytes_read = n*H*W*9 and the rate it implies;
+                            us_in_graph_* = the same call ten times in one captured graph, per call (no host enqueue cost between the three kernels)
+  jf_torch_composition      the same counts from torch ops on the same GPU: boundary maps by slicing, F.conv2d with the disk as the weight, > 0
+  jf_replay_without_meter   the Video-Swin-B replay (T = 8, 384^2, masks at 720x1280 through via_size) as a predictor without the meter launches it
+  jf_replay_with_jf_meter   the same predictor with make_jf_meter()"""
 import argparse
 import json
 import os
@@ -260,6 +269,133 @@ def text_encoder(a, report):
                text_launches_eager=n_text if name == "text_eager_then_replay" else None, speedup=round(base / statistics.median(v), 4))
 
 
+def jf(a, report):
+    """--jf: (1) lavt_boundary_counts alone against a torch composition and the bytes it must read, (2) the Video-Swin-B replay with and without the
+    J&F meter.  Device-event times per call, the regions alternating call by call."""
+    import torch.nn.functional as F
+    import lavt_hip
+    from lavt_hip import ops
+    from lavt_hip.detweights import det_inputs, fill_state_dict_
+    from lavt_hip.engine import Predictor
+    from lavt_hip.metrics import davis_bound_pix
+    from lib._utils import LAVTVideo
+    from lib.mask_predictor import SimpleDecoding
+    from lib.video_swin_transformer import MultiModalSwinTransformer3D
+    dev = "cuda:0"
+
+    def masks(n, H, W, kind, seed):
+        g = torch.Generator("cpu").manual_seed(seed)
+        if kind == "noise":          # every pixel a boundary pixel: the worst case of the boundary pass
+            return (torch.rand(n, H, W, generator=g) < 0.5).to(torch.uint8)
+        yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")          # "object": one ellipse per frame, drifting
+        out = torch.zeros(n, H, W, dtype=torch.uint8)
+        for k in range(n):
+            cy, cx, ry, rx = (torch.rand(4, generator=g) * torch.tensor([H / 2, W / 2, H / 4, W / 4]) + torch.tensor([H / 4, W / 4, H / 8, W / 8])).tolist()
+            out[k] = (((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 <= 1.0).to(torch.uint8)
+        return out
+
+    def torch_counts(P, G, r):          # boundary maps by slicing, the disk as a convolution weight
+        d = torch.arange(-r, r + 1, device=dev)
+        w = ((d[:, None] ** 2 + d[None, :] ** 2) <= r * r).float()[None, None]
+
+        def bmap(S):
+            S = S != 0
+            e, s, se = S.clone(), S.clone(), S.clone()          # (the last row / column compare with themselves: the toolkit's overwrite)
+            e[:, :, :-1] = S[:, :, 1:]
+            s[:, :-1, :] = S[:, 1:, :]
+            se[:, :-1, :-1] = S[:, 1:, 1:]
+            se[:, -1, :-1] = S[:, -1, 1:]
+            se[:, :-1, -1] = S[:, 1:, -1]
+            return (S ^ e) | (S ^ s) | (S ^ se)
+        bp, bg = bmap(P), bmap(G)
+        dp = F.conv2d(bp[:, None].float(), w, padding=r)[:, 0] > 0
+        dg = F.conv2d(bg[:, None].float(), w, padding=r)[:, 0] > 0
+        Pb, Gb = P != 0, G != 0
+        cols = [Pb & Gb, Pb | Gb, bp, bg, bp & dg, bg & dp]
+        return torch.stack([c.flatten(1).sum(1) for c in cols], 1).int()
+
+    def alternate(fns, calls, warmup):
+        for _ in range(warmup):
+            for fn in fns.values():
+                fn()
+        ts = {k: [] for k in fns}
+        for _ in range(calls):
+            for k, fn in fns.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                ts[k].append(e0.elapsed_time(e1) * 1e3)
+        return {k: sorted(v) for k, v in ts.items()}
+
+    def spread(v):
+        return dict(us_median=round(statistics.median(v), 2), us_p10=round(v[len(v) // 10], 2), us_p90=round(v[(9 * len(v)) // 10], 2), us_min=round(v[0], 2),
+                    us_max=round(v[-1], 2))
+
+    for n, H, W in ((8, 384, 384), (8, 480, 854), (36, 720, 1280)):
+        r = davis_bound_pix(H, W)
+        for kind in ("object", "noise"):
+            P, G = masks(n, H, W, kind, 1).to(dev), masks(n, H, W, kind, 2).to(dev).long()
+            out = torch.empty(n, 8, dtype=torch.int32, device=dev)
+            got, want = ops.boundary_counts(P, G, r, out=out).clone(), torch_counts(P, G, r)
+            ts = alternate({"hip": lambda: ops.boundary_counts(P, G, r, out=out), "torch": lambda: torch_counts(P, G, r)}, a.calls, a.warmup)
+            nbytes = n * H * W * 9
+            med = statistics.median(ts["hip"])
+            # the same call ten times in one captured graph: the three kernels without the host's enqueue cost, which an eager call of this size is bound by
+            g, side = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                ops.boundary_counts(P, G, r, out=out)
+            torch.cuda.current_stream().wait_stream(side)
+            with torch.cuda.graph(g):
+                for _ in range(10):
+                    ops.boundary_counts(P, G, r, out=out)
+            tg = alternate({"graph": g.replay}, a.calls, a.warmup)["graph"]
+            in_graph = statistics.median(tg) / 10.0
+            report(path="jf_boundary_counts", frames=n, H=H, W=W, bound_pix=r, masks=kind, equal_to_torch=bool(torch.equal(got[:, :6], want)), bytes_read=nbytes,
+                   gb_per_s=round(nbytes / med / 1e3, 1), us_in_graph_median=round(in_graph, 2), us_in_graph_p10=round(tg[len(tg) // 10] / 10.0, 2),
+                   us_in_graph_p90=round(tg[(9 * len(tg)) // 10] / 10.0, 2), gb_per_s_in_graph=round(nbytes / in_graph / 1e3, 1), **spread(ts["hip"]))
+            report(path="jf_torch_composition", frames=n, H=H, W=W, bound_pix=r, masks=kind, speedup_of_hip=round(statistics.median(ts["torch"]) / med, 2),
+                   **spread(ts["torch"]))
+            del P, G
+    # ---- the replay: Video-Swin-B, one clip of T = 8 frames at 384^2, masks at 720 x 1280 through via_size (test_ytvos.py:249-253)
+    T, size, out_size = 8, 384, (720, 1280)
+    lavt_hip.set_compute_dtype(torch.bfloat16 if a.dtype == "bf16" else torch.float32)
+    args = SimpleNamespace()
+    bb = MultiModalSwinTransformer3D(patch_size=(1, 4, 4), embed_dim=128, depths=[2, 2, 18, 2], num_heads=[4, 8, 16, 32], window_size=(8, 7, 7),
+                                     drop_path_rate=0.3, patch_norm=True, out_indices=(0, 1, 2, 3), num_heads_fusion=[1, 1, 1, 1], args=args)
+    parts = torch.nn.ModuleDict({"backbone": bb, "classifier": SimpleDecoding(1024, args)})
+    fill_state_dict_(parts)
+    parts.to(dev)
+    clip, l, m, _ = det_inputs(1, size, 20, seed=1234, frames=T)
+    clip, l, m = clip.to(dev), l.to(dev), m.to(dev)
+    tgt = masks(T, out_size[0], out_size[1], "object", 3).to(dev).long()
+
+    class _Text(torch.nn.Module):
+        def forward(self, ids, attention_mask=None):
+            return (l.permute(0, 2, 1),)
+
+    model = LAVTVideo.__new__(LAVTVideo)
+    torch.nn.Module.__init__(model)
+    model.backbone, model.classifier, model.text_encoder = parts["backbone"], parts["classifier"], _Text()
+    model.lazy_pred, model.seg_last = False, False
+    model.eval()
+    ids, am = torch.zeros(1, 20, dtype=torch.long, device=dev), m.squeeze(-1).contiguous()
+    plain = Predictor(model, clip, ids, am, target=tgt, out_size=out_size, via_size=(size, size), context=ops.StepContext())
+    plain.warmup_and_capture()
+    with_jf = Predictor(model, clip, ids, am, target=tgt, out_size=out_size, via_size=(size, size), context=ops.StepContext())
+    meter = with_jf.make_jf_meter(capacity=64)
+    with_jf.warmup_and_capture()
+    ts = alternate({"plain": plain.step, "jf": with_jf.step}, a.calls, a.warmup)
+    s = meter.read().summary()
+    common = dict(variant="video_swin_b", size=size, frames=T, out_size=list(out_size), bound_pix=davis_bound_pix(*out_size))
+    report(path="jf_replay_without_meter", captured=plain.captured, **spread(ts["plain"]), **common)
+    report(path="jf_replay_with_jf_meter", captured=with_jf.captured, masks_equal=bool(torch.equal(plain.mask, with_jf.mask)),
+           added_us_median=round(statistics.median(ts["jf"]) - statistics.median(ts["plain"]), 2), J=round(s["J"], 4), F=round(s["F"], 4), **spread(ts["jf"]), **common)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=30)
@@ -272,9 +408,22 @@ def main():
     ap.add_argument("--video-select", default=None, metavar="IND", help="run ONLY the annotated-frame comparison on Video-Swin-B, T=8, 384^2: all frames + index vs valid_indices=[IND]")
     ap.add_argument("--pairs", type=int, default=None, metavar="N", help="run ONLY the pair-list comparison: N batch-1 replays + EvalMeter.update vs one image_of replay + device meter")
     ap.add_argument("--text-encoder", action="store_true", help="run ONLY the text-stage comparison: eager BERT in front of an image_of replay vs Predictor(text_encoder=)")
+    ap.add_argument("--jf", action="store_true", help="run ONLY the J&F figures: lavt_boundary_counts against a torch composition, and the video replay with / without the J&F meter")
     a = ap.parse_args()
     if a.calls < 20:
         ap.error("--calls must be at least 20")
+    if a.jf:
+        lines = []
+
+        def report_jf(**kw):
+            kw.update(dtype=a.dtype, calls=a.calls)
+            lines.append(json.dumps(kw))
+            print(lines[-1], flush=True)
+        jf(a, report_jf)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if a.text_encoder:
         lines = []
 
